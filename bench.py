@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- utterances/sec of one Conformer-M hybrid RNNT-CTC + EWC training step on MI355X (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+                                                           (N>1: launched by torch.distributed.run, one rank per GPU)
 
 A "step" = zero_grad -> training_step (features, SpecAugment, Conformer encoder, prediction net, fused joint+RNNT
 loss per sub-batch, CTC head+loss) -> EWC penalty pre-loaded into .grad -> backward -> RCCL gradient all-reduce
@@ -10,7 +11,9 @@ U(0.6,1)*L with one full-length item, 7 tokens/s, language 'hi', seed 1234).  Wo
 configs[1]: Conformer-medium (d=256, 16 layers), EWC, bs=32 per GPU, 15 s utterances, bf16 projections, encoder
 layers <= 12 frozen as in the reference's config.yaml.  Weak scaling: every rank processes its own 32 utterances.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with these extra objects:
+Rank 0 prints ONE JSON line (its contract: tests/test_bench_contract_gpu.py).  A plain run sets up, warms up, times the K
+steps and prints it; `--dump-outputs DIR` first writes what the last timed step handed its caller (dump_outputs).
+Everything else is measured only with `--full`, which adds these objects:
   roofline       the HBM-bound transducer gradient kernel timed with HIP events inside the timed steps; `traffic` = HBM
                  bytes per launch from this round's PMC passes of the same command (profiles/r03_pmc_traffic.json)
   roofline_mfma  the dominant MFMA kernel of the step (fused joint hidden-gradient kernel), timed the same way
@@ -19,6 +22,8 @@ Rank 0 prints ONE JSON line (contract in the task statement) with these extra ob
                  oracle timed on BASELINE configs[0] exactly (`config1`)
   config.with_h2d_prefetch  the same step fed from pinned host memory by a one-batch-ahead asynchronous copy (PCIe
                  inclusive; never `value`)
+  config.without_wer / with_wer  the step timed the other way round (without / with the in-step greedy decode + WER)
+  peaks_measured, rooflines  the box's copy / MFMA peaks, and the per-kernel table of the committed profile passes
 """
 import argparse
 import ctypes
@@ -35,8 +40,8 @@ import torch  # noqa: E402
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (6.29 TB/s measured copy)
-MFMA_BF16_PEAK_TFS = 2500.0   # same guide: dense bf16 / f16 MFMA peak (the 5 PF headline includes 2:1 sparsity)
+HBM_PEAK_GBS = 8000.0  # MI355X datasheet: HBM3E peak 8.0 TB/s (6.29 TB/s measured copy)
+MFMA_BF16_PEAK_TFS = 2500.0   # same datasheet: dense bf16 / f16 MFMA peak (the 5 PF headline includes 2:1 sparsity)
 
 
 def measure_peaks(dev):
@@ -93,6 +98,30 @@ def synth_batch(B, seconds, device, seed=1234, vocab=256, sr=16000):
     tok = torch.randint(0, vocab, (B, U), generator=g)
     batch = (x.to(device), lens.to(device), tok.to(device), tl.to(device))
     return batch, (lens.tolist(), tl.tolist())
+
+
+def dump_outputs(out_dir, loss, monitor, flat, extra=None, wer_on=True, max_elems=1 << 22, seed=0):
+    """What the timed path hands its caller after its last step, as DIR/<name>.npy: `loss` and every `monitor_<key>` (float64
+    scalars), the updated trainable parameters (`params`) and the step's gradient (`grads`), float32, plus `extra` flat
+    buffers (MAS: `omega`).  Above `max_elems` trainable values (16 MB each) the flat buffers are dumped at one fixed,
+    seeded sample of positions, the same for all of them."""
+    import numpy as np
+    from indic_cl_asr_amd import cl
+    os.makedirs(out_dir, exist_ok=True)
+    cl.flush_pending_updates()      # data parallel: the last AdamW update waits for the next forward otherwise
+    torch.cuda.synchronize()
+    np.save(os.path.join(out_dir, "loss.npy"), np.float64(loss.item()))
+    for k, v in monitor.items():
+        if k.startswith("_") or (k.startswith("training_batch_wer") and not wer_on):   # (NaN placeholders without the WER)
+            continue
+        np.save(os.path.join(out_dir, f"monitor_{k}.npy"), np.float64(float(v)))
+    idx = torch.cat([torch.arange(o, o + n) for _, o, n, _ in flat.entries])     # without the padding between tensors
+    if idx.numel() > max_elems:
+        pick = np.sort(np.random.default_rng(seed).choice(idx.numel(), max_elems, replace=False))
+        idx = idx[torch.from_numpy(pick)]
+    idx = idx.to(flat.theta.device)
+    for name, buf in dict(params=flat.theta, grads=flat.grad, **(extra or {})).items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), buf[idx].float().cpu().numpy())
 
 
 class HipEvents:
@@ -206,6 +235,71 @@ def cpu_baseline(seconds, cfg_kw, sample_bs=4, freeze_till=12, device=None):
     return out
 
 
+def full_report(out, args, dev, cfg, world, events, mfma_events):
+    """--full: the box's peaks, the in-step kernel rooflines, the committed per-kernel table and the CPU oracle baseline
+    into the rank-0 line `out`."""
+    peaks = None
+    if not args.no_peaks:
+        try:
+            peaks = measure_peaks(dev)
+        except Exception as e:   # never lose the line to a microbenchmark
+            peaks = {"error": repr(e)}
+        out["peaks_measured"] = peaks
+
+    def frac_vs(ach, key, sheet):
+        d = {"datasheet": round(ach / sheet, 4)}
+        if peaks and key in peaks:
+            d["measured"] = round(ach / peaks[key], 4)
+        return d
+    pmc = None
+    s = events.summary()
+    if s is not None:
+        avg_ms, avg_bytes, n = s
+        ach = avg_bytes / (avg_ms * 1e-3) / 1e9
+        traffic = None
+        try:  # HBM bytes per launch from this round's PMC passes of the same command (profiles/r03_pmc_traffic.json)
+            pmc_file = "r03_pmc_traffic.json" if os.path.exists(os.path.join(ROOT, "profiles", "r03_pmc_traffic.json")) else "r02_pmc_traffic.json"
+            pmc = json.load(open(os.path.join(ROOT, "profiles", pmc_file)))
+            if args.batch == 32 and args.seconds == 15.0 and args.preset == "medium":
+                traffic = pmc["kernels"].get(events.kernel_name, {}).get("hbm_bytes_per_launch")
+        except Exception:
+            traffic = None
+        out["roofline"] = {"kernel": events.kernel_name, "bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS,
+                           "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": traffic,
+                           "launches": n, "avg_launch_ms": round(avg_ms, 4),
+                           "algorithmic_bytes_per_launch": int(avg_bytes),
+                           # the same launch priced on ALL B*T'*(U+1) cells (what the kernel streamed before it left the
+                           # tiles behind the utterances' ends alone): for comparison with earlier rounds only
+                           "full_lattice_bytes_per_launch": int(avg_bytes * events.full_scale),
+                           "frac_if_full_lattice": round(ach * events.full_scale / HBM_PEAK_GBS, 4),
+                           "frac_of": frac_vs(ach, "hbm_copy_GBs", HBM_PEAK_GBS)}
+    if mfma_events:
+        ms_l = [a.elapsed_time(b) for a, b, _ in mfma_events]
+        fl = sum(f for _, _, f in mfma_events) / len(mfma_events)
+        avg = sum(ms_l) / len(ms_l)
+        tf = fl / (avg * 1e-3) / 1e12
+        out["roofline_mfma"] = {"kernel": "joint_dh_fused_kernel", "bound": "mfma", "achieved": round(tf, 1), "peak": MFMA_BF16_PEAK_TFS,
+                                "unit": "TFLOP/s", "frac": round(tf / MFMA_BF16_PEAK_TFS, 4),
+                                "traffic": ((pmc or {}).get("kernels", {}).get("joint_dh_fused_kernel", {}).get("hbm_bytes_per_launch")
+                                            if (args.batch == 32 and args.seconds == 15.0 and args.preset == "medium") else None),
+                                "launches": len(ms_l),
+                                "avg_launch_ms": round(avg, 4), "algorithmic_flops_per_launch": int(fl),
+                                "frac_of": frac_vs(tf, "mfma_bf16_TFs", MFMA_BF16_PEAK_TFS)}
+    # per-kernel table of this round's committed profile passes (tools/make_rooflines.py: share of the step, bound, achieved,
+    # fraction) -- the dominant kernels carry the picture, not one 2 % kernel
+    try:
+        if args.batch == 32 and args.seconds == 15.0 and args.preset == "medium" and args.cl == "ewc":
+            out["rooflines"] = json.load(open(os.path.join(ROOT, "profiles", "r03_rooflines.json")))["kernels"]
+    except Exception:
+        pass
+    if not args.no_cpu_baseline and world == 1:
+        kw = dict(d_model=cfg.d_model, n_layers=cfg.n_layers, n_heads=cfg.n_heads, pred_hidden=cfg.pred_hidden,
+                  joint_hidden=cfg.joint_hidden)
+        out["cpu_baseline"] = cpu_baseline(args.seconds, kw, args.cpu_sample_bs, max(args.freeze, 0), device=dev)
+    else:
+        out["cpu_baseline"] = None       # (--no-cpu-baseline, or N > 1: rank 0 times it at N = 1 only)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -220,11 +314,15 @@ def main():
                     help="step recipe: EWC step (the headline, BASELINE configs[1]); MAS importance pass (configs[2], "
                          "R/cl_baseline_mas.py:258-270); LwF teacher + student step (configs[3], R/cl_baseline_lwf.py:212-264)")
     ap.add_argument("--fp8-prefix", action="store_true", help="e4m3 projections in the frozen prefix (BASELINE configs[4]; never the headline)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: the step the other way round "
+                                                      "(with / without the in-step WER), the PCIe-inclusive leg, in-step kernel "
+                                                      "rooflines, the box's peaks and the CPU oracle baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU oracle baseline")
     ap.add_argument("--no-wer", action="store_true", help="timed steps WITHOUT the in-step greedy decode + WER of the reference's "
                                                          "training_step (compute_wer = True there); default: with it, monitor read after every step")
-    ap.add_argument("--no-wer-leg", action="store_true", help="skip the extra leg that times the step the other way round (without / with the in-step WER)")
-    ap.add_argument("--no-peaks", action="store_true", help="skip the on-box copy / MFMA peak microbenchmarks")
+    ap.add_argument("--no-wer-leg", action="store_true", help="(--full) skip the extra leg that times the step the other way round (without / with the in-step WER)")
+    ap.add_argument("--no-peaks", action="store_true", help="(--full) skip the on-box copy / MFMA peak microbenchmarks")
     ap.add_argument("--grad-exchange", default="fp32", choices=["fp32", "bf16"], help="dtype of the data-parallel gradient all-reduce")
     ap.add_argument("--cpu-sample-bs", type=int, default=4)
     args = ap.parse_args()
@@ -271,27 +369,28 @@ def main():
     langs = ['hi'] * args.batch
 
     events = HipEvents()
-    rnnt_mod.PROFILE_HOOK = events.hook
-    try:   # cells the gradient kernel has to touch: frames < T_b + 8 of every utterance (+ the 64-cell tile that straddles the end)
-        from indic_cl_asr_amd.encoder import subsampled_length
-        from indic_cl_asr_amd.features import mel_frame_count
-        h_enc = [int(subsampled_length(mel_frame_count(int(n), cfg.n_fft, cfg.n_window_stride))) for n in host_lens[0]]
-        Tq, U1q = max(h_enc), max(int(u) for u in host_lens[1]) + 1
-        live = sum(min(Tq * U1q, (min(Tq, t + 8) * U1q + 63) // 64 * 64) for t in h_enc)
-        events.touched_fraction = live / float(len(h_enc) * Tq * U1q)
-    except Exception:
-        events.touched_fraction = None
-    from indic_cl_asr_amd.ops import joint as joint_mod
     mfma_events = []          # (start, stop, flops) of the fused hidden-gradient kernel (the dominant MFMA kernel)
     timing = {"on": False}
+    if args.full:             # kernel events inside the timed steps (roofline, roofline_mfma)
+        rnnt_mod.PROFILE_HOOK = events.hook
+        try:   # cells the gradient kernel has to touch: frames < T_b + 8 of every utterance (+ the 64-cell tile that straddles the end)
+            from indic_cl_asr_amd.encoder import subsampled_length
+            from indic_cl_asr_amd.features import mel_frame_count
+            h_enc = [int(subsampled_length(mel_frame_count(int(n), cfg.n_fft, cfg.n_window_stride))) for n in host_lens[0]]
+            Tq, U1q = max(h_enc), max(int(u) for u in host_lens[1]) + 1
+            live = sum(min(Tq * U1q, (min(Tq, t + 8) * U1q + 63) // 64 * 64) for t in h_enc)
+            events.touched_fraction = live / float(len(h_enc) * Tq * U1q)
+        except Exception:
+            events.touched_fraction = None
+        from indic_cl_asr_amd.ops import joint as joint_mod
 
-    def mfma_hook(flops):
-        if not timing["on"]:
-            return None
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        mfma_events.append((a, b, flops))
-        return a, b
-    joint_mod.MFMA_PROFILE_HOOK = mfma_hook
+        def mfma_hook(flops):
+            if not timing["on"]:
+                return None
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            mfma_events.append((a, b, flops))
+            return a, b
+        joint_mod.MFMA_PROFILE_HOOK = mfma_hook
 
     omega = cl.get_zero_params(model) if args.cl == "mas_importance" else None
     teacher = cl.get_params_clone(model) if args.cl == "lwf" else None
@@ -326,7 +425,7 @@ def main():
             loss, _, _ = cl.lwf_kd_loss(loss, prob, prob_, m_.joint.store_list, store, 0.1, 0.3)
             loss.backward()
             opt.step()
-        return loss
+        return loss, monitor
 
     for _ in range(args.warmup):
         step()
@@ -335,12 +434,12 @@ def main():
     torch.cuda.synchronize()
     events.enabled = True
     timing["on"] = True
-    opt.profile_exchange = world > 1       # events around the wait for the gradient all-reduce: exposed exchange time
+    opt.profile_exchange = args.full and world > 1     # events around the wait for the gradient all-reduce: exposed exchange time
     from indic_cl_asr_amd.ops import fast as fast_mod
     fast_mod.SYNC_BN_COLLECTIVES = 0
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, monitor = step()
     host_dt = time.perf_counter() - t0   # host enqueue time of the timed steps (no sync inside a step)
     if world > 1:
         dist.barrier()
@@ -359,10 +458,13 @@ def main():
                     "note": "one flat all-reduce per step on its own communicator, launched at optimizer.step() and waited for in "
                             "front of the first trainable module of the NEXT forward (under the frozen prefix); exposed = how long "
                             "the compute stream stalls there"}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, monitor, flat, extra=dict(omega=omega.flat) if omega is not None else None,
+                     wer_on=wer_on)
     # ---- the step the other way round: without the in-step decode + WER when the timed steps have it (what it costs), with it
     # when they were run with --no-wer
     wer_leg = None
-    if args.cl == "ewc" and not args.no_wer_leg:
+    if args.full and args.cl == "ewc" and not args.no_wer_leg:
         other = not wer_on
         n3 = max(5, args.steps // 2)
         m_.wer.log_prediction = False; m_.ctc_wer.log_prediction = False       # R/cl_baseline.py:127-128
@@ -397,7 +499,7 @@ def main():
             wer_leg["training_batch_wer_ctc"] = float(mon3["training_batch_wer_ctc"])
     # ---- the same step fed from pinned host memory (one batch ahead on a copy stream): PCIe-inclusive rate, never `value`
     h2d = None
-    if world == 1 and args.cl == "ewc":
+    if args.full and world == 1 and args.cl == "ewc":
         host_batch = tuple(t.cpu().pin_memory() for t in batch)
         copy = torch.cuda.Stream(device=dev)
 
@@ -458,68 +560,11 @@ def main():
                                                 "step, as the reference's loops do; token-level rates on random-initialised weights (no "
                                                 "tokenizer / checkpoint in the build)"}
                                        if (wer_on and last_monitor[0] is not None) else {"enabled": False}),
-                       "with_h2d_prefetch": h2d, ("without_wer" if wer_on else "with_wer"): wer_leg, "exchange": exchange},
+                       "exchange": exchange},
         }
-        peaks = None
-        if not args.no_peaks:
-            try:
-                peaks = measure_peaks(dev)
-            except Exception as e:   # never lose the line to a microbenchmark
-                peaks = {"error": repr(e)}
-            out["peaks_measured"] = peaks
-
-        def frac_vs(ach, key, sheet):
-            d = {"datasheet": round(ach / sheet, 4)}
-            if peaks and key in peaks:
-                d["measured"] = round(ach / peaks[key], 4)
-            return d
-        pmc = None
-        s = events.summary()
-        if s is not None:
-            avg_ms, avg_bytes, n = s
-            ach = avg_bytes / (avg_ms * 1e-3) / 1e9
-            traffic = None
-            try:  # HBM bytes per launch from this round's PMC passes of the same command (profiles/r03_pmc_traffic.json)
-                pmc_file = "r03_pmc_traffic.json" if os.path.exists(os.path.join(ROOT, "profiles", "r03_pmc_traffic.json")) else "r02_pmc_traffic.json"
-                pmc = json.load(open(os.path.join(ROOT, "profiles", pmc_file)))
-                if args.batch == 32 and args.seconds == 15.0 and args.preset == "medium":
-                    traffic = pmc["kernels"].get(events.kernel_name, {}).get("hbm_bytes_per_launch")
-            except Exception:
-                traffic = None
-            out["roofline"] = {"kernel": events.kernel_name, "bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS,
-                               "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": traffic,
-                               "launches": n, "avg_launch_ms": round(avg_ms, 4),
-                               "algorithmic_bytes_per_launch": int(avg_bytes),
-                               # the same launch priced on ALL B*T'*(U+1) cells (what the kernel streamed before it left the
-                               # tiles behind the utterances' ends alone): for comparison with earlier rounds only
-                               "full_lattice_bytes_per_launch": int(avg_bytes * events.full_scale),
-                               "frac_if_full_lattice": round(ach * events.full_scale / HBM_PEAK_GBS, 4),
-                               "frac_of": frac_vs(ach, "hbm_copy_GBs", HBM_PEAK_GBS)}
-        if mfma_events:
-            ms_l = [a.elapsed_time(b) for a, b, _ in mfma_events]
-            fl = sum(f for _, _, f in mfma_events) / len(mfma_events)
-            avg = sum(ms_l) / len(ms_l)
-            tf = fl / (avg * 1e-3) / 1e12
-            out["roofline_mfma"] = {"kernel": "joint_dh_fused_kernel", "bound": "mfma", "achieved": round(tf, 1), "peak": MFMA_BF16_PEAK_TFS,
-                                    "unit": "TFLOP/s", "frac": round(tf / MFMA_BF16_PEAK_TFS, 4),
-                                    "traffic": ((pmc or {}).get("kernels", {}).get("joint_dh_fused_kernel", {}).get("hbm_bytes_per_launch")
-                                                if (args.batch == 32 and args.seconds == 15.0 and args.preset == "medium") else None),
-                                    "launches": len(ms_l),
-                                    "avg_launch_ms": round(avg, 4), "algorithmic_flops_per_launch": int(fl),
-                                    "frac_of": frac_vs(tf, "mfma_bf16_TFs", MFMA_BF16_PEAK_TFS)}
-        # per-kernel table of this round's committed profile passes (tools/make_rooflines.py: share of the step, bound, achieved,
-        # fraction) -- the dominant kernels carry the picture, not one 2 % kernel
-        try:
-            if args.batch == 32 and args.seconds == 15.0 and args.preset == "medium" and args.cl == "ewc":
-                out["rooflines"] = json.load(open(os.path.join(ROOT, "profiles", "r03_rooflines.json")))["kernels"]
-        except Exception:
-            pass
-        if not args.no_cpu_baseline and world == 1:
-            kw = dict(d_model=cfg.d_model, n_layers=cfg.n_layers, n_heads=cfg.n_heads, pred_hidden=cfg.pred_hidden,
-                      joint_hidden=cfg.joint_hidden)
-            out["cpu_baseline"] = cpu_baseline(args.seconds, kw, args.cpu_sample_bs, max(args.freeze, 0), device=dev)
-        else:
-            out["cpu_baseline"] = None       # (--no-cpu-baseline, or N > 1: rank 0 times it at N = 1 only)
+        if args.full:
+            out["config"].update({"with_h2d_prefetch": h2d, ("without_wer" if wer_on else "with_wer"): wer_leg})
+            full_report(out, args, dev, cfg, world, events, mfma_events)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -53,11 +53,8 @@ def test_mel_filterbank_equals_oracle_restatement():
     assert np.allclose(mel_filterbank_slaney(), S.slaney_mel_filterbank(), atol=1e-7)
 
 
-def test_reference_config_yaml_parses_with_overrides(tmp_path):
-    ref = "/root/reference/config.yaml"
-    text = open(ref).read() if os.path.exists(ref) else (
-        "batch_size: 16\nlearning_rate: 0.0001\nepochs: 1\ndistributed: true\nmixed_precision: false\n"
-        "model:\n  freeze_encoder_till: 12\ncl_config:\n  e_lambda: 10\n  e_gamma: 1\n  mas_ctx: 0.3\n")
+def test_reference_config_yaml_parses_with_overrides(tmp_path, golden_dir):
+    text = open(os.path.join(golden_dir, "reference_config.yaml")).read()     # the reference's config.yaml, verbatim
     p = tmp_path / "config.yaml"
     p.write_text(text)
     cfg = load_config(str(p))
