@@ -535,8 +535,7 @@ extern "C" int ia_relpos_attention(const void* qkv, const void* pos_proj, const 
     const int njt = (Tp + 63) / 64;
     hipLaunchKernelGGL(attn_vt_kernel, dim3(B * H * njt), dim3(256), 0, st, (const __bf16*)qkv, (__bf16*)vt_scratch, B, T, H, Tp);
     IA_RETURN_IF_LAUNCH_FAILED();
-    const unsigned thr = (unsigned)(dropout_p * 256.f + 0.5f);
-    const float keep_scale = thr > 0 ? 256.f / (256.f - (float)thr) : 1.f;
+    const auto [thr, keep_scale] = ia_dropout_rule(dropout_p);
     const size_t lds = 4 * (size_t)AT_WAVE_LDS;
     IA_SET_MAX_LDS_ONCE((relpos_attn_kernel), (int)lds);
     const int nqt = (T + 63) / 64;
@@ -570,8 +569,7 @@ extern "C" int ia_relpos_attention_bwd(const void* qkv, const void* pos_proj, co
         return IA_INVALID_VALUE;
     int Ts, Rs, pad0;
     ia_relpos_attention_bwd_dims(T, &Ts, &Rs, &pad0);
-    const unsigned thr = (unsigned)(dropout_p * 256.f + 0.5f);
-    const float keep_scale = thr > 0 ? 256.f / (256.f - (float)thr) : 1.f;
+    const auto [thr, keep_scale] = ia_dropout_rule(dropout_p);
     const size_t lds = 4 * (size_t)(16 * AT_LDR + 80) * sizeof(float);
     IA_SET_MAX_LDS_ONCE((relpos_attn_bwd_kernel), (int)lds);
     const int nqt = (T + 63) / 64;

@@ -295,8 +295,8 @@ extern "C" int ia_relpos_attention_flash_lse(const void* qkv, const void* pos_pr
     a.qkv = (const __bf16*)qkv; a.pl = (const __bf16*)pos_proj; a.bias_u = bias_u; a.bias_v = bias_v; a.lens = lens;
     a.lse = lse;
     a.ctx = (__bf16*)ctx; a.B = B; a.T = T; a.H = H; a.dk = dk; a.scale = 1.f / sqrtf((float)dk); a.seed = seed;
-    a.thr = (unsigned)(dropout_p * 256.f + 0.5f);
-    a.keep_scale = a.thr > 0 ? 256.f / (256.f - (float)a.thr) : 1.f;
+    const ia_dropout_t drop = ia_dropout_rule(dropout_p);
+    a.thr = drop.thr; a.keep_scale = drop.keep_scale;
     const int nqt = (T + 63) / 64;
     const int grid = 8 * ((B * H + 7) / 8) * nqt;
     hipStream_t st = (hipStream_t)stream;

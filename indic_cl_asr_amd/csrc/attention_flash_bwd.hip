@@ -642,8 +642,8 @@ extern "C" int ia_relpos_attention_flash_bwd(const void* qkv, const void* pos_pr
     ia_relpos_attention_flash_bwd_dims(T, &rs, &p0);
     a.Rs = rs; a.pad0 = p0;
     a.scale = 1.f / sqrtf((float)dk); a.seed = seed;
-    a.thr = (unsigned)(dropout_p * 256.f + 0.5f);
-    a.keep_scale = a.thr > 0 ? 256.f / (256.f - (float)a.thr) : 1.f;
+    const ia_dropout_t drop = ia_dropout_rule(dropout_p);
+    a.thr = drop.thr; a.keep_scale = drop.keep_scale;
     hipStream_t st = (hipStream_t)stream;
     // band columns outside the processed key tiles (keys beyond the length, rows of padded queries) stay zero
     if (hipMemsetAsync(dBand, 0, (size_t)H * B * T * rs * sizeof(__bf16), st) != hipSuccess) return IA_LAUNCH_FAILED;

@@ -1,4 +1,5 @@
-// Counter-based dropout keep mask shared by the bf16 GEMM epilogue and the Conformer-block backward kernels:
+// Counter-based dropout keep mask shared by the projection GEMMs' epilogue (gemm_common.h) and the Conformer-block backward
+// kernels (threshold and scale: ia_dropout_rule, ia_common.h):
 // 8 consecutive columns [gn, gn+8) of row gm of an [M,N] tensor; bit j set = keep.  Keyed by (seed, gm*N + gn).
 #pragma once
 #include "ia_common.h"

@@ -324,8 +324,7 @@ extern "C" int ia_layernorm_bwd_drop(const float* x, int ldx, const float* dy_f3
         if (lddx != d || lddxh != d) return IA_UNSUPPORTED;
         return ia_scale_dropout_bf16(dx_out, N, d, alpha, dropout_p, seed, dx_bf16, stream);
     }
-    unsigned hthr = (unsigned)(dropout_p * 256.f + 0.5f);
-    const float hks = hthr > 0 ? 256.f / (256.f - (float)hthr) : 1.f;
+    const auto [hthr, hks] = ia_dropout_rule(dropout_p);
     const int G = lnb_blocks(N);
     const dim3 grid(G), blk(256);
     hipStream_t st = (hipStream_t)stream;
@@ -398,14 +397,9 @@ extern "C" int ia_partials_finish_multi(const ia_finish_job* jobs, int count, ia
     return IA_OK;
 }
 
-static inline void drop_params(float p, unsigned* thr, float* ks) {
-    *thr = (unsigned)(p * 256.f + 0.5f);
-    *ks = *thr > 0 ? 256.f / (256.f - (float)*thr) : 1.f;
-}
-
 extern "C" int ia_silu_dropout(const void* h_pre, int64_t M, int N, float dropout_p, unsigned seed, void* out, ia_stream_t stream) {
     if (!h_pre || !out || M <= 0 || N <= 0 || N % 8 != 0 || dropout_p < 0.f || dropout_p >= 1.f) return IA_INVALID_VALUE;
-    unsigned thr; float ks; drop_params(dropout_p, &thr, &ks);
+    const auto [thr, ks] = ia_dropout_rule(dropout_p);
     hipLaunchKernelGGL((silu_dropout_kernel<0>), dim3(ew_grid(M * (N / 8))), dim3(256), 0, (hipStream_t)stream,
                        (const __bf16*)h_pre, (const __bf16*)nullptr, M, N, seed, thr, ks, (__bf16*)out);
     IA_RETURN_IF_LAUNCH_FAILED();
@@ -415,7 +409,7 @@ extern "C" int ia_silu_dropout(const void* h_pre, int64_t M, int N, float dropou
 extern "C" int ia_silu_dropout_bwd(const void* h_pre, const void* dh, int64_t M, int N, float dropout_p, unsigned seed, void* out,
                                    ia_stream_t stream) {
     if (!h_pre || !dh || !out || M <= 0 || N <= 0 || N % 8 != 0 || dropout_p < 0.f || dropout_p >= 1.f) return IA_INVALID_VALUE;
-    unsigned thr; float ks; drop_params(dropout_p, &thr, &ks);
+    const auto [thr, ks] = ia_dropout_rule(dropout_p);
     hipLaunchKernelGGL((silu_dropout_kernel<1>), dim3(ew_grid(M * (N / 8))), dim3(256), 0, (hipStream_t)stream,
                        (const __bf16*)h_pre, (const __bf16*)dh, M, N, seed, thr, ks, (__bf16*)out);
     IA_RETURN_IF_LAUNCH_FAILED();
@@ -425,7 +419,7 @@ extern "C" int ia_silu_dropout_bwd(const void* h_pre, const void* dh, int64_t M,
 extern "C" int ia_scale_dropout_bf16(const float* dy, int64_t M, int N, float alpha, float dropout_p, unsigned seed, void* out,
                                      ia_stream_t stream) {
     if (!dy || !out || M <= 0 || N <= 0 || N % 8 != 0 || dropout_p < 0.f || dropout_p >= 1.f) return IA_INVALID_VALUE;
-    unsigned thr; float ks; drop_params(dropout_p, &thr, &ks);
+    const auto [thr, ks] = ia_dropout_rule(dropout_p);
     hipLaunchKernelGGL(scale_dropout_bf16_kernel, dim3(ew_grid(M * (N / 8))), dim3(256), 0, (hipStream_t)stream, dy, M, N, alpha,
                        seed, thr, ks, (__bf16*)out);
     IA_RETURN_IF_LAUNCH_FAILED();
@@ -542,7 +536,7 @@ extern "C" int ia_glu_bwd(const void* c2, const float* dG, const int64_t* lens, 
 extern "C" int ia_attn_keepmask(int B, int H, int T, float dropout_p, unsigned seed, void* mask_bf16, ia_stream_t stream) {
     if (!mask_bf16 || B <= 0 || H <= 0 || T <= 0 || dropout_p < 0.f || dropout_p >= 1.f) return IA_INVALID_VALUE;
     if ((int64_t)B * H * T * T >= ((int64_t)1 << 32)) return IA_UNSUPPORTED;
-    unsigned thr; float ks; drop_params(dropout_p, &thr, &ks);
+    const auto [thr, ks] = ia_dropout_rule(dropout_p);
     hipLaunchKernelGGL(attn_keepmask_kernel, dim3(ew_grid((int64_t)B * H * T * T)), dim3(256), 0, (hipStream_t)stream, B, H, T, seed,
                        thr, ks, (__bf16*)mask_bf16);
     IA_RETURN_IF_LAUNCH_FAILED();

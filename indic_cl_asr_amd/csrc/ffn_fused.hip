@@ -596,10 +596,9 @@ int ffn_launch(float* x, int N, int d, int d_ff, const float* ln_g, const float*
     FfnArgs a;
     a.x = x; a.N = N; a.ln_g = ln_g; a.ln_b = ln_b; a.eps = eps;
     a.W1 = (const __bf16*)W1; a.b1 = b1; a.W2 = (const __bf16*)W2; a.b2 = b2; a.dff = d_ff; a.alpha = alpha;
-    a.thr_ff = (unsigned)(p_ff * 256.f + 0.5f); a.seed_ff = seed_ff;
-    a.ks_ff = a.thr_ff > 0 ? 256.f / (256.f - (float)a.thr_ff) : 1.f;
-    a.thr_res = (unsigned)(p_res * 256.f + 0.5f); a.seed_res = seed_res;
-    a.ks_res = a.thr_res > 0 ? 256.f / (256.f - (float)a.thr_res) : 1.f;
+    const ia_dropout_t drop_ff = ia_dropout_rule(p_ff), drop_res = ia_dropout_rule(p_res);
+    a.thr_ff = drop_ff.thr; a.ks_ff = drop_ff.keep_scale; a.seed_ff = seed_ff;
+    a.thr_res = drop_res.thr; a.ks_res = drop_res.keep_scale; a.seed_res = seed_res;
     if (ln2_to_y_only && (!ln2_g || (!y_out && !Wt))) return IA_INVALID_VALUE;
     a.ln2_g = ln2_g; a.ln2_b = ln2_b; a.y_out = (__bf16*)y_out; a.ln2_y_only = ln2_to_y_only ? 1 : 0;
     a.Wt = (const __bf16*)Wt; a.bt = bt; a.t_out = (__bf16*)t_out; a.nt = nt;

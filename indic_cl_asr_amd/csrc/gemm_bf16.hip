@@ -4,9 +4,10 @@
 //
 // A and W are both K-contiguous (activations row-major, nn.Linear weight layout), so A and B MFMA fragments are
 // 16-byte ds_read_b128 from 144-byte padded LDS rows (conflict-free).  Workgroup = 4 waves (2x2), tile BM x BN x 64,
-// one LDS stage with the next k-tile prefetched in registers (37 KB per workgroup).  The epilogue goes through LDS so that bias / SiLU / dropout / scaling / fp32
-// residual add / dual fp32+bf16 output are done row-major with 16-byte coalesced accesses -- this is what removes the
-// ~40 separate elementwise launches per Conformer layer of the ATen composition.
+// one LDS stage with the next k-tile prefetched in registers (37 KB per workgroup).  The epilogue (gemm_common.h, shared with the
+// other projection GEMMs) goes through LDS so that bias / SiLU / dropout / scaling / fp32 residual add / dual fp32+bf16 output
+// are done row-major with 16-byte coalesced accesses -- this is what removes the ~40 separate elementwise launches per
+// Conformer layer of the ATen composition.
 // Replaces nn.Linear + the elementwise ops around it in ConformerFeedForward (A/parts/submodules/conformer_modules.py
 // :385-404), the Q/K/V/out projections (multi_head_attention.py:69-96,117-119), pointwise convs (:340-366) and the
 // residual updates of ConformerLayer.forward (:141-214).
@@ -14,7 +15,7 @@
 
 #include <stdlib.h>
 
-#include "gemm_args.h"
+#include "gemm_common.h"
 
 // gemm_big.hip: 256 x 256 tiles for the large shapes
 int ia_gemm_big_wanted(int M, int N, int K, int lda, int ldw, int act);
@@ -23,28 +24,10 @@ int ia_gemm_big_launch(const void* gemm_args, hipStream_t st);
 namespace {
 
 typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 constexpr int G_BK = 64;
 constexpr int G_ROWB = G_BK * 2 + 16;  // LDS bytes per tile row (padded)
-constexpr int G_THREADS = 256;
-
-
-// sum over the 32 lanes of a half wave (as csrc/ffn_fused.hip): every lane of the half wave gets the total
-__device__ __forceinline__ float gemm_half_wave_sum(float v) {
-    v += IA_DPP_F(0.f, v, 0xB1, 0xF);    // quad_perm xor 1
-    v += IA_DPP_F(0.f, v, 0x4E, 0xF);    // quad_perm xor 2
-    v += IA_DPP_F(0.f, v, 0x141, 0xF);   // row_half_mirror
-    v += IA_DPP_F(0.f, v, 0x140, 0xF);   // row_mirror
-    v += __shfl_xor(v, 16, 64);
-    return v;
-}
-
-__device__ __forceinline__ unsigned g_hash32(unsigned x) {
-    x ^= x >> 16; x *= 0x85ebca6bu; x ^= x >> 13; x *= 0xc2b2ae35u; x ^= x >> 16;
-    return x;
-}
-
+constexpr int G_THREADS = GEMM_THREADS;
 struct ConvRow { int b, t2, f2; };  // output pixel of a tile row (t2 < 0: row past M)
 
 __device__ __forceinline__ uint4 conv_a_load(const GemmArgs& a, const ConvRow& r, int k0, int kv) {
@@ -58,112 +41,18 @@ __device__ __forceinline__ uint4 conv_a_load(const GemmArgs& a, const ConvRow& r
     return *reinterpret_cast<const uint4*>(a.A + (((size_t)r.b * a.cT1 + t1) * a.cF1 + f1) * a.cC + c0);
 }
 
-// The tile epilogue shared by the projection kernels of this file: accumulators -> LDS (fp32, row-major, EP_ROWS tile rows per
-// pass) -> row-major elementwise pass with 16-byte accesses (GLU / LayerNorm variants included).  Called by ALL threads of the
-// workgroup once the stages in `smem` are free; acc = the 2 x 2 waves' [TI][TJ] 16x16 accumulator tiles.
-template <int BM, int BN>
-__device__ __forceinline__ void gemm_tile_epilogue(const GemmArgs& a, f4 (&acc)[BM / 32][BN / 32], unsigned char* smem, int m0, int n0) {
-    constexpr int WM = BM / 2, WN = BN / 2, TI = WM / 16, TJ = WN / 16;
-    constexpr int LDC = BN + 4;
-    constexpr int EP_ROWS = (BN == 256) ? 32 : ((BM == 96) ? 48 : 64);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int c = lane & 15, q = lane >> 4;
-    const int wm = wave >> 1, wn = wave & 1;
-    // ---- epilogue: accumulators -> LDS (fp32, row-major, EP_ROWS tile rows per pass) -> row-major elementwise pass with
-    // 16-byte accesses.  One LDS stage + a 64-row epilogue tile keep the workgroup at 37 KB: four workgroups per CU.
-    float* sc = reinterpret_cast<float*>(smem);
-    constexpr int VEC_PER_ROW = BN / 8;
-    for (int pass = 0; pass < BM / EP_ROWS; ++pass) {
-    if (pass > 0) __syncthreads();
-    if ((wm * WM) / EP_ROWS == pass) {
-#pragma unroll
-        for (int i = 0; i < TI; ++i)
-#pragma unroll
-            for (int j = 0; j < TJ; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    sc[(wm * WM - pass * EP_ROWS + i * 16 + q * 4 + r) * LDC + wn * WN + j * 16 + c] = acc[i][j][r];
-    }
-    __syncthreads();
-    if (a.act == 4) {
-        // GLU over the tile's column halves (weight rows regrouped by the caller: columns [0,64) of a 128-column tile are value
-        // channels, [64,128) their gates): out[gm][n0/2 + c] = (v + b) * sigmoid(g + b'), bf16, N/2 columns wide.  Thread = 4
-        // channels of one row: float4 reads of both halves, one 8-byte store, every thread busy.
-        if constexpr (BN == 128) {
-            for (int it = tid; it < EP_ROWS * 16; it += G_THREADS) {
-                const int row = it >> 4, cg = it & 15;
-                const int gm = m0 + pass * EP_ROWS + row, gc = n0 + cg * 4;
-                if (gm >= a.M) continue;
-                float4 vv = *reinterpret_cast<const float4*>(sc + row * LDC + cg * 4);
-                float4 gg = *reinterpret_cast<const float4*>(sc + row * LDC + 64 + cg * 4);
-                if (a.bias) {
-                    const float4 bv = *reinterpret_cast<const float4*>(a.bias + gc), bg = *reinterpret_cast<const float4*>(a.bias + gc + 64);
-                    vv.x += bv.x; vv.y += bv.y; vv.z += bv.z; vv.w += bv.w;
-                    gg.x += bg.x; gg.y += bg.y; gg.z += bg.z; gg.w += bg.w;
-                }
-                union { uint2 u; __bf16 h[4]; } o;
-                o.h[0] = (__bf16)(vv.x * ia_sigmoid_fast(gg.x)); o.h[1] = (__bf16)(vv.y * ia_sigmoid_fast(gg.y));
-                o.h[2] = (__bf16)(vv.z * ia_sigmoid_fast(gg.z)); o.h[3] = (__bf16)(vv.w * ia_sigmoid_fast(gg.w));
-                *reinterpret_cast<uint2*>(a.outH + (size_t)gm * a.ldoh + (n0 >> 1) + cg * 4) = o.u;
-            }
-        }
-        continue;   // next epilogue pass
-    }
-    for (int it = tid; it < EP_ROWS * VEC_PER_ROW; it += G_THREADS) {
-        const int row = it / VEC_PER_ROW, cv = it - row * VEC_PER_ROW;
-        const int gm = m0 + pass * EP_ROWS + row, gn = n0 + cv * 8;
-        if (gm >= a.M || gn >= a.N) continue;
-        float v[8];
-        const float4 x0 = *reinterpret_cast<const float4*>(sc + row * LDC + cv * 8);
-        const float4 x1 = *reinterpret_cast<const float4*>(sc + row * LDC + cv * 8 + 4);
-        v[0] = x0.x; v[1] = x0.y; v[2] = x0.z; v[3] = x0.w; v[4] = x1.x; v[5] = x1.y; v[6] = x1.z; v[7] = x1.w;
-        gemm_epilogue8(a, gm, gn, v);
-        if constexpr (BN == 256) {
-            // LayerNorm of the finished row: its 256 columns are the 32 lanes of this half wave (8 columns each; rows beyond M
-            // skip the whole half wave above), two DPP / shuffle reductions, bf16 store of the normalised row
-            if (a.ln_g) {
-                float s1 = 0.f;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) s1 += v[j];
-                const float mean = gemm_half_wave_sum(s1) * (1.f / 256.f);
-                float s2 = 0.f;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) { v[j] -= mean; s2 += v[j] * v[j]; }
-                const float rstd = rsqrtf(gemm_half_wave_sum(s2) * (1.f / 256.f) + a.ln_eps);
-                const float4 g0 = *reinterpret_cast<const float4*>(a.ln_g + gn), g1 = *reinterpret_cast<const float4*>(a.ln_g + gn + 4);
-                const float4 c0 = *reinterpret_cast<const float4*>(a.ln_b + gn), c1 = *reinterpret_cast<const float4*>(a.ln_b + gn + 4);
-                const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
-                const float bb[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
-                union { uint4 u; __bf16 h[8]; } o;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) o.h[j] = (__bf16)(v[j] * rstd * gg[j] + bb[j]);
-                *reinterpret_cast<uint4*>(a.outH + (size_t)gm * a.ldoh + gn) = o.u;
-            }
-        }
-    }
-    }
-}
-
 template <int BM, int BN, bool CONV = false>
 __global__ __launch_bounds__(G_THREADS, (BN == 256 ? 2 : (BM == 128 ? 3 : 4))) void gemm_bf16_nt_kernel(GemmArgs a) {
     static_assert(BM == 64 || BM == 96 || BM == 128, "row tiles of 64, 96 or 128");
     constexpr int WM = BM / 2, WN = BN / 2, TI = WM / 16, TJ = WN / 16;
     constexpr int A_BYTES = BM * G_ROWB;
     constexpr int AV = BM * 8 / G_THREADS, BV = BN * 8 / G_THREADS;  // 16-byte vectors per thread per stage
-    constexpr int EP_ROWS = (BN == 256) ? 32 : ((BM == 96) ? 48 : 64); // tile rows per epilogue pass through LDS
-    static_assert(BM % EP_ROWS == 0 && (EP_ROWS % WM == 0 || WM % EP_ROWS == 0), "epilogue passes cover whole wave rows");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 15, q = lane >> 4;
     const int wm = wave >> 1, wn = wave & 1;
-    // XCD-aware tile order: workgroup ids go round-robin over the 8 XCDs, so the ntn column tiles that share one row
-    // tile of A are given ids congruent mod 8 and consecutive in that XCD's dispatch order -- the A tile is then fetched
-    // into ONE XCD's L2 once instead of into all eight (W is small and lives in every L2).
-    const int ntn = (a.N + BN - 1) / BN;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int mt = xcd + 8 * (slot / ntn);
-    if (mt * BM >= a.M) return;  // padding workgroups of the last group of 8 row tiles (uniform)
-    const int m0 = mt * BM, n0 = (slot % ntn) * BN;
+    int m0, n0;
+    if (!gemm_xcd_tile<BM, BN>(a.M, a.N, m0, n0)) return;
 
     static_assert((BV == 4 || BV == 8) && (AV == 2 || AV == 3 || AV == 4), "staging registers are named (arrays end up in scratch)");
     ConvRow crow[4];
@@ -286,11 +175,8 @@ __global__ __launch_bounds__(G_THREADS, 2) void gemm_bf16_nt_dma_kernel(GemmArgs
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int c = lane & 15, q = lane >> 4;
     const int wm = wave >> 1, wn = wave & 1;
-    const int ntn = (a.N + BN - 1) / BN;
-    const int xcd = blockIdx.x & 7, slot_id = blockIdx.x >> 3;
-    const int mt = xcd + 8 * (slot_id / ntn);
-    if (mt * BM >= a.M) return;
-    const int m0 = mt * BM, n0 = (slot_id % ntn) * BN;
+    int m0, n0;
+    if (!gemm_xcd_tile<BM, BN>(a.M, a.N, m0, n0)) return;
 
     // one LDS-DMA instruction = 8 rows x 8 chunks of 16 B, lane l at position l: lane l fetches row 8 blk + (l >> 3), logical
     // chunk (l & 7) ^ (l >> 3).  Wave w issues A blocks 2 w, 2 w + 1 and B blocks 4 w .. 4 w + 3.  Rows past M / N: clamped.
@@ -402,10 +288,9 @@ __global__ __launch_bounds__(G_THREADS, 2) void gemm_bf16_nt_dma_kernel(GemmArgs
 
 template <int BM, int BN, bool CONV = false>
 int launch_gemm(const GemmArgs& a, hipStream_t st) {
-    constexpr int STAGE = (BM + BN) * G_ROWB, EPI = (BN == 256 ? 32 : (BM == 96 ? 48 : 64)) * (BN + 4) * 4;
+    constexpr int STAGE = (BM + BN) * G_ROWB, EPI = gemm_epi_bytes(BM, BN);
     const size_t lds = STAGE > EPI ? STAGE : EPI;
-    const int ntm = (a.M + BM - 1) / BM, ntn = (a.N + BN - 1) / BN;
-    const int grid = 8 * ((ntm + 7) / 8) * ntn;  // row tiles padded to a multiple of the 8 XCDs (see the kernel's tile order)
+    const int grid = gemm_xcd_grid(a.M, a.N, BM, BN);
     if (lds > 64 * 1024 &&
         hipFuncSetAttribute((const void*)gemm_bf16_nt_kernel<BM, BN, CONV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return IA_LAUNCH_FAILED;
@@ -435,27 +320,17 @@ extern "C" int ia_gemm_bf16_ex2(const void* A, int lda, const void* W, int ldw, 
                                 int act, float dropout_p, unsigned seed, float alpha, const float* R, int ldr, float* outF,
                                 int ldof, void* outH, int ldoh, void* outPre, int ldpre, const void* aux, int ldaux, int flags,
                                 ia_stream_t stream) {
-    if (!A || !W || (!outF && !outH) || M <= 0 || N <= 0 || K <= 0) return IA_INVALID_VALUE;
-    if ((act == 3) != (aux != nullptr)) return IA_INVALID_VALUE;
-    if ((outPre && (ldpre % 8 != 0 || !ia_is_aligned(outPre, 16))) || (aux && (ldaux % 8 != 0 || !ia_is_aligned(aux, 16)))) return IA_UNSUPPORTED;
-    if (K % 8 != 0 || N % 8 != 0 || lda % 8 != 0 || ldw % 8 != 0) return IA_UNSUPPORTED;
-    if ((R && ldr % 4 != 0) || (outF && ldof % 4 != 0) || (outH && ldoh % 8 != 0)) return IA_UNSUPPORTED;
-    if (!ia_is_aligned(A, 16) || !ia_is_aligned(W, 16) || (bias && !ia_is_aligned(bias, 16)) || (R && !ia_is_aligned(R, 16)) ||
-        (outF && !ia_is_aligned(outF, 16)) || (outH && !ia_is_aligned(outH, 16)))
-        return IA_INVALID_VALUE;
-    if (act < 0 || act > 4 || dropout_p < 0.f || dropout_p >= 1.f) return IA_INVALID_VALUE;
+    if (N <= 0 || K <= 0 || (act == 3) != (aux != nullptr)) return IA_INVALID_VALUE;
+    const bool unsupported = (outPre && (ldpre % 8 != 0 || !ia_is_aligned(outPre, 16))) || (aux && (ldaux % 8 != 0 || !ia_is_aligned(aux, 16))) ||
+                             K % 8 != 0 || lda % 8 != 0 || ldw % 8 != 0;
+    GemmArgs a = {};
+    if (const int rc = gemm_check_and_fill(a, A, W, unsupported, M, N, bias, act, dropout_p, seed, alpha, R, ldr, outF, ldof, outH, ldoh)) return rc;
+    if (act < 0 || act > 4) return IA_INVALID_VALUE;
     if (act == 4 && (N % 128 != 0 || !outH || outF || R || outPre || dropout_p != 0.f || alpha != 1.f || ldoh < N / 2)) return IA_INVALID_VALUE;
-    GemmArgs a;
-    a.A = (const __bf16*)A; a.W = (const __bf16*)W; a.bias = bias; a.R = R; a.outF = outF; a.outH = (__bf16*)outH;
+    a.A = (const __bf16*)A; a.W = (const __bf16*)W; a.K = K; a.lda = lda; a.ldw = ldw;
     a.outPre = (__bf16*)outPre; a.aux = (const __bf16*)aux; a.ldpre = ldpre; a.ldaux = ldaux;
-    a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldw = ldw; a.ldr = ldr; a.ldof = ldof; a.ldoh = ldoh;
-    a.act = act; a.alpha = alpha; a.seed = seed;
     a.out_f16 = (flags & 1) ? 1 : 0;
     if (a.out_f16 && act == 4) return IA_INVALID_VALUE;
-    a.thr = (unsigned)(dropout_p * 256.f + 0.5f);
-    a.keep_scale = a.thr > 0 ? 256.f / (256.f - (float)a.thr) : 1.f;
-    a.cT1 = a.cF1 = a.cC = a.cT2 = a.cF2 = 0;
-    a.ln_g = a.ln_b = nullptr; a.ln_eps = 0.f;
     hipStream_t st = (hipStream_t)stream;
     // Row-tile choice (128, 96 or 64 rows x 128 columns).  The result does not depend on it: every output element sums its
     // k-steps in the same order.  In isolation the tile sizes are within ~10 % of each other at the encoder's shapes
@@ -482,9 +357,8 @@ extern "C" int ia_gemm_bf16_ex2(const void* A, int lda, const void* W, int ldw, 
         const bool no_dma = e_dma && e_dma[0] == '0';
         if (!no_dma) {
             constexpr int LDS = GD_STAGES * (64 + 128) * 128;
-            const int ntm = (M + 63) / 64, ntn2 = (N + 127) / 128;
             IA_SET_MAX_LDS_ONCE((gemm_bf16_nt_dma_kernel<64, 128>), LDS);
-            hipLaunchKernelGGL((gemm_bf16_nt_dma_kernel<64, 128>), dim3(8 * ((ntm + 7) / 8) * ntn2), dim3(G_THREADS), LDS, st, a);
+            hipLaunchKernelGGL((gemm_bf16_nt_dma_kernel<64, 128>), dim3(gemm_xcd_grid(M, N, 64, 128)), dim3(G_THREADS), LDS, st, a);
             IA_RETURN_IF_LAUNCH_FAILED();
             return IA_OK;
         }
@@ -504,20 +378,12 @@ extern "C" int ia_gemm_bf16_ln_supported(int N, int K) { return (N == 256 && K %
 extern "C" int ia_gemm_bf16_ln(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const float* bias, float dropout_p,
                                unsigned seed, float alpha, const float* R, int ldr, float* outF, int ldof, const float* ln_g,
                                const float* ln_b, float ln_eps, void* outH, int ldoh, ia_stream_t stream) {
-    if (!A || !W || !outF || !outH || !ln_g || !ln_b || M <= 0) return IA_INVALID_VALUE;
-    if (!ia_gemm_bf16_ln_supported(N, K) || lda % 8 != 0 || ldw % 8 != 0 || (R && ldr % 4 != 0) || ldof % 4 != 0 || ldoh % 8 != 0) return IA_UNSUPPORTED;
-    if (!ia_is_aligned(A, 16) || !ia_is_aligned(W, 16) || (bias && !ia_is_aligned(bias, 16)) || (R && !ia_is_aligned(R, 16)) ||
-        !ia_is_aligned(outF, 16) || !ia_is_aligned(outH, 16) || !ia_is_aligned(ln_g, 16) || !ia_is_aligned(ln_b, 16) ||
-        dropout_p < 0.f || dropout_p >= 1.f)
-        return IA_INVALID_VALUE;
-    GemmArgs a;
-    a.A = (const __bf16*)A; a.W = (const __bf16*)W; a.bias = bias; a.R = R; a.outF = outF; a.outH = (__bf16*)outH;
-    a.outPre = nullptr; a.aux = nullptr; a.ldpre = 0; a.ldaux = 0;
-    a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldw = ldw; a.ldr = ldr; a.ldof = ldof; a.ldoh = ldoh;
-    a.act = 0; a.alpha = alpha; a.seed = seed; a.out_f16 = 0;
-    a.thr = (unsigned)(dropout_p * 256.f + 0.5f);
-    a.keep_scale = a.thr > 0 ? 256.f / (256.f - (float)a.thr) : 1.f;
-    a.cT1 = a.cF1 = a.cC = a.cT2 = a.cF2 = 0;
+    if (!outF || !outH || !ln_g || !ln_b) return IA_INVALID_VALUE;
+    const bool unsupported = !ia_gemm_bf16_ln_supported(N, K) || lda % 8 != 0 || ldw % 8 != 0;
+    GemmArgs a = {};
+    if (const int rc = gemm_check_and_fill(a, A, W, unsupported, M, N, bias, 0, dropout_p, seed, alpha, R, ldr, outF, ldof, outH, ldoh)) return rc;
+    if (!ia_is_aligned(ln_g, 16) || !ia_is_aligned(ln_b, 16)) return IA_INVALID_VALUE;
+    a.A = (const __bf16*)A; a.W = (const __bf16*)W; a.K = K; a.lda = lda; a.ldw = ldw;
     a.ln_g = ln_g; a.ln_b = ln_b; a.ln_eps = ln_eps;
     return launch_gemm<64, 256>(a, (hipStream_t)stream);
 }
@@ -600,13 +466,11 @@ extern "C" int ia_subsample_conv2(const void* in_cl, int B, int T1, int F1, int 
     if (!in_cl || !w2r || !b2 || !out || B <= 0 || T1 <= 0 || F1 <= 0) return IA_INVALID_VALUE;
     if (C % 8 != 0 || N % 8 != 0 || !ia_is_aligned(in_cl, 16) || !ia_is_aligned(w2r, 16) || !ia_is_aligned(out, 16))
         return IA_UNSUPPORTED;
-    GemmArgs a;
-    a.A = (const __bf16*)in_cl; a.W = (const __bf16*)w2r; a.bias = b2; a.R = nullptr; a.outF = nullptr; a.outH = (__bf16*)out;
-    a.outPre = nullptr; a.aux = nullptr; a.ldpre = 0; a.ldaux = 0;
+    GemmArgs a = {};
+    a.A = (const __bf16*)in_cl; a.W = (const __bf16*)w2r; a.bias = b2; a.outH = (__bf16*)out;
     a.cT1 = T1; a.cF1 = F1; a.cC = C; a.cT2 = (T1 - 1) / 2 + 1; a.cF2 = (F1 - 1) / 2 + 1;
-    a.M = B * a.cT2 * a.cF2; a.N = N; a.K = 9 * C; a.lda = 0; a.ldw = 9 * C; a.ldr = 0; a.ldof = 0; a.ldoh = N;
-    a.act = 2; a.alpha = 1.f; a.seed = 0; a.thr = 0; a.keep_scale = 1.f; a.out_f16 = 0;
-    a.ln_g = a.ln_b = nullptr; a.ln_eps = 0.f;
+    a.M = B * a.cT2 * a.cF2; a.N = N; a.K = 9 * C; a.ldw = 9 * C; a.ldoh = N;
+    a.act = 2; a.alpha = 1.f; a.keep_scale = 1.f;
     {   // K-pipelined LDS-DMA variant (C % 64 == 0), opt-in with IA_CONV_DMA=1: bit-identical, and measured at the SAME step
         // time as the register-staged 128 x 128 kernel below (8.36 / 8.38 against 8.36 / 8.32 ms): its 64-row tiles read the
         // weight fragments twice as often, which costs what the pipelining gains
@@ -614,9 +478,8 @@ extern "C" int ia_subsample_conv2(const void* in_cl, int B, int T1, int F1, int 
         const bool dma = (e && e[0] == '1') && C % G_BK == 0 && (long long)B * T1 * F1 * C * 2 < (1ll << 31) && (long long)N * 9 * C * 2 < (1ll << 32);
         if (dma) {
             constexpr int LDS = GD_STAGES * (64 + 128) * 128;
-            const int ntm = (a.M + 63) / 64, ntn2 = (N + 127) / 128;
             IA_SET_MAX_LDS_ONCE((gemm_bf16_nt_dma_kernel<64, 128, true>), LDS);
-            hipLaunchKernelGGL((gemm_bf16_nt_dma_kernel<64, 128, true>), dim3(8 * ((ntm + 7) / 8) * ntn2), dim3(G_THREADS), LDS,
+            hipLaunchKernelGGL((gemm_bf16_nt_dma_kernel<64, 128, true>), dim3(gemm_xcd_grid(a.M, N, 64, 128)), dim3(G_THREADS), LDS,
                                (hipStream_t)stream, a);
             IA_RETURN_IF_LAUNCH_FAILED();
             return IA_OK;

@@ -1,5 +1,6 @@
-// Large-shape variant of the bf16 projection GEMM for gfx950:   out = epilogue(A[M,K] @ W[N,K]^T)   (same arguments and
-// epilogue as gemm_bf16.hip; chosen by ia_gemm_bf16_ex2 when the problem has enough 256 x 256 tiles).
+// Large-shape variant of the bf16 projection GEMM for gfx950:   out = epilogue(A[M,K] @ W[N,K]^T)   (GemmArgs, per-vector
+// epilogue and tile order of gemm_common.h, as gemm_bf16.hip; chosen by ia_gemm_bf16_ex2 when the problem has enough 256 x 256
+// tiles).
 //
 // gemm_bf16_nt_kernel gives every wave a 64 x 64 output tile on 16x16x32 MFMAs: per 32-deep k-step a wave reads 8 KB of
 // fragments for 16 matrix instructions of 16 cycles -- 32 B per clock and wave, the CU's whole LDS bandwidth at the matrix
@@ -21,7 +22,7 @@
 
 #include <stdlib.h>
 
-#include "gemm_args.h"
+#include "gemm_common.h"
 
 namespace {
 
@@ -30,25 +31,20 @@ typedef float f16v __attribute__((ext_vector_type(16)));
 
 constexpr int GB_T = 256;                   // tile rows and columns
 constexpr int GB_BK = 64;                   // k per stage
-constexpr int GB_THREADS = 256;
 constexpr int GB_TILE = GB_T * GB_BK * 2;   // 32 KB per operand per stage
 constexpr int GB_STAGE = 2 * GB_TILE;       // 64 KB
 constexpr int GB_LDC = 132;                 // floats per row of the epilogue block (128 + 4: conflict-free 16-byte column writes)
 constexpr int GB_EPI = 64 * GB_LDC * 4;     // 33 792 B per wave and pass
 constexpr int GB_LDS = 2 * GB_STAGE > 4 * GB_EPI ? 2 * GB_STAGE : 4 * GB_EPI;   // 135 168 B
 
-__global__ __launch_bounds__(GB_THREADS, 1) void gemm_big_kernel(GemmArgs a) {
+__global__ __launch_bounds__(GEMM_THREADS, 1) void gemm_big_kernel(GemmArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hh = lane >> 5;
     const int wm = wave >> 1, wn = wave & 1;
-    // XCD-aware tile order (as gemm_bf16_nt_kernel): the column tiles that share a row tile of A run on one XCD
-    const int ntn = a.N / GB_T;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int mt = xcd + 8 * (slot / ntn);
-    if (mt * GB_T >= a.M) return;   // padding workgroups of the last group of 8 row tiles (uniform)
-    const int m0 = mt * GB_T, n0 = (slot % ntn) * GB_T;
+    int m0, n0;
+    if (!gemm_xcd_tile<GB_T, GB_T>(a.M, a.N, m0, n0)) return;
 
     // ---- stage loader.  One LDS-DMA instruction moves 1 KB = 8 rows x 8 chunks with lane l at position l: lane l fetches,
     // for row 8 blk + (l >> 3), the chunk that belongs at position l & 7, i.e. logical chunk (l & 7) ^ (l >> 3).  Wave w
@@ -217,14 +213,12 @@ int ia_gemm_big_wanted(int M, int N, int K, int lda, int ldw, int act) {
     return (K >= 1024 && tiles >= 512) ? 1 : 0;
 }
 
-// `args` = the caller's GemmArgs (gemm_args.h: the same struct on both sides; passed as an untyped pointer because the type
+// `args` = the caller's GemmArgs (gemm_common.h: the same struct on both sides; passed as an untyped pointer because the type
 // lives in each translation unit's anonymous namespace)
 int ia_gemm_big_launch(const void* args, hipStream_t st) {
     const GemmArgs& a = *static_cast<const GemmArgs*>(args);
-    const int ntm = (a.M + GB_T - 1) / GB_T, ntn = a.N / GB_T;
-    const int grid = 8 * ((ntm + 7) / 8) * ntn;
     IA_SET_MAX_LDS_ONCE(gemm_big_kernel, GB_LDS);
-    hipLaunchKernelGGL(gemm_big_kernel, dim3(grid), dim3(GB_THREADS), GB_LDS, st, a);
+    hipLaunchKernelGGL(gemm_big_kernel, dim3(gemm_xcd_grid(a.M, a.N, GB_T, GB_T)), dim3(GEMM_THREADS), GB_LDS, st, a);
     IA_RETURN_IF_LAUNCH_FAILED();
     return IA_OK;
 }

@@ -7,37 +7,32 @@
 // ConformerLayer.forward, A/parts/submodules/conformer_modules.py:354-366,182-186).  z is the fp32 output of the depthwise
 // convolution; every workgroup derives the per-channel scale / shift from the batch sums (train mode) or the running
 // statistics (eval) exactly as ia_bn_silu does, rounds SiLU(BN(z)) to bf16 on its way into LDS, and runs the same
-// 16x16x32 bf16 MFMA loop and row-major epilogue as csrc/gemm_bf16.hip -- the result is bit-identical to ia_bn_silu followed
-// by ia_gemm_bf16 (same rounding points, same k order, same dropout mask), but the [M,K] bf16 tensor between them and one
-// launch per block (>= 5 us of stream time however little it does) are gone.  Train-mode running statistics are updated
-// by workgroup 0.  Workgroup = 64 rows x 128 columns, 4 waves (2 x 2), k-tiles of 64, one LDS stage + register prefetch.
+// 16x16x32 bf16 MFMA loop as csrc/gemm_bf16.hip and the tile epilogue both share (gemm_common.h) -- the result is bit-identical
+// to ia_bn_silu followed by ia_gemm_bf16 (same rounding points, same k order, same dropout mask), but the [M,K] bf16 tensor
+// between them and one launch per block (>= 5 us of stream time however little it does) are gone.  Train-mode running
+// statistics are updated by workgroup 0.  Workgroup = 64 rows x 128 columns, 4 waves (2 x 2), k-tiles of 64, one LDS stage +
+// register prefetch.
 #include <hip/hip_bf16.h>
 
-#include "ia_common.h"
-#include "dropout_mask.h"
+#include "gemm_common.h"
 
 namespace {
 
 typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 constexpr int BS_BM = 64, BS_BN = 128, BS_BK = 64;
 constexpr int BS_ROWB = BS_BK * 2 + 16;   // LDS bytes per tile row (padded: conflict-free 16-byte fragment reads)
-constexpr int BS_THREADS = 256;
-constexpr int BS_LDC = BS_BN + 4;         // fp32 epilogue row stride
+constexpr int BS_THREADS = GEMM_THREADS;
 constexpr int BS_MAIN = (BS_BM + BS_BN) * BS_ROWB;          // 27 648 B
-constexpr int BS_EPI = BS_BM * BS_LDC * 4;                  // 33 792 B
+constexpr int BS_EPI = gemm_epi_bytes(BS_BM, BS_BN);        // 33 792 B
 constexpr int BS_REGION = BS_EPI > BS_MAIN ? BS_EPI : BS_MAIN;
 
-struct BsArgs {
+struct BsArgs : GemmEpi {
     const float* z; int ldz;
     const float* bn_sum; const float* bn_sumsq; const long long* fixed; const float* gamma; const float* beta;
     float* rm; float* rv; int64_t* nbt; float momentum, eps; int training; int64_t n_rows;
-    const __bf16* W; int ldw; const float* bias; const float* R; int ldr;
-    float* outF; int ldof; __bf16* outH; int ldoh;
+    const __bf16* W; int ldw, K;
     __bf16* outA; int ldoa;   // optional: SiLU(BN(z)) itself, bf16 [M,K] (kept for a backward), written by the first column tile
-    int M, N, K;
-    float alpha; unsigned seed, thr; float keep_scale;
 };
 
 template <bool KEEP>   // KEEP: also write SiLU(BN(z)) to a.outA (first column tile)
@@ -75,12 +70,8 @@ __global__ __launch_bounds__(BS_THREADS, 4) void gemm_bnsilu_kernel(BsArgs a) {
             }
         }
     }
-    // XCD-aware tile order (as gemm_bf16_nt_kernel): the column tiles of one row tile get ids congruent mod 8
-    const int ntn = (a.N + BS_BN - 1) / BS_BN;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int mt = xcd + 8 * (slot / ntn);
-    if (mt * BS_BM >= a.M) return;   // padding workgroups (uniform; after the running-statistics update of workgroup 0, mt = 0)
-    const int m0 = mt * BS_BM, n0 = (slot % ntn) * BS_BN;
+    int m0, n0;   // (padding workgroups leave after the running-statistics update of workgroup 0, which is row tile 0)
+    if (!gemm_xcd_tile<BS_BM, BS_BN>(a.M, a.N, m0, n0)) return;
 
     // ---- staging: A = 64 rows x 64 k fp32 (4 float4 per thread), W = 128 rows x 64 k bf16 (4 uint4 per thread)
     float4 fa0, fa1, fa2, fa3;
@@ -177,55 +168,7 @@ __global__ __launch_bounds__(BS_THREADS, 4) void gemm_bnsilu_kernel(BsArgs a) {
 #undef BS_STB
 #undef BS_STORE
 
-    // ---- epilogue through LDS (fp32, row-major), 16-byte accesses: bias, dropout, alpha, residual, fp32 / bf16 outputs
-    float* sc = reinterpret_cast<float*>(smem);
-#pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int j = 0; j < TJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                sc[(wm * WM + i * 16 + q * 4 + r) * BS_LDC + wn * WN + j * 16 + c] = acc[i][j][r];
-    __syncthreads();
-    constexpr int VEC_PER_ROW = BS_BN / 8;
-    for (int it = tid; it < BS_BM * VEC_PER_ROW; it += BS_THREADS) {
-        const int row = it / VEC_PER_ROW, cv = it - row * VEC_PER_ROW;
-        const int gm = m0 + row, gn = n0 + cv * 8;
-        if (gm >= a.M || gn >= a.N) continue;
-        float v[8];
-        const float4 x0 = *reinterpret_cast<const float4*>(sc + row * BS_LDC + cv * 8);
-        const float4 x1 = *reinterpret_cast<const float4*>(sc + row * BS_LDC + cv * 8 + 4);
-        v[0] = x0.x; v[1] = x0.y; v[2] = x0.z; v[3] = x0.w; v[4] = x1.x; v[5] = x1.y; v[6] = x1.z; v[7] = x1.w;
-        if (a.bias) {
-            const float4 b0 = *reinterpret_cast<const float4*>(a.bias + gn), b1 = *reinterpret_cast<const float4*>(a.bias + gn + 4);
-            v[0] += b0.x; v[1] += b0.y; v[2] += b0.z; v[3] += b0.w; v[4] += b1.x; v[5] += b1.y; v[6] += b1.z; v[7] += b1.w;
-        }
-        float sc_all = a.alpha;
-        if (a.thr > 0) {
-            const unsigned m = ia_keep8(a.seed, (unsigned)gm, (unsigned)a.N, (unsigned)gn, a.thr);
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (!((m >> j) & 1u)) v[j] = 0.f;
-            sc_all *= a.keep_scale;
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] *= sc_all;
-        if (a.R) {
-            const float4 r0 = *reinterpret_cast<const float4*>(a.R + (size_t)gm * a.ldr + gn);
-            const float4 r1 = *reinterpret_cast<const float4*>(a.R + (size_t)gm * a.ldr + gn + 4);
-            v[0] += r0.x; v[1] += r0.y; v[2] += r0.z; v[3] += r0.w; v[4] += r1.x; v[5] += r1.y; v[6] += r1.z; v[7] += r1.w;
-        }
-        if (a.outF) {
-            *reinterpret_cast<float4*>(a.outF + (size_t)gm * a.ldof + gn) = make_float4(v[0], v[1], v[2], v[3]);
-            *reinterpret_cast<float4*>(a.outF + (size_t)gm * a.ldof + gn + 4) = make_float4(v[4], v[5], v[6], v[7]);
-        }
-        if (a.outH) {
-            union { uint4 u; __bf16 h[8]; } o;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o.h[j] = (__bf16)v[j];
-            *reinterpret_cast<uint4*>(a.outH + (size_t)gm * a.ldoh + gn) = o.u;
-        }
-    }
+    gemm_tile_epilogue<BS_BM, BS_BN>(a, acc, smem, m0, n0);   // bias, dropout, alpha, residual, fp32 / bf16 outputs
 }
 
 }  // namespace
@@ -250,25 +193,16 @@ extern "C" int ia_gemm_bnsilu_bf16_keep(const float* z, int ldz, int64_t n_rows,
                                         float alpha, const float* R, int ldr, float* outF, int ldof, void* outH, int ldoh,
                                         const long long* bn_sums_fixed, void* outA, int ldoa, ia_stream_t stream) {
     if (outA && (ldoa % 4 != 0 || ldoa < K || !ia_is_aligned(outA, 8))) return IA_INVALID_VALUE;
-    if (!z || !gamma || !beta || !W || (!outF && !outH) || M <= 0 || N <= 0 || n_rows <= 0) return IA_INVALID_VALUE;
+    if (!gamma || !beta || N <= 0 || n_rows <= 0) return IA_INVALID_VALUE;
     if (training ? (!bn_sums_fixed && (!bn_sum || !bn_sumsq)) : (!running_mean || !running_var)) return IA_INVALID_VALUE;
-    if (!ia_gemm_bnsilu_supported(K)) return IA_UNSUPPORTED;
-    if (N % 8 != 0 || ldz % 4 != 0 || ldw % 8 != 0 || (R && ldr % 4 != 0) || (outF && ldof % 4 != 0) || (outH && ldoh % 8 != 0))
-        return IA_UNSUPPORTED;
-    if (!ia_is_aligned(z, 16) || !ia_is_aligned(W, 16) || (bias && !ia_is_aligned(bias, 16)) || (R && !ia_is_aligned(R, 16)) ||
-        (outF && !ia_is_aligned(outF, 16)) || (outH && !ia_is_aligned(outH, 16)))
-        return IA_INVALID_VALUE;
-    if (dropout_p < 0.f || dropout_p >= 1.f) return IA_INVALID_VALUE;
-    BsArgs a;
+    const bool unsupported = !ia_gemm_bnsilu_supported(K) || ldz % 4 != 0 || ldw % 8 != 0;
+    BsArgs a = {};
+    if (const int rc = gemm_check_and_fill(a, z, W, unsupported, M, N, bias, 0, dropout_p, seed, alpha, R, ldr, outF, ldof, outH, ldoh)) return rc;
     a.z = z; a.ldz = ldz; a.bn_sum = bn_sum; a.bn_sumsq = bn_sumsq; a.fixed = bn_sums_fixed; a.gamma = gamma; a.beta = beta;
     a.rm = running_mean; a.rv = running_var; a.nbt = num_batches_tracked; a.momentum = momentum; a.eps = eps;
     a.training = training; a.n_rows = n_rows;
-    a.W = (const __bf16*)W; a.ldw = ldw; a.bias = bias; a.R = R; a.ldr = ldr; a.outF = outF; a.ldof = ldof;
-    a.outH = (__bf16*)outH; a.ldoh = ldoh; a.outA = (__bf16*)outA; a.ldoa = ldoa; a.M = M; a.N = N; a.K = K; a.alpha = alpha; a.seed = seed;
-    a.thr = (unsigned)(dropout_p * 256.f + 0.5f);
-    a.keep_scale = a.thr > 0 ? 256.f / (256.f - (float)a.thr) : 1.f;
-    const int ntm = (M + BS_BM - 1) / BS_BM, ntn = (N + BS_BN - 1) / BS_BN;
-    const int grid = 8 * ((ntm + 7) / 8) * ntn;
+    a.W = (const __bf16*)W; a.ldw = ldw; a.K = K; a.outA = (__bf16*)outA; a.ldoa = ldoa;
+    const int grid = gemm_xcd_grid(M, N, BS_BM, BS_BN);
     const size_t lds = (size_t)BS_REGION + (size_t)2 * K * sizeof(float);
     if (outA) hipLaunchKernelGGL(gemm_bnsilu_kernel<true>, dim3(grid), dim3(BS_THREADS), lds, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(gemm_bnsilu_kernel<false>, dim3(grid), dim3(BS_THREADS), lds, (hipStream_t)stream, a);

@@ -4,8 +4,8 @@
 //
 //   out = alpha * dropout(act( (A o 2^sa)[M,K] @ (W o 2^sw)[N,K]^T + bias )) + R
 //
-// BASELINE configs[4] names "fp8 MFMA" for the Conformer-large projections; same operator and epilogue as
-// csrc/gemm_bf16.hip (A/parts/submodules/conformer_modules.py:340-404, multi_head_attention.py:69-119).
+// BASELINE configs[4] names "fp8 MFMA" for the Conformer-large projections; same operator as csrc/gemm_bf16.hip
+// (A/parts/submodules/conformer_modules.py:340-404, multi_head_attention.py:69-119), epilogue and tile order are gemm_common.h's.
 //
 // Operand maps of the instruction, found with exact integer data (tools/probe_mfma_scale.hip, probe_mfma_scale2.hip; the
 // programming guide gives the C/D map only):
@@ -19,39 +19,29 @@
 // registers; the product is computed transposed (A operand = weight rows) so that a lane owns 4 consecutive output columns.
 #include <hip/hip_bf16.h>
 
-#include "ia_common.h"
-#include "dropout_mask.h"
+#include "gemm_common.h"
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
 typedef int v8i __attribute__((ext_vector_type(8)));
 
-constexpr int MX_BM = 128, MX_BN = 128, MX_BK = 128;
+constexpr int MX_BM = GEMM_T_BM, MX_BN = GEMM_T_BN, MX_BK = 128;
 constexpr int MX_ROWB = MX_BK + 16;
-constexpr int MX_THREADS = 256;
-constexpr int MX_LDC = MX_BN + 4;
 constexpr int MX_STAGE = (MX_BM + MX_BN) * MX_ROWB;
-constexpr int MX_EPI = 64 * MX_LDC * 4;
-constexpr int MX_LDS = MX_STAGE > MX_EPI ? MX_STAGE : MX_EPI;
+constexpr int MX_LDS = MX_STAGE > GEMM_T_EPI ? MX_STAGE : GEMM_T_EPI;
 
-struct MxArgs {
+struct MxArgs : GemmEpi {
     const unsigned char* A; const unsigned char* W; const unsigned char* sa; const unsigned char* sw;
-    const float* bias; const float* R; float* outF; __bf16* outH;
-    int M, N, K, lda, ldw, ldsa, ldsw, ldr, ldof, ldoh, act;
-    float alpha; unsigned seed, thr; float keep_scale;
+    int K, lda, ldw, ldsa, ldsw;
 };
 
-__global__ __launch_bounds__(MX_THREADS, 2) void gemm_mxfp8_nt_kernel(MxArgs a) {
+__global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_mxfp8_nt_kernel(MxArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 15, kg = lane >> 4;
     const int wm = wave >> 1, wn = wave & 1;
-    const int ntn = (a.N + MX_BN - 1) / MX_BN;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;   // XCD-aware tile order, as in gemm_bf16.hip
-    const int mt = xcd + 8 * (slot / ntn);
-    if (mt * MX_BM >= a.M) return;
-    const int m0 = mt * MX_BM, n0 = (slot % ntn) * MX_BN;
+    int m0, n0;
+    if (!gemm_xcd_tile<MX_BM, MX_BN>(a.M, a.N, m0, n0)) return;
     const int bsh = 8 * (2 * (kg & 1) + (kg >> 1));           // this lane's 32-block inside a k-tile -> byte of the scale word
 
     // staging (named scalars / fully unrolled arrays only: pointer arrays captured by lambdas end up in scratch memory)
@@ -142,66 +132,7 @@ __global__ __launch_bounds__(MX_THREADS, 2) void gemm_mxfp8_nt_kernel(MxArgs a) 
 #undef MX_LOAD
 #undef MX_STORE
 #undef MX_LOAD_SCALES
-    // ---- epilogue through LDS, 64 tile rows per pass (the bf16 GEMM's epilogue; no operand scales left to apply)
-    float* sc = reinterpret_cast<float*>(smem);
-    constexpr int VEC_PER_ROW = MX_BN / 8;
-    for (int pass = 0; pass < 2; ++pass) {
-        if (pass) __syncthreads();
-        if (wm == pass) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    *reinterpret_cast<float4*>(sc + (i * 16 + c) * MX_LDC + wn * 64 + j * 16 + kg * 4) =
-                        make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
-        }
-        __syncthreads();
-        for (int it = tid; it < 64 * VEC_PER_ROW; it += MX_THREADS) {
-            const int row = it / VEC_PER_ROW, cv = it - row * VEC_PER_ROW;
-            const int gm = m0 + pass * 64 + row, gn = n0 + cv * 8;
-            if (gm >= a.M || gn >= a.N) continue;
-            float v[8];
-            const float4 x0 = *reinterpret_cast<const float4*>(sc + row * MX_LDC + cv * 8);
-            const float4 x1 = *reinterpret_cast<const float4*>(sc + row * MX_LDC + cv * 8 + 4);
-            v[0] = x0.x; v[1] = x0.y; v[2] = x0.z; v[3] = x0.w; v[4] = x1.x; v[5] = x1.y; v[6] = x1.z; v[7] = x1.w;
-            if (a.bias) {
-                const float4 b0 = *reinterpret_cast<const float4*>(a.bias + gn), b1 = *reinterpret_cast<const float4*>(a.bias + gn + 4);
-                v[0] += b0.x; v[1] += b0.y; v[2] += b0.z; v[3] += b0.w; v[4] += b1.x; v[5] += b1.y; v[6] += b1.z; v[7] += b1.w;
-            }
-            if (a.act == 1) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] = ia_silu_fast(v[j]);
-            } else if (a.act == 2) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] = fmaxf(v[j], 0.f);
-            }
-            float sc_all = a.alpha;
-            if (a.thr > 0) {
-                const unsigned m = ia_keep8(a.seed, (unsigned)gm, (unsigned)a.N, (unsigned)gn, a.thr);
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    if (!((m >> j) & 1u)) v[j] = 0.f;
-                sc_all *= a.keep_scale;
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] *= sc_all;
-            if (a.R) {
-                const float4 r0 = *reinterpret_cast<const float4*>(a.R + (size_t)gm * a.ldr + gn);
-                const float4 r1 = *reinterpret_cast<const float4*>(a.R + (size_t)gm * a.ldr + gn + 4);
-                v[0] += r0.x; v[1] += r0.y; v[2] += r0.z; v[3] += r0.w; v[4] += r1.x; v[5] += r1.y; v[6] += r1.z; v[7] += r1.w;
-            }
-            if (a.outF) {
-                *reinterpret_cast<float4*>(a.outF + (size_t)gm * a.ldof + gn) = make_float4(v[0], v[1], v[2], v[3]);
-                *reinterpret_cast<float4*>(a.outF + (size_t)gm * a.ldof + gn + 4) = make_float4(v[4], v[5], v[6], v[7]);
-            }
-            if (a.outH) {
-                union { uint4 u; __bf16 h[8]; } o;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) o.h[j] = (__bf16)v[j];
-                *reinterpret_cast<uint4*>(a.outH + (size_t)gm * a.ldoh + gn) = o.u;
-            }
-        }
-    }
+    gemm_tile_epilogue_t<false>(a, acc, smem, m0, n0);   // (no operand scales left to apply)
 }
 
 // MX quantiser: per 32 consecutive k of a row, e = smallest exponent with amax / 2^e <= 448 (ilogb(amax) - 8, + 1 if that
@@ -275,26 +206,14 @@ extern "C" int ia_quantize_mxfp8(const void* x, int is_f32, int ld, int64_t M, i
 extern "C" int ia_gemm_mxfp8(const void* Aq, int lda, const void* a_scales, int ldsa, const void* Wq, int ldw, const void* w_scales,
                              int ldsw, int M, int N, int K, const float* bias, int act, float dropout_p, unsigned seed, float alpha,
                              const float* R, int ldr, float* outF, int ldof, void* outH, int ldoh, ia_stream_t stream) {
-    if (!Aq || !Wq || !a_scales || !w_scales || (!outF && !outH) || M <= 0 || N <= 0 || K <= 0) return IA_INVALID_VALUE;
-    if (K % MX_BK != 0 || N % 8 != 0 || lda % 16 != 0 || ldw % 16 != 0 || ldsa % 4 != 0 || ldsw % 4 != 0 || ldsa < K / 32 ||
-        ldsw < K / 32)
-        return IA_UNSUPPORTED;
-    if ((R && ldr % 4 != 0) || (outF && ldof % 4 != 0) || (outH && ldoh % 8 != 0)) return IA_UNSUPPORTED;
-    if (!ia_is_aligned(Aq, 16) || !ia_is_aligned(Wq, 16) || !ia_is_aligned(a_scales, 4) || !ia_is_aligned(w_scales, 4) ||
-        (bias && !ia_is_aligned(bias, 16)) || (R && !ia_is_aligned(R, 16)) || (outF && !ia_is_aligned(outF, 16)) ||
-        (outH && !ia_is_aligned(outH, 16)))
-        return IA_INVALID_VALUE;
-    if (act < 0 || act > 2 || dropout_p < 0.f || dropout_p >= 1.f) return IA_INVALID_VALUE;
-    MxArgs a;
-    a.A = (const unsigned char*)Aq; a.W = (const unsigned char*)Wq; a.sa = (const unsigned char*)a_scales;
-    a.sw = (const unsigned char*)w_scales; a.bias = bias; a.R = R; a.outF = outF; a.outH = (__bf16*)outH;
-    a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldw = ldw; a.ldsa = ldsa; a.ldsw = ldsw; a.ldr = ldr; a.ldof = ldof; a.ldoh = ldoh;
-    a.act = act; a.alpha = alpha; a.seed = seed;
-    a.thr = (unsigned)(dropout_p * 256.f + 0.5f);
-    a.keep_scale = a.thr > 0 ? 256.f / (256.f - (float)a.thr) : 1.f;
-    const int ntm = (M + MX_BM - 1) / MX_BM, ntn = (N + MX_BN - 1) / MX_BN;
-    const int grid = 8 * ((ntm + 7) / 8) * ntn;
-    hipLaunchKernelGGL(gemm_mxfp8_nt_kernel, dim3(grid), dim3(MX_THREADS), MX_LDS, (hipStream_t)stream, a);
+    if (!a_scales || !w_scales || N <= 0 || K <= 0) return IA_INVALID_VALUE;
+    const bool unsupported = K % MX_BK != 0 || lda % 16 != 0 || ldw % 16 != 0 || ldsa % 4 != 0 || ldsw % 4 != 0 || ldsa < K / 32 || ldsw < K / 32;
+    MxArgs a = {};
+    if (const int rc = gemm_check_and_fill(a, Aq, Wq, unsupported, M, N, bias, act, dropout_p, seed, alpha, R, ldr, outF, ldof, outH, ldoh)) return rc;
+    if (!ia_is_aligned(a_scales, 4) || !ia_is_aligned(w_scales, 4) || act < 0 || act > 2) return IA_INVALID_VALUE;
+    a.A = (const unsigned char*)Aq; a.W = (const unsigned char*)Wq; a.sa = (const unsigned char*)a_scales; a.sw = (const unsigned char*)w_scales;
+    a.K = K; a.lda = lda; a.ldw = ldw; a.ldsa = ldsa; a.ldsw = ldsw;
+    hipLaunchKernelGGL(gemm_mxfp8_nt_kernel, dim3(gemm_xcd_grid(M, N, MX_BM, MX_BN)), dim3(GEMM_THREADS), MX_LDS, (hipStream_t)stream, a);
     IA_RETURN_IF_LAUNCH_FAILED();
     return IA_OK;
 }

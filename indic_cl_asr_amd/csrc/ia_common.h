@@ -28,6 +28,15 @@
         }                                                                                                   \
     } while (0)
 
+// THE dropout rule of every kernel in the step: an element is kept if its mask byte >= thr = round(256 p), survivors are
+// scaled by 256 / (256 - thr).  The forward and the backward of a dropout agree because both take thr and the scale from
+// here; fp32 arithmetic exactly as written (tests/test_block_reference_gpu.py restates it).
+struct ia_dropout_t { unsigned thr; float keep_scale; };
+static inline ia_dropout_t ia_dropout_rule(float p) {
+    const unsigned thr = (unsigned)(p * 256.f + 0.5f);
+    return {thr, thr > 0 ? 256.f / (256.f - (float)thr) : 1.f};
+}
+
 static inline size_t ia_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline int ia_is_aligned(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
 

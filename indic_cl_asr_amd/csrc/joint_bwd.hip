@@ -507,7 +507,7 @@ extern "C" int ia_joint_hidden(const void* f, const void* g, void* hidden, int B
         return IA_INVALID_VALUE;
     if (!ia_is_aligned(f, 16) || !ia_is_aligned(g, 16) || !ia_is_aligned(hidden, 16)) return IA_INVALID_VALUE;
     const int64_t cells = (int64_t)B * T * U1;
-    const unsigned thr = (unsigned)(dropout_p * 256.f + 0.5f);
+    const unsigned thr = ia_dropout_rule(dropout_p).thr;
     const dim3 grid(grid_for(cells * (LDH / 8))), blk(256);
     if (thr > 0)
         hipLaunchKernelGGL((joint_hidden_kernel<true>), grid, blk, 0, (hipStream_t)stream, (const _Float16*)f,
@@ -531,7 +531,7 @@ extern "C" int ia_joint_dh_reduce(const void* dh, const void* f, const void* g, 
         return IA_INVALID_VALUE;
     if (H % 8 != 0 || !ia_is_aligned(df, 16) || !ia_is_aligned(dg, 16) || !ia_is_aligned(scratch, 16) || !ia_is_aligned(dh, 16))
         return IA_UNSUPPORTED;
-    const unsigned thr = (unsigned)(dropout_p * 256.f + 0.5f);
+    const unsigned thr = ia_dropout_rule(dropout_p).thr;
     const int ntc = (T + DHR_T - 1) / DHR_T;
     const dim3 grid(grid_for((int64_t)B * ntc * (H / 8))), blk(256);
     hipStream_t st = (hipStream_t)stream;
@@ -554,7 +554,7 @@ extern "C" int ia_joint_hidden_t(const void* f, const void* g, void* hidden_t, i
         return IA_INVALID_VALUE;
     const int64_t cells = (int64_t)B * T * U1;
     if ((int64_t)S * Kc < cells || !ia_is_aligned(hidden_t, 16)) return IA_INVALID_VALUE;
-    const unsigned thr = (unsigned)(dropout_p * 256.f + 0.5f);
+    const unsigned thr = ia_dropout_rule(dropout_p).thr;
     if (LDH % 8 != 0 || H % 8 != 0) return IA_UNSUPPORTED;
     const int64_t nitems = (int64_t)S * (LDH / 8) * (Kc / 8);
     const dim3 grid(grid_for(nitems)), blk(256);

@@ -393,7 +393,7 @@ extern "C" int ia_joint_dh_fused_ex(const void* G, const void* Wt, const void* f
     a.B = B; a.T = T; a.U1 = U1; a.H = H; a.LD = LD;
     a.nh = 0;   // (set with the decomposition below)
     a.inv_kappa = inv_kappa; a.seed = seed;
-    a.thr = (unsigned)(dropout_p * 256.f + 0.5f);
+    a.thr = ia_dropout_rule(dropout_p).thr;
     const char* wv_env = getenv("IA_DH_WAVES");
     int waves = (H % 32 == 0) ? 10 : 4;
     if (wv_env && atoi(wv_env) == 4) waves = 4;

@@ -491,7 +491,7 @@ extern "C" int ia_joint_dw_fused_ex(const void* G, const void* f, const void* g,
     a.steps_per_split = (int)((nsteps + S - 1) / S);
     const int Seff = (int)((nsteps + a.steps_per_split - 1) / a.steps_per_split);   // every split < Seff owns >= 1 step
     a.row_stride = (size_t)LD * H;
-    a.seed = seed; a.thr = (unsigned)(dropout_p * 256.f + 0.5f);
+    a.seed = seed; a.thr = ia_dropout_rule(dropout_p).thr;
     auto magic = [](unsigned d) { return d <= 1 ? 0xFFFFFFFFu : (unsigned)(((1ull << 32) + d - 1) / d); };
     a.mU1 = magic((unsigned)U1); a.mV = magic((unsigned)(LD / 8)); a.mSpu = magic((unsigned)a.spu);
     hipStream_t st = (hipStream_t)stream;

@@ -276,7 +276,7 @@ extern "C" int ia_joint_fwd_box(const void* f, const void* g, const void* W, con
     a.PLa = (float*)(ws + w.off_pla);
     a.B = B; a.T = T; a.U1 = U1; a.H = H; a.V = V; a.LD = LD; a.blank = blank; a.rows = w.rows; a.U1s = w.U1s;
     a.seed = seed;
-    a.thr = (unsigned)(dropout_p * 256.f + 0.5f);
+    a.thr = ia_dropout_rule(dropout_p).thr;
     const int frow = H * 2 + 16;
     const char* wv_env = getenv("IA_JFWD_WAVES");       // A/B switch: 4 = one wave per SIMD x 3 frames, 8 = two waves per SIMD x 2 frames
     const int waves = (wv_env && atoi(wv_env) == 4) ? 4 : 8;

@@ -17,7 +17,7 @@ Rounding points of the executor (file:line of the csrc/ call each one mirrors):
   forward (straight-through: value rounded, gradient passed unchanged)
     bf16 weight images of the nine projections ........ ops/fast.py bf16_shadow, consumed by every ia_gemm_bf16 of the block
     y1..y4 = LayerNorm outputs ......................... block_train.hip:301, 306, 312, 328 (ia_layernorm -> bf16)
-    h1p / h4p pre-activations, SiLU of the rounded value gemm_args.h:38-42 (outPre rounded, v = (float)bf16) ; :44-47
+    h1p / h4p pre-activations, SiLU of the rounded value gemm_common.h:59-64 (outPre rounded, v = (float)bf16) ; :66-68
     h1 / h4 = dropout(SiLU(h_p)) ....................... block_train.hip:302, 329 (outH bf16)
     qkv, pl, ctx ....................................... block_train.hip:307, 308, 309
     c2 (pointwise conv 1), c3 = SiLU(BN(z)) ............ block_train.hip:313, 319 (c3 kept bf16 by the fused BN+SiLU GEMM)
@@ -26,7 +26,7 @@ Rounding points of the executor (file:line of the csrc/ call each one mirrors):
     dB = bf16(alpha * dropout(d x)) that each LayerNorm backward emits for the branch in front of it
                                                        block_train.hip:385, 393, 420 and 494 (ia_layernorm_bwd_drop)
     d h = bf16(acc) of the act-3 epilogue, d h_p = bf16(bf16(acc) * SiLU'(h_p) * keep)
-                                                       gemm_args.h:48-55 ; block_train.hip:389, 497
+                                                       gemm_common.h:73-80 ; block_train.hip:389, 497
     dy (into every LayerNorm backward) ................. block_train.hip:392, 419, 482, 507 (dX of the data-gradient GEMM, bf16)
     dc3 ................................................ block_train.hip:396
     dc2 ................................................ block_train.hip:410 (ia_dwconv_glu_bwd -> bf16)

@@ -89,7 +89,7 @@ def _hash32(x):
 
 
 def keep_mask(seed, M, N, p):
-    """csrc/dropout_mask.h ia_keep8 + the epilogue's scale (gemm_bf16.hip: thr = (unsigned)(p*256 + 0.5) in fp32, keep if the
+    """csrc/dropout_mask.h ia_keep8 + the epilogue's scale (ia_common.h ia_dropout_rule: thr = (unsigned)(p*256 + 0.5) in fp32, keep if the
     byte >= thr, kept values * 256 / (256 - thr)): [M, N] float32 tensor of 0 / keep_scale."""
     thr = int(np.float32(p) * np.float32(256.0) + np.float32(0.5))
     if thr == 0:
