@@ -384,44 +384,16 @@ int ia_dwconv_gated_fixed(const void* g, const int64_t* lens, int B, int T, int 
 int ia_glu_dwconv_fixed(const void* x2, const int64_t* lens, int B, int T, int d, int ksz, const float* w, const float* bias,
                         float* z, long long* bn_sums_fixed, ia_stream_t stream);
 
-/* ia_relpos_attention: RelPositionMultiHeadAttention.forward core (A/parts/submodules/multi_head_attention.py:197-250,
- * rel_shift :184-195, masking :108-111) without materialising any [B,h,T,T] / [B,h,T,2T-1] tensor.
- *   qkv [B*T, 3*H*dk] bf16 (q | k | v, head-major inside each third), pos_proj [2T-1, H*dk] bf16 (linear_pos(pos_emb)),
- *   bias_u / bias_v [H,dk] f32, lens [B] i64, ctx out [B*T, H*dk] bf16 (zero rows for queries >= lens[b]).
- *   vt_scratch: ia_attn_vt_elems(B,T,H) bf16 elements, caller-owned (holds V^T, filled by this call).
- *   Attention dropout keyed by (seed, b, h, i, j).  Limits: dk == 64, T <= 384 (IA_UNSUPPORTED otherwise). */
-size_t ia_attn_vt_elems(int B, int T, int H);
-int ia_relpos_attention(const void* qkv, const void* pos_proj, const float* bias_u, const float* bias_v,
-                        const int64_t* lens, int B, int T, int H, int dk, float dropout_p, unsigned seed,
-                        void* vt_scratch, void* ctx, ia_stream_t stream);
-/* Backward of ia_relpos_attention, row pass (one wave = 16 queries): recomputes the probabilities and writes three bf16
- * matrices on which every remaining contraction is a plain (batched) GEMM with 16-byte aligned rows:
- *   Pd    [B,H,T,Ts]  dropout(P)                          dV     = Pd^T dctx
- *   dS    [B,H,T,Ts]  P o (keep*dctx V^T - dctx.ctx)/sqrt(dk)   dK = dS^T (q+u),  d(q+u) = dS K
- *   dBand [H,B,T,Rs]  dS skewed to column pad0 + (T-1-i+j)       d(q+v) = dBand p, dp = dBand^T (q+v) summed over B
- * with Ts, Rs, pad0 from ia_relpos_attention_bwd_dims (Ts = ceil8(T), pad0 = (8 - T%8)%8, Rs = ceil8(pad0 + 2T-1)).
- * ctx = the forward's output, dctx its gradient (bf16 [B*T, H*dk]); same seed / dropout_p / limits as the forward. */
-int ia_relpos_attention_bwd_dims(int T, int* Ts, int* Rs, int* pad0);
-int ia_relpos_attention_bwd(const void* qkv, const void* pos_proj, const float* bias_u, const float* bias_v,
-                            const int64_t* lens, const void* ctx, const void* dctx, int B, int T, int H, int dk,
-                            float dropout_p, unsigned seed, void* Pd, void* dS, void* dBand, void* Qu, void* Qv, void* K,
-                            void* dO, ia_stream_t stream);
-/* The row pass also writes the head-major bf16 operands of those GEMMs: Qu = q+u, K, dO as [B,H,T,dk], Qv = q+v as
- * [H,B,T,dk].  ia_attn_bwd_unpack folds their outputs back: dqkv [B*T, 3*H*dk] bf16 = (dQu + dQv | dK | dV) and
- * dbias_u / dbias_v [H*dk] f32 = column sums of dQu / dQv (block partial rows in `scratch`, f32 x
- * ia_attn_bwd_unpack_scratch_elems).  dQu, dK, dV are [B,H,T,dk], dQv is [H,B,T,dk] (bf16).  H*dk <= 2048. */
-int ia_attn_bwd_unpack(const void* dQu, const void* dQv, const void* dK, const void* dV, void* dqkv, float* dbias_u,
-                       float* dbias_v, int B, int T, int H, int dk, float* scratch, ia_stream_t stream);
-int64_t ia_attn_bwd_unpack_scratch_elems(int B, int T, int H);
-
 /* ------------------------------------------------------------------------------------------------
- * Rel-pos attention forward with a key-tile loop and online softmax (csrc/attention_flash.hip): the same function as
- * ia_relpos_attention (RelPositionMultiHeadAttention.forward, multi_head_attention.py:197-250) without its limits:
- * any T (30 s audio: T' = 751), head dim any multiple of 4 up to 64 (d = 144 / 4 heads = 36), no V^T scratch.
- * qkv [B*T, 3*H*dk] bf16 (q|k|v), pos_proj [>= 2T-1, H*dk] bf16 (row r <-> relative position T-1-r), bias_u/bias_v
- * [H*dk] f32, lens [B] i64 -> ctx [B*T, H*dk] bf16 (rows of padded queries are zero).  Attention dropout draws its
- * own mask (one hash per (head, query, 4 keys)); it is the forward of no-autograd passes (frozen prefix, teacher,
- * eval), so no backward has to reproduce it. */
+ * Rel-pos attention core, key-tile loop with online softmax (csrc/attention_flash.hip):
+ * RelPositionMultiHeadAttention.forward (A/parts/submodules/multi_head_attention.py:197-250, rel_shift :184-195, masking
+ * :108-111) without materialising any [B,h,T,T] / [B,h,T,2T-1] tensor.  Any T (30 s audio: T' = 751), head dim any
+ * multiple of 4 up to 64 (d = 144 / 4 heads = 36); ia_relpos_attention_flash_supported says so, IA_UNSUPPORTED otherwise.
+ *   qkv [B*T, 3*H*dk] bf16 (q | k | v, head-major inside each third), pos_proj [>= 2T-1, H*dk] bf16 (linear_pos(pos_emb),
+ *   row r <-> relative position T-1-r), bias_u / bias_v [H,dk] f32, lens [B] i64, ctx out [B*T, H*dk] bf16 (zero rows for
+ *   queries >= lens[b]; keys >= lens[b] take no part).
+ *   Attention dropout: one hash word per (seed, b, h, T, query, group of 4 keys); ia_relpos_attention_flash_bwd
+ *   regenerates exactly that mask from the same dropout_p / seed. */
 int ia_relpos_attention_flash_supported(int T, int dk);
 int ia_relpos_attention_flash(const void* qkv, const void* pos_proj, const float* bias_u, const float* bias_v,
                               const int64_t* lens, int B, int T, int H, int dk, float dropout_p, unsigned seed, void* ctx,
@@ -443,6 +415,14 @@ int ia_relpos_attention_flash_bwd(const void* qkv, const void* pos_proj, const f
                                   const int64_t* lens, const void* ctx, const void* dctx, const float* lse, int B, int T, int H,
                                   int dk, float dropout_p, unsigned seed, void* dqkv, void* dpl, int pl_rows, float* dbias_u,
                                   float* dbias_v, void* dBand, void* QvHM, float* ws, ia_stream_t stream);
+/* Round-1 forward of the same core (csrc/attention.hip: all keys of a 16-query strip in registers), kept only as the
+ * independent implementation the tests compare against; no product path calls it.  Operands as above, pos_proj [2T-1, H*dk];
+ * vt_scratch: ia_attn_vt_elems(B,T,H) bf16 elements, caller-owned (holds V^T, filled by this call).  Its own dropout mask
+ * (one hash per (seed, b, h, 4 queries, key)): no backward reproduces it.  Limits: dk == 64, T <= 384 (IA_UNSUPPORTED otherwise). */
+size_t ia_attn_vt_elems(int B, int T, int H);
+int ia_relpos_attention(const void* qkv, const void* pos_proj, const float* bias_u, const float* bias_v,
+                        const int64_t* lens, int B, int T, int H, int dk, float dropout_p, unsigned seed,
+                        void* vt_scratch, void* ctx, ia_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Persistent single-layer LSTM: the recurrence of the RNNT prediction network (RNNTDecoder.predict
@@ -622,9 +602,9 @@ int ia_conformer_prefix_fwd_seg(const ia_block_params* layers, int n_layers, flo
  *   ia_block_grads  where the parameter gradients are WRITTEN (f32, caller-owned; the q|k|v weight / bias gradients are
  *                   one [3d,d] / [3d] block in that order).
  *   forward   x0 [N,d] f32 -> out [N,d] f32 (= norm_out(...)); train-mode BatchNorm (running statistics updated); dropout
- *             sites seed + {1..7} as in ia_conformer_prefix_fwd; vt_scratch = ia_attn_vt_elems bf16, dw_scratch =
- *             ia_dwconv_scratch_elems f32.  Limits: ia_conformer_block_supported (head dim 64, taps <= 31; any T: the
- *             attention core is the key-tiled ia_relpos_attention_flash_lse, vt_scratch is unused).
+ *             sites seed + {1..7} as in ia_conformer_prefix_fwd; dw_scratch = ia_dwconv_scratch_elems f32.  Limits:
+ *             ia_conformer_block_supported (head dim 64, taps <= 31; any T: the attention core is the key-tiled
+ *             ia_relpos_attention_flash_lse).
  *   bwd_a     dout [N,d] f32 -> gradients of norm_out, feed_forward2, conv module, linear_out; *dx2_out (f32 [N,d]) and
  *             *dctx_out (bf16 [N,d]) point INTO the workspace: d(residual in front of the attention branch), d(ctx).
  *   bwd_b     dqkv [N,3d], dpl [pos_rows,d] (bf16, from the attention backward) -> remaining gradients, dx0 [N,d] f32,
@@ -649,7 +629,7 @@ int ia_conformer_block_supported(int d, int d_ff, int H, int ksz, int T);
 size_t ia_conformer_block_bwd_ws_bytes(int B, int T, int d, int d_ff, int ksz);
 int ia_conformer_block_fwd(const struct ia_block_params* layer, const float* x0, const void* pos_emb, int pos_rows,
                            const int64_t* lens, int B, int T, unsigned seed, const ia_block_saved* saved, float* out,
-                           void* vt_scratch, float* dw_scratch, ia_stream_t stream);
+                           float* dw_scratch, ia_stream_t stream);
 int ia_conformer_block_bwd_a(const struct ia_block_params* layer, const ia_block_saved* saved, const ia_block_grads* grads,
                              const float* dout, const int64_t* lens, int B, int T, unsigned seed, void* workspace,
                              size_t workspace_bytes, float** dx2_out, void** dctx_out, ia_stream_t stream);
@@ -658,7 +638,7 @@ int ia_conformer_block_bwd_a(const struct ia_block_params* layer, const ia_block
  * 2 = from dz onwards with bn_S12 = the all-reduced sums rescaled by n_local / n_global). */
 int ia_conformer_block_fwd_phase(const struct ia_block_params* layer, const float* x0, const void* pos_emb, int pos_rows,
                                  const int64_t* lens, int B, int T, unsigned seed, const ia_block_saved* saved, float* out,
-                                 void* vt_scratch, float* dw_scratch, int phase, ia_stream_t stream);
+                                 float* dw_scratch, int phase, ia_stream_t stream);
 int ia_conformer_block_bwd_a_phase(const struct ia_block_params* layer, const ia_block_saved* saved, const ia_block_grads* grads,
                                    const float* dout, const int64_t* lens, int B, int T, unsigned seed, void* workspace,
                                    size_t workspace_bytes, float** dx2_out, void** dctx_out, int phase, const float* bn_S12,
@@ -680,7 +660,6 @@ int ia_conformer_block_bwd_b(const struct ia_block_params* layer, const ia_block
  *                         S2 = dgamma (both written: block partial rows in `scratch`, f32 x ia_bn_silu_bwd_scratch_elems),
  *                         dz [n_rows,d] f32
  *   ia_glu_mask / ia_glu_bwd   G = mask(GLU(c2)) f32;  dc2 bf16 [rows,2d] from dG
- *   ia_attn_keepmask      attention-dropout keep mask of ia_relpos_attention as a bf16 [B,H,T,T] tensor (0 or 1/(1-p))
  */
 int ia_layernorm_bwd(const float* x, int ldx, const float* dy_f32, const void* dy_bf16, int ldy, int N, int d,
                      const float* gamma, float eps, const float* dx_in, float* dx_out, int lddx, float* dgamma,
@@ -727,7 +706,6 @@ int ia_bn_silu_bwd_apply(const float* z, const void* dc3, int64_t n_rows, int d,
                          ia_stream_t stream);
 int ia_glu_mask(const void* c2, const int64_t* lens, int B, int T, int d, float* G, ia_stream_t stream);
 int ia_glu_bwd(const void* c2, const float* dG, const int64_t* lens, int B, int T, int d, void* dc2, ia_stream_t stream);
-int ia_attn_keepmask(int B, int H, int T, float dropout_p, unsigned seed, void* mask_bf16, ia_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Continual-learning regularisers and optimizer over ONE flat fp32 buffer holding every trainable parameter

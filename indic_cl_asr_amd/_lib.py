@@ -146,11 +146,6 @@ SIGNATURES = {
     "ia_relpos_attention": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _c.c_uint, _vp, _vp, _vp]),
     "ia_relpos_attention_flash_supported": (_i, [_i, _i]),
     "ia_relpos_attention_flash": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _c.c_uint, _vp, _vp]),
-    "ia_relpos_attention_bwd_dims": (_i, [_i, _vp, _vp, _vp]),
-    "ia_relpos_attention_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _c.c_uint, _vp, _vp, _vp, _vp, _vp,
-                                     _vp, _vp, _vp]),
-    "ia_attn_bwd_unpack": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "ia_attn_bwd_unpack_scratch_elems": (_i64, [_i, _i, _i]),
     "ia_lstm_scratch_bytes": (_sz, [_i, _i]),
     "ia_lstm_lds_bytes": (_i, [_i, _i]),
     "ia_lstm_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
@@ -179,8 +174,8 @@ SIGNATURES = {
     "ia_conformer_prefix_fwd": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _c.c_uint, _c.c_uint, _i, _vp, _sz, _vp]),
     "ia_conformer_block_supported": (_i, [_i, _i, _i, _i, _i]),
     "ia_conformer_block_bwd_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "ia_conformer_block_fwd": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _c.c_uint, _vp, _vp, _vp, _vp, _vp]),
-    "ia_conformer_block_fwd_phase": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _c.c_uint, _vp, _vp, _vp, _vp, _i, _vp]),
+    "ia_conformer_block_fwd": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _c.c_uint, _vp, _vp, _vp, _vp]),
+    "ia_conformer_block_fwd_phase": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _c.c_uint, _vp, _vp, _vp, _i, _vp]),
     "ia_conformer_block_bwd_a": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _c.c_uint, _vp, _sz, _vp, _vp, _vp]),
     "ia_conformer_block_bwd_a_phase": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _c.c_uint, _vp, _sz, _vp, _vp, _i, _vp, _vp]),
     "ia_conformer_block_bwd_b": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _c.c_uint, _vp, _sz, _vp, _vp, _i, _vp]),
@@ -199,7 +194,6 @@ SIGNATURES = {
     "ia_bn_silu_bwd_apply": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
     "ia_glu_mask": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "ia_glu_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
-    "ia_attn_keepmask": (_i, [_i, _i, _i, _f, _c.c_uint, _vp, _vp]),
     "ia_cl_chunk_elems": (_i, []),
     "ia_cl_penalty": (_i, [_vp, _vp, _vp, _f, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "ia_cl_fisher_accumulate": (_i, [_vp, _vp, _vp, _i64, _vp]),

@@ -4,9 +4,9 @@
 //
 // RelPositionMultiHeadAttention.forward A/parts/submodules/multi_head_attention.py:197-250: rel_shift (:184-195) as index
 // arithmetic, the [B,T,T] mask replaced by lengths (keys >= len excluded = "-10000 then zero", :108-111; padded queries
-// give zero context), attention dropout on the probabilities.  Unlike csrc/attention.hip (all keys of a 16-query strip in
-// registers: T <= 384, head dim 64) this kernel walks 64-key tiles, so T is unbounded (30 s audio: T' = 751) and the
-// head dim is any multiple of 4 up to 64 (d = 144 / 4 heads = 36: tiles zero-padded to 64 in LDS).
+// give zero context), attention dropout on the probabilities.  The kernel walks 64-key tiles and keeps only the running
+// maximum, sum and output of a 16-query strip in registers, so T is unbounded (30 s audio: T' = 751); the head dim is any
+// multiple of 4 up to 64 (d = 144 / 4 heads = 36: tiles zero-padded to 64 in LDS).
 //
 // Workgroup = (utterance, head, 64 queries), 4 waves x 16 queries.  Per 64-key tile, staged once per workgroup in LDS
 // (K, V row-major [key][dk], 128 position rows covering the four waves' bands; 16-byte slots XOR-swizzled by row & 7):

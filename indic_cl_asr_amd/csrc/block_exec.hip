@@ -16,10 +16,10 @@ inline size_t up256(size_t x) { return (x + 255) / 256 * 256; }
 constexpr int PREFIX_ACC_LAYERS = 64;
 
 struct PrefixWs {
-    size_t y, h, qkv, pl, ctx, c2, z, sums, acc, c3, vt, scr, total;
+    size_t y, h, qkv, pl, ctx, c2, z, sums, acc, c3, scr, total;
 };
 
-PrefixWs prefix_ws(int B, int T, int d, int d_ff, int H, int ksz, int pos_rows) {
+PrefixWs prefix_ws(int B, int T, int d, int d_ff, int ksz, int pos_rows) {
     const size_t N = (size_t)B * T;
     PrefixWs w;
     size_t o = 0;
@@ -33,16 +33,16 @@ PrefixWs prefix_ws(int B, int T, int d, int d_ff, int H, int ksz, int pos_rows) 
     w.sums = o; o = up256(o + (2 * (size_t)d + 64) * 4);   // [sum | sumsq | row count (SyncBatchNorm exchange)]
     w.acc = o;  o = up256(o + (size_t)PREFIX_ACC_LAYERS * IA_BN_ACC_COPIES * 2 * d * 8);   // per-layer fixed-point BatchNorm sums (one memset per call)
     w.c3 = o;   o = up256(o + N * d * 2);
-    w.vt = o;   o = up256(o + ia_attn_vt_elems(B, T, H) * 2);
     w.scr = o;  o = up256(o + (size_t)ia_dwconv_scratch_elems(B, T, d, ksz) * 4);
     w.total = o;
     return w;
 }
 }  // namespace
 
+// H sizes no region of the workspace; the two prototypes keep it (and reject H <= 0) for their callers
 extern "C" size_t ia_conformer_prefix_ws_bytes(int B, int T, int d, int d_ff, int H, int ksz, int pos_rows) {
     if (B <= 0 || T <= 0 || d <= 0 || d_ff <= 0 || H <= 0 || ksz <= 0 || pos_rows <= 0) return 0;
-    return prefix_ws(B, T, d, d_ff, H, ksz, pos_rows).total;
+    return prefix_ws(B, T, d, d_ff, ksz, pos_rows).total;
 }
 
 #define IA_TRY(call)               \
@@ -53,7 +53,7 @@ extern "C" size_t ia_conformer_prefix_ws_bytes(int B, int T, int d, int d_ff, in
 
 extern "C" size_t ia_conformer_prefix_ws_sums_offset(int B, int T, int d, int d_ff, int H, int ksz, int pos_rows) {
     if (B <= 0 || T <= 0 || d <= 0 || d_ff <= 0 || H <= 0 || ksz <= 0 || pos_rows <= 0) return 0;
-    return prefix_ws(B, T, d, d_ff, H, ksz, pos_rows).sums;
+    return prefix_ws(B, T, d, d_ff, ksz, pos_rows).sums;
 }
 
 extern "C" int ia_conformer_prefix_fwd(const ia_block_params* layers, int n_layers, float* x, const void* pos_emb,
@@ -79,11 +79,12 @@ extern "C" int ia_conformer_prefix_fwd_seg(const ia_block_params* layers, int n_
     const ia_block_params& l0 = layers[0];
     const int d = l0.d, d_ff = l0.d_ff, H = l0.n_heads, dk = d / (H > 0 ? H : 1), ksz = l0.ksz;
     if (pos_rows < 2 * T - 1) return IA_INVALID_VALUE;
-    const PrefixWs w = prefix_ws(B, T, d, d_ff, H, ksz, pos_rows);
+    const PrefixWs w = prefix_ws(B, T, d, d_ff, ksz, pos_rows);
     if (workspace_bytes < w.total) return IA_WORKSPACE_TOO_SMALL;
+    if (H <= 0) return IA_INVALID_VALUE;
+    if (!ia_relpos_attention_flash_supported(T, dk)) return IA_UNSUPPORTED;   // before anything rewrites x in place
     char* ws = (char*)workspace;
-    void *y = ws + w.y, *h = ws + w.h, *qkv = ws + w.qkv, *pl = ws + w.pl, *ctx = ws + w.ctx, *c2 = ws + w.c2, *c3 = ws + w.c3,
-         *vt = ws + w.vt;
+    void *y = ws + w.y, *h = ws + w.h, *qkv = ws + w.qkv, *pl = ws + w.pl, *ctx = ws + w.ctx, *c2 = ws + w.c2, *c3 = ws + w.c3;
     float *z = (float*)(ws + w.z), *sums = (float*)(ws + w.sums), *scr = (float*)(ws + w.scr);
     long long* acc = (long long*)(ws + w.acc);
     const int N = B * T;
@@ -101,9 +102,6 @@ extern "C" int ia_conformer_prefix_fwd_seg(const ia_block_params* layers, int n_
         return IA_LAUNCH_FAILED;
     const char* glu_env = getenv("IA_PREFIX_GLU");   // "dwconv": GLU inside the depthwise-conv kernel (A/B switch)
     const bool glu_in_gemm = d % 64 == 0 && !(glu_env && glu_env[0] == 'd');
-    // attention: key-tile loop kernel (any T, head dim <= 64); IA_PREFIX_ATTN=old selects the all-keys-in-registers kernel
-    const char* attn_env = getenv("IA_PREFIX_ATTN");
-    const bool use_flash = ia_relpos_attention_flash_supported(T, dk) != 0 && !(attn_env && attn_env[0] == 'o');
     // LayerNorm in front of the first block's first feed-forward; later ones are chained behind the previous norm_out
     if (!ffn_fused && seg_begin == 0)
         IA_TRY(ia_layernorm(x, d, N, d, l0.ln_ff1_g, l0.ln_ff1_b, l0.ln_eps, nullptr, 0, nullptr, nullptr, y, d, stream));
@@ -141,10 +139,7 @@ extern "C" int ia_conformer_prefix_fwd_seg(const ia_block_params* layers, int n_
             IA_TRY(ia_gemm_bf16(pos_emb, d, L.w_pos, d, pos_rows, d, d, nullptr, 0, 0.f, 0, 1.f, nullptr, 0, nullptr, 0, pl, d, stream));
             plu = pl;
         }
-        if (use_flash)
-            IA_TRY(ia_relpos_attention_flash(qkv, plu, L.pos_u, L.pos_v, lens, B, T, H, dk, patt, seed + 7, ctx, stream));
-        else
-            IA_TRY(ia_relpos_attention(qkv, plu, L.pos_u, L.pos_v, lens, B, T, H, dk, patt, seed + 7, vt, ctx, stream));
+        IA_TRY(ia_relpos_attention_flash(qkv, plu, L.pos_u, L.pos_v, lens, B, T, H, dk, patt, seed + 7, ctx, stream));
         // out-projection (+ residual) and the convolution module's LayerNorm: one launch at d_model = 256 (64 x 256 tiles own
         // whole rows), two otherwise
         static const bool ln_in_gemm = [] { const char* e = getenv("IA_LN_IN_GEMM"); return !(e && e[0] == '0'); }();

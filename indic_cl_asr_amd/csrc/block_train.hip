@@ -279,8 +279,8 @@ extern "C" int ia_conformer_block_supported(int d, int d_ff, int H, int ksz, int
 // ------------------------------------------------------------------------------------------------ forward
 extern "C" int ia_conformer_block_fwd(const ia_block_params* Lp, const float* x0, const void* pos_emb, int pos_rows,
                                       const int64_t* lens, int B, int T, unsigned seed, const ia_block_saved* Sp, float* out,
-                                      void* vt_scratch, float* dw_scratch, ia_stream_t stream) {
-    return ia_conformer_block_fwd_phase(Lp, x0, pos_emb, pos_rows, lens, B, T, seed, Sp, out, vt_scratch, dw_scratch, 0, stream);
+                                      float* dw_scratch, ia_stream_t stream) {
+    return ia_conformer_block_fwd_phase(Lp, x0, pos_emb, pos_rows, lens, B, T, seed, Sp, out, dw_scratch, 0, stream);
 }
 
 // phase 0: the whole block.  SyncBatchNorm over several ranks: phase 1 = up to and including the BatchNorm sums (saved->sums =
@@ -288,9 +288,9 @@ extern "C" int ia_conformer_block_fwd(const ia_block_params* Lp, const float* x0
 // + SiLU onwards (running statistics untouched: ia_bn_sync_finish updated them from the global batch).
 extern "C" int ia_conformer_block_fwd_phase(const ia_block_params* Lp, const float* x0, const void* pos_emb, int pos_rows,
                                             const int64_t* lens, int B, int T, unsigned seed, const ia_block_saved* Sp,
-                                            float* out, void* vt_scratch, float* dw_scratch, int phase, ia_stream_t stream) {
+                                            float* out, float* dw_scratch, int phase, ia_stream_t stream) {
     if (phase < 0 || phase > 2) return IA_INVALID_VALUE;
-    if (!Lp || !x0 || !pos_emb || !lens || !Sp || !out || !vt_scratch || !dw_scratch || B <= 0 || T <= 0) return IA_INVALID_VALUE;
+    if (!Lp || !x0 || !pos_emb || !lens || !Sp || !out || !dw_scratch || B <= 0 || T <= 0) return IA_INVALID_VALUE;
     const ia_block_params& L = *Lp;
     const ia_block_saved& S = *Sp;
     const int d = L.d, d_ff = L.d_ff, H = L.n_heads, dk = d / (H > 0 ? H : 1), ksz = L.ksz, N = B * T;

@@ -6,7 +6,6 @@
 //   ia_scale_dropout_bf16 .. branch-output gradient: bf16(alpha * keep * scale * d y)   (residual dropout + fc_factor)
 //   ia_bn_silu_bwd_reduce / _apply   SiLU' + train-mode BatchNorm backward (per-channel sums, then d z, d gamma, d beta)
 //   ia_glu_mask ............ G = mask(GLU(c2)) in fp32 (depthwise-conv weight gradient needs it), ia_glu_bwd: d c2 from d G
-//   ia_attn_keepmask ....... the attention-dropout keep mask of attention.hip as a tensor (autograd recompute path)
 #include <hip/hip_bf16.h>
 
 #include "dropout_mask.h"
@@ -274,20 +273,6 @@ __global__ __launch_bounds__(256) void glu_kernel(const __bf16* __restrict__ c2,
     }
 }
 
-__global__ __launch_bounds__(256) void attn_keepmask_kernel(int B, int H, int T, unsigned seed, unsigned thr, float keep_scale,
-                                                            __bf16* __restrict__ mask) {
-    // attention.hip's at_keep_rand4: one hash per (head, 4 query rows, key), row i takes byte i & 3
-    const int64_t total = (int64_t)B * H * T * T;
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-        const int j = (int)(e % T);
-        const int64_t r = e / T;
-        const int i = (int)(r % T), bh = (int)(r / T);
-        const unsigned idx = ((unsigned)bh * (unsigned)((T + 3) >> 2) + (unsigned)(i >> 2)) * (unsigned)T + (unsigned)j;
-        const unsigned rnd = (ia_dm_hash32(idx * 0x9E3779B1u + seed) >> (8 * (i & 3))) & 0xFFu;
-        mask[e] = (__bf16)((rnd >= thr) ? keep_scale : 0.f);
-    }
-}
-
 inline int ew_grid(int64_t items) {
     const int64_t b = (items + 255) / 256;
     return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
@@ -529,16 +514,6 @@ extern "C" int ia_glu_bwd(const void* c2, const float* dG, const int64_t* lens, 
     if (!c2 || !dG || !lens || !dc2 || B <= 0 || T <= 0 || d <= 0) return IA_INVALID_VALUE;
     hipLaunchKernelGGL((glu_kernel<1>), dim3(ew_grid((int64_t)B * T * d)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)c2, dG,
                        lens, B, T, d, (float*)nullptr, (__bf16*)dc2);
-    IA_RETURN_IF_LAUNCH_FAILED();
-    return IA_OK;
-}
-
-extern "C" int ia_attn_keepmask(int B, int H, int T, float dropout_p, unsigned seed, void* mask_bf16, ia_stream_t stream) {
-    if (!mask_bf16 || B <= 0 || H <= 0 || T <= 0 || dropout_p < 0.f || dropout_p >= 1.f) return IA_INVALID_VALUE;
-    if ((int64_t)B * H * T * T >= ((int64_t)1 << 32)) return IA_UNSUPPORTED;
-    const auto [thr, ks] = ia_dropout_rule(dropout_p);
-    hipLaunchKernelGGL(attn_keepmask_kernel, dim3(ew_grid((int64_t)B * H * T * T)), dim3(256), 0, (hipStream_t)stream, B, H, T, seed,
-                       thr, ks, (__bf16*)mask_bf16);
     IA_RETURN_IF_LAUNCH_FAILED();
     return IA_OK;
 }

@@ -200,10 +200,7 @@ class ConformerLayer(nn.Module):
         if fast.attention_flash_supported(T, att.d_k):
             ctx = fast.relpos_attention_flash(qkv, pl, att.pos_bias_u, att.pos_bias_v, lens, B, T, att.h, att.d_k,
                                               att.dropout_rate if tr else 0.0, seed + 7)
-        elif fast.attention_supported(T, att.d_k):
-            ctx = fast.relpos_attention(qkv, pl, att.pos_bias_u, att.pos_bias_v, lens, B, T, att.h, att.d_k,
-                                        att.dropout_rate if tr else 0.0, seed + 7)
-        else:  # long inputs (T' > 384) / other head sizes: ATen composition
+        else:  # head sizes the key-tiled kernel does not take (above 64, or no multiple of 4): ATen composition
             qkv = qkv.view(B, T, 3, att.h, att.d_k)
             q, k, v = (qkv[:, :, i].transpose(1, 2) for i in range(3))
             ctx = ops.rel_pos_attention(q, k, v, pl.view(-1, att.h, att.d_k).transpose(0, 1), att.pos_bias_u,
@@ -376,8 +373,7 @@ class ConformerEncoder(nn.Module):
             l.fp8_projections = fp8
         # native executor: one C call for the whole prefix; with SyncBatchNorm over several ranks one call per block boundary,
         # the all-reduce of the BatchNorm sums in between (ops/fast.conformer_prefix).  fp8 projections: per-op path below.
-        if ((fast.attention_flash_supported(T, l0.self_attn.d_k) or fast.attention_supported(T, l0.self_attn.d_k)) and bn_ok
-                and same_mode and not fp8):
+        if fast.attention_flash_supported(T, l0.self_attn.d_k) and bn_ok and same_mode and not fp8:
             # native executor: one C call enqueues the 14 kernels of every block (csrc/block_exec.hip)
             fast.conformer_prefix(list(self.layers[:n_fast]), xr, pe, length, B, T, base, 16, l0.training)
             return xr.view(B, T, d), n_fast

@@ -385,16 +385,11 @@ class _ConformerBlockNativeFn(torch.autograd.Function):
         for f in _SAVED_FIELDS:
             setattr(saved, f, base + lay[f][0])
         out = torch.empty(N, d, dtype=torch.float32, device=dev)
-        att = layer.self_attn
-        nvt = L.ia_attn_vt_elems(B, T, att.h)
-        vt = fast._VT.get((dev.index, nvt))
-        if vt is None:
-            vt = fast._VT[(dev.index, nvt)] = torch.empty(nvt, dtype=torch.bfloat16, device=dev)
         dw_scr = fast.scratch(dev, L.ia_dwconv_scratch_elems(B, T, d, rt.ksz))
         bn = layer.conv.batch_norm
         group = fast.bn_sync_group(bn)
         fwd_args = (ctypes.addressof(bp), _ptr(x0), _ptr(pe), pe.shape[0], _ptr(lens), B, T, int(seed) & 0xFFFFFFFF,
-                    ctypes.addressof(saved), _ptr(out), _ptr(vt), _ptr(dw_scr))
+                    ctypes.addressof(saved), _ptr(out), _ptr(dw_scr))
         if group is None:
             _lib.check(L.ia_conformer_block_fwd(*fwd_args, _lib.stream_ptr()), "ia_conformer_block_fwd")
         else:   # SyncBatchNorm over several ranks: split at the exchange of the BatchNorm sums

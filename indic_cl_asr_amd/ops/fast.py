@@ -431,16 +431,8 @@ def glu_dwconv_bn_silu_fast(x2_bf16, lens, B, T, d, dw_weight, dw_bias, bn, trai
     return out
 
 
-def attention_supported(T, dk):
-    """The all-keys-in-registers kernel pair (forward + backward row pass) of the trainable blocks."""
-    return dk == 64 and T <= 384
-
-
-USE_FLASH_ATTN = True   # tests flip this to compare the two forward kernels
-
-
 def attention_flash_supported(T, dk):
-    return USE_FLASH_ATTN and bool(_lib.lib().ia_relpos_attention_flash_supported(int(T), int(dk)))
+    return bool(_lib.lib().ia_relpos_attention_flash_supported(int(T), int(dk)))
 
 
 def relpos_attention_flash(qkv_bf16, pos_proj_bf16, bias_u, bias_v, lens, B, T, H, dk, dropout_p=0.0, seed=0, want_lse=False):
@@ -488,71 +480,18 @@ def relpos_attention_flash_bwd(qkv, pl, bias_u, bias_v, lens, ctx, dctx, lse, B,
     return dqkv, dpl, dub[0], dub[1]
 
 
-_VT = {}
-
-
 def relpos_attention(qkv_bf16, pos_proj_bf16, bias_u, bias_v, lens, B, T, H, dk, dropout_p=0.0, seed=0):
-    """qkv [B*T, 3*H*dk] bf16, pos_proj [2T-1, H*dk] bf16 -> ctx [B*T, H*dk] bf16 (csrc/attention.hip)."""
+    """The round-1 forward (csrc/attention.hip; head dim 64, T <= 384), kept for the tests' cross-checks only:
+    qkv [B*T, 3*H*dk] bf16, pos_proj [2T-1, H*dk] bf16 -> ctx [B*T, H*dk] bf16."""
     L = _lib.lib()
     dev = qkv_bf16.device
-    n = L.ia_attn_vt_elems(B, T, H)
-    key = (dev.index, n)
-    vt = _VT.get(key)
-    if vt is None:
-        vt = _VT[key] = torch.empty(n, dtype=torch.bfloat16, device=dev)
+    vt = torch.empty(L.ia_attn_vt_elems(B, T, H), dtype=torch.bfloat16, device=dev)
     ctx = torch.empty(B * T, H * dk, dtype=torch.bfloat16, device=dev)
     st = L.ia_relpos_attention(_lib.ptr(qkv_bf16), _lib.ptr(pos_proj_bf16), _lib.ptr(bias_u), _lib.ptr(bias_v),
                                _lib.ptr(lens), B, T, H, dk, float(dropout_p), int(seed) & 0xFFFFFFFF, _lib.ptr(vt),
                                _lib.ptr(ctx), _lib.stream_ptr())
     _lib.check(st, "ia_relpos_attention")
     return ctx
-
-
-def attention_bwd_dims(T):
-    import ctypes
-    ts, rs, p0 = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    _lib.check(_lib.lib().ia_relpos_attention_bwd_dims(int(T), ctypes.byref(ts), ctypes.byref(rs), ctypes.byref(p0)), "dims")
-    return ts.value, rs.value, p0.value
-
-
-def relpos_attention_bwd(qkv, pl, bias_u, bias_v, lens, ctx, dctx, B, T, H, dk, dropout_p=0.0, seed=0, dub_out=None):
-    """Backward of relpos_attention.  qkv [B*T,3d], pl [>=2T-1, d], ctx/dctx [B*T, d] (bf16) ->
-    (dqkv [B*T,3d] bf16, dpl [pl rows, d] bf16, dbias_u [H,dk] f32, dbias_v [H,dk] f32).
-    csrc/attention.hip writes dropout(P), dS and the band-skewed dS; the five contractions are batched GEMMs on them."""
-    L = _lib.lib()
-    dev = qkv.device
-    d = H * dk
-    Ts, Rs, pad0 = attention_bwd_dims(T)
-    bf = torch.bfloat16
-    Pd = torch.empty(B, H, T, Ts, dtype=bf, device=dev)
-    dS = torch.empty(B, H, T, Ts, dtype=bf, device=dev)
-    dBand = torch.empty(H, B * T, Rs, dtype=bf, device=dev)
-    Qu, K, dO = (torch.empty(B, H, T, dk, dtype=bf, device=dev) for _ in range(3))
-    Qv = torch.empty(H, B * T, dk, dtype=bf, device=dev)
-    dctx = dctx.contiguous()
-    st = L.ia_relpos_attention_bwd(_lib.ptr(qkv), _lib.ptr(pl), _lib.ptr(bias_u), _lib.ptr(bias_v), _lib.ptr(lens), _lib.ptr(ctx),
-                                   _lib.ptr(dctx), B, T, H, dk, float(dropout_p), int(seed) & 0xFFFFFFFF, _lib.ptr(Pd),
-                                   _lib.ptr(dS), _lib.ptr(dBand), _lib.ptr(Qu), _lib.ptr(Qv), _lib.ptr(K), _lib.ptr(dO),
-                                   _lib.stream_ptr())
-    _lib.check(st, "ia_relpos_attention_bwd")
-    Pv, dSv = (Pd, dS) if Ts == T else (Pd[..., :T], dS[..., :T])
-    dV = torch.matmul(Pv.transpose(-1, -2), dO)                                                # [B,H,T,dk]
-    dK = torch.matmul(dSv.transpose(-1, -2), Qu)
-    dQu = torch.matmul(dSv, K)
-    R = 2 * T - 1
-    posB = torch.zeros(H, Rs, dk, dtype=bf, device=dev)
-    posB[:, pad0:pad0 + R] = pl[:R].view(R, H, dk).permute(1, 0, 2)
-    dQv = torch.bmm(dBand, posB)                                                               # [H,B*T,dk]
-    dposB = torch.bmm(dBand.transpose(1, 2), Qv)                                               # [H,Rs,dk]
-    dqkv = torch.empty(B * T, 3 * d, dtype=bf, device=dev)
-    dub = dub_out if dub_out is not None else torch.empty(2, H, dk, dtype=torch.float32, device=dev)   # (dbias_u, dbias_v) destinations
-    st = L.ia_attn_bwd_unpack(_lib.ptr(dQu), _lib.ptr(dQv), _lib.ptr(dK), _lib.ptr(dV), _lib.ptr(dqkv), _lib.ptr(dub[0]),
-                              _lib.ptr(dub[1]), B, T, H, dk, _lib.ptr(scratch(dev, L.ia_attn_bwd_unpack_scratch_elems(B, T, H))),
-                              _lib.stream_ptr())
-    _lib.check(st, "ia_attn_bwd_unpack")
-    dpl = torch.zeros_like(pl)
-    dpl[:R] = dposB[:, pad0:pad0 + R].permute(1, 0, 2).reshape(R, d)
-    return dqkv, dpl, dub[0], dub[1]
 
 
 def colsum(x_bf16):

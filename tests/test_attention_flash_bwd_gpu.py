@@ -105,18 +105,20 @@ def test_flash_backward_regenerates_the_forward_dropout_mask():
     _check("du", du, r_u, 3e-2)
 
 
-def test_flash_backward_agrees_with_the_row_pass_backward():
+def test_flash_backward_matches_fp64_autograd_at_the_bench_shape():
+    """Four utterances of the benchmark's T' = 376, 4 heads of 64; every gradient held on its own."""
     from indic_cl_asr_amd.ops import fast
     B, T, H, dk = 4, 376, 4, 64
     qkv, pl, bu, bv, ln = _inputs(B, T, H, dk, seed=3)
     dctx = (torch.randn(B * T, H * dk, device="cuda") * 0.5).bfloat16()
     ctx, lse = fast.relpos_attention_flash(qkv, pl, bu, bv, ln, B, T, H, dk, want_lse=True)
-    a = fast.relpos_attention_flash_bwd(qkv, pl, bu, bv, ln, ctx, dctx, lse, B, T, H, dk)
-    ctx2 = fast.relpos_attention(qkv, pl, bu, bv, ln, B, T, H, dk)
-    b = fast.relpos_attention_bwd(qkv, pl, bu, bv, ln, ctx2, dctx, B, T, H, dk)
-    for x, y, nm in zip(a, b, ("dqkv", "dpl", "du", "dv")):
-        err = (x.float() - y.float()).abs().max().item()
-        assert err <= 3e-2 * y.float().abs().max().item() + 1e-4, (nm, err)
+    dqkv, dpl, du, dv = fast.relpos_attention_flash_bwd(qkv, pl, bu, bv, ln, ctx, dctx, lse, B, T, H, dk)
+    r_qkv, r_pl, r_u, r_v = _grads64(qkv, pl, bu, bv, ln, dctx, B, T, H, dk)
+    d = H * dk
+    pairs = (("dq", dqkv[:, :d], r_qkv[:, :d]), ("dk", dqkv[:, d:2 * d], r_qkv[:, d:2 * d]), ("dv", dqkv[:, 2 * d:], r_qkv[:, 2 * d:]),
+             ("dpl", dpl[:2 * T - 1], r_pl), ("du", du, r_u), ("dv_bias", dv, r_v))
+    for nm, x, y in pairs:
+        _check(nm, x, y, 3e-2)
 
 
 def test_flash_backward_with_an_empty_utterance_gives_zero_gradients_for_it():

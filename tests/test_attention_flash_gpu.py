@@ -68,6 +68,18 @@ def test_flash_attention_agrees_with_the_register_resident_kernel():
     assert (a - b).abs().max().item() <= 2e-2 * b.abs().max().item()
 
 
+def test_flash_attention_matches_fp64_restatement_at_the_bench_shape():
+    """The inputs of the cross-check above against the fp64 restatement itself: the pure relative bound, without the
+    absolute slack of the parametrised cases."""
+    from indic_cl_asr_amd.ops import fast
+    B, T, H, dk = 4, 376, 4, 64
+    qkv, pl, bu, bv, ln = _inputs(B, T, H, dk, seed=3)
+    a = fast.relpos_attention_flash(qkv, pl, bu, bv, ln, B, T, H, dk).double()
+    b = _reference(qkv, pl, bu, bv, ln, B, T, H, dk)
+    err = (a - b).abs().max().item()
+    assert err <= 2e-2 * b.abs().max().item(), err
+
+
 def test_flash_attention_dropout_is_unbiased_and_deterministic():
     from indic_cl_asr_amd.ops import fast
     B, T, H, dk = 2, 256, 2, 64

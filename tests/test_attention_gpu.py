@@ -1,5 +1,6 @@
-"""HIP rel-pos attention kernel against an fp64 restatement of the reference's arithmetic (rel_shift pad/view trick
-included) on the same bf16-quantised operands."""
+"""Rel-pos attention against an fp64 restatement of the reference's arithmetic (rel_shift through the pad / view trick,
+independent of the gather-index restatement in test_attention_flash_gpu.py) on the same bf16-quantised operands: both
+forward kernels and the key-tiled backward."""
 import math
 
 import pytest
@@ -24,9 +25,10 @@ def _reference(q, k, v, p, u, vb, lens):
     return attn @ v.double()
 
 
-@pytest.mark.parametrize("B,T,H", [(2, 37, 2), (3, 64, 1), (2, 376, 4), (1, 17, 3)])
-def test_relpos_attention_matches_reference_formula(B, T, H):
-    from indic_cl_asr_amd.ops import fast
+_FORWARD_CASES = [(2, 37, 2), (3, 64, 1), (2, 376, 4), (1, 17, 3)]
+
+
+def _forward_matches_reference_formula(forward, B, T, H):
     dk = 64
     g = torch.Generator().manual_seed(T)
     d = H * dk
@@ -35,7 +37,7 @@ def test_relpos_attention_matches_reference_formula(B, T, H):
     u = torch.randn(H, dk, generator=g) * 0.3
     vb = torch.randn(H, dk, generator=g) * 0.3
     lens = torch.randint(max(1, T // 2), T + 1, (B,), generator=g); lens[0] = T
-    ctx = fast.relpos_attention(qkv.cuda(), pl.cuda(), u.cuda(), vb.cuda(), lens.cuda(), B, T, H, dk).float().cpu()
+    ctx = forward(qkv.cuda(), pl.cuda(), u.cuda(), vb.cuda(), lens.cuda(), B, T, H, dk).float().cpu()
     x = qkv.float().view(B, T, 3, H, dk)
     q, k, v = (x[:, :, i].transpose(1, 2) for i in range(3))
     ref = _reference(q, k, v, pl.float().view(-1, H, dk).transpose(0, 1), u, vb, lens)   # [B,h,T,dk]
@@ -46,17 +48,46 @@ def test_relpos_attention_matches_reference_formula(B, T, H):
     assert (ctx * (~valid)).abs().max().item() == 0.0        # padded queries -> zero context
 
 
-def _keepmask(B, H, T, p, seed):
-    from indic_cl_asr_amd import _lib
-    keep = torch.empty(B, H, T, T, dtype=torch.bfloat16, device="cuda")
-    _lib.check(_lib.lib().ia_attn_keepmask(B, H, T, float(p), seed, _lib.ptr(keep), _lib.stream_ptr()), "keepmask")
-    return keep.float().cpu()
+@pytest.mark.parametrize("B,T,H", _FORWARD_CASES)
+def test_relpos_attention_matches_reference_formula(B, T, H):
+    """The round-1 forward (csrc/attention.hip), which no product path runs any more."""
+    from indic_cl_asr_amd.ops import fast
+    _forward_matches_reference_formula(fast.relpos_attention, B, T, H)
+
+
+@pytest.mark.parametrize("B,T,H", _FORWARD_CASES)
+def test_relpos_attention_flash_matches_reference_formula(B, T, H):
+    """The key-tiled forward (csrc/attention_flash.hip), the one that ships: same cases, same assertions."""
+    from indic_cl_asr_amd.ops import fast
+    _forward_matches_reference_formula(fast.relpos_attention_flash, B, T, H)
+
+
+def _keepmask(qkv, pl, u, vb, lens, B, T, H, dk, p, seed):
+    """The forward kernel's own keep mask times its keep scale, [B,H,T,T]: per block of 64 keys one forward call with the
+    same (p, seed) whose V rows are one-hot inside the block and zero outside, so the output is dropout(P) restricted to
+    that block.  The mask depends on (seed, b, h, T, query, key) only, never on V.  Keys at or beyond the length never show
+    (P = 0 there) and count as kept: they carry no gradient either way."""
+    from indic_cl_asr_amd.ops import fast
+    keep = torch.ones(B, H, T, T, dtype=torch.float64)
+    for k0 in range(0, T, 64):
+        n = min(64, T - k0)
+        probe = qkv.clone().view(B, T, 3, H, dk)
+        probe[:, :, 2] = 0
+        probe[:, k0:k0 + n, 2] = torch.eye(64, dtype=torch.bfloat16)[None, :n, None, :dk]
+        pd = fast.relpos_attention_flash(probe.view(B * T, -1).cuda(), pl, u, vb, lens, B, T, H, dk, p, seed)
+        keep[..., k0:k0 + n] = (pd.view(B, T, H, dk).transpose(1, 2)[..., :n] > 0).double().cpu()
+    q = 1.0 - round(256 * p) / 256.0                                            # utterance 0 has full length: all of it shows
+    frac = keep[0].mean().item()
+    assert abs(frac - q) < 5 * math.sqrt(q * (1 - q) / keep[0].numel()), (frac, q)   # five sigma of a fair mask
+    beyond = torch.arange(T)[None, :] >= lens.cpu()[:, None]                    # [B,T] keys
+    keep.masked_fill_(beyond[:, None, None, :], 1.0)
+    return keep * (256.0 / (256.0 - round(256 * p)))
 
 
 @pytest.mark.parametrize("B,T,H,p", [(2, 37, 2, 0.0), (2, 40, 1, 0.25), (2, 376, 4, 0.1), (1, 17, 3, 0.0), (3, 100, 2, 0.5)])
 def test_relpos_attention_backward_matches_autograd_of_reference_formula(B, T, H, p):
-    """dqkv, d(pos projection), d(pos_bias_u/v) of the HIP backward (row pass + batched GEMMs) against fp64 autograd of
-    the reference formula on the same bf16 operands and -- with dropout -- the same counter-based keep mask."""
+    """dqkv, d(pos projection), d(pos_bias_u/v) of the key-tiled backward against fp64 autograd of the reference formula on
+    the same bf16 operands and -- with dropout -- the keep mask read back from the forward kernel (_keepmask)."""
     from indic_cl_asr_amd.ops import fast
     dk, seed = 64, 977
     g = torch.Generator().manual_seed(T + 1)
@@ -69,8 +100,9 @@ def test_relpos_attention_backward_matches_autograd_of_reference_formula(B, T, H
     valid = (torch.arange(T)[None, :] < lens[:, None]).reshape(B * T, 1)
     dctx = ((torch.randn(B * T, d, generator=g) * valid).bfloat16())     # padded frames never receive gradient
     dev = lambda t: t.cuda()
-    ctx = fast.relpos_attention(dev(qkv), dev(pl), dev(u), dev(vb), dev(lens), B, T, H, dk, p, seed)
-    dqkv, dpl, du, dvb = fast.relpos_attention_bwd(dev(qkv), dev(pl), dev(u), dev(vb), dev(lens), ctx, dev(dctx), B, T, H, dk, p, seed)
+    args = (dev(pl), dev(u), dev(vb), dev(lens))
+    ctx, lse = fast.relpos_attention_flash(dev(qkv), *args, B, T, H, dk, p, seed, want_lse=True)
+    dqkv, dpl, du, dvb = fast.relpos_attention_flash_bwd(dev(qkv), *args, ctx, dev(dctx), lse, B, T, H, dk, p, seed)
     # fp64 autograd reference
     x = qkv.double().view(B, T, 3, H, dk).requires_grad_(True)
     P = pl.double().view(-1, H, dk).requires_grad_(True)
@@ -85,7 +117,7 @@ def test_relpos_attention_backward_matches_autograd_of_reference_formula(B, T, H
     mask = ~(vm[:, :, None] & vm[:, None, :])
     attn = torch.softmax(scores.masked_fill(mask.unsqueeze(1), -10000.0), -1).masked_fill(mask.unsqueeze(1), 0.0)
     if p > 0:
-        attn = attn * _keepmask(B, H, T, p, seed).double()
+        attn = attn * _keepmask(qkv, *args, B, T, H, dk, p, seed)
     out = (attn @ v).transpose(1, 2).reshape(B * T, d)
     out.backward(dctx.double())
     def rel(a, b):
