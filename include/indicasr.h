@@ -733,6 +733,27 @@ int ia_glu_bwd(const void* c2, const float* dG, const int64_t* lens, int B, int 
  *                          exit), seg_step[nseg] i32 per-tensor step counters (advanced here); a tensor is live when any
  *                          bit of its gradient is set, or always when all_active != 0 (a penalty was pre-loaded into
  *                          every .grad: set_grads R/utils.py:316-321).  Three launches on `stream`.
+ * ia_grad_norm             torch.nn.utils.clip_grad_norm_'s L2 norm and coefficient of the flat gradient, left on the device
+ *                          and bitwise reproducible (no float atomics).  Two launches: (1) workgroup c stores the fp32 sum of
+ *                          squares of chunk c into workspace[c] (ia_grad_norm_workspace_bytes(nchunks) bytes) and, when
+ *                          seg_active is not NULL, sets seg_active[k] for every tensor with a set gradient bit -- the pass
+ *                          ia_adamw_step_segmented makes for its live-tensor flags, so the norm adds no pass over the
+ *                          gradient; (2) one workgroup adds the chunk sums in fp64 in a fixed order, per tensor first
+ *                          (seg_chunk_begin: int32[nseg+1], chunks [begin[k], begin[k+1]) of the table belong to tensor k),
+ *                          then over tensors, and writes
+ *                            seg_norm[k]   = (float)sqrt(sum_k) * |grad_scale|
+ *                            norm_state[0] = total_norm = (float)sqrt(sum) * |grad_scale|
+ *                            norm_state[1] = coef = min(1, max_norm / (total_norm + 1e-6f)) in fp32 (NaN stays NaN);
+ *                                            max_norm <= 0 ("measure only") gives 1
+ *                            norm_state[2] = 1.0f when the sum is inf or NaN, else 0.0f
+ *                            norm_state[3] = max_norm
+ * ia_adamw_step_segmented_clipped  ia_adamw_step_segmented on the gradient (grad * grad_scale) * coef (two fp32 roundings
+ *                          in that order: with grad_scale == 1 it is torch's g.mul_(coef) bit for bit), coef and the
+ *                          non-finite flag read from norm_state on the device.  Unless all_active != 0, seg_active must hold
+ *                          what ia_grad_norm left there for the same gradient.  With skip_nonfinite != 0 and the flag set
+ *                          the launch leaves theta, both moments and the shadow untouched, clears seg_active, advances no
+ *                          seg_step and increments counters[1]; otherwise counters[0] is incremented when coef < 1
+ *                          (counters: int32[2] = {clipped steps, skipped steps}).  Two launches (+ a memset) on `stream`.
  */
 int ia_cl_chunk_elems(void);
 int ia_cl_penalty(const float* theta, const float* theta_star, const float* weight, float coef, float* grad,
@@ -747,6 +768,15 @@ int ia_adamw_step_segmented(float* theta, const float* grad, float* exp_avg, flo
                             int nchunks, int32_t* seg_active, int32_t* seg_step, int nseg, int all_active, float lr,
                             float beta1, float beta2, float eps, float weight_decay, float grad_scale, void* shadow_bf16,
                             ia_stream_t stream);
+size_t ia_grad_norm_workspace_bytes(int nchunks);
+int ia_grad_norm(const float* grad, const int32_t* chunk_table, int nchunks, const int32_t* seg_chunk_begin, int nseg,
+                 float grad_scale, float max_norm, int32_t* seg_active, float* seg_norm, float* norm_state, void* workspace,
+                 size_t workspace_bytes, ia_stream_t stream);
+int ia_adamw_step_segmented_clipped(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq,
+                                    const int32_t* chunk_table, int nchunks, int32_t* seg_active, int32_t* seg_step, int nseg,
+                                    int all_active, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                    float grad_scale, void* shadow_bf16, const float* norm_state, int skip_nonfinite,
+                                    int32_t* counters, ia_stream_t stream);
 
 /* ---- CTC head + loss on RAW logits (ConvASRDecoder.forward + CTCLoss.forward, A/modules/conv_asr.py:459-490 and
  * A/losses/ctc.py:68-82, without the [B,T,V] log-prob tensor and without a softmax backward pass): logits [B*T, ld] f32 with V

@@ -200,6 +200,10 @@ SIGNATURES = {
     "ia_cl_abs_accumulate": (_i, [_vp, _vp, _i64, _vp]),
     "ia_adamw_step": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _f, _vp, _vp]),
     "ia_adamw_step_segmented": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp]),
+    "ia_grad_norm_workspace_bytes": (_sz, [_i]),
+    "ia_grad_norm": (_i, [_vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ia_adamw_step_segmented_clipped": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _i,
+                                             _vp, _vp]),
 }
 
 _lib = None

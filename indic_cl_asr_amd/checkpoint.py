@@ -9,6 +9,8 @@
   the same two members so that weights trained here load back into the reference.
 * continual-learning state -- Fisher / omega / theta* flat buffers with their tensor table (`save_cl_state` /
   `load_cl_state`); the reference keeps these in process memory only and loses them on restart.
+* optimizer state -- FusedAdamW's moments, per-tensor step counters, hyper-parameters and clip / skip counters
+  (`save_optimizer` / `load_optimizer`), with the same layout check, so that a task can be resumed.
 """
 import io
 import os
@@ -150,3 +152,14 @@ def load_cl_state(path, flat):
             raise ValueError(f"{path}: '{key}' was saved for a different set of trainable tensors")
         res[key] = FlatDict(flat, rec["flat"].to(flat.theta.device))
     return res
+
+
+def save_optimizer(opt, path):
+    """Persist cl.FusedAdamW.state_dict() (a pending deferred update is applied first)."""
+    torch.save(opt.state_dict(), path)
+
+
+def load_optimizer(opt, path):
+    """Inverse of save_optimizer; refuses a file whose tensor table differs from the optimizer's model."""
+    opt.load_state_dict(torch.load(path, map_location="cpu"), source=path)
+    return opt

@@ -68,6 +68,11 @@ class FlatParams:
             for c0 in range(0, k, ch):
                 rows.append((o + c0, min(ch, k - c0), seg, 0))
         self.chunk_table = torch.tensor(rows, dtype=torch.int32, device=dev)
+        # chunks of tensor k are rows [seg_chunk_begin[k], seg_chunk_begin[k+1]) of the table (ia_grad_norm's per-tensor sums)
+        begin = [0]
+        for n, o, k, shape in self.entries:
+            begin.append(begin[-1] + (k + ch - 1) // ch)
+        self.seg_chunk_begin = torch.tensor(begin, dtype=torch.int32, device=dev)
         self.seg_inv_numel = torch.tensor([1.0 / e[2] for e in self.entries], dtype=torch.float32, device=dev)
         # True once something gave EVERY trainable tensor a gradient since the last zero_grad (a pre-loaded EWC penalty /
         # the MAS penalty: R/utils.py:316-321, R/cl_baseline_mas.py:231-234) -- torch.optim.AdamW then updates them all
@@ -332,8 +337,17 @@ class FusedAdamW:
     exists -- the reference wraps the model in DDP but never arms its reducer."""
 
     def __init__(self, model_or_flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, group=None,
-                 bf16_shadow=None, defer_update=True, grad_exchange_dtype=None):
-        """`grad_exchange_dtype="bf16"` ("fp32 or bf16"): the data-parallel exchange all-reduces a bf16 image of the
+                 bf16_shadow=None, defer_update=True, grad_exchange_dtype=None, max_grad_norm=None, skip_nonfinite=False,
+                 track_grad_norm=False):
+        """`max_grad_norm=c`: torch.nn.utils.clip_grad_norm_(parameters, c) applied inside the step, to the gradient the
+        update consumes -- after the data-parallel all-reduce, so every rank clips the AVERAGED gradient by the same factor
+        (the torch call between backward() and step() would clip each rank's local gradient: the exchange happens in here).
+        `skip_nonfinite=True`: a step whose gradient norm is inf or NaN changes nothing (torch.amp.GradScaler.step's skip)
+        and is counted.  `track_grad_norm=True`: measure the norms without clipping.  Norm, coefficient and counters stay
+        on the device: `last_grad_norm`, `stats()`, `grad_norms()`.  With all three at their defaults the step is the plain
+        ia_adamw_step_segmented.  `max_grad_norm` / `skip_nonfinite` live in param_groups[0] and are read per step, as lr is.
+
+        `grad_exchange_dtype="bf16"` ("fp32 or bf16"): the data-parallel exchange all-reduces a bf16 image of the
         flat gradient (half the bytes over xGMI: 80 instead of 160 MB per step at 40 M trainable parameters); every rank
         then applies AdamW to the same bf16-rounded sum, so the weights stay identical across ranks.  None: fp32 exchange."""
         self.flat = model_or_flat if isinstance(model_or_flat, FlatParams) else flat_of(model_or_flat)
@@ -363,7 +377,16 @@ class FusedAdamW:
         if bf16_shadow is None:  # the HIP GEMM paths consume bf16 weights: let the optimizer kernel emit them (one launch)
             bf16_shadow = self.flat.theta.is_cuda
         self.shadow = self.flat.theta.to(torch.bfloat16) if bf16_shadow else None
-        self.param_groups = [dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, params=self.flat.params)]
+        self.param_groups = [dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
+                                  skip_nonfinite=skip_nonfinite, params=self.flat.params)]
+        self.track_grad_norm = track_grad_norm
+        # {total_norm, coef, non-finite flag, max_norm} as fp32 + {clipped steps, skipped steps} as int32 in ONE device buffer
+        # (stats() reads it in one copy); the per-tensor norms and the chunk sums are allocated by the first clipped step
+        self._norm_buf = torch.zeros(6, dtype=torch.int32, device=self.flat.theta.device)
+        self._norm_state = self._norm_buf[:4].view(torch.float32)
+        self._norm_state.copy_(torch.tensor([float("nan"), 1.0, 0.0, 0.0]))
+        self._counters = self._norm_buf[4:]
+        self._seg_norm = self._norm_ws = None
         self.defer_update = defer_update   # data parallel only: overlap the gradient all-reduce with the next forward
         self._pending, self._zero_after_flush = None, False
 
@@ -437,16 +460,59 @@ class FusedAdamW:
             self._zero_after_flush = False
             self.flat.zero_grad()
 
+    # -- gradient norm / clip / skip ------------------------------------------------------------------------------
+    @property
+    def last_grad_norm(self) -> torch.Tensor:
+        """0-dim device view of the latest step's gradient norm (NaN before the first measured step); no sync, valid until
+        the next step."""
+        return self._norm_state[0]
+
+    def stats(self) -> dict:
+        """One small device-to-host read: the latest norm and coefficient, and how many steps were clipped / skipped."""
+        self.flush()
+        host = self._norm_buf.cpu()
+        norm, coef = host[:2].view(torch.float32).tolist()
+        return {"grad_norm": norm, "clip_coef": coef, "clipped_steps": int(host[4]), "skipped_steps": int(host[5])}
+
+    def grad_norms(self) -> Dict[str, float]:
+        """name -> L2 norm of that tensor's gradient in the latest step (0 for a tensor that received none)."""
+        self.flush()
+        if self._seg_norm is None:
+            raise RuntimeError("grad_norms(): no step has measured the gradient yet (max_grad_norm / skip_nonfinite / "
+                               "track_grad_norm are all off, or step() has not run)")
+        return dict(zip(self.flat.names, self._seg_norm.tolist()))
+
     def _apply(self, scale, all_live=False):
         self.step_count += 1
         g = self.param_groups[0]
         f = self.flat
-        st = _lib.lib().ia_adamw_step_segmented(
-            _lib.ptr(f.theta), _lib.ptr(f.grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), _lib.ptr(f.chunk_table),
-            f.chunk_table.shape[0], _lib.ptr(self.seg_active), _lib.ptr(self.seg_step), len(f.entries), int(bool(all_live)),
-            float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
-            float(scale), _lib.ptr(self.shadow), _lib.stream_ptr())
-        _lib.check(st, "ia_adamw_step_segmented")
+        L = _lib.lib()
+        max_norm, skip = g.get("max_grad_norm"), bool(g.get("skip_nonfinite", False))
+        if max_norm is None and not skip and not self.track_grad_norm:
+            st = L.ia_adamw_step_segmented(
+                _lib.ptr(f.theta), _lib.ptr(f.grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), _lib.ptr(f.chunk_table),
+                f.chunk_table.shape[0], _lib.ptr(self.seg_active), _lib.ptr(self.seg_step), len(f.entries), int(bool(all_live)),
+                float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
+                float(scale), _lib.ptr(self.shadow), _lib.stream_ptr())
+            _lib.check(st, "ia_adamw_step_segmented")
+        else:
+            nchunks, nseg = f.chunk_table.shape[0], len(f.entries)
+            if self._seg_norm is None:
+                self._seg_norm = torch.zeros(nseg, dtype=torch.float32, device=f.theta.device)
+                self._norm_ws = torch.empty(L.ia_grad_norm_workspace_bytes(nchunks), dtype=torch.uint8, device=f.theta.device)
+            st = L.ia_grad_norm(
+                _lib.ptr(f.grad), _lib.ptr(f.chunk_table), nchunks, _lib.ptr(f.seg_chunk_begin), nseg, float(scale),
+                0.0 if max_norm is None else float(max_norm), None if all_live else _lib.ptr(self.seg_active),
+                _lib.ptr(self._seg_norm), _lib.ptr(self._norm_state), _lib.ptr(self._norm_ws), self._norm_ws.numel(),
+                _lib.stream_ptr())
+            _lib.check(st, "ia_grad_norm")
+            st = L.ia_adamw_step_segmented_clipped(
+                _lib.ptr(f.theta), _lib.ptr(f.grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), _lib.ptr(f.chunk_table),
+                nchunks, _lib.ptr(self.seg_active), _lib.ptr(self.seg_step), nseg, int(bool(all_live)),
+                float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
+                float(scale), _lib.ptr(self.shadow), _lib.ptr(self._norm_state), int(skip), _lib.ptr(self._counters),
+                _lib.stream_ptr())
+            _lib.check(st, "ia_adamw_step_segmented_clipped")
         if self.flat.theta.is_cuda:
             global LAST_UPDATE_EVENT
             LAST_UPDATE_EVENT = torch.cuda.Event()
@@ -457,6 +523,33 @@ class FusedAdamW:
             for (n, o, k, shape), q in zip(self.flat.entries, self.flat.params):
                 if q.dim() >= 2:
                     fast.register_flat_shadow(q, self.shadow[o:o + k].view(shape[0], -1))
+
+    # -- resumable state --------------------------------------------------------------------------------------------
+    def state_dict(self) -> dict:
+        """Moments, per-tensor step counters, hyper-parameters and the clip / skip counters as CPU tensors and plain values,
+        with the flat layout they belong to (a pending deferred update is applied first)."""
+        self.flush()
+        counters = self._counters.cpu()
+        return {"entries": list(self.flat.entries),
+                "exp_avg": self.exp_avg.detach().to("cpu", copy=True), "exp_avg_sq": self.exp_avg_sq.detach().to("cpu", copy=True),
+                "seg_step": self.seg_step.to("cpu", copy=True), "step_count": self.step_count,
+                "param_group": {k: v for k, v in self.param_groups[0].items() if k != "params"},
+                "clipped_steps": int(counters[0]), "skipped_steps": int(counters[1])}
+
+    def load_state_dict(self, sd: dict, source="state dict"):
+        """Inverse of state_dict(); refuses a state saved for another set of trainable tensors.  Weights and their bf16
+        images are not part of the optimizer state and are left alone."""
+        if [tuple(e[:3]) + (tuple(e[3]),) for e in sd["entries"]] != list(self.flat.entries):
+            raise ValueError(f"{source}: 'optimizer' was saved for a different set of trainable tensors")
+        self.flush()
+        self.exp_avg.copy_(sd["exp_avg"])
+        self.exp_avg_sq.copy_(sd["exp_avg_sq"])
+        self.seg_step.copy_(sd["seg_step"])
+        self.step_count = int(sd["step_count"])
+        hyper = dict(sd["param_group"])
+        hyper["betas"] = tuple(hyper["betas"])
+        self.param_groups[0].update(hyper)
+        self._counters.copy_(torch.tensor([sd["clipped_steps"], sd["skipped_steps"]], dtype=torch.int32))
 
 
 _PENDING_OPTIMIZERS = set()

@@ -5,6 +5,8 @@
 //   ia_cl_fisher_accumulate .. R/cl_baseline_ewc.py:245-255  F += mean(loss) * g^2
 //   ia_cl_abs_accumulate ..... R/cl_baseline_mas.py:267-270  omega += |g|
 //   ia_adamw_step ............ torch.optim.AdamW single-tensor update (R/cl_baseline.py:137 defaults)
+//   ia_grad_norm ............. torch.nn.utils.clip_grad_norm_'s norm and coefficient of the flat gradient, on the device
+//   ia_adamw_step_segmented_clipped .. the per-tensor AdamW on (g * grad_scale) * coef, skipped when the norm is not finite
 // All are HBM-streaming kernels: 16-byte accesses, grid capped at 2048 workgroups, fp32 math.
 #include "ia_common.h"
 
@@ -133,29 +135,109 @@ __global__ __launch_bounds__(CL_THREADS) void adamw_kernel(float* __restrict__ p
 // heads, heads of finished tasks) -- no weight decay, no moment decay, its own step counter.  With one flat gradient
 // buffer "None" is "the segment received nothing since zero_grad": all-zero bits (or the host says every segment is
 // live because a penalty was pre-loaded into .grad: R/utils.py:316-321 gives EVERY trainable tensor a gradient then).
+// SUMSQ folds the first half of the gradient's L2 norm into the same pass over the raw gradient: workgroup c also leaves the
+// fp32 sum of squares of chunk c in chunk_sumsq[c] with a plain store (no float atomics: grad_norm_finish_kernel adds the
+// partials in a fixed order, so the norm reproduces bit for bit), and seg_active may then be NULL (every segment live: the
+// caller memsets).  Rounding depth of one chunk sum: 4 (x*x + y*y + z*z + w*w) + 4 (a thread's <= 4 float4 of a
+// 4096-element chunk) + 6 (DPP wave sum) + 3 (the four wave sums) = 17 fp32 roundings.
+template <bool SUMSQ>
 __global__ __launch_bounds__(CL_THREADS) void seg_activity_kernel(const float* __restrict__ g, const int4* __restrict__ table,
-                                                                  int nchunks, int* __restrict__ seg_active) {
+                                                                  int nchunks, int* __restrict__ seg_active,
+                                                                  float* __restrict__ chunk_sumsq) {
+    __shared__ float sh[CL_THREADS / 64];
     for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
         const int4 e = table[c];
         const int off = e.x, cnt = e.y, n4 = cnt >> 2;
         unsigned nz = 0;
+        float ss = 0.f;
         for (int q = threadIdx.x; q < n4; q += CL_THREADS) {
             const uint4 x = reinterpret_cast<const uint4*>(g + off)[q];
             nz |= (x.x | x.y | x.z | x.w) & 0x7FFFFFFFu;   // -0.0 counts as zero
+            if constexpr (SUMSQ) {
+                const float a = __uint_as_float(x.x), b = __uint_as_float(x.y), cc = __uint_as_float(x.z), d = __uint_as_float(x.w);
+                ss += a * a + b * b + cc * cc + d * d;
+            }
         }
-        for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) nz |= __float_as_uint(g[off + i]) & 0x7FFFFFFFu;
-        if (__any(nz != 0) && (threadIdx.x & 63) == 0) atomicOr(seg_active + e.z, 1);
+        for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) {
+            nz |= __float_as_uint(g[off + i]) & 0x7FFFFFFFu;
+            if constexpr (SUMSQ) ss += g[off + i] * g[off + i];
+        }
+        if ((!SUMSQ || seg_active) && __any(nz != 0) && (threadIdx.x & 63) == 0) atomicOr(seg_active + e.z, 1);
+        if constexpr (SUMSQ) {
+            const float t = block_sum(ss, sh);
+            if (threadIdx.x == 0) chunk_sumsq[c] = t;
+        }
     }
 }
 
+// Second half: ONE workgroup of GN_THREADS adds the chunk sums in fp64 in a fixed order -- wave w takes segments w, w + 16,
+// ...; its lanes stride over the segment's chunks (contiguous in the table: seg_chunk_begin), then a butterfly over the
+// lanes; the wave keeps a running fp64 total of its segments and thread 0 adds the 16 wave totals in order.
+// norm_state = {total_norm, coef, non-finite flag (0 / 1), max_norm}.
+constexpr int GN_THREADS = 1024;
+__global__ __launch_bounds__(GN_THREADS) void grad_norm_finish_kernel(const float* __restrict__ chunk_sumsq,
+                                                                      const int* __restrict__ seg_chunk_begin, int nseg,
+                                                                      float abs_scale, float max_norm,
+                                                                      float* __restrict__ seg_norm, float* __restrict__ norm_state) {
+    __shared__ double sh_w[GN_THREADS / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double wave_total = 0.0;
+    for (int s = wave; s < nseg; s += GN_THREADS / 64) {
+        const int c0 = seg_chunk_begin[s], c1 = seg_chunk_begin[s + 1];
+        double a = 0.0;
+        for (int c = c0 + lane; c < c1; c += 64) a += (double)chunk_sumsq[c];
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) a += __shfl_xor(a, d);
+        if (lane == 0) seg_norm[s] = (float)sqrt(a) * abs_scale;
+        wave_total += a;
+    }
+    if (lane == 0) sh_w[wave] = wave_total;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double sum = 0.0;
+        for (int w = 0; w < GN_THREADS / 64; ++w) sum += sh_w[w];
+        const float total = (float)sqrt(sum) * abs_scale;
+        float coef = 1.f;
+        if (max_norm > 0.f) {                      // clip_grad_norm_: clamp(max_norm / (total_norm + 1e-6), max=1); NaN stays NaN
+            coef = max_norm / (total + 1e-6f);
+            if (coef > 1.f) coef = 1.f;
+        }
+        norm_state[0] = total;
+        norm_state[1] = coef;
+        norm_state[2] = isfinite(sum) ? 0.f : 1.f;
+        norm_state[3] = max_norm;
+    }
+}
+
+// CLIP: the gradient is (g * grad_scale) * coef with coef = norm_state[1] read from the device, each product rounded to
+// fp32 on its own (never fused into the moment update), so that with grad_scale == 1 it is torch's g.mul_(coef) bit for
+// bit; when norm_state[2] flags a non-finite norm and skip_nonfinite is set the launch writes nothing at all.
+template <bool CLIP>
+__device__ __forceinline__ float eff_grad(float g, float grad_scale, float coef) {
+    if constexpr (!CLIP) {
+        return g * grad_scale;
+    } else {
+#pragma clang fp contract(off)
+        const float gs = g * grad_scale;
+        return gs * coef;
+    }
+}
+
+template <bool CLIP>
 __global__ __launch_bounds__(CL_THREADS) void adamw_seg_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                                float* __restrict__ m, float* __restrict__ v,
                                                                const int4* __restrict__ table, int nchunks,
                                                                const int* __restrict__ seg_active,
                                                                const int* __restrict__ seg_step, float lr, float b1, float b2,
                                                                float eps, float wd, float grad_scale,
-                                                               unsigned short* __restrict__ shadow_bf16) {
+                                                               unsigned short* __restrict__ shadow_bf16,
+                                                               const float* __restrict__ norm_state, int skip_nonfinite) {
     __shared__ float sh_c[2];
+    float coef = 1.f;
+    if (CLIP) {
+        if (skip_nonfinite && norm_state[2] != 0.f) return;
+        coef = norm_state[1];
+    }
     for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
         const int4 e = table[c];
         if (!seg_active[e.z]) {           // workgroup-uniform: untouched tensor -- only keep its bf16 image in step
@@ -180,10 +262,10 @@ __global__ __launch_bounds__(CL_THREADS) void adamw_seg_kernel(float* __restrict
             const float4 G = reinterpret_cast<const float4*>(g + off)[q];
             float4 M = reinterpret_cast<float4*>(m + off)[q];
             float4 V = reinterpret_cast<float4*>(v + off)[q];
-            adamw1(P.x, G.x * grad_scale, M.x, V.x, lr, b1, b2, eps, wd, step_size, inv_bc2_sqrt);
-            adamw1(P.y, G.y * grad_scale, M.y, V.y, lr, b1, b2, eps, wd, step_size, inv_bc2_sqrt);
-            adamw1(P.z, G.z * grad_scale, M.z, V.z, lr, b1, b2, eps, wd, step_size, inv_bc2_sqrt);
-            adamw1(P.w, G.w * grad_scale, M.w, V.w, lr, b1, b2, eps, wd, step_size, inv_bc2_sqrt);
+            adamw1(P.x, eff_grad<CLIP>(G.x, grad_scale, coef), M.x, V.x, lr, b1, b2, eps, wd, step_size, inv_bc2_sqrt);
+            adamw1(P.y, eff_grad<CLIP>(G.y, grad_scale, coef), M.y, V.y, lr, b1, b2, eps, wd, step_size, inv_bc2_sqrt);
+            adamw1(P.z, eff_grad<CLIP>(G.z, grad_scale, coef), M.z, V.z, lr, b1, b2, eps, wd, step_size, inv_bc2_sqrt);
+            adamw1(P.w, eff_grad<CLIP>(G.w, grad_scale, coef), M.w, V.w, lr, b1, b2, eps, wd, step_size, inv_bc2_sqrt);
             reinterpret_cast<float4*>(p + off)[q] = P;
             reinterpret_cast<float4*>(m + off)[q] = M;
             reinterpret_cast<float4*>(v + off)[q] = V;
@@ -198,7 +280,7 @@ __global__ __launch_bounds__(CL_THREADS) void adamw_seg_kernel(float* __restrict
         }
         for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) {
             float P = p[off + i], M = m[off + i], V = v[off + i];
-            adamw1(P, g[off + i] * grad_scale, M, V, lr, b1, b2, eps, wd, step_size, inv_bc2_sqrt);
+            adamw1(P, eff_grad<CLIP>(g[off + i], grad_scale, coef), M, V, lr, b1, b2, eps, wd, step_size, inv_bc2_sqrt);
             p[off + i] = P; m[off + i] = M; v[off + i] = V;
             if (shadow_bf16) { __hip_bfloat16 a = __float2bfloat16(P); shadow_bf16[off + i] = *reinterpret_cast<unsigned short*>(&a); }
         }
@@ -208,6 +290,19 @@ __global__ __launch_bounds__(CL_THREADS) void adamw_seg_kernel(float* __restrict
 __global__ void seg_step_advance_kernel(int* __restrict__ seg_active, int* __restrict__ seg_step, int nseg) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s < nseg) { seg_step[s] += seg_active[s] ? 1 : 0; seg_active[s] = 0; }
+}
+
+// ... after a clipped step: a skipped step only clears the flags; counters = {clipped steps, skipped steps}
+__global__ void seg_step_advance_clipped_kernel(int* __restrict__ seg_active, int* __restrict__ seg_step, int nseg,
+                                                const float* __restrict__ norm_state, int skip_nonfinite,
+                                                int* __restrict__ counters) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool skipped = skip_nonfinite && norm_state[2] != 0.f;
+    if (s < nseg) { seg_step[s] += (!skipped && seg_active[s]) ? 1 : 0; seg_active[s] = 0; }
+    if (s == 0) {
+        if (skipped) counters[1] += 1;
+        else if (norm_state[1] < 1.f) counters[0] += 1;
+    }
 }
 
 inline int cap_grid(int64_t work_items, int per_block) {
@@ -281,13 +376,55 @@ extern "C" int ia_adamw_step_segmented(float* theta, const float* grad, float* e
     if (all_active) {
         if (hipMemsetAsync(seg_active, 1, (size_t)nseg * sizeof(int32_t), st) != hipSuccess) return IA_LAUNCH_FAILED;  // 0x01010101: non-zero
     } else {
-        hipLaunchKernelGGL(seg_activity_kernel, dim3(grid), dim3(CL_THREADS), 0, st, grad, (const int4*)chunk_table, nchunks,
-                           seg_active);
+        hipLaunchKernelGGL(seg_activity_kernel<false>, dim3(grid), dim3(CL_THREADS), 0, st, grad, (const int4*)chunk_table, nchunks,
+                           seg_active, (float*)nullptr);
     }
-    hipLaunchKernelGGL(adamw_seg_kernel, dim3(grid), dim3(CL_THREADS), 0, st, theta, grad, exp_avg, exp_avg_sq,
+    hipLaunchKernelGGL(adamw_seg_kernel<false>, dim3(grid), dim3(CL_THREADS), 0, st, theta, grad, exp_avg, exp_avg_sq,
                        (const int4*)chunk_table, nchunks, seg_active, seg_step, lr, beta1, beta2, eps, weight_decay, grad_scale,
-                       (unsigned short*)shadow_bf16);
+                       (unsigned short*)shadow_bf16, (const float*)nullptr, 0);
     hipLaunchKernelGGL(seg_step_advance_kernel, dim3((nseg + 255) / 256), dim3(256), 0, st, seg_active, seg_step, nseg);
+    IA_RETURN_IF_LAUNCH_FAILED();
+    return IA_OK;
+}
+
+extern "C" size_t ia_grad_norm_workspace_bytes(int nchunks) { return nchunks > 0 ? (size_t)nchunks * sizeof(float) : 0; }
+
+extern "C" int ia_grad_norm(const float* grad, const int32_t* chunk_table, int nchunks, const int32_t* seg_chunk_begin, int nseg,
+                            float grad_scale, float max_norm, int32_t* seg_active, float* seg_norm, float* norm_state,
+                            void* workspace, size_t workspace_bytes, ia_stream_t stream) {
+    if (!grad || !chunk_table || !seg_chunk_begin || !seg_norm || !norm_state || !workspace || nchunks <= 0 || nseg <= 0)
+        return IA_INVALID_VALUE;
+    if (!ia_is_aligned(grad, 16) || !ia_is_aligned(chunk_table, 16) || !ia_is_aligned(workspace, 4)) return IA_INVALID_VALUE;
+    if (workspace_bytes < ia_grad_norm_workspace_bytes(nchunks)) return IA_WORKSPACE_TOO_SMALL;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(seg_activity_kernel<true>, dim3(nchunks < 2048 ? nchunks : 2048), dim3(CL_THREADS), 0, st, grad,
+                       (const int4*)chunk_table, nchunks, seg_active, (float*)workspace);
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(GN_THREADS), 0, st, (const float*)workspace, seg_chunk_begin, nseg,
+                       fabsf(grad_scale), max_norm, seg_norm, norm_state);
+    IA_RETURN_IF_LAUNCH_FAILED();
+    return IA_OK;
+}
+
+extern "C" int ia_adamw_step_segmented_clipped(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq,
+                                               const int32_t* chunk_table, int nchunks, int32_t* seg_active, int32_t* seg_step,
+                                               int nseg, int all_active, float lr, float beta1, float beta2, float eps,
+                                               float weight_decay, float grad_scale, void* shadow_bf16, const float* norm_state,
+                                               int skip_nonfinite, int32_t* counters, ia_stream_t stream) {
+    if (!theta || !grad || !exp_avg || !exp_avg_sq || !chunk_table || !seg_active || !seg_step || !norm_state || !counters ||
+        nchunks <= 0 || nseg <= 0)
+        return IA_INVALID_VALUE;
+    if (!ia_is_aligned(theta, 16) || !ia_is_aligned(grad, 16) || !ia_is_aligned(exp_avg, 16) ||
+        !ia_is_aligned(exp_avg_sq, 16) || !ia_is_aligned(chunk_table, 16) || (shadow_bf16 && !ia_is_aligned(shadow_bf16, 8)))
+        return IA_INVALID_VALUE;
+    hipStream_t st = (hipStream_t)stream;
+    const int grid = nchunks < 2048 ? nchunks : 2048;
+    if (all_active)   // otherwise ia_grad_norm's first pass has set the flags
+        if (hipMemsetAsync(seg_active, 1, (size_t)nseg * sizeof(int32_t), st) != hipSuccess) return IA_LAUNCH_FAILED;
+    hipLaunchKernelGGL(adamw_seg_kernel<true>, dim3(grid), dim3(CL_THREADS), 0, st, theta, grad, exp_avg, exp_avg_sq,
+                       (const int4*)chunk_table, nchunks, seg_active, seg_step, lr, beta1, beta2, eps, weight_decay, grad_scale,
+                       (unsigned short*)shadow_bf16, norm_state, skip_nonfinite);
+    hipLaunchKernelGGL(seg_step_advance_clipped_kernel, dim3((nseg + 255) / 256), dim3(256), 0, st, seg_active, seg_step, nseg,
+                       norm_state, skip_nonfinite, counters);
     IA_RETURN_IF_LAUNCH_FAILED();
     return IA_OK;
 }

@@ -1,0 +1,53 @@
+"""FusedAdamW._apply on the flat buffers of BASELINE configs[1]'s trainable set (Conformer-medium, freeze_layer(m, 12)):
+plain, and with max_grad_norm=1.0 (live-segment detection on / every segment live).  Developer tool; one JSON line.
+
+`--legs plain` uses nothing newer than the segmented AdamW itself, so the same file times an older checkout."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def timeit(fn, warmup=5, n=20):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(n):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / n * 1e3
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--legs", default="plain,clip,clip_all_live")
+    args = ap.parse_args()
+    from indic_cl_asr_amd import cl
+    from indic_cl_asr_amd.config import model_config
+    from indic_cl_asr_amd.model import EncDecHybridRNNTCTCModel, freeze_layer
+    torch.manual_seed(0)
+    m = EncDecHybridRNNTCTCModel(model_config("medium", compute_dtype="bf16")).cuda()
+    freeze_layer(m, 12)
+    flat = cl.FlatParams(m)
+    grad = torch.randn(flat.numel, device="cuda") * 1e-2
+    out = {"numel": flat.numel, "segments": len(flat.entries), "chunks": int(flat.chunk_table.shape[0])}
+    for leg in args.legs.split(","):
+        kw, live = {"plain": ({}, False), "clip": ({"max_grad_norm": 1.0}, False),
+                    "clip_all_live": ({"max_grad_norm": 1.0}, True)}[leg]
+        opt = cl.FusedAdamW(flat, lr=1e-4, **kw)
+        flat.grad.copy_(grad)
+        out[leg + "_us"] = round(timeit(lambda: opt._apply(1.0, live)), 2)
+        del opt
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
