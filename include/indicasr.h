@@ -754,6 +754,21 @@ int ia_glu_bwd(const void* c2, const float* dG, const int64_t* lens, int B, int 
  *                          the launch leaves theta, both moments and the shadow untouched, clears seg_active, advances no
  *                          seg_step and increments counters[1]; otherwise counters[0] is incremented when coef < 1
  *                          (counters: int32[2] = {clipped steps, skipped steps}).  Two launches (+ a memset) on `stream`.
+ * ia_adamw_step_segmented_si  the segmented step with Synaptic Intelligence (Zenke, Poole, Ganguli 2017) in the AdamW launch.
+ *                          Per element of a live tensor, every product / difference / sum below rounded to fp32 on its own:
+ *                            ge = grad * grad_scale                               (the task gradient: no coef, no penalty)
+ *                            G  = ge * coef + (2*penalty_coef * omega) * (theta - theta_star)
+ *                            theta', exp_avg, exp_avg_sq = AdamW(theta, G)        (the routine of the other entries)
+ *                            path_w -= ge * (theta' - theta)                      (on the stored fp32 weights)
+ *                          norm_state and counters both NULL: no coef, no skip, the activity pass runs here unless
+ *                          all_active != 0 (ia_adamw_step_segmented's three launches); both set: coef, flag and seg_active as
+ *                          for ia_adamw_step_segmented_clipped (the norm is the task gradient's; the penalty is added AFTER
+ *                          the clip), and a skipped step leaves path_w untouched as well.  omega and theta_star both NULL
+ *                          (first task): no penalty term, neither is read, penalty_coef ignored.  A tensor that is not live
+ *                          keeps its path_w.  With a penalty the caller passes all_active != 0 (autograd on loss + surrogate
+ *                          gives every trainable tensor a gradient).
+ * ia_si_consolidate        end of a task, one pass over n elements: omega += max(0, path_w / ((theta - theta_star)^2 + xi)),
+ *                          path_w = 0, theta_star = theta; xi > 0 (IA_INVALID_VALUE otherwise).
  */
 int ia_cl_chunk_elems(void);
 int ia_cl_penalty(const float* theta, const float* theta_star, const float* weight, float coef, float* grad,
@@ -777,6 +792,13 @@ int ia_adamw_step_segmented_clipped(float* theta, const float* grad, float* exp_
                                     int all_active, float lr, float beta1, float beta2, float eps, float weight_decay,
                                     float grad_scale, void* shadow_bf16, const float* norm_state, int skip_nonfinite,
                                     int32_t* counters, ia_stream_t stream);
+int ia_adamw_step_segmented_si(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq, const int32_t* chunk_table,
+                               int nchunks, int32_t* seg_active, int32_t* seg_step, int nseg, int all_active, float lr,
+                               float beta1, float beta2, float eps, float weight_decay, float grad_scale, void* shadow_bf16,
+                               const float* norm_state, int skip_nonfinite, int32_t* counters, float* path_w,
+                               const float* omega, const float* theta_star, float penalty_coef, ia_stream_t stream);
+int ia_si_consolidate(const float* theta, float* theta_star, float* path_w, float* omega, float xi, int64_t n,
+                      ia_stream_t stream);
 
 /* ---- CTC head + loss on RAW logits (ConvASRDecoder.forward + CTCLoss.forward, A/modules/conv_asr.py:459-490 and
  * A/losses/ctc.py:68-82, without the [B,T,V] log-prob tensor and without a softmax backward pass): logits [B*T, ld] f32 with V

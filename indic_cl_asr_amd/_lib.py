@@ -204,6 +204,9 @@ SIGNATURES = {
     "ia_grad_norm": (_i, [_vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ia_adamw_step_segmented_clipped": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _i,
                                              _vp, _vp]),
+    "ia_adamw_step_segmented_si": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _i,
+                                        _vp, _vp, _vp, _vp, _f, _vp]),
+    "ia_si_consolidate": (_i, [_vp, _vp, _vp, _vp, _f, _i64, _vp]),
 }
 
 _lib = None

@@ -293,6 +293,100 @@ def importance_finish(importance: FlatDict, n_batches: int, group=None) -> FlatD
     return importance
 
 
+# ----------------------------------------------------------------------------- SI
+class SynapticIntelligence:
+    """Synaptic Intelligence (Zenke, Poole, Ganguli 2017): importance integrated online, inside the optimizer step, from the
+    task gradient and the parameter's own movement -- no Fisher / importance epoch after the task.
+
+    Three flat fp32 buffers over the layout (12 B per parameter): `w` the running path integral of the current task, `omega`
+    the consolidated importance of the earlier tasks, `theta_star` the weights at the end of the previous task (= at the start
+    of this one; initialised to the current weights).  Attach it with `FusedAdamW(..., path_integral=si)`: each step then
+    updates `w -= ge * (theta' - theta)` with ge the (data-parallel averaged) task gradient, and from the second task on adds
+    the surrogate's gradient `2 * si_c * omega * (theta - theta_star)` to what AdamW consumes.  `consolidate()` at the end of
+    a task: `omega += max(0, w / ((theta - theta_star)^2 + xi))`, `w = 0`, `theta_star = theta` (negative contributions are
+    dropped so that the surrogate stays convex).
+
+    Clip order: with `max_grad_norm` the norm and the coefficient are those of the task gradient and the surrogate's gradient
+    is added AFTER clipping -- not `clip_grad_norm_` of the total gradient (for that, add the penalty to `.grad` with
+    `mas_penalty_add_grads(flat, si.omega, si.theta_star, si.si_c)`; `w` would then integrate the penalised gradient)."""
+
+    def __init__(self, model_or_flat, si_c=1.0, xi=1e-3):
+        if not float(xi) > 0.0:
+            raise ValueError(f"SynapticIntelligence: xi must be > 0 (got {xi})")
+        self.flat = model_or_flat if isinstance(model_or_flat, FlatParams) else flat_of(model_or_flat)
+        self.si_c, self.xi = float(si_c), float(xi)
+        flush_pending_updates()
+        self.w = self.flat.zeros()
+        self.omega = self.flat.zeros()
+        self.theta_star = FlatDict(self.flat, self.flat.theta.clone())
+        self.tasks_consolidated = 0
+
+    @classmethod
+    def from_config(cls, model_or_flat, config):
+        """`cl_config.si_c` / `cl_config.si_xi` when the config has them (the reference's config.yaml has neither key)."""
+        cc = getattr(config, "cl_config", None) or {}
+        return cls(model_or_flat, si_c=cc.get("si_c", 1.0), xi=cc.get("si_xi", 1e-3))
+
+    def penalty_value(self) -> torch.Tensor:
+        """Sum omega * (theta - theta_star)^2 as a 0-dim device tensor (the 'si_penalty' monitor; un-weighted, as 'mass_loss').
+        One pass over three flat buffers: call it only when the value is logged."""
+        flush_pending_updates()
+        f = self.flat
+        val = torch.zeros(1, dtype=torch.float32, device=f.theta.device)
+        st = _lib.lib().ia_cl_penalty(_lib.ptr(f.theta), _lib.ptr(self.theta_star.flat), _lib.ptr(self.omega.flat), 0.0, None, 0,
+                                      _lib.ptr(f.chunk_table), f.chunk_table.shape[0], None, None, _lib.ptr(val),
+                                      _lib.stream_ptr())
+        _lib.check(st, "ia_cl_penalty")
+        return val[0]
+
+    def consolidate(self):
+        """End of a task (one launch).  Under data parallelism every rank holds the same w, theta and theta_star, so no
+        collective is needed."""
+        flush_pending_updates()
+        f = self.flat
+        st = _lib.lib().ia_si_consolidate(_lib.ptr(f.theta), _lib.ptr(self.theta_star.flat), _lib.ptr(self.w.flat),
+                                          _lib.ptr(self.omega.flat), self.xi, f.numel, _lib.stream_ptr())
+        _lib.check(st, "ia_si_consolidate")
+        self.tasks_consolidated += 1
+
+    def flat_dicts(self) -> Dict[str, FlatDict]:
+        """For `checkpoint.save_cl_state(path, **si.flat_dicts())`; `load_flat_dicts(checkpoint.load_cl_state(path, flat))`
+        is the way back."""
+        flush_pending_updates()
+        return {"si_w": self.w, "si_omega": self.omega, "si_theta_star": self.theta_star}
+
+    def load_flat_dicts(self, dicts, tasks_consolidated=None):
+        """Copies the three buffers in place (an attached optimizer keeps pointing at them).  The file carries no task count:
+        unless given, the penalty counts as attached (tasks_consolidated = 1) when the loaded omega has a non-zero entry."""
+        flush_pending_updates()
+        for key, mine in self.flat_dicts().items():
+            if dicts[key].layout.entries != self.flat.entries:
+                raise ValueError(f"'{key}' was saved for a different set of trainable tensors")
+            mine.flat.copy_(dicts[key].flat)
+        if tasks_consolidated is None:
+            tasks_consolidated = int(bool(self.omega.flat.any()))
+        self.tasks_consolidated = int(tasks_consolidated)
+
+    def state_dict(self) -> dict:
+        flush_pending_updates()
+        return {"entries": list(self.flat.entries), "w": self.w.flat.detach().to("cpu", copy=True),
+                "omega": self.omega.flat.detach().to("cpu", copy=True),
+                "theta_star": self.theta_star.flat.detach().to("cpu", copy=True), "si_c": self.si_c, "xi": self.xi,
+                "tasks_consolidated": self.tasks_consolidated}
+
+    def load_state_dict(self, sd: dict, source="state dict"):
+        if [tuple(e[:3]) + (tuple(e[3]),) for e in sd["entries"]] != list(self.flat.entries):
+            raise ValueError(f"{source}: 'si' was saved for a different set of trainable tensors")
+        if not float(sd["xi"]) > 0.0:
+            raise ValueError(f"{source}: xi must be > 0")
+        flush_pending_updates()
+        self.w.flat.copy_(sd["w"])
+        self.omega.flat.copy_(sd["omega"])
+        self.theta_star.flat.copy_(sd["theta_star"])
+        self.si_c, self.xi = float(sd["si_c"]), float(sd["xi"])
+        self.tasks_consolidated = int(sd["tasks_consolidated"])
+
+
 # ----------------------------------------------------------------------------- LwF
 def lwf_kd_loss(loss, prob, prob_, pred_store_list, store_list, knowledge_distillation: float, kd_ctx: float):
     """R/cl_baseline_lwf.py:242-264.  Returns (total loss, rnnt_kd, ctc_kd) -- device tensors."""
@@ -338,7 +432,7 @@ class FusedAdamW:
 
     def __init__(self, model_or_flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, group=None,
                  bf16_shadow=None, defer_update=True, grad_exchange_dtype=None, max_grad_norm=None, skip_nonfinite=False,
-                 track_grad_norm=False):
+                 track_grad_norm=False, path_integral=None):
         """`max_grad_norm=c`: torch.nn.utils.clip_grad_norm_(parameters, c) applied inside the step, to the gradient the
         update consumes -- after the data-parallel all-reduce, so every rank clips the AVERAGED gradient by the same factor
         (the torch call between backward() and step() would clip each rank's local gradient: the exchange happens in here).
@@ -349,8 +443,17 @@ class FusedAdamW:
 
         `grad_exchange_dtype="bf16"` ("fp32 or bf16"): the data-parallel exchange all-reduces a bf16 image of the
         flat gradient (half the bytes over xGMI: 80 instead of 160 MB per step at 40 M trainable parameters); every rank
-        then applies AdamW to the same bf16-rounded sum, so the weights stay identical across ranks.  None: fp32 exchange."""
+        then applies AdamW to the same bf16-rounded sum, so the weights stay identical across ranks.  None: fp32 exchange.
+
+        `path_integral=si` (a `SynapticIntelligence` on the same FlatParams): the step runs ia_adamw_step_segmented_si, which
+        also updates si.w from the averaged task gradient and the weights' movement and, once si.tasks_consolidated > 0, adds
+        the surrogate's gradient 2 * si_c * omega * (theta - theta_star) -- AFTER the clip: norm and coefficient stay those of
+        the task gradient (torch's clip_grad_norm_ on `loss + surrogate` would clip the total).  Every tensor is live then.
+        The SI buffers are not optimizer state: they are saved through si.state_dict() / si.flat_dicts()."""
         self.flat = model_or_flat if isinstance(model_or_flat, FlatParams) else flat_of(model_or_flat)
+        if path_integral is not None and path_integral.flat is not self.flat:
+            raise ValueError("path_integral belongs to another FlatParams")
+        self.path_integral = path_integral
         if grad_exchange_dtype not in (None, "fp32", "bf16"):
             raise ValueError("grad_exchange_dtype: None | 'fp32' | 'bf16'")
         self.grad_exchange_dtype = None if grad_exchange_dtype == "fp32" else grad_exchange_dtype
@@ -488,15 +591,14 @@ class FusedAdamW:
         f = self.flat
         L = _lib.lib()
         max_norm, skip = g.get("max_grad_norm"), bool(g.get("skip_nonfinite", False))
-        if max_norm is None and not skip and not self.track_grad_norm:
-            st = L.ia_adamw_step_segmented(
-                _lib.ptr(f.theta), _lib.ptr(f.grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), _lib.ptr(f.chunk_table),
-                f.chunk_table.shape[0], _lib.ptr(self.seg_active), _lib.ptr(self.seg_step), len(f.entries), int(bool(all_live)),
-                float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
-                float(scale), _lib.ptr(self.shadow), _lib.stream_ptr())
-            _lib.check(st, "ia_adamw_step_segmented")
-        else:
-            nchunks, nseg = f.chunk_table.shape[0], len(f.entries)
+        si = self.path_integral
+        measured = max_norm is not None or skip or self.track_grad_norm
+        penalised = si is not None and si.tasks_consolidated > 0
+        all_live = bool(all_live) or penalised       # autograd on loss + surrogate gives every trainable tensor a gradient
+        nchunks, nseg = f.chunk_table.shape[0], len(f.entries)
+        hyper = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
+                 float(scale), _lib.ptr(self.shadow))
+        if measured:
             if self._seg_norm is None:
                 self._seg_norm = torch.zeros(nseg, dtype=torch.float32, device=f.theta.device)
                 self._norm_ws = torch.empty(L.ia_grad_norm_workspace_bytes(nchunks), dtype=torch.uint8, device=f.theta.device)
@@ -506,13 +608,21 @@ class FusedAdamW:
                 _lib.ptr(self._seg_norm), _lib.ptr(self._norm_state), _lib.ptr(self._norm_ws), self._norm_ws.numel(),
                 _lib.stream_ptr())
             _lib.check(st, "ia_grad_norm")
-            st = L.ia_adamw_step_segmented_clipped(
-                _lib.ptr(f.theta), _lib.ptr(f.grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), _lib.ptr(f.chunk_table),
-                nchunks, _lib.ptr(self.seg_active), _lib.ptr(self.seg_step), nseg, int(bool(all_live)),
-                float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
-                float(scale), _lib.ptr(self.shadow), _lib.ptr(self._norm_state), int(skip), _lib.ptr(self._counters),
-                _lib.stream_ptr())
+        head = (_lib.ptr(f.theta), _lib.ptr(f.grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), _lib.ptr(f.chunk_table),
+                nchunks, _lib.ptr(self.seg_active), _lib.ptr(self.seg_step), nseg, int(all_live)) + hyper
+        if si is not None:
+            st = L.ia_adamw_step_segmented_si(
+                *head, _lib.ptr(self._norm_state) if measured else None, int(skip), _lib.ptr(self._counters) if measured else None,
+                _lib.ptr(si.w.flat), _lib.ptr(si.omega.flat) if penalised else None,
+                _lib.ptr(si.theta_star.flat) if penalised else None, float(si.si_c), _lib.stream_ptr())
+            _lib.check(st, "ia_adamw_step_segmented_si")
+        elif measured:
+            st = L.ia_adamw_step_segmented_clipped(*head, _lib.ptr(self._norm_state), int(skip), _lib.ptr(self._counters),
+                                                   _lib.stream_ptr())
             _lib.check(st, "ia_adamw_step_segmented_clipped")
+        else:
+            st = L.ia_adamw_step_segmented(*head, _lib.stream_ptr())
+            _lib.check(st, "ia_adamw_step_segmented")
         if self.flat.theta.is_cuda:
             global LAST_UPDATE_EVENT
             LAST_UPDATE_EVENT = torch.cuda.Event()

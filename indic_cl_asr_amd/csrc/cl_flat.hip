@@ -7,6 +7,9 @@
 //   ia_adamw_step ............ torch.optim.AdamW single-tensor update (R/cl_baseline.py:137 defaults)
 //   ia_grad_norm ............. torch.nn.utils.clip_grad_norm_'s norm and coefficient of the flat gradient, on the device
 //   ia_adamw_step_segmented_clipped .. the per-tensor AdamW on (g * grad_scale) * coef, skipped when the norm is not finite
+//   ia_adamw_step_segmented_si ....... the same step with Synaptic Intelligence's path integral w -= ge * (theta' - theta) and,
+//                              from the second task on, the surrogate's gradient 2c*omega*(theta-theta*) added after the clip
+//   ia_si_consolidate ........ end of a task: omega += max(0, w / ((theta-theta*)^2 + xi)), w = 0, theta* = theta
 // All are HBM-streaming kernels: 16-byte accesses, grid capped at 2048 workgroups, fp32 math.
 #include "ia_common.h"
 
@@ -287,6 +290,185 @@ __global__ __launch_bounds__(CL_THREADS) void adamw_seg_kernel(float* __restrict
     }
 }
 
+// ---- Synaptic Intelligence (Zenke, Poole, Ganguli 2017) inside the AdamW launch.  Per element of a live tensor:
+//   ge = g * grad_scale                      the task gradient (before the clip coefficient, without the penalty)
+//   G  = ge [* coef] [+ (c2 * omega) * (theta - theta_star)]      the gradient AdamW consumes (PEN: a penalty is attached)
+//   theta', m, v = adamw1(theta, G, ...)
+//   w  = w - ge * (theta' - theta)           the path integral, on the fp32 weight that is stored (weight decay included)
+// Every product, difference and sum of these lines is rounded to fp32 on its own (contraction off), so that one torch op
+// per rounding reproduces G and w bit for bit; adamw1 itself is the routine of the plain kernel.
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+
+template <bool PEN>
+__device__ __forceinline__ float si_grad(float eff, float theta, float omega, float star, float c2) {
+#pragma clang fp contract(off)
+    if constexpr (!PEN) {
+        return eff;
+    } else {
+        const float cw = c2 * omega;
+        const float d = theta - star;
+        const float pen = cw * d;
+        return eff + pen;
+    }
+}
+
+__device__ __forceinline__ float si_path(float w, float ge, float p_new, float p_old) {
+#pragma clang fp contract(off)
+    const float dp = p_new - p_old;
+    const float t = ge * dp;
+    return w - t;
+}
+
+// adamw1 with every rounding written out.  Left to the compiler, the contraction of adamw1 depends on the code around it: in
+// adamw_seg_kernel (both instantiations) it comes out as below, the second moment as fma(g, (1-b2)*g, b2*v) in the float4 body
+// and as fma(b2, v, ((1-b2)*g)*g) in the scalar tail; inside this kernel the same source lost some of the fmas.  The SI step has
+// to move the weights exactly as the plain step does on the same gradient (an element is in the body of both kernels or in the
+// tail of both), so it restates that arithmetic with explicit fmas; tests/test_si_gpu.py compares the two bit for bit.
+template <bool TAIL>
+__device__ __forceinline__ void adamw1_rn(float& p, float g, float& m, float& v, float decay, float omb1, float b2, float omb2,
+                                          float eps, float step_size, float inv_bc2_sqrt) {
+#pragma clang fp contract(off)
+    const float t = omb2 * g;
+    if constexpr (TAIL) {
+        const float tg = t * g;
+        v = __builtin_fmaf(b2, v, tg);
+    } else {
+        const float vb = b2 * v;
+        v = __builtin_fmaf(g, t, vb);
+    }
+    const float gm = g - m;
+    m = __builtin_fmaf(omb1, gm, m);
+    const float denom = __builtin_fmaf(inv_bc2_sqrt, sqrtf(v), eps);
+    const float q = m / denom;
+    const float u = step_size * q;
+    p = __builtin_fmaf(decay, p, -u);
+}
+
+struct si_consts {   // workgroup-uniform operands of one chunk
+    float decay, omb1, b2, omb2, eps, step_size, inv_bc2_sqrt, grad_scale, coef, c2;
+};
+
+template <bool CLIP, bool PEN, bool TAIL>
+__device__ __forceinline__ void adamw_si1(float& p, float g, float& m, float& v, float& w, float omega, float star,
+                                          const si_consts& k) {
+    const float ge = mul_rn(g, k.grad_scale);
+    const float eff = CLIP ? mul_rn(ge, k.coef) : ge;           // eff_grad<true>'s two products
+    const float p_old = p;
+    adamw1_rn<TAIL>(p, si_grad<PEN>(eff, p_old, omega, star, k.c2), m, v, k.decay, k.omb1, k.b2, k.omb2, k.eps, k.step_size,
+                    k.inv_bc2_sqrt);
+    w = si_path(w, ge, p, p_old);
+}
+
+template <bool CLIP, bool PEN>
+__global__ __launch_bounds__(CL_THREADS) void adamw_seg_si_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                                  float* __restrict__ m, float* __restrict__ v,
+                                                                  const int4* __restrict__ table, int nchunks,
+                                                                  const int* __restrict__ seg_active,
+                                                                  const int* __restrict__ seg_step, float lr, float b1, float b2,
+                                                                  float eps, float wd, float grad_scale,
+                                                                  unsigned short* __restrict__ shadow_bf16,
+                                                                  const float* __restrict__ norm_state, int skip_nonfinite,
+                                                                  float* __restrict__ path_w, const float* __restrict__ omega,
+                                                                  const float* __restrict__ star, float c2) {
+    __shared__ float sh_c[2];
+    float coef = 1.f;
+    if (CLIP) {
+        if (skip_nonfinite && norm_state[2] != 0.f) return;
+        coef = norm_state[1];
+    }
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const int4 e = table[c];
+        if (!seg_active[e.z]) {           // workgroup-uniform: untouched tensor -- its w stays, only the bf16 image is kept in step
+            if (shadow_bf16)
+                for (int i = threadIdx.x; i < e.y; i += CL_THREADS) {
+                    __hip_bfloat16 a = __float2bfloat16(p[e.x + i]);
+                    shadow_bf16[e.x + i] = *reinterpret_cast<unsigned short*>(&a);
+                }
+            continue;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const double step = (double)(seg_step[e.z] + 1);
+            sh_c[0] = (float)((double)lr / (1.0 - pow((double)b1, step)));
+            sh_c[1] = (float)(1.0 / sqrt(1.0 - pow((double)b2, step)));
+        }
+        __syncthreads();
+        const si_consts k = {__builtin_fmaf(-lr, wd, 1.f), 1.f - b1, b2, 1.f - b2, eps, sh_c[0], sh_c[1], grad_scale, coef, c2};
+        const int off = e.x, cnt = e.y, n4 = cnt >> 2;
+        for (int q = threadIdx.x; q < n4; q += CL_THREADS) {
+            float4 P = reinterpret_cast<float4*>(p + off)[q];
+            const float4 G = reinterpret_cast<const float4*>(g + off)[q];
+            float4 M = reinterpret_cast<float4*>(m + off)[q];
+            float4 V = reinterpret_cast<float4*>(v + off)[q];
+            float4 W = reinterpret_cast<float4*>(path_w + off)[q];
+            float4 O = make_float4(0.f, 0.f, 0.f, 0.f), S = O;
+            if constexpr (PEN) {
+                O = reinterpret_cast<const float4*>(omega + off)[q];
+                S = reinterpret_cast<const float4*>(star + off)[q];
+            }
+            adamw_si1<CLIP, PEN, false>(P.x, G.x, M.x, V.x, W.x, O.x, S.x, k);
+            adamw_si1<CLIP, PEN, false>(P.y, G.y, M.y, V.y, W.y, O.y, S.y, k);
+            adamw_si1<CLIP, PEN, false>(P.z, G.z, M.z, V.z, W.z, O.z, S.z, k);
+            adamw_si1<CLIP, PEN, false>(P.w, G.w, M.w, V.w, W.w, O.w, S.w, k);
+            reinterpret_cast<float4*>(p + off)[q] = P;
+            reinterpret_cast<float4*>(m + off)[q] = M;
+            reinterpret_cast<float4*>(v + off)[q] = V;
+            reinterpret_cast<float4*>(path_w + off)[q] = W;
+            if (shadow_bf16) {
+                __hip_bfloat16 a = __float2bfloat16(P.x), b = __float2bfloat16(P.y), cc = __float2bfloat16(P.z),
+                               d = __float2bfloat16(P.w);
+                ushort4 o;
+                o.x = *reinterpret_cast<unsigned short*>(&a); o.y = *reinterpret_cast<unsigned short*>(&b);
+                o.z = *reinterpret_cast<unsigned short*>(&cc); o.w = *reinterpret_cast<unsigned short*>(&d);
+                reinterpret_cast<ushort4*>(shadow_bf16 + off)[q] = o;
+            }
+        }
+        for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) {
+            float P = p[off + i], M = m[off + i], V = v[off + i], W = path_w[off + i];
+            const float O = PEN ? omega[off + i] : 0.f, S = PEN ? star[off + i] : 0.f;
+            adamw_si1<CLIP, PEN, true>(P, g[off + i], M, V, W, O, S, k);
+            p[off + i] = P; m[off + i] = M; v[off + i] = V; path_w[off + i] = W;
+            if (shadow_bf16) { __hip_bfloat16 a = __float2bfloat16(P); shadow_bf16[off + i] = *reinterpret_cast<unsigned short*>(&a); }
+        }
+    }
+}
+
+// End of a task: omega += max(0, w / ((theta - theta_star)^2 + xi)); w = 0; theta_star = theta.  One pass, 28 B per element.
+__device__ __forceinline__ void si_consolidate1(float t, float& s, float& w, float& o, float xi) {
+    const float d = t - s;
+    o += fmaxf(0.f, w / (d * d + xi));
+    w = 0.f;
+    s = t;
+}
+
+__global__ __launch_bounds__(CL_THREADS) void si_consolidate_kernel(const float* __restrict__ theta, float* __restrict__ star,
+                                                                    float* __restrict__ path_w, float* __restrict__ omega,
+                                                                    float xi, int64_t n) {
+    const int64_t n4 = n >> 2;
+    for (int64_t q = (int64_t)blockIdx.x * CL_THREADS + threadIdx.x; q < n4; q += (int64_t)gridDim.x * CL_THREADS) {
+        const float4 T = reinterpret_cast<const float4*>(theta)[q];
+        float4 S = reinterpret_cast<float4*>(star)[q];
+        float4 W = reinterpret_cast<float4*>(path_w)[q];
+        float4 O = reinterpret_cast<float4*>(omega)[q];
+        si_consolidate1(T.x, S.x, W.x, O.x, xi);
+        si_consolidate1(T.y, S.y, W.y, O.y, xi);
+        si_consolidate1(T.z, S.z, W.z, O.z, xi);
+        si_consolidate1(T.w, S.w, W.w, O.w, xi);
+        reinterpret_cast<float4*>(star)[q] = S;
+        reinterpret_cast<float4*>(path_w)[q] = W;
+        reinterpret_cast<float4*>(omega)[q] = O;
+    }
+    if (blockIdx.x == 0)
+        for (int64_t i = (n4 << 2) + threadIdx.x; i < n; i += CL_THREADS) {
+            float S = star[i], W = path_w[i], O = omega[i];
+            si_consolidate1(theta[i], S, W, O, xi);
+            star[i] = S; path_w[i] = W; omega[i] = O;
+        }
+}
+
 __global__ void seg_step_advance_kernel(int* __restrict__ seg_active, int* __restrict__ seg_step, int nseg) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s < nseg) { seg_step[s] += seg_active[s] ? 1 : 0; seg_active[s] = 0; }
@@ -425,6 +607,56 @@ extern "C" int ia_adamw_step_segmented_clipped(float* theta, const float* grad, 
                        (unsigned short*)shadow_bf16, norm_state, skip_nonfinite);
     hipLaunchKernelGGL(seg_step_advance_clipped_kernel, dim3((nseg + 255) / 256), dim3(256), 0, st, seg_active, seg_step, nseg,
                        norm_state, skip_nonfinite, counters);
+    IA_RETURN_IF_LAUNCH_FAILED();
+    return IA_OK;
+}
+
+extern "C" int ia_adamw_step_segmented_si(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq,
+                                          const int32_t* chunk_table, int nchunks, int32_t* seg_active, int32_t* seg_step, int nseg,
+                                          int all_active, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                          float grad_scale, void* shadow_bf16, const float* norm_state, int skip_nonfinite,
+                                          int32_t* counters, float* path_w, const float* omega, const float* theta_star,
+                                          float penalty_coef, ia_stream_t stream) {
+    if (!theta || !grad || !exp_avg || !exp_avg_sq || !chunk_table || !seg_active || !seg_step || !path_w || nchunks <= 0 ||
+        nseg <= 0)
+        return IA_INVALID_VALUE;
+    if ((norm_state == nullptr) != (counters == nullptr) || (omega == nullptr) != (theta_star == nullptr))
+        return IA_INVALID_VALUE;
+    if (!ia_is_aligned(theta, 16) || !ia_is_aligned(grad, 16) || !ia_is_aligned(exp_avg, 16) ||
+        !ia_is_aligned(exp_avg_sq, 16) || !ia_is_aligned(chunk_table, 16) || (shadow_bf16 && !ia_is_aligned(shadow_bf16, 8)) ||
+        !ia_is_aligned(path_w, 16) || (omega && (!ia_is_aligned(omega, 16) || !ia_is_aligned(theta_star, 16))))
+        return IA_INVALID_VALUE;
+    hipStream_t st = (hipStream_t)stream;
+    const int grid = nchunks < 2048 ? nchunks : 2048;
+    const bool clip = norm_state != nullptr, pen = omega != nullptr;
+    if (all_active) {
+        if (hipMemsetAsync(seg_active, 1, (size_t)nseg * sizeof(int32_t), st) != hipSuccess) return IA_LAUNCH_FAILED;
+    } else if (!clip) {   // with norm_state, ia_grad_norm's first pass has set the flags
+        hipLaunchKernelGGL(seg_activity_kernel<false>, dim3(grid), dim3(CL_THREADS), 0, st, grad, (const int4*)chunk_table, nchunks,
+                           seg_active, (float*)nullptr);
+    }
+    const float c2 = 2.f * penalty_coef;
+    auto kernel = clip ? (pen ? adamw_seg_si_kernel<true, true> : adamw_seg_si_kernel<true, false>)
+                       : (pen ? adamw_seg_si_kernel<false, true> : adamw_seg_si_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(CL_THREADS), 0, st, theta, grad, exp_avg, exp_avg_sq, (const int4*)chunk_table,
+                       nchunks, seg_active, seg_step, lr, beta1, beta2, eps, weight_decay, grad_scale,
+                       (unsigned short*)shadow_bf16, norm_state, skip_nonfinite, path_w, omega, theta_star, c2);
+    if (clip)
+        hipLaunchKernelGGL(seg_step_advance_clipped_kernel, dim3((nseg + 255) / 256), dim3(256), 0, st, seg_active, seg_step, nseg,
+                           norm_state, skip_nonfinite, counters);
+    else
+        hipLaunchKernelGGL(seg_step_advance_kernel, dim3((nseg + 255) / 256), dim3(256), 0, st, seg_active, seg_step, nseg);
+    IA_RETURN_IF_LAUNCH_FAILED();
+    return IA_OK;
+}
+
+extern "C" int ia_si_consolidate(const float* theta, float* theta_star, float* path_w, float* omega, float xi, int64_t n,
+                                 ia_stream_t stream) {
+    if (!theta || !theta_star || !path_w || !omega || n <= 0 || !(xi > 0.f)) return IA_INVALID_VALUE;
+    if (!ia_is_aligned(theta, 16) || !ia_is_aligned(theta_star, 16) || !ia_is_aligned(path_w, 16) || !ia_is_aligned(omega, 16))
+        return IA_INVALID_VALUE;
+    hipLaunchKernelGGL(si_consolidate_kernel, dim3(cap_grid(n >> 2, CL_THREADS * 4)), dim3(CL_THREADS), 0, (hipStream_t)stream,
+                       theta, theta_star, path_w, omega, xi, n);
     IA_RETURN_IF_LAUNCH_FAILED();
     return IA_OK;
 }

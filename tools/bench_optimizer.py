@@ -1,5 +1,6 @@
 """FusedAdamW._apply on the flat buffers of BASELINE configs[1]'s trainable set (Conformer-medium, freeze_layer(m, 12)):
-plain, and with max_grad_norm=1.0 (live-segment detection on / every segment live).  Developer tool; one JSON line.
+plain, with max_grad_norm=1.0 (live-segment detection on / every segment live), and with a Synaptic Intelligence path integral
+attached (first task: w only; later tasks: omega and theta* read as well, every segment live).  Developer tool; one JSON line.
 
 `--legs plain` uses nothing newer than the segmented AdamW itself, so the same file times an older checkout."""
 import argparse
@@ -28,7 +29,7 @@ def timeit(fn, warmup=5, n=20):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--legs", default="plain,clip,clip_all_live")
+    ap.add_argument("--legs", default="plain,clip,clip_all_live,si_first_task,si_penalty")
     args = ap.parse_args()
     from indic_cl_asr_amd import cl
     from indic_cl_asr_amd.config import model_config
@@ -41,7 +42,13 @@ def main():
     out = {"numel": flat.numel, "segments": len(flat.entries), "chunks": int(flat.chunk_table.shape[0])}
     for leg in args.legs.split(","):
         kw, live = {"plain": ({}, False), "clip": ({"max_grad_norm": 1.0}, False),
-                    "clip_all_live": ({"max_grad_norm": 1.0}, True)}[leg]
+                    "clip_all_live": ({"max_grad_norm": 1.0}, True), "si_first_task": ({}, False),
+                    "si_penalty": ({}, True)}[leg]
+        if leg.startswith("si_"):
+            kw["path_integral"] = si = cl.SynapticIntelligence(flat)
+            if leg == "si_penalty":                  # a consolidated task: the step reads omega and theta* and adds the penalty
+                si.omega.flat.uniform_(0.0, 1.0)
+                si.tasks_consolidated = 1
         opt = cl.FusedAdamW(flat, lr=1e-4, **kw)
         flat.grad.copy_(grad)
         out[leg + "_us"] = round(timeit(lambda: opt._apply(1.0, live)), 2)
