@@ -769,6 +769,44 @@ int ia_glu_bwd(const void* c2, const float* dG, const int64_t* lens, int B, int 
  *                          gives every trainable tensor a gradient).
  * ia_si_consolidate        end of a task, one pass over n elements: omega += max(0, path_w / ((theta - theta_star)^2 + xi)),
  *                          path_w = 0, theta_star = theta; xi > 0 (IA_INVALID_VALUE otherwise).
+ *
+ * Averaged GEM (Chaudhry, Ranzato, Rohrbach, Elhoseiny, ICLR 2019).  ref is the gradient of a batch drawn from an episodic
+ * memory of earlier tasks, a flat buffer laid out as grad, stored already averaged and in true units; grad is still to be
+ * multiplied by grad_scale (the step's scale: 1/world x the user's).  When the two point against each other the step consumes
+ * grad * grad_scale - (g.r / r.r) * ref.  The decision never leaves the device; no kernel uses a float atomic and every sum has
+ * a fixed order, so all results reproduce bit for bit from run to run.
+ * ia_agem_dots             two launches.  (1) one pass over grad and ref (8 B per element): workgroup c stores the fp32
+ *                          partials {sum g*r, sum r*r} of chunk c in workspace (ia_agem_workspace_bytes(nchunks) = two floats per
+ *                          chunk, 8-byte aligned) and, when seg_active is not NULL, sets seg_active[k] for every tensor with a
+ *                          set bit in grad, exactly as ia_grad_norm / ia_adamw_step_segmented do: no later liveness pass is
+ *                          needed.  (2) one workgroup adds the partials in fp64 in a fixed order and writes
+ *                            proj_state[0] = dot    = grad_scale * sum g*r
+ *                            proj_state[1] = ref_sq = sum r*r          (over the WHOLE buffer, dead tensors included)
+ *                            proj_state[3] = violated = 1.0f iff dot < 0 and ref_sq > 0 and both are finite, else 0.0f
+ *                            proj_state[2] = alpha  = (float)(dot / ref_sq) when violated (fp64 quotient, rounded once), else 0
+ *                          A non-finite grad or ref therefore never projects; skipping such a step stays the norm's job.
+ *                          nseg is the length of seg_active.
+ * ia_grad_norm_projected   ia_grad_norm (same outputs, same workspace size) of the gradient the projected step consumes; runs
+ *                          after ia_agem_dots on the same stream and branches on proj_state[3] on the device, uniformly.
+ *                          violated == 0: ia_grad_norm's arithmetic exactly (raw sum of g^2, grad_scale applied after the root).
+ *                          violated == 1: the sum of G^2, G = g * grad_scale - alpha * ref (each product and the difference
+ *                          rounded to fp32 on their own), over live tensors only -- a dead tensor's .grad is None and does not
+ *                          enter torch's clip norm; its seg_norm is 0.  seg_active is read only here (what ia_agem_dots left;
+ *                          NULL: every tensor live).
+ * ia_adamw_step_segmented_projected  the segmented step on the projected gradient.  Per element of a live tensor, every
+ *                          product and difference rounded to fp32 on its own:
+ *                            ge = grad * grad_scale
+ *                            gp = violated ? ge - (alpha * ref) : ge
+ *                            G  = gp * coef        (only with norm_state; coef = norm_state[1]: project, then clip)
+ *                            theta, exp_avg, exp_avg_sq = AdamW(theta, G)         (the routine of the other entries)
+ *                          An un-projected step moves weights, moments, step counters and the bf16 shadow exactly as
+ *                          ia_adamw_step_segmented[_clipped] does, and does not read ref.  Liveness is that of the TASK gradient:
+ *                          a tensor that received no task gradient is untouched even where ref is non-zero (the usual torch
+ *                          implementations leave a .grad of None alone), although r.r runs over the whole buffer.  Unless
+ *                          all_active != 0, seg_active must hold what ia_agem_dots left there for the same gradient.
+ *                          norm_state and counters are both NULL (no coef, no skip) or both set (as for
+ *                          ia_adamw_step_segmented_clipped, norm_state from ia_grad_norm_projected).  proj_counters: int32[1],
+ *                          incremented when the step projected; a step skipped as non-finite does not count.
  */
 int ia_cl_chunk_elems(void);
 int ia_cl_penalty(const float* theta, const float* theta_star, const float* weight, float coef, float* grad,
@@ -799,6 +837,19 @@ int ia_adamw_step_segmented_si(float* theta, const float* grad, float* exp_avg, 
                                const float* omega, const float* theta_star, float penalty_coef, ia_stream_t stream);
 int ia_si_consolidate(const float* theta, float* theta_star, float* path_w, float* omega, float xi, int64_t n,
                       ia_stream_t stream);
+size_t ia_agem_workspace_bytes(int nchunks);
+int ia_agem_dots(const float* grad, const float* ref, const int32_t* chunk_table, int nchunks, int nseg, float grad_scale,
+                 int32_t* seg_active, float* proj_state, void* workspace, size_t workspace_bytes, ia_stream_t stream);
+int ia_grad_norm_projected(const float* grad, const int32_t* chunk_table, int nchunks, const int32_t* seg_chunk_begin, int nseg,
+                           float grad_scale, float max_norm, const int32_t* seg_active, float* seg_norm, float* norm_state,
+                           void* workspace, size_t workspace_bytes, const float* ref, const float* proj_state,
+                           ia_stream_t stream);
+int ia_adamw_step_segmented_projected(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq,
+                                      const int32_t* chunk_table, int nchunks, int32_t* seg_active, int32_t* seg_step, int nseg,
+                                      int all_active, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                      float grad_scale, void* shadow_bf16, const float* norm_state, int skip_nonfinite,
+                                      int32_t* counters, const float* ref, const float* proj_state, int32_t* proj_counters,
+                                      ia_stream_t stream);
 
 /* ---- CTC head + loss on RAW logits (ConvASRDecoder.forward + CTCLoss.forward, A/modules/conv_asr.py:459-490 and
  * A/losses/ctc.py:68-82, without the [B,T,V] log-prob tensor and without a softmax backward pass): logits [B*T, ld] f32 with V

@@ -11,6 +11,7 @@
   `load_cl_state`); the reference keeps these in process memory only and loses them on restart.
 * optimizer state -- FusedAdamW's moments, per-tensor step counters, hyper-parameters and clip / skip counters
   (`save_optimizer` / `load_optimizer`), with the same layout check, so that a task can be resumed.
+* episodic memory -- cl.EpisodicMemory's utterances, counts and generator state (`save_memory` / `load_memory`).
 """
 import io
 import os
@@ -163,3 +164,14 @@ def load_optimizer(opt, path):
     """Inverse of save_optimizer; refuses a file whose tensor table differs from the optimizer's model."""
     opt.load_state_dict(torch.load(path, map_location="cpu"), source=path)
     return opt
+
+
+def save_memory(memory, path):
+    """Persist cl.EpisodicMemory.state_dict(): the stored utterances, the per-language counts and the generator state."""
+    torch.save(memory.state_dict(), path)
+
+
+def load_memory(memory, path):
+    """Inverse of save_memory: the loaded memory holds the same utterances and continues the same sequence of draws."""
+    memory.load_state_dict(torch.load(path, map_location="cpu"))
+    return memory

@@ -15,7 +15,7 @@ The dict-of-tensors API of the reference is kept: the dicts handed out are `Flat
 """
 import math
 from contextlib import contextmanager
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 import torch
 import torch.distributed as dist
@@ -387,6 +387,128 @@ class SynapticIntelligence:
         self.tasks_consolidated = int(sd["tasks_consolidated"])
 
 
+# ----------------------------------------------------------------------------- A-GEM
+class AveragedGEM:
+    """Averaged GEM (Chaudhry, Ranzato, Rohrbach, Elhoseiny, ICLR 2019): the gradient `ref` of a batch drawn from an episodic
+    memory of earlier tasks constrains the task gradient g.  When they point against each other (g.ref < 0) the step consumes
+    g - (g.ref / ref.ref) * ref, whose product with ref is zero: to first order the step no longer raises the memory's loss.
+
+    One flat fp32 buffer over the layout (4 B per parameter) plus {dot, ref_sq, alpha, violated} and a counter on the device.
+    Attach it with `FusedAdamW(..., projection=agem)`; per step: memory batch -> backward -> `agem.store_reference(opt)`, then
+    task batch -> backward -> `opt.step()`.  The two dots, the decision and the projection run inside the step, after the
+    data-parallel all-reduce; nothing is read back unless `stats()` is called.  With `max_grad_norm` the order is project, then
+    clip -- what `clip_grad_norm_` after a torch projection gives.  Liveness is that of the task gradient: a tensor that received
+    no task gradient (another language's heads) is untouched even where `ref` is non-zero, as the usual torch implementations
+    leave a `.grad` of None alone; ref.ref still runs over the whole buffer."""
+
+    def __init__(self, model_or_flat):
+        self.flat = model_or_flat if isinstance(model_or_flat, FlatParams) else flat_of(model_or_flat)
+        self.ref = self.flat.zeros()
+        # {dot, ref_sq, alpha, violated} as fp32 + {projected steps} as int32 in ONE device buffer (stats() reads it in one copy)
+        self._buf = torch.zeros(5, dtype=torch.int32, device=self.flat.theta.device)
+        self.proj_state = self._buf[:4].view(torch.float32)
+        self.proj_counters = self._buf[4:]
+        self._ws = None
+        self.has_reference = False
+
+    def store_reference(self, optimizer: Optional["FusedAdamW"] = None):
+        """The flat gradient (of the memory batch just back-propagated) becomes `ref`; the flat gradient is then zeroed, ready
+        for the task batch.  Under data parallelism `ref` is averaged over `optimizer`'s group first: a synchronous fp32
+        all-reduce, then times 1/world, so every rank projects onto the same reference."""
+        flush_pending_updates()
+        self.ref.flat.copy_(self.flat.grad)
+        if optimizer is not None:
+            ws = optimizer._world()
+            if ws > 1:
+                dist.all_reduce(self.ref.flat, group=optimizer.group)
+                self.ref.flat.mul_(1.0 / ws)
+        self.flat.zero_grad()
+        self.has_reference = True
+
+    def clear(self):
+        """Forget the reference: the following steps are plain steps until the next store_reference() (a deferred update
+        that was issued with the reference is applied with it first)."""
+        flush_pending_updates()
+        self.has_reference = False
+
+    def workspace(self, nchunks):
+        if self._ws is None:
+            self._ws = torch.empty(_lib.lib().ia_agem_workspace_bytes(nchunks), dtype=torch.uint8, device=self.flat.theta.device)
+        return self._ws
+
+    def stats(self) -> dict:
+        """One small device-to-host read: the latest step's dot (g.ref, of the averaged gradient), ref.ref, alpha and whether it
+        projected, and how many steps have projected so far."""
+        flush_pending_updates()
+        host = self._buf.cpu()
+        dot, ref_sq, alpha, violated = host[:4].view(torch.float32).tolist()
+        return {"dot": dot, "ref_sq": ref_sq, "alpha": alpha, "projected": int(violated != 0.0), "projected_steps": int(host[4])}
+
+
+class EpisodicMemory:
+    """Host-side episodic memory for replay methods: up to `per_language` utterances of every language seen, chosen by reservoir
+    sampling (Vitter's algorithm R), so that each utterance of a language's stream is kept with equal probability.  Utterances
+    are stored trimmed to their lengths on the CPU; `sample` re-pads them with data.speech_collate.  Every draw comes from the
+    memory's own seeded generator, whose state is part of state_dict()."""
+
+    def __init__(self, per_language: int, seed: int = 0):
+        if int(per_language) < 1:
+            raise ValueError(f"EpisodicMemory: per_language must be >= 1 (got {per_language})")
+        self.per_language = int(per_language)
+        self.gen = torch.Generator().manual_seed(int(seed))
+        self.items: Dict[str, List[tuple]] = {}    # language -> [(signal [n] f32, tokens [m] i64)]
+        self.seen: Dict[str, int] = {}             # language -> utterances offered so far
+
+    def __len__(self):
+        return sum(len(v) for v in self.items.values())
+
+    def languages(self) -> List[str]:
+        return list(self.items)
+
+    def add(self, batch, lang_ids):
+        """batch = (signal [B, L], signal lengths [B], tokens [B, U], token lengths [B]) on any device; lang_ids: B names."""
+        sig, sig_len, tok, tok_len = (t.detach().cpu() for t in batch)
+        if len(lang_ids) != sig.shape[0]:
+            raise ValueError("EpisodicMemory.add: one language id per utterance")
+        for i, lang in enumerate(lang_ids):
+            n, m = int(sig_len[i]), int(tok_len[i])
+            item = (sig[i, :n].to(torch.float32).clone(), tok[i, :m].to(torch.long).clone())
+            kept = self.items.setdefault(lang, [])
+            seen = self.seen.get(lang, 0)
+            if len(kept) < self.per_language:
+                kept.append(item)
+            else:
+                j = int(torch.randint(0, seen + 1, (1,), generator=self.gen))
+                if j < self.per_language:
+                    kept[j] = item
+            self.seen[lang] = seen + 1
+
+    def sample(self, n: int, device=None):
+        """-> ((signal, signal lengths, tokens, token lengths), lang_ids): n utterances drawn uniformly (with replacement) over
+        everything stored, languages mixed, collated as a training batch and moved to `device` (None: left on the host)."""
+        from . import data
+        pool = [(lang, it) for lang, kept in self.items.items() for it in kept]
+        if not pool:
+            raise ValueError("EpisodicMemory.sample: the memory is empty")
+        picks = torch.randint(0, len(pool), (int(n),), generator=self.gen).tolist()
+        samples = [(pool[j][1][0], torch.tensor(pool[j][1][0].shape[0], dtype=torch.long), pool[j][1][1],
+                    torch.tensor(pool[j][1][1].shape[0], dtype=torch.long)) for j in picks]
+        batch = data.speech_collate(samples)
+        if device is not None:
+            batch = data.move_to_device(batch, device)
+        return batch, [pool[j][0] for j in picks]
+
+    def state_dict(self) -> dict:
+        return {"per_language": self.per_language, "generator": self.gen.get_state(), "seen": dict(self.seen),
+                "items": {lang: [(x.clone(), t.clone()) for x, t in kept] for lang, kept in self.items.items()}}
+
+    def load_state_dict(self, sd: dict):
+        self.per_language = int(sd["per_language"])
+        self.gen.set_state(sd["generator"])
+        self.seen = {k: int(v) for k, v in sd["seen"].items()}
+        self.items = {lang: [(x.clone(), t.clone()) for x, t in kept] for lang, kept in sd["items"].items()}
+
+
 # ----------------------------------------------------------------------------- LwF
 def lwf_kd_loss(loss, prob, prob_, pred_store_list, store_list, knowledge_distillation: float, kd_ctx: float):
     """R/cl_baseline_lwf.py:242-264.  Returns (total loss, rnnt_kd, ctc_kd) -- device tensors."""
@@ -432,7 +554,7 @@ class FusedAdamW:
 
     def __init__(self, model_or_flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, group=None,
                  bf16_shadow=None, defer_update=True, grad_exchange_dtype=None, max_grad_norm=None, skip_nonfinite=False,
-                 track_grad_norm=False, path_integral=None):
+                 track_grad_norm=False, path_integral=None, projection=None):
         """`max_grad_norm=c`: torch.nn.utils.clip_grad_norm_(parameters, c) applied inside the step, to the gradient the
         update consumes -- after the data-parallel all-reduce, so every rank clips the AVERAGED gradient by the same factor
         (the torch call between backward() and step() would clip each rank's local gradient: the exchange happens in here).
@@ -449,11 +571,22 @@ class FusedAdamW:
         also updates si.w from the averaged task gradient and the weights' movement and, once si.tasks_consolidated > 0, adds
         the surrogate's gradient 2 * si_c * omega * (theta - theta_star) -- AFTER the clip: norm and coefficient stay those of
         the task gradient (torch's clip_grad_norm_ on `loss + surrogate` would clip the total).  Every tensor is live then.
-        The SI buffers are not optimizer state: they are saved through si.state_dict() / si.flat_dicts()."""
+        The SI buffers are not optimizer state: they are saved through si.state_dict() / si.flat_dicts().
+
+        `projection=agem` (an `AveragedGEM` on the same FlatParams): once agem.has_reference, the step runs ia_agem_dots,
+        ia_grad_norm_projected (if the norm is measured) and ia_adamw_step_segmented_projected: the averaged task gradient is
+        projected off agem.ref when their dot is negative, then clipped.  Without a reference the step is the one described
+        above.  Not combinable with `path_integral`; projection state is not optimizer state and is not in state_dict()."""
         self.flat = model_or_flat if isinstance(model_or_flat, FlatParams) else flat_of(model_or_flat)
         if path_integral is not None and path_integral.flat is not self.flat:
             raise ValueError("path_integral belongs to another FlatParams")
+        if projection is not None and path_integral is not None:
+            raise ValueError("projection and path_integral cannot be combined: the path integral has no agreed meaning under a "
+                             "projected gradient")
+        if projection is not None and projection.flat is not self.flat:
+            raise ValueError("projection belongs to another FlatParams")
         self.path_integral = path_integral
+        self.projection = projection
         if grad_exchange_dtype not in (None, "fp32", "bf16"):
             raise ValueError("grad_exchange_dtype: None | 'fp32' | 'bf16'")
         self.grad_exchange_dtype = None if grad_exchange_dtype == "fp32" else grad_exchange_dtype
@@ -598,10 +731,24 @@ class FusedAdamW:
         nchunks, nseg = f.chunk_table.shape[0], len(f.entries)
         hyper = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
                  float(scale), _lib.ptr(self.shadow))
-        if measured:
-            if self._seg_norm is None:
-                self._seg_norm = torch.zeros(nseg, dtype=torch.float32, device=f.theta.device)
-                self._norm_ws = torch.empty(L.ia_grad_norm_workspace_bytes(nchunks), dtype=torch.uint8, device=f.theta.device)
+        agem = self.projection if self.projection is not None and self.projection.has_reference else None
+        if measured and self._seg_norm is None:
+            self._seg_norm = torch.zeros(nseg, dtype=torch.float32, device=f.theta.device)
+            self._norm_ws = torch.empty(L.ia_grad_norm_workspace_bytes(nchunks), dtype=torch.uint8, device=f.theta.device)
+        if agem is not None:       # dots (and the liveness flags) -> norm of the projected gradient -> projected step
+            ws = agem.workspace(nchunks)
+            st = L.ia_agem_dots(_lib.ptr(f.grad), _lib.ptr(agem.ref.flat), _lib.ptr(f.chunk_table), nchunks, nseg, float(scale),
+                                None if all_live else _lib.ptr(self.seg_active), _lib.ptr(agem.proj_state), _lib.ptr(ws),
+                                ws.numel(), _lib.stream_ptr())
+            _lib.check(st, "ia_agem_dots")
+            if measured:
+                st = L.ia_grad_norm_projected(
+                    _lib.ptr(f.grad), _lib.ptr(f.chunk_table), nchunks, _lib.ptr(f.seg_chunk_begin), nseg, float(scale),
+                    0.0 if max_norm is None else float(max_norm), None if all_live else _lib.ptr(self.seg_active),
+                    _lib.ptr(self._seg_norm), _lib.ptr(self._norm_state), _lib.ptr(self._norm_ws), self._norm_ws.numel(),
+                    _lib.ptr(agem.ref.flat), _lib.ptr(agem.proj_state), _lib.stream_ptr())
+                _lib.check(st, "ia_grad_norm_projected")
+        elif measured:
             st = L.ia_grad_norm(
                 _lib.ptr(f.grad), _lib.ptr(f.chunk_table), nchunks, _lib.ptr(f.seg_chunk_begin), nseg, float(scale),
                 0.0 if max_norm is None else float(max_norm), None if all_live else _lib.ptr(self.seg_active),
@@ -610,7 +757,12 @@ class FusedAdamW:
             _lib.check(st, "ia_grad_norm")
         head = (_lib.ptr(f.theta), _lib.ptr(f.grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), _lib.ptr(f.chunk_table),
                 nchunks, _lib.ptr(self.seg_active), _lib.ptr(self.seg_step), nseg, int(all_live)) + hyper
-        if si is not None:
+        if agem is not None:
+            st = L.ia_adamw_step_segmented_projected(
+                *head, _lib.ptr(self._norm_state) if measured else None, int(skip), _lib.ptr(self._counters) if measured else None,
+                _lib.ptr(agem.ref.flat), _lib.ptr(agem.proj_state), _lib.ptr(agem.proj_counters), _lib.stream_ptr())
+            _lib.check(st, "ia_adamw_step_segmented_projected")
+        elif si is not None:
             st = L.ia_adamw_step_segmented_si(
                 *head, _lib.ptr(self._norm_state) if measured else None, int(skip), _lib.ptr(self._counters) if measured else None,
                 _lib.ptr(si.w.flat), _lib.ptr(si.omega.flat) if penalised else None,

@@ -10,6 +10,10 @@
 //   ia_adamw_step_segmented_si ....... the same step with Synaptic Intelligence's path integral w -= ge * (theta' - theta) and,
 //                              from the second task on, the surrogate's gradient 2c*omega*(theta-theta*) added after the clip
 //   ia_si_consolidate ........ end of a task: omega += max(0, w / ((theta-theta*)^2 + xi)), w = 0, theta* = theta
+//   ia_agem_dots ............. Averaged GEM (Chaudhry et al. 2019): g.r and r.r of the flat gradient and the episodic-memory
+//                              reference gradient, the decision g.r < 0 and alpha = g.r / r.r left on the device
+//   ia_grad_norm_projected ... ia_grad_norm of the gradient the projected step consumes (g - alpha * r when the flag is set)
+//   ia_adamw_step_segmented_projected .. the per-tensor AdamW on that gradient, r as one more operand of the launch
 // All are HBM-streaming kernels: 16-byte accesses, grid capped at 2048 workgroups, fp32 math.
 #include "ia_common.h"
 
@@ -178,10 +182,9 @@ __global__ __launch_bounds__(CL_THREADS) void seg_activity_kernel(const float* _
 // lanes; the wave keeps a running fp64 total of its segments and thread 0 adds the 16 wave totals in order.
 // norm_state = {total_norm, coef, non-finite flag (0 / 1), max_norm}.
 constexpr int GN_THREADS = 1024;
-__global__ __launch_bounds__(GN_THREADS) void grad_norm_finish_kernel(const float* __restrict__ chunk_sumsq,
-                                                                      const int* __restrict__ seg_chunk_begin, int nseg,
-                                                                      float abs_scale, float max_norm,
-                                                                      float* __restrict__ seg_norm, float* __restrict__ norm_state) {
+__device__ __forceinline__ void grad_norm_finish(const float* __restrict__ chunk_sumsq, const int* __restrict__ seg_chunk_begin,
+                                                 int nseg, float abs_scale, float max_norm, float* __restrict__ seg_norm,
+                                                 float* __restrict__ norm_state) {
     __shared__ double sh_w[GN_THREADS / 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double wave_total = 0.0;
@@ -210,6 +213,13 @@ __global__ __launch_bounds__(GN_THREADS) void grad_norm_finish_kernel(const floa
         norm_state[2] = isfinite(sum) ? 0.f : 1.f;
         norm_state[3] = max_norm;
     }
+}
+
+__global__ __launch_bounds__(GN_THREADS) void grad_norm_finish_kernel(const float* __restrict__ chunk_sumsq,
+                                                                      const int* __restrict__ seg_chunk_begin, int nseg,
+                                                                      float abs_scale, float max_norm,
+                                                                      float* __restrict__ seg_norm, float* __restrict__ norm_state) {
+    grad_norm_finish(chunk_sumsq, seg_chunk_begin, nseg, abs_scale, max_norm, seg_norm, norm_state);
 }
 
 // CLIP: the gradient is (g * grad_scale) * coef with coef = norm_state[1] read from the device, each product rounded to
@@ -469,6 +479,222 @@ __global__ __launch_bounds__(CL_THREADS) void si_consolidate_kernel(const float*
         }
 }
 
+// ---- Averaged GEM (Chaudhry, Ranzato, Rohrbach, Elhoseiny 2019).  r is the gradient of a batch drawn from the episodic memory,
+// stored averaged and in true units; g is the flat task gradient, still to be multiplied by grad_scale.  When g.r < 0 the step
+// consumes g - (g.r / r.r) * r.  Three passes, none with a float atomic, each with a fixed summation order:
+//   agem_dots_kernel     workgroup c leaves {sum g*r, sum r*r} of chunk c (fp32, the reduction shape of
+//                        seg_activity_kernel<true>) in chunk_dots[c] and sets the liveness flags from g as that kernel does
+//   agem_finish_kernel   one workgroup adds the partials in fp64 (thread t takes chunks t, t + 1024, ...; butterfly over the
+//                        lanes; thread 0 adds the 16 wave totals in order) and writes proj_state = {dot, ref_sq, alpha, violated}
+//   proj_norm_kernel     the chunk sums of squares of the gradient the step will consume, branching on the device flag
+__global__ __launch_bounds__(CL_THREADS) void agem_dots_kernel(const float* __restrict__ g, const float* __restrict__ r,
+                                                               const int4* __restrict__ table, int nchunks,
+                                                               int* __restrict__ seg_active, float2* __restrict__ chunk_dots) {
+    __shared__ float sh[CL_THREADS / 64];
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const int4 e = table[c];
+        const int off = e.x, cnt = e.y, n4 = cnt >> 2;
+        unsigned nz = 0;
+        float gr = 0.f, rr = 0.f;
+        for (int q = threadIdx.x; q < n4; q += CL_THREADS) {
+            const uint4 x = reinterpret_cast<const uint4*>(g + off)[q];
+            const float4 y = reinterpret_cast<const float4*>(r + off)[q];
+            nz |= (x.x | x.y | x.z | x.w) & 0x7FFFFFFFu;   // -0.0 counts as zero
+            const float a = __uint_as_float(x.x), b = __uint_as_float(x.y), cc = __uint_as_float(x.z), d = __uint_as_float(x.w);
+            gr += a * y.x + b * y.y + cc * y.z + d * y.w;
+            rr += y.x * y.x + y.y * y.y + y.z * y.z + y.w * y.w;
+        }
+        for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) {
+            const float a = g[off + i], y = r[off + i];
+            nz |= __float_as_uint(a) & 0x7FFFFFFFu;
+            gr += a * y;
+            rr += y * y;
+        }
+        if (seg_active && __any(nz != 0) && (threadIdx.x & 63) == 0) atomicOr(seg_active + e.z, 1);
+        const float t0 = block_sum(gr, sh);
+        const float t1 = block_sum(rr, sh);
+        if (threadIdx.x == 0) chunk_dots[c] = make_float2(t0, t1);
+    }
+}
+
+__global__ __launch_bounds__(GN_THREADS) void agem_finish_kernel(const float2* __restrict__ chunk_dots, int nchunks,
+                                                                 float grad_scale, float* __restrict__ proj_state) {
+    __shared__ double sh_d[GN_THREADS / 64], sh_r[GN_THREADS / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double d = 0.0, q = 0.0;
+    for (int c = threadIdx.x; c < nchunks; c += GN_THREADS) {
+        const float2 p = chunk_dots[c];
+        d += (double)p.x;
+        q += (double)p.y;
+    }
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) { d += __shfl_xor(d, s); q += __shfl_xor(q, s); }
+    if (lane == 0) { sh_d[wave] = d; sh_r[wave] = q; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double sd = 0.0, sq = 0.0;
+        for (int w = 0; w < GN_THREADS / 64; ++w) { sd += sh_d[w]; sq += sh_r[w]; }
+        const double dot = (double)grad_scale * sd;
+        const bool violated = isfinite(dot) && isfinite(sq) && dot < 0.0 && sq > 0.0;   // a non-finite g or r never projects
+        proj_state[0] = (float)dot;
+        proj_state[1] = (float)sq;
+        proj_state[2] = violated ? (float)(dot / sq) : 0.f;    // the quotient in fp64, rounded once
+        proj_state[3] = violated ? 1.f : 0.f;
+    }
+}
+
+__device__ __forceinline__ float sub_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
+
+// (g * grad_scale) - (alpha * r): both products and the difference rounded to fp32 on their own
+__device__ __forceinline__ float proj_grad(float g, float r, float grad_scale, float alpha) {
+    return sub_rn(mul_rn(g, grad_scale), mul_rn(alpha, r));
+}
+
+// seg_activity_kernel<true>'s sum as the compiler emits it there, written out so that an un-projected step measures the norm
+// ia_grad_norm measures bit for bit (tests/test_agem_gpu.py compares them): in the float4 body four separately rounded squares
+// added left to right and then to the running sum, in the scalar tail one fma.
+__device__ __forceinline__ float sumsq4_rn(float ss, float a, float b, float c, float d) {
+#pragma clang fp contract(off)
+    const float aa = a * a, bb = b * b, cc = c * c, dd = d * d;
+    const float t = ((aa + bb) + cc) + dd;
+    return ss + t;
+}
+
+// violated == 0: the raw sum of g^2 over every chunk, as ia_grad_norm's first pass.  violated == 1: the sum of G^2 with
+// G = g * grad_scale - alpha * r over the chunks of live tensors; a dead tensor's chunk stores 0 (its .grad is None for torch's
+// clip norm) and is not read.  seg_active is read only (NULL: every tensor live): agem_dots_kernel has set it.
+__global__ __launch_bounds__(CL_THREADS) void proj_norm_kernel(const float* __restrict__ g, const float* __restrict__ r,
+                                                               const int4* __restrict__ table, int nchunks,
+                                                               const int* __restrict__ seg_active,
+                                                               const float* __restrict__ proj_state, float grad_scale,
+                                                               float* __restrict__ chunk_sumsq) {
+    __shared__ float sh[CL_THREADS / 64];
+    const bool violated = proj_state[3] != 0.f;
+    const float alpha = proj_state[2];
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const int4 e = table[c];
+        const int off = e.x, cnt = e.y, n4 = cnt >> 2;
+        float ss = 0.f;
+        if (!violated) {
+            for (int q = threadIdx.x; q < n4; q += CL_THREADS) {
+                const float4 x = reinterpret_cast<const float4*>(g + off)[q];
+                ss = sumsq4_rn(ss, x.x, x.y, x.z, x.w);
+            }
+            for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) ss = __builtin_fmaf(g[off + i], g[off + i], ss);
+        } else if (!seg_active || seg_active[e.z]) {
+            for (int q = threadIdx.x; q < n4; q += CL_THREADS) {
+                const float4 x = reinterpret_cast<const float4*>(g + off)[q];
+                const float4 y = reinterpret_cast<const float4*>(r + off)[q];
+                ss = sumsq4_rn(ss, proj_grad(x.x, y.x, grad_scale, alpha), proj_grad(x.y, y.y, grad_scale, alpha),
+                               proj_grad(x.z, y.z, grad_scale, alpha), proj_grad(x.w, y.w, grad_scale, alpha));
+            }
+            for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) {
+                const float G = proj_grad(g[off + i], r[off + i], grad_scale, alpha);
+                ss = __builtin_fmaf(G, G, ss);
+            }
+        }
+        const float t = block_sum(ss, sh);
+        if (threadIdx.x == 0) chunk_sumsq[c] = t;
+    }
+}
+
+// ... the projected gradient already carries grad_scale: the root is scaled only when the step did not project
+__global__ __launch_bounds__(GN_THREADS) void grad_norm_finish_projected_kernel(const float* __restrict__ chunk_sumsq,
+                                                                                const int* __restrict__ seg_chunk_begin, int nseg,
+                                                                                float abs_scale, float max_norm,
+                                                                                float* __restrict__ seg_norm,
+                                                                                float* __restrict__ norm_state,
+                                                                                const float* __restrict__ proj_state) {
+    grad_norm_finish(chunk_sumsq, seg_chunk_begin, nseg, proj_state[3] != 0.f ? 1.f : abs_scale, max_norm, seg_norm, norm_state);
+}
+
+// The segmented AdamW on the projected gradient.  Per element of a live tensor (liveness is that of the task gradient g):
+//   ge = g * grad_scale;   gp = violated ? ge - (alpha * r) : ge;   G = CLIP ? gp * coef : gp;   theta, m, v = AdamW(theta, G)
+// with the explicit roundings of adamw1_rn, so that an un-projected step moves weights, moments, counters and the bf16 image
+// exactly as adamw_seg_kernel does (r is then not read at all).
+template <bool CLIP, bool TAIL>
+__device__ __forceinline__ void adamw_proj1(float& p, float g, float r, float& m, float& v, bool violated, float alpha,
+                                            const si_consts& k) {
+    const float ge = mul_rn(g, k.grad_scale);
+    const float gp = violated ? sub_rn(ge, mul_rn(alpha, r)) : ge;
+    const float G = CLIP ? mul_rn(gp, k.coef) : gp;
+    adamw1_rn<TAIL>(p, G, m, v, k.decay, k.omb1, k.b2, k.omb2, k.eps, k.step_size, k.inv_bc2_sqrt);
+}
+
+template <bool CLIP>
+__global__ __launch_bounds__(CL_THREADS) void adamw_seg_proj_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                                    float* __restrict__ m, float* __restrict__ v,
+                                                                    const int4* __restrict__ table, int nchunks,
+                                                                    const int* __restrict__ seg_active,
+                                                                    const int* __restrict__ seg_step, float lr, float b1, float b2,
+                                                                    float eps, float wd, float grad_scale,
+                                                                    unsigned short* __restrict__ shadow_bf16,
+                                                                    const float* __restrict__ norm_state, int skip_nonfinite,
+                                                                    const float* __restrict__ ref,
+                                                                    const float* __restrict__ proj_state) {
+    __shared__ float sh_c[2];
+    float coef = 1.f;
+    if (CLIP) {
+        if (skip_nonfinite && norm_state[2] != 0.f) return;
+        coef = norm_state[1];
+    }
+    const bool violated = proj_state[3] != 0.f;      // uniform over the launch
+    const float alpha = proj_state[2];
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const int4 e = table[c];
+        if (!seg_active[e.z]) {           // workgroup-uniform: no task gradient -- untouched whatever r holds there
+            if (shadow_bf16)
+                for (int i = threadIdx.x; i < e.y; i += CL_THREADS) {
+                    __hip_bfloat16 a = __float2bfloat16(p[e.x + i]);
+                    shadow_bf16[e.x + i] = *reinterpret_cast<unsigned short*>(&a);
+                }
+            continue;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const double step = (double)(seg_step[e.z] + 1);
+            sh_c[0] = (float)((double)lr / (1.0 - pow((double)b1, step)));
+            sh_c[1] = (float)(1.0 / sqrt(1.0 - pow((double)b2, step)));
+        }
+        __syncthreads();
+        const si_consts k = {__builtin_fmaf(-lr, wd, 1.f), 1.f - b1, b2, 1.f - b2, eps, sh_c[0], sh_c[1], grad_scale, coef, 0.f};
+        const int off = e.x, cnt = e.y, n4 = cnt >> 2;
+        for (int q = threadIdx.x; q < n4; q += CL_THREADS) {
+            float4 P = reinterpret_cast<float4*>(p + off)[q];
+            const float4 G = reinterpret_cast<const float4*>(g + off)[q];
+            float4 M = reinterpret_cast<float4*>(m + off)[q];
+            float4 V = reinterpret_cast<float4*>(v + off)[q];
+            float4 R = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (violated) R = reinterpret_cast<const float4*>(ref + off)[q];
+            adamw_proj1<CLIP, false>(P.x, G.x, R.x, M.x, V.x, violated, alpha, k);
+            adamw_proj1<CLIP, false>(P.y, G.y, R.y, M.y, V.y, violated, alpha, k);
+            adamw_proj1<CLIP, false>(P.z, G.z, R.z, M.z, V.z, violated, alpha, k);
+            adamw_proj1<CLIP, false>(P.w, G.w, R.w, M.w, V.w, violated, alpha, k);
+            reinterpret_cast<float4*>(p + off)[q] = P;
+            reinterpret_cast<float4*>(m + off)[q] = M;
+            reinterpret_cast<float4*>(v + off)[q] = V;
+            if (shadow_bf16) {
+                __hip_bfloat16 a = __float2bfloat16(P.x), b = __float2bfloat16(P.y), cc = __float2bfloat16(P.z),
+                               d = __float2bfloat16(P.w);
+                ushort4 o;
+                o.x = *reinterpret_cast<unsigned short*>(&a); o.y = *reinterpret_cast<unsigned short*>(&b);
+                o.z = *reinterpret_cast<unsigned short*>(&cc); o.w = *reinterpret_cast<unsigned short*>(&d);
+                reinterpret_cast<ushort4*>(shadow_bf16 + off)[q] = o;
+            }
+        }
+        for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) {
+            float P = p[off + i], M = m[off + i], V = v[off + i];
+            const float R = violated ? ref[off + i] : 0.f;
+            adamw_proj1<CLIP, true>(P, g[off + i], R, M, V, violated, alpha, k);
+            p[off + i] = P; m[off + i] = M; v[off + i] = V;
+            if (shadow_bf16) { __hip_bfloat16 a = __float2bfloat16(P); shadow_bf16[off + i] = *reinterpret_cast<unsigned short*>(&a); }
+        }
+    }
+}
+
 __global__ void seg_step_advance_kernel(int* __restrict__ seg_active, int* __restrict__ seg_step, int nseg) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s < nseg) { seg_step[s] += seg_active[s] ? 1 : 0; seg_active[s] = 0; }
@@ -484,6 +710,22 @@ __global__ void seg_step_advance_clipped_kernel(int* __restrict__ seg_active, in
     if (s == 0) {
         if (skipped) counters[1] += 1;
         else if (norm_state[1] < 1.f) counters[0] += 1;
+    }
+}
+
+// ... after a projected step: norm_state / counters may both be NULL (nothing measured); proj_counters[0] counts the steps that
+// projected, a skipped step not among them
+__global__ void seg_step_advance_projected_kernel(int* __restrict__ seg_active, int* __restrict__ seg_step, int nseg,
+                                                  const float* __restrict__ norm_state, int skip_nonfinite,
+                                                  int* __restrict__ counters, const float* __restrict__ proj_state,
+                                                  int* __restrict__ proj_counters) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool skipped = norm_state && skip_nonfinite && norm_state[2] != 0.f;
+    if (s < nseg) { seg_step[s] += (!skipped && seg_active[s]) ? 1 : 0; seg_active[s] = 0; }
+    if (s == 0) {
+        if (skipped) counters[1] += 1;
+        else if (norm_state && norm_state[1] < 1.f) counters[0] += 1;
+        if (!skipped && proj_state[3] != 0.f) proj_counters[0] += 1;
     }
 }
 
@@ -657,6 +899,73 @@ extern "C" int ia_si_consolidate(const float* theta, float* theta_star, float* p
         return IA_INVALID_VALUE;
     hipLaunchKernelGGL(si_consolidate_kernel, dim3(cap_grid(n >> 2, CL_THREADS * 4)), dim3(CL_THREADS), 0, (hipStream_t)stream,
                        theta, theta_star, path_w, omega, xi, n);
+    IA_RETURN_IF_LAUNCH_FAILED();
+    return IA_OK;
+}
+
+extern "C" size_t ia_agem_workspace_bytes(int nchunks) { return nchunks > 0 ? (size_t)nchunks * 2 * sizeof(float) : 0; }
+
+extern "C" int ia_agem_dots(const float* grad, const float* ref, const int32_t* chunk_table, int nchunks, int nseg,
+                            float grad_scale, int32_t* seg_active, float* proj_state, void* workspace, size_t workspace_bytes,
+                            ia_stream_t stream) {
+    if (!grad || !ref || !chunk_table || !proj_state || !workspace || nchunks <= 0 || nseg <= 0) return IA_INVALID_VALUE;
+    if (!ia_is_aligned(grad, 16) || !ia_is_aligned(ref, 16) || !ia_is_aligned(chunk_table, 16) || !ia_is_aligned(proj_state, 4) ||
+        !ia_is_aligned(workspace, 8))
+        return IA_INVALID_VALUE;
+    if (workspace_bytes < ia_agem_workspace_bytes(nchunks)) return IA_WORKSPACE_TOO_SMALL;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(agem_dots_kernel, dim3(nchunks < 2048 ? nchunks : 2048), dim3(CL_THREADS), 0, st, grad, ref,
+                       (const int4*)chunk_table, nchunks, seg_active, (float2*)workspace);
+    hipLaunchKernelGGL(agem_finish_kernel, dim3(1), dim3(GN_THREADS), 0, st, (const float2*)workspace, nchunks, grad_scale,
+                       proj_state);
+    IA_RETURN_IF_LAUNCH_FAILED();
+    return IA_OK;
+}
+
+extern "C" int ia_grad_norm_projected(const float* grad, const int32_t* chunk_table, int nchunks, const int32_t* seg_chunk_begin,
+                                      int nseg, float grad_scale, float max_norm, const int32_t* seg_active, float* seg_norm,
+                                      float* norm_state, void* workspace, size_t workspace_bytes, const float* ref,
+                                      const float* proj_state, ia_stream_t stream) {
+    if (!grad || !chunk_table || !seg_chunk_begin || !seg_norm || !norm_state || !workspace || !ref || !proj_state ||
+        nchunks <= 0 || nseg <= 0)
+        return IA_INVALID_VALUE;
+    if (!ia_is_aligned(grad, 16) || !ia_is_aligned(ref, 16) || !ia_is_aligned(chunk_table, 16) || !ia_is_aligned(workspace, 4) ||
+        !ia_is_aligned(proj_state, 4))
+        return IA_INVALID_VALUE;
+    if (workspace_bytes < ia_grad_norm_workspace_bytes(nchunks)) return IA_WORKSPACE_TOO_SMALL;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(proj_norm_kernel, dim3(nchunks < 2048 ? nchunks : 2048), dim3(CL_THREADS), 0, st, grad, ref,
+                       (const int4*)chunk_table, nchunks, seg_active, proj_state, grad_scale, (float*)workspace);
+    hipLaunchKernelGGL(grad_norm_finish_projected_kernel, dim3(1), dim3(GN_THREADS), 0, st, (const float*)workspace,
+                       seg_chunk_begin, nseg, fabsf(grad_scale), max_norm, seg_norm, norm_state, proj_state);
+    IA_RETURN_IF_LAUNCH_FAILED();
+    return IA_OK;
+}
+
+extern "C" int ia_adamw_step_segmented_projected(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq,
+                                                 const int32_t* chunk_table, int nchunks, int32_t* seg_active, int32_t* seg_step,
+                                                 int nseg, int all_active, float lr, float beta1, float beta2, float eps,
+                                                 float weight_decay, float grad_scale, void* shadow_bf16, const float* norm_state,
+                                                 int skip_nonfinite, int32_t* counters, const float* ref, const float* proj_state,
+                                                 int32_t* proj_counters, ia_stream_t stream) {
+    if (!theta || !grad || !exp_avg || !exp_avg_sq || !chunk_table || !seg_active || !seg_step || !ref || !proj_state ||
+        !proj_counters || nchunks <= 0 || nseg <= 0)
+        return IA_INVALID_VALUE;
+    if ((norm_state == nullptr) != (counters == nullptr)) return IA_INVALID_VALUE;
+    if (!ia_is_aligned(theta, 16) || !ia_is_aligned(grad, 16) || !ia_is_aligned(exp_avg, 16) ||
+        !ia_is_aligned(exp_avg_sq, 16) || !ia_is_aligned(chunk_table, 16) || (shadow_bf16 && !ia_is_aligned(shadow_bf16, 8)) ||
+        !ia_is_aligned(ref, 16) || !ia_is_aligned(proj_state, 4) || !ia_is_aligned(proj_counters, 4))
+        return IA_INVALID_VALUE;
+    hipStream_t st = (hipStream_t)stream;
+    const int grid = nchunks < 2048 ? nchunks : 2048;
+    if (all_active)   // otherwise ia_agem_dots has set the flags from the task gradient
+        if (hipMemsetAsync(seg_active, 1, (size_t)nseg * sizeof(int32_t), st) != hipSuccess) return IA_LAUNCH_FAILED;
+    auto kernel = norm_state ? adamw_seg_proj_kernel<true> : adamw_seg_proj_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(CL_THREADS), 0, st, theta, grad, exp_avg, exp_avg_sq, (const int4*)chunk_table,
+                       nchunks, seg_active, seg_step, lr, beta1, beta2, eps, weight_decay, grad_scale,
+                       (unsigned short*)shadow_bf16, norm_state, skip_nonfinite, ref, proj_state);
+    hipLaunchKernelGGL(seg_step_advance_projected_kernel, dim3((nseg + 255) / 256), dim3(256), 0, st, seg_active, seg_step, nseg,
+                       norm_state, skip_nonfinite, counters, proj_state, proj_counters);
     IA_RETURN_IF_LAUNCH_FAILED();
     return IA_OK;
 }
