@@ -850,6 +850,30 @@ int ia_adamw_step_segmented_projected(float* theta, const float* grad, float* ex
                                       float grad_scale, void* shadow_bf16, const float* norm_state, int skip_nonfinite,
                                       int32_t* counters, const float* ref, const float* proj_state, int32_t* proj_counters,
                                       ia_stream_t stream);
+/* Parameter groups: per-tensor learning rate and weight decay for every kind of segmented step.  seg_group: int32[nseg] on the
+ * device, tensor k belongs to group seg_group[k] (NULL: every tensor in group 0; entries outside 0..ngroups-1 are clamped).
+ * group_lr / group_weight_decay: ngroups floats each in HOST memory, read during the call and handed to the kernel by value
+ * inside its arguments -- changing them every step costs no copy, no staging buffer and no synchronisation.  beta1, beta2, eps,
+ * the clip coefficient, the non-finite skip and the projection are per step, not per group.  The optional operands select the
+ * step and carry the meaning they have in the entry points above:
+ *   ref, proj_state, proj_counters (all three or none) ... ia_adamw_step_segmented_projected; norm_state / counters optional
+ *   path_w [, omega and theta_star together] ............. ia_adamw_step_segmented_si; norm_state / counters optional
+ *   norm_state and counters (both or neither) ............ ia_adamw_step_segmented_clipped
+ *   none .................................................. ia_adamw_step_segmented
+ * and the launches are those of that entry point: with ngroups == 1 the results are its results bit for bit.
+ * IA_INVALID_VALUE before any device work: a NULL required pointer, ngroups outside 1..IA_MAX_PARAM_GROUPS, NULL seg_group with
+ * ngroups > 1, NULL group_lr / group_weight_decay, counters without norm_state (or the reverse), omega without theta_star (or
+ * the reverse) or without path_w, an incomplete ref / proj_state / proj_counters triple, SI and projection operands together,
+ * and the alignment conditions of the four entry points. */
+#define IA_MAX_PARAM_GROUPS 64
+int ia_adamw_step_segmented_grouped(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq,
+                                    const int32_t* chunk_table, int nchunks, int32_t* seg_active, int32_t* seg_step, int nseg,
+                                    int all_active, float beta1, float beta2, float eps, float grad_scale, void* shadow_bf16,
+                                    const int32_t* seg_group, int ngroups, const float* group_lr,
+                                    const float* group_weight_decay, const float* norm_state, int skip_nonfinite,
+                                    int32_t* counters, float* path_w, const float* omega, const float* theta_star,
+                                    float penalty_coef, const float* ref, const float* proj_state, int32_t* proj_counters,
+                                    ia_stream_t stream);
 
 /* ---- CTC head + loss on RAW logits (ConvASRDecoder.forward + CTCLoss.forward, A/modules/conv_asr.py:459-490 and
  * A/losses/ctc.py:68-82, without the [B,T,V] log-prob tensor and without a softmax backward pass): logits [B*T, ld] f32 with V

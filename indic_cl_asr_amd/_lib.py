@@ -212,6 +212,8 @@ SIGNATURES = {
     "ia_grad_norm_projected": (_i, [_vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "ia_adamw_step_segmented_projected": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _i,
                                                _vp, _vp, _vp, _vp, _vp]),
+    "ia_adamw_step_segmented_grouped": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _f, _vp, _vp, _i, _vp, _vp,
+                                             _vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -13,7 +13,9 @@ of ONE flat gradient buffer, so the penalty, Fisher/omega accumulation, AdamW an
 a single launch / a single collective over ~N*4 bytes instead of ~300 per-tensor kernels.
 The dict-of-tensors API of the reference is kept: the dicts handed out are `FlatDict`s (name -> view).
 """
+import ctypes
 import math
+import re
 from contextlib import contextmanager
 from typing import Dict, List, Optional
 
@@ -547,14 +549,118 @@ def lwf_teacher_forward(model, flat: FlatParams, teacher: FlatDict, batch, lang_
 
 
 # ----------------------------------------------------------------------------- optimizer + DP
-class FusedAdamW:
+MAX_PARAM_GROUPS = 64      # IA_MAX_PARAM_GROUPS of include/indicasr.h: the group table travels in the kernel arguments
+_GROUP_KEYS = ("params", "match", "lr", "weight_decay", "name")
+
+
+def _as_flat(model_or_flat) -> FlatParams:
+    return model_or_flat if isinstance(model_or_flat, FlatParams) else flat_of(model_or_flat)
+
+
+def _default_no_decay(name: str, p: torch.Tensor) -> bool:
+    return p.ndim <= 1 or name.endswith("pos_bias_u") or name.endswith("pos_bias_v")
+
+
+def no_decay_groups(model_or_flat, no_decay=None) -> List[dict]:
+    """`param_groups=` for FusedAdamW: ONE group with weight_decay=0.0 holding every trainable tensor for which
+    `no_decay(name, parameter)` holds -- by default biases, norm scales and every other tensor with ndim <= 1, plus the
+    relative-position biases `pos_bias_u` / `pos_bias_v` (Loshchilov & Hutter 2019 decay weights, not these).  Everything else
+    stays in group 0 with the constructor's weight decay.  An empty list when nothing qualifies."""
+    flat = _as_flat(model_or_flat)
+    pred = no_decay or _default_no_decay
+    names = [n for n, p in zip(flat.names, flat.params) if pred(n, p)]
+    return [dict(params=names, weight_decay=0.0, name="no_decay")] if names else []
+
+
+def layerwise_lr_groups(model_or_flat, lr, decay, no_decay_1d=True) -> List[dict]:
+    """`param_groups=` for FusedAdamW: layer-wise learning-rate decay (Howard & Ruder 2018) over the hybrid model.  Depth 0 is
+    `decoder.*`, `joint.*` and `ctc_decoder.*` at `lr`; `encoder.layers.i.*` sits at `lr * decay**(L - i)` with
+    L = len(encoder.layers); `encoder.pre_encode.*` at `lr * decay**(L + 1)`.  With `no_decay_1d` every depth is split into
+    its decayed tensors and a second group with weight_decay=0.0 (the predicate of `no_decay_groups`).  Depths without a
+    trainable tensor are left out; a trainable tensor under none of these prefixes is not claimed and stays in group 0."""
+    flat = _as_flat(model_or_flat)
+    L = len(flat.model.encoder.layers)
+    by_depth: Dict[int, List[str]] = {}
+    for n in flat.names:
+        if n.startswith(("decoder.", "joint.", "ctc_decoder.")):
+            d = 0
+        elif n.startswith("encoder.layers."):
+            d = L - int(n.split(".")[2])
+        elif n.startswith("encoder.pre_encode."):
+            d = L + 1
+        else:
+            continue
+        by_depth.setdefault(d, []).append(n)
+    param = dict(zip(flat.names, flat.params))
+    groups = []
+    for d in sorted(by_depth):
+        names, rate = by_depth[d], lr * decay ** d
+        plain = [n for n in names if not (no_decay_1d and _default_no_decay(n, param[n]))]
+        bare = [n for n in names if no_decay_1d and _default_no_decay(n, param[n])]
+        if plain:
+            groups.append(dict(params=plain, lr=rate, name=f"depth{d}"))
+        if bare:
+            groups.append(dict(params=bare, lr=rate, weight_decay=0.0, name=f"depth{d}.no_decay"))
+    return groups
+
+
+def _resolve_param_groups(flat: FlatParams, specs) -> List[List[str]]:
+    """Names per group, group 0 first (every trainable tensor no spec claims); raises ValueError naming the offender."""
+    specs = list(specs)
+    if 1 + len(specs) > MAX_PARAM_GROUPS:
+        raise ValueError(f"param_groups: {len(specs)} groups + group 0 exceed the limit of {MAX_PARAM_GROUPS} groups")
+    by_id = {id(p): n for n, p in zip(flat.names, flat.params)}
+    known, owner, out = set(flat.names), {}, []
+    for k, spec in enumerate(specs, start=1):
+        label = f"group {k}" + (f" ('{spec['name']}')" if isinstance(spec, dict) and "name" in spec else "")
+        if not isinstance(spec, dict):
+            raise ValueError(f"param_groups: {label} is not a dict")
+        for key in spec:
+            if key not in _GROUP_KEYS:
+                raise ValueError(f"param_groups: {label} has the unknown key '{key}' (allowed: {', '.join(_GROUP_KEYS)}; betas, "
+                                 "eps and the clip settings are per optimizer)")
+        if ("params" in spec) == ("match" in spec):
+            raise ValueError(f"param_groups: {label} needs either 'params' or 'match'")
+        if "match" in spec:
+            names = [n for n in flat.names if re.search(spec["match"], n)]
+            if not names:
+                raise ValueError(f"param_groups: {label}: match '{spec['match']}' matches no trainable tensor")
+        else:
+            given = spec["params"]
+            given = [given] if isinstance(given, (str, torch.Tensor)) else list(given)
+            names = []
+            for item in given:
+                if isinstance(item, str):
+                    if item not in known:
+                        raise ValueError(f"param_groups: {label}: '{item}' is not a trainable tensor of this FlatParams")
+                    names.append(item)
+                elif id(item) in by_id:
+                    names.append(by_id[id(item)])
+                else:
+                    what = f"a tensor of shape {tuple(item.shape)}" if isinstance(item, torch.Tensor) else repr(item)
+                    raise ValueError(f"param_groups: {label}: {what} is not a trainable tensor of this FlatParams")
+        for n in names:
+            if n in owner:
+                raise ValueError(f"param_groups: '{n}' is claimed by {owner[n]} and by {label}")
+            owner[n] = label
+        out.append(names)
+    return [[n for n in flat.names if n not in owner]] + out
+
+
+class FusedAdamW(torch.optim.Optimizer):
     """torch.optim.AdamW(model.parameters(), lr) of R/cl_baseline.py:137 as one launch over the flat buffers.
     step() first averages the flat gradient across ranks (RCCL all-reduce over xGMI) when a process group
-    exists -- the reference wraps the model in DDP but never arms its reducer."""
+    exists -- the reference wraps the model in DDP but never arms its reducer.
+
+    A torch.optim.Optimizer, so torch.optim.lr_scheduler.* attach and write param_groups[k]["lr"]; zero_grad, step,
+    state_dict and load_state_dict are this class's own, and the layout is fixed at construction (add_param_group raises).
+    Per group: `lr` and `weight_decay`.  Per optimizer: `betas` and `eps` (a step that finds a group whose betas or eps differ
+    from group 0's raises ValueError -- e.g. OneCycleLR needs cycle_momentum=False), and `max_grad_norm` / `skip_nonfinite`,
+    which are read from group 0 only."""
 
     def __init__(self, model_or_flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, group=None,
                  bf16_shadow=None, defer_update=True, grad_exchange_dtype=None, max_grad_norm=None, skip_nonfinite=False,
-                 track_grad_norm=False, path_integral=None, projection=None):
+                 track_grad_norm=False, path_integral=None, projection=None, param_groups=None):
         """`max_grad_norm=c`: torch.nn.utils.clip_grad_norm_(parameters, c) applied inside the step, to the gradient the
         update consumes -- after the data-parallel all-reduce, so every rank clips the AVERAGED gradient by the same factor
         (the torch call between backward() and step() would clip each rank's local gradient: the exchange happens in here).
@@ -576,7 +682,14 @@ class FusedAdamW:
         `projection=agem` (an `AveragedGEM` on the same FlatParams): once agem.has_reference, the step runs ia_agem_dots,
         ia_grad_norm_projected (if the norm is measured) and ia_adamw_step_segmented_projected: the averaged task gradient is
         projected off agem.ref when their dot is negative, then clipped.  Without a reference the step is the one described
-        above.  Not combinable with `path_integral`; projection state is not optimizer state and is not in state_dict()."""
+        above.  Not combinable with `path_integral`; projection state is not optimizer state and is not in state_dict().
+
+        `param_groups=[{...}, ...]`: dicts in torch's shape.  Each names its tensors with "params" (parameter names and / or
+        the Parameter objects) or "match" (a regular expression, re.search on the parameter name), may override "lr" and / or
+        "weight_decay", and may carry a "name".  Every trainable tensor nobody claims stays in group 0, which carries this
+        constructor's values; `no_decay_groups` and `layerwise_lr_groups` build such lists.  All groups go through ONE launch
+        (ia_adamw_step_segmented_grouped; clipping, the non-finite skip, path_integral and projection included).  A deferred
+        update applies the lr / weight_decay its step() saw, whatever a scheduler has written since."""
         self.flat = model_or_flat if isinstance(model_or_flat, FlatParams) else flat_of(model_or_flat)
         if path_integral is not None and path_integral.flat is not self.flat:
             raise ValueError("path_integral belongs to another FlatParams")
@@ -613,8 +726,29 @@ class FusedAdamW:
         if bf16_shadow is None:  # the HIP GEMM paths consume bf16 weights: let the optimizer kernel emit them (one launch)
             bf16_shadow = self.flat.theta.is_cuda
         self.shadow = self.flat.theta.to(torch.bfloat16) if bf16_shadow else None
-        self.param_groups = [dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
-                                  skip_nonfinite=skip_nonfinite, params=self.flat.params)]
+        group0 = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
+                      skip_nonfinite=skip_nonfinite, params=self.flat.params)
+        if param_groups is None:
+            self._group_names, groups = [list(self.flat.names)], [group0]
+        else:
+            self._group_names = _resolve_param_groups(self.flat, param_groups)
+            param = dict(zip(self.flat.names, self.flat.params))
+            groups = []
+            for k, names in enumerate(self._group_names):
+                spec = {} if k == 0 else param_groups[k - 1]
+                g = dict(params=[param[n] for n in names], names=list(names), lr=spec.get("lr", lr),
+                         weight_decay=spec.get("weight_decay", weight_decay), betas=betas, eps=eps)
+                if k == 0:
+                    g.update(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+                elif "name" in spec:
+                    g["name"] = spec["name"]
+                groups.append(g)
+        self._layout_fixed = False
+        torch.optim.Optimizer.__init__(self, groups, {})      # sets self.param_groups (through add_param_group) and self.state
+        self._layout_fixed = True
+        # tensor -> group, built once; the per-group lr / weight_decay go to the kernel by value at every step
+        index = {n: k for k, names in enumerate(self._group_names) for n in names}
+        self.seg_group = torch.tensor([index[n] for n in self.flat.names], dtype=torch.int32, device=self.flat.theta.device)
         self.track_grad_norm = track_grad_norm
         # {total_norm, coef, non-finite flag, max_norm} as fp32 + {clipped steps, skipped steps} as int32 in ONE device buffer
         # (stats() reads it in one copy); the per-tensor norms and the chunk sums are allocated by the first clipped step
@@ -625,6 +759,25 @@ class FusedAdamW:
         self._seg_norm = self._norm_ws = None
         self.defer_update = defer_update   # data parallel only: overlap the gradient all-reduce with the next forward
         self._pending, self._zero_after_flush = None, False
+
+    def add_param_group(self, param_group):
+        if self._layout_fixed:
+            raise NotImplementedError("FusedAdamW: the flat layout and its groups are fixed at construction; pass param_groups= "
+                                      "to the constructor")
+        super().add_param_group(param_group)
+
+    def _group_hyper(self):
+        """Every group's (lr, weight_decay) as floats; ValueError when a group's betas / eps left group 0's."""
+        g0 = self.param_groups[0]
+        for k, g in enumerate(self.param_groups[1:], start=1):
+            for key in ("betas", "eps"):
+                if key not in g:
+                    continue
+                same = tuple(g[key]) == tuple(g0[key]) if key == "betas" else g[key] == g0[key]
+                if not same:
+                    raise ValueError(f"FusedAdamW: param_groups[{k}]['{key}'] = {g[key]} differs from group 0's {g0[key]}: "
+                                     f"{key} is one per optimizer (schedulers that cycle momentum need cycle_momentum=False)")
+        return [float(g["lr"]) for g in self.param_groups], [float(g["weight_decay"]) for g in self.param_groups]
 
     def zero_grad(self, set_to_none: bool = False):
         if self._pending is not None:
@@ -667,19 +820,21 @@ class FusedAdamW:
         subsampling and the frozen encoder prefix, none of which read trainable weights, so the result is bit-identical to
         updating immediately.  Everything here that reads or swaps the flat weights flushes first."""
         self.flush()
+        hyper = self._group_hyper()        # raises before anything is launched or exchanged
         ws = self._world()
         gs = 1.0 if grad_scale is None else grad_scale
         if ws > 1 and self.defer_update:
             work = dist.all_reduce(self._exchange_buffer(), group=self.group, async_op=True)
-            self._pending = (work, gs / ws, self.flat.all_grads_live)
+            # lr / weight_decay as they are NOW: a scheduler stepped before the next forward must not reach this update
+            self._pending = (work, gs / ws, self.flat.all_grads_live, hyper)
             _PENDING_OPTIMIZERS.add(self)
             return
-        self._apply(self.allreduce_grads() * gs, self.flat.all_grads_live)
+        self._apply(self.allreduce_grads() * gs, self.flat.all_grads_live, hyper)
 
     def flush(self):
         if self._pending is None:
             return
-        work, scale, live = self._pending
+        work, scale, live, hyper = self._pending
         self._pending = None
         _PENDING_OPTIMIZERS.discard(self)
         if self.profile_exchange and self.flat.theta.is_cuda:   # how long the compute stream stalls for the exchange
@@ -691,7 +846,7 @@ class FusedAdamW:
         else:
             work.wait()
         self._exchange_done()
-        self._apply(scale, live)
+        self._apply(scale, live, hyper)
         if self._zero_after_flush:
             self._zero_after_flush = False
             self.flat.zero_grad()
@@ -718,9 +873,10 @@ class FusedAdamW:
                                "track_grad_norm are all off, or step() has not run)")
         return dict(zip(self.flat.names, self._seg_norm.tolist()))
 
-    def _apply(self, scale, all_live=False):
+    def _apply(self, scale, all_live=False, hyper=None):
         self.step_count += 1
         g = self.param_groups[0]
+        lrs, wds = self._group_hyper() if hyper is None else hyper
         f = self.flat
         L = _lib.lib()
         max_norm, skip = g.get("max_grad_norm"), bool(g.get("skip_nonfinite", False))
@@ -729,8 +885,7 @@ class FusedAdamW:
         penalised = si is not None and si.tasks_consolidated > 0
         all_live = bool(all_live) or penalised       # autograd on loss + surrogate gives every trainable tensor a gradient
         nchunks, nseg = f.chunk_table.shape[0], len(f.entries)
-        hyper = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
-                 float(scale), _lib.ptr(self.shadow))
+        b1, b2, eps = float(g["betas"][0]), float(g["betas"][1]), float(g["eps"])
         agem = self.projection if self.projection is not None and self.projection.has_reference else None
         if measured and self._seg_norm is None:
             self._seg_norm = torch.zeros(nseg, dtype=torch.float32, device=f.theta.device)
@@ -756,7 +911,20 @@ class FusedAdamW:
                 _lib.stream_ptr())
             _lib.check(st, "ia_grad_norm")
         head = (_lib.ptr(f.theta), _lib.ptr(f.grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), _lib.ptr(f.chunk_table),
-                nchunks, _lib.ptr(self.seg_active), _lib.ptr(self.seg_step), nseg, int(all_live)) + hyper
+                nchunks, _lib.ptr(self.seg_active), _lib.ptr(self.seg_step), nseg, int(all_live))
+        if len(lrs) > 1:           # every kind of step through the one grouped entry point: the operands select the kernel
+            n = len(lrs)
+            st = L.ia_adamw_step_segmented_grouped(
+                *head, b1, b2, eps, float(scale), _lib.ptr(self.shadow), _lib.ptr(self.seg_group), n,
+                (ctypes.c_float * n)(*lrs), (ctypes.c_float * n)(*wds),
+                _lib.ptr(self._norm_state) if measured else None, int(skip), _lib.ptr(self._counters) if measured else None,
+                _lib.ptr(si.w.flat) if si is not None else None, _lib.ptr(si.omega.flat) if penalised else None,
+                _lib.ptr(si.theta_star.flat) if penalised else None, float(si.si_c) if si is not None else 0.0,
+                _lib.ptr(agem.ref.flat) if agem is not None else None, _lib.ptr(agem.proj_state) if agem is not None else None,
+                _lib.ptr(agem.proj_counters) if agem is not None else None, _lib.stream_ptr())
+            _lib.check(st, "ia_adamw_step_segmented_grouped")
+            return self._after_update()
+        head += (lrs[0], b1, b2, eps, wds[0], float(scale), _lib.ptr(self.shadow))
         if agem is not None:
             st = L.ia_adamw_step_segmented_projected(
                 *head, _lib.ptr(self._norm_state) if measured else None, int(skip), _lib.ptr(self._counters) if measured else None,
@@ -775,6 +943,9 @@ class FusedAdamW:
         else:
             st = L.ia_adamw_step_segmented(*head, _lib.stream_ptr())
             _lib.check(st, "ia_adamw_step_segmented")
+        self._after_update()
+
+    def _after_update(self):
         if self.flat.theta.is_cuda:
             global LAST_UPDATE_EVENT
             LAST_UPDATE_EVENT = torch.cuda.Event()
@@ -792,17 +963,26 @@ class FusedAdamW:
         with the flat layout they belong to (a pending deferred update is applied first)."""
         self.flush()
         counters = self._counters.cpu()
-        return {"entries": list(self.flat.entries),
-                "exp_avg": self.exp_avg.detach().to("cpu", copy=True), "exp_avg_sq": self.exp_avg_sq.detach().to("cpu", copy=True),
-                "seg_step": self.seg_step.to("cpu", copy=True), "step_count": self.step_count,
-                "param_group": {k: v for k, v in self.param_groups[0].items() if k != "params"},
-                "clipped_steps": int(counters[0]), "skipped_steps": int(counters[1])}
+        sd = {"entries": list(self.flat.entries),
+              "exp_avg": self.exp_avg.detach().to("cpu", copy=True), "exp_avg_sq": self.exp_avg_sq.detach().to("cpu", copy=True),
+              "seg_step": self.seg_step.to("cpu", copy=True), "step_count": self.step_count,
+              "param_group": {k: v for k, v in self.param_groups[0].items() if k not in ("params", "names")},
+              "clipped_steps": int(counters[0]), "skipped_steps": int(counters[1])}
+        if len(self.param_groups) > 1:      # the partition and every group's values (with whatever keys a scheduler added)
+            sd["param_groups"] = [dict({k: v for k, v in g.items() if k != "params"}, names=list(names))
+                                  for g, names in zip(self.param_groups, self._group_names)]
+        return sd
 
     def load_state_dict(self, sd: dict, source="state dict"):
         """Inverse of state_dict(); refuses a state saved for another set of trainable tensors.  Weights and their bf16
         images are not part of the optimizer state and are left alone."""
         if [tuple(e[:3]) + (tuple(e[3]),) for e in sd["entries"]] != list(self.flat.entries):
             raise ValueError(f"{source}: 'optimizer' was saved for a different set of trainable tensors")
+        saved_groups = sd.get("param_groups")
+        partition = [list(g["names"]) for g in saved_groups] if saved_groups is not None else [list(self.flat.names)]
+        if partition != self._group_names:
+            raise ValueError(f"{source}: 'optimizer' was saved for a different partition into parameter groups "
+                             f"({len(partition)} groups saved, {len(self._group_names)} here, compared by names and order)")
         self.flush()
         self.exp_avg.copy_(sd["exp_avg"])
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
@@ -811,6 +991,11 @@ class FusedAdamW:
         hyper = dict(sd["param_group"])
         hyper["betas"] = tuple(hyper["betas"])
         self.param_groups[0].update(hyper)
+        for g, saved in zip(self.param_groups, saved_groups or []):
+            values = {k: v for k, v in saved.items() if k != "names"}
+            if "betas" in values:
+                values["betas"] = tuple(values["betas"])
+            g.update(values)
         self._counters.copy_(torch.tensor([sd["clipped_steps"], sd["skipped_steps"]], dtype=torch.int32))
 
 

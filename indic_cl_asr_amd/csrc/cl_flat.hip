@@ -14,6 +14,8 @@
 //                              reference gradient, the decision g.r < 0 and alpha = g.r / r.r left on the device
 //   ia_grad_norm_projected ... ia_grad_norm of the gradient the projected step consumes (g - alpha * r when the flag is set)
 //   ia_adamw_step_segmented_projected .. the per-tensor AdamW on that gradient, r as one more operand of the launch
+//   ia_adamw_step_segmented_grouped .... any of the four segmented steps with lr and weight_decay per parameter group
+//                              (torch.optim.AdamW's param_groups): the same kernels, the group table by value in their arguments
 // All are HBM-streaming kernels: 16-byte accesses, grid capped at 2048 workgroups, fp32 math.
 #include "ia_common.h"
 
@@ -222,6 +224,21 @@ __global__ __launch_bounds__(GN_THREADS) void grad_norm_finish_kernel(const floa
     grad_norm_finish(chunk_sumsq, seg_chunk_begin, nseg, abs_scale, max_norm, seg_norm, norm_state);
 }
 
+// Parameter groups: learning rate and weight decay per group, by value in the kernel arguments (the host fills them from two host
+// arrays at every call: no copy, no staging buffer).  seg_group[k] is tensor k's group (NULL: group 0), so the lookup is
+// workgroup-uniform per chunk: a scalar load of the index and two scalar loads from the argument segment.  It has to sit INSIDE
+// the chunk loop: with more than 2048 chunks one workgroup visits chunks of different tensors.
+struct group_table {
+    int32_t n;
+    float lr[IA_MAX_PARAM_GROUPS];
+    float weight_decay[IA_MAX_PARAM_GROUPS];
+};
+
+__device__ __forceinline__ int group_of(const int* __restrict__ seg_group, int seg, int n) {
+    const int gi = seg_group ? seg_group[seg] : 0;
+    return gi < 0 ? 0 : (gi >= n ? n - 1 : gi);      // the argument segment is never indexed outside the table
+}
+
 // CLIP: the gradient is (g * grad_scale) * coef with coef = norm_state[1] read from the device, each product rounded to
 // fp32 on its own (never fused into the moment update), so that with grad_scale == 1 it is torch's g.mul_(coef) bit for
 // bit; when norm_state[2] flags a non-finite norm and skip_nonfinite is set the launch writes nothing at all.
@@ -241,8 +258,9 @@ __global__ __launch_bounds__(CL_THREADS) void adamw_seg_kernel(float* __restrict
                                                                float* __restrict__ m, float* __restrict__ v,
                                                                const int4* __restrict__ table, int nchunks,
                                                                const int* __restrict__ seg_active,
-                                                               const int* __restrict__ seg_step, float lr, float b1, float b2,
-                                                               float eps, float wd, float grad_scale,
+                                                               const int* __restrict__ seg_step, const group_table groups,
+                                                               const int* __restrict__ seg_group, float b1, float b2, float eps,
+                                                               float grad_scale,
                                                                unsigned short* __restrict__ shadow_bf16,
                                                                const float* __restrict__ norm_state, int skip_nonfinite) {
     __shared__ float sh_c[2];
@@ -261,6 +279,8 @@ __global__ __launch_bounds__(CL_THREADS) void adamw_seg_kernel(float* __restrict
                 }
             continue;
         }
+        const int gi = group_of(seg_group, e.z, groups.n);      // workgroup-uniform
+        const float lr = groups.lr[gi], wd = groups.weight_decay[gi];
         __syncthreads();
         if (threadIdx.x == 0) {
             const double step = (double)(seg_step[e.z] + 1);
@@ -377,8 +397,9 @@ __global__ __launch_bounds__(CL_THREADS) void adamw_seg_si_kernel(float* __restr
                                                                   float* __restrict__ m, float* __restrict__ v,
                                                                   const int4* __restrict__ table, int nchunks,
                                                                   const int* __restrict__ seg_active,
-                                                                  const int* __restrict__ seg_step, float lr, float b1, float b2,
-                                                                  float eps, float wd, float grad_scale,
+                                                                  const int* __restrict__ seg_step, const group_table groups,
+                                                                  const int* __restrict__ seg_group, float b1, float b2, float eps,
+                                                                  float grad_scale,
                                                                   unsigned short* __restrict__ shadow_bf16,
                                                                   const float* __restrict__ norm_state, int skip_nonfinite,
                                                                   float* __restrict__ path_w, const float* __restrict__ omega,
@@ -399,6 +420,8 @@ __global__ __launch_bounds__(CL_THREADS) void adamw_seg_si_kernel(float* __restr
                 }
             continue;
         }
+        const int gi = group_of(seg_group, e.z, groups.n);      // workgroup-uniform
+        const float lr = groups.lr[gi], wd = groups.weight_decay[gi];
         __syncthreads();
         if (threadIdx.x == 0) {
             const double step = (double)(seg_step[e.z] + 1);
@@ -629,8 +652,9 @@ __global__ __launch_bounds__(CL_THREADS) void adamw_seg_proj_kernel(float* __res
                                                                     float* __restrict__ m, float* __restrict__ v,
                                                                     const int4* __restrict__ table, int nchunks,
                                                                     const int* __restrict__ seg_active,
-                                                                    const int* __restrict__ seg_step, float lr, float b1, float b2,
-                                                                    float eps, float wd, float grad_scale,
+                                                                    const int* __restrict__ seg_step, const group_table groups,
+                                                                    const int* __restrict__ seg_group, float b1, float b2, float eps,
+                                                                    float grad_scale,
                                                                     unsigned short* __restrict__ shadow_bf16,
                                                                     const float* __restrict__ norm_state, int skip_nonfinite,
                                                                     const float* __restrict__ ref,
@@ -653,6 +677,8 @@ __global__ __launch_bounds__(CL_THREADS) void adamw_seg_proj_kernel(float* __res
                 }
             continue;
         }
+        const int gi = group_of(seg_group, e.z, groups.n);      // workgroup-uniform
+        const float lr = groups.lr[gi], wd = groups.weight_decay[gi];
         __syncthreads();
         if (threadIdx.x == 0) {
             const double step = (double)(seg_step[e.z] + 1);
@@ -733,6 +759,115 @@ inline int cap_grid(int64_t work_items, int per_block) {
     int64_t b = (work_items + per_block - 1) / per_block;
     return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
 }
+
+inline group_table one_group(float lr, float weight_decay) {
+    group_table t = {};
+    t.n = 1;
+    t.lr[0] = lr;
+    t.weight_decay[0] = weight_decay;
+    return t;
+}
+
+// The launches of the four kinds of segmented step, shared by their entry points (one group, seg_group NULL) and by
+// ia_adamw_step_segmented_grouped.  Arguments are validated by the callers.
+struct step_head {
+    float *theta; const float* grad; float *exp_avg, *exp_avg_sq;
+    const int4* table; int nchunks; int32_t *seg_active, *seg_step; int nseg, all_active;
+    float b1, b2, eps, grad_scale; unsigned short* shadow;
+};
+
+inline bool step_head_ok(const float* theta, const float* grad, const float* exp_avg, const float* exp_avg_sq,
+                         const int32_t* chunk_table, int nchunks, const int32_t* seg_active, const int32_t* seg_step, int nseg,
+                         const void* shadow_bf16) {
+    if (!theta || !grad || !exp_avg || !exp_avg_sq || !chunk_table || !seg_active || !seg_step || nchunks <= 0 || nseg <= 0)
+        return false;
+    return ia_is_aligned(theta, 16) && ia_is_aligned(grad, 16) && ia_is_aligned(exp_avg, 16) && ia_is_aligned(exp_avg_sq, 16) &&
+           ia_is_aligned(chunk_table, 16) && (!shadow_bf16 || ia_is_aligned(shadow_bf16, 8));
+}
+
+inline bool si_operands_ok(const float* norm_state, const int32_t* counters, const float* path_w, const float* omega,
+                           const float* theta_star) {
+    if (!path_w || (norm_state == nullptr) != (counters == nullptr) || (omega == nullptr) != (theta_star == nullptr)) return false;
+    return ia_is_aligned(path_w, 16) && (!omega || (ia_is_aligned(omega, 16) && ia_is_aligned(theta_star, 16)));
+}
+
+inline bool proj_operands_ok(const float* norm_state, const int32_t* counters, const float* ref, const float* proj_state,
+                             const int32_t* proj_counters) {
+    if (!ref || !proj_state || !proj_counters || (norm_state == nullptr) != (counters == nullptr)) return false;
+    return ia_is_aligned(ref, 16) && ia_is_aligned(proj_state, 4) && ia_is_aligned(proj_counters, 4);
+}
+
+inline int step_grid(const step_head& h) { return h.nchunks < 2048 ? h.nchunks : 2048; }
+
+inline bool mark_all_active(const step_head& h, hipStream_t st) {   // 0x01010101: non-zero
+    return hipMemsetAsync(h.seg_active, 1, (size_t)h.nseg * sizeof(int32_t), st) == hipSuccess;
+}
+
+inline void launch_activity(const step_head& h, hipStream_t st) {
+    hipLaunchKernelGGL(seg_activity_kernel<false>, dim3(step_grid(h)), dim3(CL_THREADS), 0, st, h.grad, h.table, h.nchunks,
+                       h.seg_active, (float*)nullptr);
+}
+
+inline void launch_advance(const step_head& h, const float* norm_state, int skip_nonfinite, int32_t* counters, hipStream_t st) {
+    const dim3 grid((h.nseg + 255) / 256), block(256);
+    if (norm_state)
+        hipLaunchKernelGGL(seg_step_advance_clipped_kernel, grid, block, 0, st, h.seg_active, h.seg_step, h.nseg, norm_state,
+                           skip_nonfinite, counters);
+    else
+        hipLaunchKernelGGL(seg_step_advance_kernel, grid, block, 0, st, h.seg_active, h.seg_step, h.nseg);
+}
+
+// plain (norm_state NULL: the activity pass runs here unless all_active) or clipped (ia_grad_norm has set the flags)
+int run_step(const step_head& h, const group_table& gt, const int32_t* seg_group, const float* norm_state, int skip_nonfinite,
+             int32_t* counters, hipStream_t st) {
+    if (h.all_active) {
+        if (!mark_all_active(h, st)) return IA_LAUNCH_FAILED;
+    } else if (!norm_state) {
+        launch_activity(h, st);
+    }
+    auto kernel = norm_state ? adamw_seg_kernel<true> : adamw_seg_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(step_grid(h)), dim3(CL_THREADS), 0, st, h.theta, h.grad, h.exp_avg, h.exp_avg_sq, h.table,
+                       h.nchunks, h.seg_active, h.seg_step, gt, seg_group, h.b1, h.b2, h.eps, h.grad_scale, h.shadow, norm_state,
+                       skip_nonfinite);
+    launch_advance(h, norm_state, skip_nonfinite, counters, st);
+    IA_RETURN_IF_LAUNCH_FAILED();
+    return IA_OK;
+}
+
+int run_step_si(const step_head& h, const group_table& gt, const int32_t* seg_group, const float* norm_state, int skip_nonfinite,
+                int32_t* counters, float* path_w, const float* omega, const float* theta_star, float penalty_coef,
+                hipStream_t st) {
+    const bool clip = norm_state != nullptr, pen = omega != nullptr;
+    if (h.all_active) {
+        if (!mark_all_active(h, st)) return IA_LAUNCH_FAILED;
+    } else if (!clip) {   // with norm_state, ia_grad_norm's first pass has set the flags
+        launch_activity(h, st);
+    }
+    const float c2 = 2.f * penalty_coef;
+    auto kernel = clip ? (pen ? adamw_seg_si_kernel<true, true> : adamw_seg_si_kernel<true, false>)
+                       : (pen ? adamw_seg_si_kernel<false, true> : adamw_seg_si_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(step_grid(h)), dim3(CL_THREADS), 0, st, h.theta, h.grad, h.exp_avg, h.exp_avg_sq, h.table,
+                       h.nchunks, h.seg_active, h.seg_step, gt, seg_group, h.b1, h.b2, h.eps, h.grad_scale, h.shadow, norm_state,
+                       skip_nonfinite, path_w, omega, theta_star, c2);
+    launch_advance(h, norm_state, skip_nonfinite, counters, st);
+    IA_RETURN_IF_LAUNCH_FAILED();
+    return IA_OK;
+}
+
+int run_step_projected(const step_head& h, const group_table& gt, const int32_t* seg_group, const float* norm_state,
+                       int skip_nonfinite, int32_t* counters, const float* ref, const float* proj_state, int32_t* proj_counters,
+                       hipStream_t st) {
+    if (h.all_active)   // otherwise ia_agem_dots has set the flags from the task gradient
+        if (!mark_all_active(h, st)) return IA_LAUNCH_FAILED;
+    auto kernel = norm_state ? adamw_seg_proj_kernel<true> : adamw_seg_proj_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(step_grid(h)), dim3(CL_THREADS), 0, st, h.theta, h.grad, h.exp_avg, h.exp_avg_sq, h.table,
+                       h.nchunks, h.seg_active, h.seg_step, gt, seg_group, h.b1, h.b2, h.eps, h.grad_scale, h.shadow, norm_state,
+                       skip_nonfinite, ref, proj_state);
+    hipLaunchKernelGGL(seg_step_advance_projected_kernel, dim3((h.nseg + 255) / 256), dim3(256), 0, st, h.seg_active, h.seg_step,
+                       h.nseg, norm_state, skip_nonfinite, counters, proj_state, proj_counters);
+    IA_RETURN_IF_LAUNCH_FAILED();
+    return IA_OK;
+}
 }  // namespace
 
 extern "C" int ia_cl_chunk_elems(void) { return CL_CHUNK; }
@@ -790,25 +925,11 @@ extern "C" int ia_adamw_step_segmented(float* theta, const float* grad, float* e
                                        const int32_t* chunk_table, int nchunks, int32_t* seg_active, int32_t* seg_step, int nseg,
                                        int all_active, float lr, float beta1, float beta2, float eps, float weight_decay,
                                        float grad_scale, void* shadow_bf16, ia_stream_t stream) {
-    if (!theta || !grad || !exp_avg || !exp_avg_sq || !chunk_table || !seg_active || !seg_step || nchunks <= 0 || nseg <= 0)
+    if (!step_head_ok(theta, grad, exp_avg, exp_avg_sq, chunk_table, nchunks, seg_active, seg_step, nseg, shadow_bf16))
         return IA_INVALID_VALUE;
-    if (!ia_is_aligned(theta, 16) || !ia_is_aligned(grad, 16) || !ia_is_aligned(exp_avg, 16) ||
-        !ia_is_aligned(exp_avg_sq, 16) || !ia_is_aligned(chunk_table, 16) || (shadow_bf16 && !ia_is_aligned(shadow_bf16, 8)))
-        return IA_INVALID_VALUE;
-    hipStream_t st = (hipStream_t)stream;
-    const int grid = nchunks < 2048 ? nchunks : 2048;
-    if (all_active) {
-        if (hipMemsetAsync(seg_active, 1, (size_t)nseg * sizeof(int32_t), st) != hipSuccess) return IA_LAUNCH_FAILED;  // 0x01010101: non-zero
-    } else {
-        hipLaunchKernelGGL(seg_activity_kernel<false>, dim3(grid), dim3(CL_THREADS), 0, st, grad, (const int4*)chunk_table, nchunks,
-                           seg_active, (float*)nullptr);
-    }
-    hipLaunchKernelGGL(adamw_seg_kernel<false>, dim3(grid), dim3(CL_THREADS), 0, st, theta, grad, exp_avg, exp_avg_sq,
-                       (const int4*)chunk_table, nchunks, seg_active, seg_step, lr, beta1, beta2, eps, weight_decay, grad_scale,
-                       (unsigned short*)shadow_bf16, (const float*)nullptr, 0);
-    hipLaunchKernelGGL(seg_step_advance_kernel, dim3((nseg + 255) / 256), dim3(256), 0, st, seg_active, seg_step, nseg);
-    IA_RETURN_IF_LAUNCH_FAILED();
-    return IA_OK;
+    const step_head h = {theta, grad, exp_avg, exp_avg_sq, (const int4*)chunk_table, nchunks, seg_active, seg_step, nseg, all_active,
+                         beta1, beta2, eps, grad_scale, (unsigned short*)shadow_bf16};
+    return run_step(h, one_group(lr, weight_decay), nullptr, nullptr, 0, nullptr, (hipStream_t)stream);
 }
 
 extern "C" size_t ia_grad_norm_workspace_bytes(int nchunks) { return nchunks > 0 ? (size_t)nchunks * sizeof(float) : 0; }
@@ -834,23 +955,12 @@ extern "C" int ia_adamw_step_segmented_clipped(float* theta, const float* grad, 
                                                int nseg, int all_active, float lr, float beta1, float beta2, float eps,
                                                float weight_decay, float grad_scale, void* shadow_bf16, const float* norm_state,
                                                int skip_nonfinite, int32_t* counters, ia_stream_t stream) {
-    if (!theta || !grad || !exp_avg || !exp_avg_sq || !chunk_table || !seg_active || !seg_step || !norm_state || !counters ||
-        nchunks <= 0 || nseg <= 0)
+    if (!norm_state || !counters ||
+        !step_head_ok(theta, grad, exp_avg, exp_avg_sq, chunk_table, nchunks, seg_active, seg_step, nseg, shadow_bf16))
         return IA_INVALID_VALUE;
-    if (!ia_is_aligned(theta, 16) || !ia_is_aligned(grad, 16) || !ia_is_aligned(exp_avg, 16) ||
-        !ia_is_aligned(exp_avg_sq, 16) || !ia_is_aligned(chunk_table, 16) || (shadow_bf16 && !ia_is_aligned(shadow_bf16, 8)))
-        return IA_INVALID_VALUE;
-    hipStream_t st = (hipStream_t)stream;
-    const int grid = nchunks < 2048 ? nchunks : 2048;
-    if (all_active)   // otherwise ia_grad_norm's first pass has set the flags
-        if (hipMemsetAsync(seg_active, 1, (size_t)nseg * sizeof(int32_t), st) != hipSuccess) return IA_LAUNCH_FAILED;
-    hipLaunchKernelGGL(adamw_seg_kernel<true>, dim3(grid), dim3(CL_THREADS), 0, st, theta, grad, exp_avg, exp_avg_sq,
-                       (const int4*)chunk_table, nchunks, seg_active, seg_step, lr, beta1, beta2, eps, weight_decay, grad_scale,
-                       (unsigned short*)shadow_bf16, norm_state, skip_nonfinite);
-    hipLaunchKernelGGL(seg_step_advance_clipped_kernel, dim3((nseg + 255) / 256), dim3(256), 0, st, seg_active, seg_step, nseg,
-                       norm_state, skip_nonfinite, counters);
-    IA_RETURN_IF_LAUNCH_FAILED();
-    return IA_OK;
+    const step_head h = {theta, grad, exp_avg, exp_avg_sq, (const int4*)chunk_table, nchunks, seg_active, seg_step, nseg, all_active,
+                         beta1, beta2, eps, grad_scale, (unsigned short*)shadow_bf16};
+    return run_step(h, one_group(lr, weight_decay), nullptr, norm_state, skip_nonfinite, counters, (hipStream_t)stream);
 }
 
 extern "C" int ia_adamw_step_segmented_si(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq,
@@ -859,37 +969,13 @@ extern "C" int ia_adamw_step_segmented_si(float* theta, const float* grad, float
                                           float grad_scale, void* shadow_bf16, const float* norm_state, int skip_nonfinite,
                                           int32_t* counters, float* path_w, const float* omega, const float* theta_star,
                                           float penalty_coef, ia_stream_t stream) {
-    if (!theta || !grad || !exp_avg || !exp_avg_sq || !chunk_table || !seg_active || !seg_step || !path_w || nchunks <= 0 ||
-        nseg <= 0)
+    if (!step_head_ok(theta, grad, exp_avg, exp_avg_sq, chunk_table, nchunks, seg_active, seg_step, nseg, shadow_bf16) ||
+        !si_operands_ok(norm_state, counters, path_w, omega, theta_star))
         return IA_INVALID_VALUE;
-    if ((norm_state == nullptr) != (counters == nullptr) || (omega == nullptr) != (theta_star == nullptr))
-        return IA_INVALID_VALUE;
-    if (!ia_is_aligned(theta, 16) || !ia_is_aligned(grad, 16) || !ia_is_aligned(exp_avg, 16) ||
-        !ia_is_aligned(exp_avg_sq, 16) || !ia_is_aligned(chunk_table, 16) || (shadow_bf16 && !ia_is_aligned(shadow_bf16, 8)) ||
-        !ia_is_aligned(path_w, 16) || (omega && (!ia_is_aligned(omega, 16) || !ia_is_aligned(theta_star, 16))))
-        return IA_INVALID_VALUE;
-    hipStream_t st = (hipStream_t)stream;
-    const int grid = nchunks < 2048 ? nchunks : 2048;
-    const bool clip = norm_state != nullptr, pen = omega != nullptr;
-    if (all_active) {
-        if (hipMemsetAsync(seg_active, 1, (size_t)nseg * sizeof(int32_t), st) != hipSuccess) return IA_LAUNCH_FAILED;
-    } else if (!clip) {   // with norm_state, ia_grad_norm's first pass has set the flags
-        hipLaunchKernelGGL(seg_activity_kernel<false>, dim3(grid), dim3(CL_THREADS), 0, st, grad, (const int4*)chunk_table, nchunks,
-                           seg_active, (float*)nullptr);
-    }
-    const float c2 = 2.f * penalty_coef;
-    auto kernel = clip ? (pen ? adamw_seg_si_kernel<true, true> : adamw_seg_si_kernel<true, false>)
-                       : (pen ? adamw_seg_si_kernel<false, true> : adamw_seg_si_kernel<false, false>);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(CL_THREADS), 0, st, theta, grad, exp_avg, exp_avg_sq, (const int4*)chunk_table,
-                       nchunks, seg_active, seg_step, lr, beta1, beta2, eps, weight_decay, grad_scale,
-                       (unsigned short*)shadow_bf16, norm_state, skip_nonfinite, path_w, omega, theta_star, c2);
-    if (clip)
-        hipLaunchKernelGGL(seg_step_advance_clipped_kernel, dim3((nseg + 255) / 256), dim3(256), 0, st, seg_active, seg_step, nseg,
-                           norm_state, skip_nonfinite, counters);
-    else
-        hipLaunchKernelGGL(seg_step_advance_kernel, dim3((nseg + 255) / 256), dim3(256), 0, st, seg_active, seg_step, nseg);
-    IA_RETURN_IF_LAUNCH_FAILED();
-    return IA_OK;
+    const step_head h = {theta, grad, exp_avg, exp_avg_sq, (const int4*)chunk_table, nchunks, seg_active, seg_step, nseg, all_active,
+                         beta1, beta2, eps, grad_scale, (unsigned short*)shadow_bf16};
+    return run_step_si(h, one_group(lr, weight_decay), nullptr, norm_state, skip_nonfinite, counters, path_w, omega, theta_star,
+                       penalty_coef, (hipStream_t)stream);
 }
 
 extern "C" int ia_si_consolidate(const float* theta, float* theta_star, float* path_w, float* omega, float xi, int64_t n,
@@ -948,24 +1034,41 @@ extern "C" int ia_adamw_step_segmented_projected(float* theta, const float* grad
                                                  float weight_decay, float grad_scale, void* shadow_bf16, const float* norm_state,
                                                  int skip_nonfinite, int32_t* counters, const float* ref, const float* proj_state,
                                                  int32_t* proj_counters, ia_stream_t stream) {
-    if (!theta || !grad || !exp_avg || !exp_avg_sq || !chunk_table || !seg_active || !seg_step || !ref || !proj_state ||
-        !proj_counters || nchunks <= 0 || nseg <= 0)
+    if (!step_head_ok(theta, grad, exp_avg, exp_avg_sq, chunk_table, nchunks, seg_active, seg_step, nseg, shadow_bf16) ||
+        !proj_operands_ok(norm_state, counters, ref, proj_state, proj_counters))
         return IA_INVALID_VALUE;
-    if ((norm_state == nullptr) != (counters == nullptr)) return IA_INVALID_VALUE;
-    if (!ia_is_aligned(theta, 16) || !ia_is_aligned(grad, 16) || !ia_is_aligned(exp_avg, 16) ||
-        !ia_is_aligned(exp_avg_sq, 16) || !ia_is_aligned(chunk_table, 16) || (shadow_bf16 && !ia_is_aligned(shadow_bf16, 8)) ||
-        !ia_is_aligned(ref, 16) || !ia_is_aligned(proj_state, 4) || !ia_is_aligned(proj_counters, 4))
+    const step_head h = {theta, grad, exp_avg, exp_avg_sq, (const int4*)chunk_table, nchunks, seg_active, seg_step, nseg, all_active,
+                         beta1, beta2, eps, grad_scale, (unsigned short*)shadow_bf16};
+    return run_step_projected(h, one_group(lr, weight_decay), nullptr, norm_state, skip_nonfinite, counters, ref, proj_state,
+                              proj_counters, (hipStream_t)stream);
+}
+
+// Any of the four steps with per-group lr / weight_decay: the operands that are present select the step.
+extern "C" int ia_adamw_step_segmented_grouped(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq,
+                                               const int32_t* chunk_table, int nchunks, int32_t* seg_active, int32_t* seg_step,
+                                               int nseg, int all_active, float beta1, float beta2, float eps, float grad_scale,
+                                               void* shadow_bf16, const int32_t* seg_group, int ngroups, const float* group_lr,
+                                               const float* group_weight_decay, const float* norm_state, int skip_nonfinite,
+                                               int32_t* counters, float* path_w, const float* omega, const float* theta_star,
+                                               float penalty_coef, const float* ref, const float* proj_state,
+                                               int32_t* proj_counters, ia_stream_t stream) {
+    if (!step_head_ok(theta, grad, exp_avg, exp_avg_sq, chunk_table, nchunks, seg_active, seg_step, nseg, shadow_bf16))
         return IA_INVALID_VALUE;
+    if (ngroups < 1 || ngroups > IA_MAX_PARAM_GROUPS || !group_lr || !group_weight_decay || (ngroups > 1 && !seg_group) ||
+        (seg_group && !ia_is_aligned(seg_group, 4)))
+        return IA_INVALID_VALUE;
+    const bool si = path_w || omega || theta_star, proj = ref || proj_state || proj_counters;
+    if ((si && proj) || (norm_state == nullptr) != (counters == nullptr)) return IA_INVALID_VALUE;
+    if (si && !si_operands_ok(norm_state, counters, path_w, omega, theta_star)) return IA_INVALID_VALUE;
+    if (proj && !proj_operands_ok(norm_state, counters, ref, proj_state, proj_counters)) return IA_INVALID_VALUE;
+    group_table gt = {};
+    gt.n = ngroups;
+    for (int k = 0; k < ngroups; ++k) { gt.lr[k] = group_lr[k]; gt.weight_decay[k] = group_weight_decay[k]; }
+    const step_head h = {theta, grad, exp_avg, exp_avg_sq, (const int4*)chunk_table, nchunks, seg_active, seg_step, nseg, all_active,
+                         beta1, beta2, eps, grad_scale, (unsigned short*)shadow_bf16};
     hipStream_t st = (hipStream_t)stream;
-    const int grid = nchunks < 2048 ? nchunks : 2048;
-    if (all_active)   // otherwise ia_agem_dots has set the flags from the task gradient
-        if (hipMemsetAsync(seg_active, 1, (size_t)nseg * sizeof(int32_t), st) != hipSuccess) return IA_LAUNCH_FAILED;
-    auto kernel = norm_state ? adamw_seg_proj_kernel<true> : adamw_seg_proj_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(CL_THREADS), 0, st, theta, grad, exp_avg, exp_avg_sq, (const int4*)chunk_table,
-                       nchunks, seg_active, seg_step, lr, beta1, beta2, eps, weight_decay, grad_scale,
-                       (unsigned short*)shadow_bf16, norm_state, skip_nonfinite, ref, proj_state);
-    hipLaunchKernelGGL(seg_step_advance_projected_kernel, dim3((nseg + 255) / 256), dim3(256), 0, st, seg_active, seg_step, nseg,
-                       norm_state, skip_nonfinite, counters, proj_state, proj_counters);
-    IA_RETURN_IF_LAUNCH_FAILED();
-    return IA_OK;
+    if (proj) return run_step_projected(h, gt, seg_group, norm_state, skip_nonfinite, counters, ref, proj_state, proj_counters, st);
+    if (si)
+        return run_step_si(h, gt, seg_group, norm_state, skip_nonfinite, counters, path_w, omega, theta_star, penalty_coef, st);
+    return run_step(h, gt, seg_group, norm_state, skip_nonfinite, counters, st);
 }

@@ -1,12 +1,16 @@
 """FusedAdamW._apply on the flat buffers of BASELINE configs[1]'s trainable set (Conformer-medium, freeze_layer(m, 12)):
 plain, with max_grad_norm=1.0 (live-segment detection on / every segment live), and with a Synaptic Intelligence path integral
-attached (first task: w only; later tasks: omega and theta* read as well, every segment live).  Developer tool; one JSON line.
+attached (first task: w only; later tasks: omega and theta* read as well, every segment live), and `grouped`: the plain step
+with layerwise_lr_groups + no-decay parameter groups (ia_adamw_step_segmented_grouped).  Per leg: `<leg>_us` device time of one
+_apply between two events, `<leg>_host_us` host wall-clock of one step() call with no synchronisation inside the timed loop
+(what the training loop's thread pays: Python, ctypes and the launches).  Developer tool; one JSON line.
 
 `--legs plain` uses nothing newer than the segmented AdamW itself, so the same file times an older checkout."""
 import argparse
 import json
 import os
 import sys
+import time
 
 import torch
 
@@ -27,9 +31,21 @@ def timeit(fn, warmup=5, n=20):
     return a.elapsed_time(b) / n * 1e3
 
 
+def host_timeit(fn, warmup=5, n=50):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(n):
+        fn()
+    t1 = time.perf_counter()
+    torch.cuda.synchronize()
+    return (t1 - t0) / n * 1e6
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--legs", default="plain,clip,clip_all_live,si_first_task,si_penalty")
+    ap.add_argument("--legs", default="plain,clip,clip_all_live,si_first_task,si_penalty,grouped")
     args = ap.parse_args()
     from indic_cl_asr_amd import cl
     from indic_cl_asr_amd.config import model_config
@@ -43,7 +59,9 @@ def main():
     for leg in args.legs.split(","):
         kw, live = {"plain": ({}, False), "clip": ({"max_grad_norm": 1.0}, False),
                     "clip_all_live": ({"max_grad_norm": 1.0}, True), "si_first_task": ({}, False),
-                    "si_penalty": ({}, True)}[leg]
+                    "si_penalty": ({}, True), "grouped": ({}, False)}[leg]
+        if leg == "grouped":
+            kw["param_groups"] = cl.layerwise_lr_groups(flat, 1e-4, 0.9)
         if leg.startswith("si_"):
             kw["path_integral"] = si = cl.SynapticIntelligence(flat)
             if leg == "si_penalty":                  # a consolidated task: the step reads omega and theta* and adds the penalty
@@ -51,7 +69,12 @@ def main():
                 si.tasks_consolidated = 1
         opt = cl.FusedAdamW(flat, lr=1e-4, **kw)
         flat.grad.copy_(grad)
+        if leg == "grouped":
+            out["groups"] = len(opt.param_groups)
         out[leg + "_us"] = round(timeit(lambda: opt._apply(1.0, live)), 2)
+        flat.all_grads_live = live
+        out[leg + "_host_us"] = round(host_timeit(opt.step), 2)
+        flat.all_grads_live = False
         del opt
     print(json.dumps(out), flush=True)
 
