@@ -150,7 +150,7 @@ SIGNATURES = {
     "ia_lstm_lds_bytes": (_i, [_i, _i]),
     "ia_lstm_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
     "ia_lstm_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
-    "ia_feat_frames": (_i, [_vp, _i, _i, _i, _i, _i, _f, _f, _c.c_uint, _vp, _i, _vp]),
+    "ia_feat_frames": (_i, [_vp, _i, _i, _i, _i, _i, _i, _f, _f, _c.c_uint, _vp, _i, _vp]),
     "ia_gemm_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "ia_feat_power": (_i, [_vp, _i64, _i, _i, _i, _vp, _i, _vp]),
     "ia_feat_logmel_t": (_i, [_vp, _i, _i, _i, _i, _f, _vp, _vp]),

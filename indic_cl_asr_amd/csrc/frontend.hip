@@ -82,11 +82,12 @@ __device__ __forceinline__ float fe_sample(const float* __restrict__ x, int L, i
     return v;
 }
 
-// frames[b*Tm + t][n] = y[reflect(t*hop - (win/2) + n)], y = pre-emphasised (dithered) signal, n < win; columns
-// [win, ldf) zero.  (dither + pre-emphasis + centred reflect-padded framing of features.py:408-418; the Hann window
-// is folded into the DFT basis.)
+// frames[b*Tm + t][n] = y[reflect(t*hop - lead + n)], y = pre-emphasised (dithered) signal, n < win; columns
+// [win, ldf) zero.  lead = n_fft/2 - (n_fft - win)/2: torch.stft pads the window to n_fft with (n_fft - win)/2 zeros on
+// the left and centres the n_fft-point frame (win/2 for even win, (win + 1)/2 for odd win).  (dither + pre-emphasis +
+// centred reflect-padded framing of features.py:408-418; the Hann window is folded into the DFT basis.)
 __global__ __launch_bounds__(256) void feat_frames_kernel(const float* __restrict__ audio, int B, int L, int Tm, int win,
-                                                          int hop, float preemph, float dither, unsigned seed,
+                                                          int lead, int hop, float preemph, float dither, unsigned seed,
                                                           float* __restrict__ frames, int ldf) {
     const int64_t total = (int64_t)B * Tm * ldf;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
@@ -95,7 +96,7 @@ __global__ __launch_bounds__(256) void feat_frames_kernel(const float* __restric
         const int t = (int)(row % Tm), b = (int)(row / Tm);
         float v = 0.f;
         if (n < win) {
-            int p = t * hop - win / 2 + n;
+            int p = t * hop - lead + n;
             if (p < 0) p = -p;
             if (p >= L) p = 2 * L - 2 - p;
             const float* x = audio + (size_t)b * L;
@@ -143,14 +144,17 @@ __global__ __launch_bounds__(256) void feat_logmel_t_kernel(const float* __restr
 
 }  // namespace
 
-extern "C" int ia_feat_frames(const float* audio, int B, int L, int Tm, int win, int hop, float preemph, float dither,
-                              unsigned seed, float* frames, int ldf, ia_stream_t stream) {
-    if (!audio || !frames || B <= 0 || L < 2 || Tm <= 0 || win <= 0 || hop <= 0 || ldf < win) return IA_INVALID_VALUE;
-    if (win / 2 >= L) return IA_UNSUPPORTED;  // reflect padding needs L > win/2 (as torch.stft)
+extern "C" int ia_feat_frames(const float* audio, int B, int L, int Tm, int win, int n_fft, int hop, float preemph,
+                              float dither, unsigned seed, float* frames, int ldf, ia_stream_t stream) {
+    if (!audio || !frames || B <= 0 || L < 2 || Tm <= 0 || win <= 0 || n_fft < win || hop <= 0 || ldf < win) return IA_INVALID_VALUE;
+    const int lead = n_fft / 2 - (n_fft - win) / 2;   // samples of the window in front of the frame's centre
+    if (lead >= L) return IA_UNSUPPORTED;             // one reflection must reach every tap of frame 0
+    if ((int64_t)(Tm - 1) * hop - lead >= L) return IA_INVALID_VALUE;      // a frame entirely beyond the reflected signal
+    if ((int64_t)(Tm - 1) * hop + (win - 1 - lead) > 2 * (int64_t)L - 2) return IA_INVALID_VALUE;
     const int64_t total = (int64_t)B * Tm * ldf;
     const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-    hipLaunchKernelGGL(feat_frames_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, audio, B, L, Tm, win, hop, preemph,
-                       dither, seed, frames, ldf);
+    hipLaunchKernelGGL(feat_frames_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, audio, B, L, Tm, win, lead, hop,
+                       preemph, dither, seed, frames, ldf);
     IA_RETURN_IF_LAUNCH_FAILED();
     return IA_OK;
 }

@@ -111,13 +111,15 @@ __global__ __launch_bounds__(64) void feat_logmel_fft_kernel(FfArgs a) {
     const int off = (FF_N - a.win) / 2;
 
     // ---- per-lane constants: window taps of this lane's 8 points, twiddles of passes 1 and 2, filterbank chunks
+    // torch.stft pads the window to n_fft with (n_fft - win) / 2 zeros on the left and centres the n_fft-point frame: tap n
+    // reads sample t * hop + n + off - n_fft / 2 (n - win / 2 only for even win; an odd window sits one sample further left)
     float wv[8]; int sidx[8];           // invalid points (outside the centred window): weight 0, any in-range sample
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
         const int n = lane + 64 * k - off;
         const bool ok = n >= 0 && n < a.win;
         wv[k] = ok ? a.window[n] : 0.f;
-        sidx[k] = ok ? n - a.win / 2 : 0;
+        sidx[k] = ok ? n + off - FF_N / 2 : 0;
     }
     c2 tw1[8], tw2[8];
     {
@@ -252,9 +254,10 @@ extern "C" int ia_feat_logmel_fft(const float* y, int B, int L, int Tm, const fl
     if (!y || !window || !twiddle || !chunk_start || !chunk_vals || !filt_chunks || !out || B <= 0 || L < 2 || Tm <= 0 || hop <= 0)
         return IA_INVALID_VALUE;
     if (!ia_feat_logmel_fft_supported(n_fft, win, n_mels, n_chunks)) return IA_UNSUPPORTED;
-    if (win / 2 >= L) return IA_UNSUPPORTED;                       // reflect padding needs L > win / 2 (as torch.stft)
-    if ((int64_t)(Tm - 1) * hop - win / 2 >= L) return IA_INVALID_VALUE;   // a frame entirely beyond the reflected signal
-    if ((int64_t)(Tm - 1) * hop + (win - 1 - win / 2) > 2 * (int64_t)L - 2) return IA_INVALID_VALUE;
+    const int lead = n_fft / 2 - (n_fft - win) / 2;                // samples of the window in front of the frame's centre
+    if (lead >= L) return IA_UNSUPPORTED;                          // one reflection must reach every tap of frame 0
+    if ((int64_t)(Tm - 1) * hop - lead >= L) return IA_INVALID_VALUE;      // a frame entirely beyond the reflected signal
+    if ((int64_t)(Tm - 1) * hop + (win - 1 - lead) > 2 * (int64_t)L - 2) return IA_INVALID_VALUE;
     FfArgs a;
     a.y = y; a.B = B; a.L = L; a.Tm = Tm; a.window = window; a.win = win; a.hop = hop; a.tw = (const c2*)twiddle;
     a.chunk_start = chunk_start; a.chunk_vals = chunk_vals; a.filt_chunks = filt_chunks; a.nm = n_mels; a.guard = guard; a.out = out;

@@ -14,7 +14,7 @@ def _dft_basis(window, n_fft, ldf, device):
     key = (window.data_ptr(), window._version, n_fft, ldf, str(device))
     hit = _BASIS.get(key)
     if hit is not None:
-        return hit
+        return hit[0]
     win = window.numel()
     nb = n_fft // 2 + 1
     half = (nb + 15) // 16 * 16
@@ -27,7 +27,7 @@ def _dft_basis(window, n_fft, ldf, device):
     basis[:nb, :win] = torch.cos(ang) * w
     basis[half:half + nb, :win] = torch.sin(ang) * w
     out = (basis.float().to(device).contiguous(), half, nb)
-    _BASIS[key] = out
+    _BASIS[key] = (out, window)    # window kept alive: the key is its data pointer (a freed window's address is reused)
     return out
 
 
@@ -109,8 +109,8 @@ def log_mel(signal, window, fb, n_fft=512, hop=160, preemph=0.97, dither=0.0, se
     M = B * Tm
     dev = x.device
     frames = torch.empty(M, ldf, dtype=torch.float32, device=dev)
-    _lib.check(L_.ia_feat_frames(_lib.ptr(x), B, L, Tm, win, hop, float(preemph), float(dither), int(seed) & 0xFFFFFFFF,
-                                 _lib.ptr(frames), ldf, _lib.stream_ptr()), "ia_feat_frames")
+    _lib.check(L_.ia_feat_frames(_lib.ptr(x), B, L, Tm, win, n_fft, hop, float(preemph), float(dither),
+                                 int(seed) & 0xFFFFFFFF, _lib.ptr(frames), ldf, _lib.stream_ptr()), "ia_feat_frames")
     spec = torch.empty(M, 2 * half, dtype=torch.float32, device=dev)
     _lib.check(L_.ia_gemm_f32(_lib.ptr(frames), ldf, _lib.ptr(basis), ldf, M, 2 * half, ldf, _lib.ptr(spec), 2 * half,
                               _lib.stream_ptr()), "ia_gemm_f32")
@@ -118,11 +118,12 @@ def log_mel(signal, window, fb, n_fft=512, hop=160, preemph=0.97, dither=0.0, se
     _lib.check(L_.ia_feat_power(_lib.ptr(spec), M, 2 * half, half, nb, _lib.ptr(power), half, _lib.stream_ptr()),
                "ia_feat_power")
     nm = fb.shape[0]
-    fbp = _BASIS.get(("fb", fb.data_ptr(), fb._version, half))
-    if fbp is None:
+    hit = _BASIS.get(("fb", fb.data_ptr(), fb._version, half))
+    if hit is None:
         fbp = torch.zeros(nm, half, dtype=torch.float32, device=dev)
-        fbp[:, :nb] = fb.float()
-        _BASIS[("fb", fb.data_ptr(), fb._version, half)] = fbp
+        fbp[:, :nb] = fb.float()[:, :nb]
+        hit = _BASIS[("fb", fb.data_ptr(), fb._version, half)] = (fbp, fb)    # fb kept alive: the key is its data pointer
+    fbp = hit[0]
     mel = torch.empty(M, nm, dtype=torch.float32, device=dev)
     _lib.check(L_.ia_gemm_f32(_lib.ptr(power), half, _lib.ptr(fbp), half, M, nm, half, _lib.ptr(mel), nm,
                               _lib.stream_ptr()), "ia_gemm_f32")
