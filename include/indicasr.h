@@ -851,6 +851,65 @@ int ia_adamw_step_segmented_projected(float* theta, const float* grad, float* ex
                                       float grad_scale, void* shadow_bf16, const float* norm_state, int skip_nonfinite,
                                       int32_t* counters, const float* ref, const float* proj_state, int32_t* proj_counters,
                                       ia_stream_t stream);
+/* ---- GEM (Lopez-Paz, Ranzato, NeurIPS 2017): one constraint per earlier task instead of A-GEM's averaged one.  refs is ONE fp32
+ * buffer [max_tasks, stride], stride a multiple of 4 and >= the flat buffers' length, row k the reference gradient of task k laid
+ * out as grad (averaged, in true units); rows 0 .. ntasks-1 are in use, 1 <= ntasks <= IA_GEM_MAX_TASKS.  With s = grad_scale:
+ *   d_k = s * <grad, r_k>;   P = R R^T + eps * I;   violated = some d_k < 0
+ *   v   = argmin 1/2 v^T P v + d^T v  subject to  v_k >= memory_strength       (the program the paper's code hands to quadprog)
+ * and the step consumes, per element of a live tensor, every product and sum rounded to fp32 on its own,
+ *   acc = grad * s;   for k ascending with v_k != 0: acc = acc + v_k * r_k;   G = acc * coef (only when clipping)
+ * gem_sums: IA_GEM_SUMS_DOUBLES doubles on the device = d[16], then the Gram matrix R R^T as [16, 16] row-major: the fp64 sums
+ * exactly as the solver consumes them.  gem_state: IA_GEM_STATE_FLOATS floats on the device = v[16], violated (0 / 1), active (the
+ * number of v_k > memory_strength), iterations (linear systems the solver factored), solved (0 / 1).  No kernel uses a float
+ * atomic and every sum has a fixed order, so all results reproduce bit for bit; nothing is read back by any of the calls.
+ * ia_gem_dots              two launches, (ntasks + 1) * 4 B per element.  (1) workgroup c keeps chunk c of x in registers, reads
+ *                          each of the ntasks rows once and stores the fp32 sums <x, r_k> of the chunk in workspace
+ *                          (ia_gem_workspace_bytes(nchunks, ntasks) = ntasks floats per chunk); per row the reduction has the
+ *                          shape of ia_agem_dots.  (2) one workgroup adds the partials in fp64 in a fixed order.
+ *                          gram_row < 0 (x is the task gradient): d[k] = grad_scale * sum for k < ntasks, 0 beyond, and, when
+ *                          seg_active is not NULL, the liveness flags are set from x exactly as ia_agem_dots sets them.
+ *                          0 <= gram_row < ntasks (x is row gram_row itself, after it was stored): gram[gram_row][k] =
+ *                          gram[k][gram_row] = sum for k < ntasks; grad_scale and seg_active are ignored, d is not written.
+ *                          The Gram matrix is thus kept up to date when a reference is stored, not once per step.
+ * ia_gem_solve             one workgroup, fp64: reads d and the Gram matrix, builds P, decides violated and solves the program by an
+ *                          active-set method (free coordinates by Cholesky of the free block, one coordinate joining per outer
+ *                          step: finitely many steps), then writes v rounded once to fp32 and the rest of gem_state.  Not
+ *                          violated: v = 0, active = iterations = 0, solved = 1.  A non-finite d or gram entry, a free block
+ *                          that is not positive definite (eps == 0 with dependent rows) or the iteration cap: solved = 0,
+ *                          violated = 0, v = 0 -- such a step never projects.  memory_strength >= 0, eps >= 0.
+ * ia_grad_norm_gem         ia_grad_norm (same outputs, same workspace size) of the gradient the step will consume, branching on
+ *                          gem_state's violated on the device as ia_grad_norm_projected does: un-projected it is ia_grad_norm's
+ *                          arithmetic exactly; projected it is the sum of G^2 over live tensors (seg_active read only; NULL:
+ *                          every tensor live), rows with v_k == 0 not read.
+ * ia_adamw_step_segmented_gem  the segmented AdamW on that gradient, (7 + rows with v_k != 0) * 4 B + 2 B per element, with a
+ *                          group table as ia_adamw_step_segmented_grouped takes it (ngroups >= 1; seg_group may be NULL for
+ *                          one group).  An un-projected step moves weights, moments, step counters and the bf16 shadow exactly
+ *                          as the plain (or clipped) step does and reads no row.  Liveness is that of the task gradient.
+ *                          norm_state and counters: both NULL or both set (from ia_grad_norm_gem: project, then clip; a
+ *                          non-finite norm skips the step).  gem_counters: int32[2] = {projected steps, unsolved steps}: the
+ *                          first counts the steps that projected and were not skipped, the second every step whose program
+ *                          came back with solved == 0.
+ * IA_INVALID_VALUE before any device work: a NULL required pointer, ntasks outside 1..IA_GEM_MAX_TASKS, gram_row >= ntasks, a
+ * stride that is not a positive multiple of 4, misaligned buffers (16 bytes for x, grad, refs and the chunk table, 8 for
+ * gem_sums). */
+#define IA_GEM_MAX_TASKS 16
+#define IA_GEM_STATE_FLOATS 20
+#define IA_GEM_SUMS_DOUBLES 272
+size_t ia_gem_workspace_bytes(int nchunks, int max_tasks);
+int ia_gem_dots(const float* x, const float* refs, int64_t stride, int ntasks, const int32_t* chunk_table, int nchunks, int nseg,
+                float grad_scale, int32_t* seg_active, int gram_row, double* gem_sums, void* workspace, size_t workspace_bytes,
+                ia_stream_t stream);
+int ia_gem_solve(const double* gem_sums, float* gem_state, int ntasks, float memory_strength, float eps, ia_stream_t stream);
+int ia_grad_norm_gem(const float* grad, const int32_t* chunk_table, int nchunks, const int32_t* seg_chunk_begin, int nseg,
+                     float grad_scale, float max_norm, const int32_t* seg_active, float* seg_norm, float* norm_state,
+                     void* workspace, size_t workspace_bytes, const float* refs, int64_t stride, int ntasks,
+                     const float* gem_state, ia_stream_t stream);
+int ia_adamw_step_segmented_gem(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq, const int32_t* chunk_table,
+                                int nchunks, int32_t* seg_active, int32_t* seg_step, int nseg, int all_active, float beta1,
+                                float beta2, float eps, float grad_scale, void* shadow_bf16, const int32_t* seg_group, int ngroups,
+                                const float* group_lr, const float* group_weight_decay, const float* norm_state,
+                                int skip_nonfinite, int32_t* counters, const float* refs, int64_t stride, int ntasks,
+                                const float* gem_state, int32_t* gem_counters, ia_stream_t stream);
 /* Parameter groups: per-tensor learning rate and weight decay for every kind of segmented step.  seg_group: int32[nseg] on the
  * device, tensor k belongs to group seg_group[k] (NULL: every tensor in group 0; entries outside 0..ngroups-1 are clamped).
  * group_lr / group_weight_decay: ngroups floats each in HOST memory, read during the call and handed to the kernel by value

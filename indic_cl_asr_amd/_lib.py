@@ -212,6 +212,12 @@ SIGNATURES = {
     "ia_grad_norm_projected": (_i, [_vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "ia_adamw_step_segmented_projected": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _i,
                                                _vp, _vp, _vp, _vp, _vp]),
+    "ia_gem_workspace_bytes": (_sz, [_i, _i]),
+    "ia_gem_dots": (_i, [_vp, _vp, _i64, _i, _vp, _i, _i, _f, _vp, _i, _vp, _vp, _sz, _vp]),
+    "ia_gem_solve": (_i, [_vp, _vp, _i, _f, _f, _vp]),
+    "ia_grad_norm_gem": (_i, [_vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp, _i64, _i, _vp, _vp]),
+    "ia_adamw_step_segmented_gem": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _f, _vp, _vp, _i, _vp, _vp,
+                                         _vp, _i, _vp, _vp, _i64, _i, _vp, _vp, _vp]),
     "ia_adamw_step_segmented_grouped": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _f, _vp, _vp, _i, _vp, _vp,
                                              _vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
 }

@@ -447,6 +447,120 @@ class AveragedGEM:
         return {"dot": dot, "ref_sq": ref_sq, "alpha": alpha, "projected": int(violated != 0.0), "projected_steps": int(host[4])}
 
 
+GEM_MAX_TASKS = 16         # IA_GEM_MAX_TASKS of include/indicasr.h
+_GEM_STATE = 20            # IA_GEM_STATE_FLOATS: v[16], violated, active, iterations, solved
+_GEM_SUMS = 272            # IA_GEM_SUMS_DOUBLES: d[16], Gram matrix [16, 16]
+
+
+class GEM:
+    """GEM (Lopez-Paz and Ranzato, NeurIPS 2017): one reference gradient r_k per earlier task, each from a batch of that task
+    drawn from an episodic memory, and one constraint per task.  With d_k = <g, r_k> for the (data-parallel averaged) task
+    gradient g: when no d_k is negative the step is the plain step; otherwise it consumes g + sum_k v_k r_k with
+    v = argmin 1/2 v'Pv + d'v subject to v_k >= memory_strength, P = R R' + eps I -- the program the paper's code hands to
+    quadprog -- so that to first order the step raises none of the earlier tasks' losses.  AveragedGEM is the cheap member of
+    the family: it can agree with the mean memory gradient and still raise the loss of one task.
+
+    Cost: the reference buffer `refs` [max_tasks, numel] is allocated here, 4 B * trainable parameters * max_tasks (1.76 GB for
+    40 M parameters and 11 earlier languages), plus a few hundred bytes of solver state.  Attach it with
+    `FusedAdamW(..., projection=gem)`; per step, for each earlier task: memory batch of that task
+    (`EpisodicMemory.sample(n, device, language=task)`) -> backward -> `gem.store_reference(task, opt)`; then task batch ->
+    backward -> `opt.step()`.  The K dots, the program and the projected step run on the device after the data-parallel
+    all-reduce (ia_gem_dots, ia_gem_solve, ia_grad_norm_gem, ia_adamw_step_segmented_gem); nothing is read back unless `stats()`
+    is called.  With `max_grad_norm` the order is project, then clip.  Liveness is the task gradient's, as for AveragedGEM: a
+    tensor that received no task gradient stays untouched whatever the references hold there.  A non-finite reference, or a
+    program the solver cannot finish, never projects: that step is the plain step and counts in `unsolved_steps`.
+
+    Nothing of this goes into a checkpoint: the references are gradients at the current weights and are recomputed from the
+    memory (which `checkpoint.py` does save) at every step."""
+
+    def __init__(self, model_or_flat, max_tasks=11, memory_strength=0.5, eps=1e-3):
+        if not 1 <= int(max_tasks) <= GEM_MAX_TASKS:
+            raise ValueError(f"GEM: max_tasks must be in 1..{GEM_MAX_TASKS} (got {max_tasks})")
+        if not (float(memory_strength) >= 0.0 and math.isfinite(memory_strength)):
+            raise ValueError(f"GEM: memory_strength must be >= 0 (got {memory_strength})")
+        if not (float(eps) >= 0.0 and math.isfinite(eps)):
+            raise ValueError(f"GEM: eps must be >= 0 (got {eps})")
+        self.flat = model_or_flat if isinstance(model_or_flat, FlatParams) else flat_of(model_or_flat)
+        self.max_tasks, self.memory_strength, self.eps = int(max_tasks), float(memory_strength), float(eps)
+        dev = self.flat.theta.device
+        self.stride = (self.flat.numel + 3) // 4 * 4           # float4 loads of every row stay aligned
+        self.refs = torch.zeros(self.max_tasks, self.stride, dtype=torch.float32, device=dev)
+        # d[16] and the Gram matrix [16, 16] as fp64, then v[16], {violated, active, iterations, solved} as fp32 and {projected
+        # steps, unsolved steps} as int32, in ONE device buffer (stats() reads it in one copy)
+        self._buf = torch.zeros(2 * _GEM_SUMS + _GEM_STATE + 2, dtype=torch.int32, device=dev)
+        self.sums = self._buf[:2 * _GEM_SUMS].view(torch.float64)
+        self.state = self._buf[2 * _GEM_SUMS:2 * _GEM_SUMS + _GEM_STATE].view(torch.float32)
+        self.counters = self._buf[2 * _GEM_SUMS + _GEM_STATE:]
+        self._ws = None
+        self._rows: Dict[object, int] = {}                      # task -> row of refs, in order of first use
+
+    @property
+    def has_reference(self) -> bool:
+        return bool(self._rows)
+
+    def tasks(self) -> list:
+        """The tasks that hold a reference, in row order."""
+        return list(self._rows)
+
+    def workspace(self, nchunks):
+        if self._ws is None:
+            self._ws = torch.empty(_lib.lib().ia_gem_workspace_bytes(nchunks, self.max_tasks), dtype=torch.uint8,
+                                   device=self.flat.theta.device)
+        return self._ws
+
+    def store_reference(self, task, optimizer: Optional["FusedAdamW"] = None):
+        """The flat gradient (of the memory batch of `task` just back-propagated) becomes the task's row; `task` is a language
+        name or any hashable and gets the next free row on first use.  Under data parallelism the row is averaged over
+        `optimizer`'s group first (a synchronous fp32 all-reduce, then times 1/world), so every rank solves the same program.
+        The row's dots with every stored row refresh row and column of the Gram matrix (one ia_gem_dots), and the flat
+        gradient is zeroed, ready for the next batch."""
+        if task not in self._rows and len(self._rows) >= self.max_tasks:
+            raise ValueError(f"GEM: max_tasks = {self.max_tasks} references are stored already; '{task}' would be one more")
+        flush_pending_updates()
+        f = self.flat
+        row = self._rows.setdefault(task, len(self._rows))
+        ref = self.refs[row]
+        ref[:f.numel].copy_(f.grad)
+        if optimizer is not None:
+            ws = optimizer._world()
+            if ws > 1:
+                dist.all_reduce(ref, group=optimizer.group)
+                ref.mul_(1.0 / ws)
+        nchunks = f.chunk_table.shape[0]
+        wsp = self.workspace(nchunks)
+        st = _lib.lib().ia_gem_dots(_lib.ptr(ref), _lib.ptr(self.refs), self.stride, len(self._rows), _lib.ptr(f.chunk_table),
+                                    nchunks, len(f.entries), 1.0, None, row, _lib.ptr(self.sums), _lib.ptr(wsp), wsp.numel(),
+                                    _lib.stream_ptr())
+        _lib.check(st, "ia_gem_dots")
+        f.zero_grad()
+
+    def clear(self):
+        """Forget every reference: the following steps are plain steps until the next store_reference() (a deferred update
+        that was issued with the references is applied with them first).  The step counters stay."""
+        flush_pending_updates()
+        self._rows = {}
+        self.state.zero_()
+        self.sums[:GEM_MAX_TASKS].zero_()
+
+    def gram_matrix(self) -> torch.Tensor:
+        """The K x K Gram matrix R R' of the stored references as the solver reads it (fp64, on the host; eps not added)."""
+        flush_pending_updates()
+        k = len(self._rows)
+        return self.sums[GEM_MAX_TASKS:].view(GEM_MAX_TASKS, GEM_MAX_TASKS)[:k, :k].cpu()
+
+    def stats(self) -> dict:
+        """One small device-to-host read.  Of the latest step: `dots` (d_k of the averaged gradient), `v`, both one entry per
+        stored task in row order, whether it `projected`, how many v_k lie above memory_strength (`active`) and how many linear
+        systems the solver factored (`qp_iterations`); and how many steps have projected / could not be solved so far."""
+        flush_pending_updates()
+        host = self._buf.cpu()
+        k, c = len(self._rows), 2 * _GEM_SUMS + _GEM_STATE
+        s = host[2 * _GEM_SUMS:c].view(torch.float32).tolist()
+        return {"dots": host[:2 * k].view(torch.float64).tolist(), "v": s[:k], "projected": int(s[16] != 0.0),
+                "active": int(s[17]), "qp_iterations": int(s[18]), "projected_steps": int(host[c]),
+                "unsolved_steps": int(host[c + 1])}
+
+
 class EpisodicMemory:
     """Host-side episodic memory for replay methods: up to `per_language` utterances of every language seen, chosen by reservoir
     sampling (Vitter's algorithm R), so that each utterance of a language's stream is kept with equal probability.  Utterances
@@ -485,11 +599,14 @@ class EpisodicMemory:
                     kept[j] = item
             self.seen[lang] = seen + 1
 
-    def sample(self, n: int, device=None):
+    def sample(self, n: int, device=None, language=None):
         """-> ((signal, signal lengths, tokens, token lengths), lang_ids): n utterances drawn uniformly (with replacement) over
-        everything stored, languages mixed, collated as a training batch and moved to `device` (None: left on the host)."""
+        everything stored, languages mixed, collated as a training batch and moved to `device` (None: left on the host).
+        `language`: draw from that language's utterances only (GEM's one batch per earlier task)."""
         from . import data
-        pool = [(lang, it) for lang, kept in self.items.items() for it in kept]
+        if language is not None and not self.items.get(language):
+            raise ValueError(f"EpisodicMemory.sample: nothing is stored for language '{language}'")
+        pool = [(lang, it) for lang, kept in self.items.items() for it in kept if language is None or lang == language]
         if not pool:
             raise ValueError("EpisodicMemory.sample: the memory is empty")
         picks = torch.randint(0, len(pool), (int(n),), generator=self.gen).tolist()
@@ -683,6 +800,8 @@ class FusedAdamW(torch.optim.Optimizer):
         ia_grad_norm_projected (if the norm is measured) and ia_adamw_step_segmented_projected: the averaged task gradient is
         projected off agem.ref when their dot is negative, then clipped.  Without a reference the step is the one described
         above.  Not combinable with `path_integral`; projection state is not optimizer state and is not in state_dict().
+        `projection=gem` (a `GEM`): the same place in the step, with one constraint per stored task -- ia_gem_dots, ia_gem_solve,
+        ia_grad_norm_gem (if the norm is measured) and ia_adamw_step_segmented_gem, which takes the group table itself.
 
         `param_groups=[{...}, ...]`: dicts in torch's shape.  Each names its tensors with "params" (parameter names and / or
         the Parameter objects) or "match" (a regular expression, re.search on the parameter name), may override "lr" and / or
@@ -890,6 +1009,8 @@ class FusedAdamW(torch.optim.Optimizer):
         if measured and self._seg_norm is None:
             self._seg_norm = torch.zeros(nseg, dtype=torch.float32, device=f.theta.device)
             self._norm_ws = torch.empty(L.ia_grad_norm_workspace_bytes(nchunks), dtype=torch.uint8, device=f.theta.device)
+        if isinstance(agem, GEM):
+            return self._apply_gem(agem, float(scale), all_live, lrs, wds, measured, max_norm, skip)
         if agem is not None:       # dots (and the liveness flags) -> norm of the projected gradient -> projected step
             ws = agem.workspace(nchunks)
             st = L.ia_agem_dots(_lib.ptr(f.grad), _lib.ptr(agem.ref.flat), _lib.ptr(f.chunk_table), nchunks, nseg, float(scale),
@@ -943,6 +1064,36 @@ class FusedAdamW(torch.optim.Optimizer):
         else:
             st = L.ia_adamw_step_segmented(*head, _lib.stream_ptr())
             _lib.check(st, "ia_adamw_step_segmented")
+        self._after_update()
+
+    def _apply_gem(self, gem, scale, all_live, lrs, wds, measured, max_norm, skip):
+        """K dots (and the liveness flags) -> the program -> norm of the projected gradient -> projected step, all on the
+        device; one entry point for one or many parameter groups."""
+        f, L = self.flat, _lib.lib()
+        g = self.param_groups[0]
+        nchunks, nseg, k, n = f.chunk_table.shape[0], len(f.entries), len(gem.tasks()), len(lrs)
+        ws = gem.workspace(nchunks)
+        rows = (_lib.ptr(gem.refs), gem.stride, k, _lib.ptr(gem.state))
+        st = L.ia_gem_dots(_lib.ptr(f.grad), _lib.ptr(gem.refs), gem.stride, k, _lib.ptr(f.chunk_table), nchunks, nseg, scale,
+                           None if all_live else _lib.ptr(self.seg_active), -1, _lib.ptr(gem.sums), _lib.ptr(ws), ws.numel(),
+                           _lib.stream_ptr())
+        _lib.check(st, "ia_gem_dots")
+        st = L.ia_gem_solve(_lib.ptr(gem.sums), _lib.ptr(gem.state), k, gem.memory_strength, gem.eps, _lib.stream_ptr())
+        _lib.check(st, "ia_gem_solve")
+        if measured:
+            st = L.ia_grad_norm_gem(
+                _lib.ptr(f.grad), _lib.ptr(f.chunk_table), nchunks, _lib.ptr(f.seg_chunk_begin), nseg, scale,
+                0.0 if max_norm is None else float(max_norm), None if all_live else _lib.ptr(self.seg_active),
+                _lib.ptr(self._seg_norm), _lib.ptr(self._norm_state), _lib.ptr(self._norm_ws), self._norm_ws.numel(), *rows,
+                _lib.stream_ptr())
+            _lib.check(st, "ia_grad_norm_gem")
+        st = L.ia_adamw_step_segmented_gem(
+            _lib.ptr(f.theta), _lib.ptr(f.grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), _lib.ptr(f.chunk_table),
+            nchunks, _lib.ptr(self.seg_active), _lib.ptr(self.seg_step), nseg, int(all_live), float(g["betas"][0]),
+            float(g["betas"][1]), float(g["eps"]), scale, _lib.ptr(self.shadow), _lib.ptr(self.seg_group), n,
+            (ctypes.c_float * n)(*lrs), (ctypes.c_float * n)(*wds), _lib.ptr(self._norm_state) if measured else None, int(skip),
+            _lib.ptr(self._counters) if measured else None, *rows, _lib.ptr(gem.counters), _lib.stream_ptr())
+        _lib.check(st, "ia_adamw_step_segmented_gem")
         self._after_update()
 
     def _after_update(self):

@@ -14,6 +14,9 @@
 //                              reference gradient, the decision g.r < 0 and alpha = g.r / r.r left on the device
 //   ia_grad_norm_projected ... ia_grad_norm of the gradient the projected step consumes (g - alpha * r when the flag is set)
 //   ia_adamw_step_segmented_projected .. the per-tensor AdamW on that gradient, r as one more operand of the launch
+//   ia_gem_dots, ia_gem_solve, ia_grad_norm_gem, ia_adamw_step_segmented_gem .. GEM (Lopez-Paz, Ranzato 2017): the K dots of the
+//                              flat gradient with one reference row per earlier task (and the rows' Gram matrix), the
+//                              bound-constrained quadratic program in fp64, and norm and AdamW on g * s + sum_k v_k * r_k
 //   ia_adamw_step_segmented_grouped .... any of the four segmented steps with lr and weight_decay per parameter group
 //                              (torch.optim.AdamW's param_groups): the same kernels, the group table by value in their arguments
 // All are HBM-streaming kernels: 16-byte accesses, grid capped at 2048 workgroups, fp32 math.
@@ -755,6 +758,409 @@ __global__ void seg_step_advance_projected_kernel(int* __restrict__ seg_active, 
     }
 }
 
+// ---- GEM (Lopez-Paz, Ranzato 2017): one constraint per earlier task.  refs is [max_tasks, stride] fp32, row k the reference
+// gradient of task k laid out as grad; K = ntasks rows are in use.  gem_sums (IA_GEM_SUMS_DOUBLES doubles) = d[16], then the
+// Gram matrix [16, 16]: the fp64 sums as the finish kernel left them, which is what the solver consumes.  gem_state
+// (IA_GEM_STATE_FLOATS floats) = v[16], violated, active, iterations, solved.
+//   gem_dots_kernel      workgroup c holds chunk c of x in registers (a 4096-element chunk is four float4 per thread), reads each
+//                        of the K rows once and leaves the K fp32 sums in chunk_dots[c * K + k]; per row the thread's partial,
+//                        the DPP wave sum and the four wave sums in order: the reduction shape of agem_dots_kernel
+//   gem_finish_kernel    one workgroup adds the partials in fp64 (agem_finish_kernel's order) and writes d, or row and column
+//                        gram_row of the Gram matrix
+//   gem_solve_kernel     the bound-constrained QP in fp64, by an active-set method
+//   gem_norm_kernel, adamw_seg_gem_kernel   proj_norm_kernel / adamw_seg_proj_kernel with g * s + sum_k v_k * r_k
+constexpr int GEM_MAX = IA_GEM_MAX_TASKS;
+constexpr int GEM_V = 0, GEM_VIOLATED = GEM_MAX, GEM_ACTIVE = GEM_VIOLATED + 1, GEM_ITERATIONS = GEM_VIOLATED + 2,
+              GEM_SOLVED = GEM_VIOLATED + 3;
+constexpr int GEM_D = 0, GEM_GRAM = GEM_MAX;                  // offsets into gem_sums
+constexpr int GEM_CHUNK_F4 = CL_CHUNK / (4 * CL_THREADS);   // float4 of a full chunk per thread
+static_assert(GEM_CHUNK_F4 * 4 * CL_THREADS == CL_CHUNK && IA_GEM_STATE_FLOATS == GEM_SOLVED + 1 &&
+              IA_GEM_SUMS_DOUBLES == GEM_GRAM + GEM_MAX * GEM_MAX, "GEM layout");
+
+__global__ __launch_bounds__(CL_THREADS) void gem_dots_kernel(const float* __restrict__ x, const float* __restrict__ refs,
+                                                              int64_t stride, int K, const int4* __restrict__ table, int nchunks,
+                                                              int* __restrict__ seg_active, float* __restrict__ chunk_dots) {
+    __shared__ float sh[GEM_MAX][CL_THREADS / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const int4 e = table[c];
+        const int off = e.x, cnt = e.y, n4 = cnt >> 2;    // cnt <= CL_CHUNK: at most GEM_CHUNK_F4 float4 per thread
+        const int tail = (n4 << 2) + threadIdx.x;          // the chunk's last cnt & 3 elements, one per thread
+        float4 X[GEM_CHUNK_F4];
+        unsigned nz = 0;
+#pragma unroll
+        for (int u = 0; u < GEM_CHUNK_F4; ++u) {
+            const int q = threadIdx.x + u * CL_THREADS;
+            X[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (q < n4) X[u] = reinterpret_cast<const float4*>(x + off)[q];
+            nz |= (__float_as_uint(X[u].x) | __float_as_uint(X[u].y) | __float_as_uint(X[u].z) | __float_as_uint(X[u].w)) &
+                  0x7FFFFFFFu;                             // -0.0 counts as zero
+        }
+        const float xt = tail < cnt ? x[off + tail] : 0.f;
+        nz |= __float_as_uint(xt) & 0x7FFFFFFFu;
+        if (seg_active && __any(nz != 0) && lane == 0) atomicOr(seg_active + e.z, 1);
+        for (int k = 0; k < K; ++k) {
+            const float* __restrict__ r = refs + (int64_t)k * stride + off;
+            float a = 0.f;
+#pragma unroll
+            for (int u = 0; u < GEM_CHUNK_F4; ++u) {
+                const int q = threadIdx.x + u * CL_THREADS;
+                if (q < n4) {
+                    const float4 y = reinterpret_cast<const float4*>(r)[q];
+                    a += X[u].x * y.x + X[u].y * y.y + X[u].z * y.z + X[u].w * y.w;
+                }
+            }
+            if (tail < cnt) a += xt * r[tail];
+            a = ia_wave_sum_dpp(a);
+            if (lane == 0) sh[k][wave] = a;
+        }
+        __syncthreads();
+        if (threadIdx.x < K) {
+            float t = 0.f;
+#pragma unroll
+            for (int i = 0; i < CL_THREADS / 64; ++i) t += sh[threadIdx.x][i];
+            chunk_dots[(int64_t)c * K + threadIdx.x] = t;
+        }
+        __syncthreads();
+    }
+}
+
+// gram_row < 0: d[k] = scale * sum (k < K), 0 beyond.  Otherwise gram[gram_row][k] = gram[k][gram_row] = sum (k < K).
+__global__ __launch_bounds__(GN_THREADS) void gem_finish_kernel(const float* __restrict__ chunk_dots, int nchunks, int K,
+                                                                float scale, int gram_row, double* __restrict__ gem_sums) {
+    __shared__ double sh_d[GN_THREADS / 64][GEM_MAX];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double a[GEM_MAX];
+#pragma unroll
+    for (int k = 0; k < GEM_MAX; ++k) a[k] = 0.0;
+    for (int c = threadIdx.x; c < nchunks; c += GN_THREADS) {
+        const float* p = chunk_dots + (int64_t)c * K;
+#pragma unroll
+        for (int k = 0; k < GEM_MAX; ++k)
+            if (k < K) a[k] += (double)p[k];
+    }
+#pragma unroll
+    for (int k = 0; k < GEM_MAX; ++k) {
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) a[k] += __shfl_xor(a[k], s);
+        if (lane == 0) sh_d[wave][k] = a[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < GEM_MAX) {
+        const int k = threadIdx.x;
+        double sum = 0.0;
+        for (int w = 0; w < GN_THREADS / 64; ++w) sum += sh_d[w][k];
+        if (gram_row < 0) {
+            gem_sums[GEM_D + k] = k < K ? (double)scale * sum : 0.0;
+        } else if (k < K) {
+            gem_sums[GEM_GRAM + gram_row * GEM_MAX + k] = sum;
+            gem_sums[GEM_GRAM + k * GEM_MAX + gram_row] = sum;
+        }
+    }
+}
+
+// v = argmin 1/2 v'Pv + d'v subject to v >= gamma, P = gram + eps I (K x K), in fp64 by the active-set method of Lawson and
+// Hanson's NNLS carried over to a lower bound: F is the set of free coordinates, every other one sits at gamma.  Outer step: the
+// bound coordinate with the most negative multiplier lambda_j = (Pv + d)_j joins F; inner steps: the minimiser z of the face
+// (Cholesky of P_FF) is taken whole when it is inside the bounds, otherwise v moves towards z up to the first bound and the
+// coordinates that reached it leave F.  Every completed outer step lowers the objective on a face not visited before, so the
+// method ends after finitely many; K <= 16 needs a handful, and GEM_SOLVE_CAP is there for inputs no arithmetic can serve.
+// One lane does the work: the systems are at most 16 x 16 and every step depends on the one before.
+constexpr int GEM_SOLVE_CAP = 256;
+
+__device__ bool gem_face_minimiser(const double (*P)[GEM_MAX], double (*L)[GEM_MAX], const double* d, int K, unsigned free_set,
+                                   double gamma, double* z) {
+    int idx[GEM_MAX], n = 0;
+    for (int k = 0; k < K; ++k)
+        if (free_set >> k & 1u) idx[n++] = k;
+    double b[GEM_MAX];
+    for (int i = 0; i < n; ++i) {
+        double rhs = -d[idx[i]];
+        for (int k = 0; k < K; ++k)
+            if (!(free_set >> k & 1u)) rhs -= P[idx[i]][k] * gamma;
+        b[i] = rhs;
+    }
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j <= i; ++j) {
+            double s = P[idx[i]][idx[j]];
+            for (int t = 0; t < j; ++t) s -= L[i][t] * L[j][t];
+            if (i == j) {
+                if (!(s > 0.0)) return false;       // not positive definite (or NaN)
+                L[i][i] = sqrt(s);
+            } else {
+                L[i][j] = s / L[j][j];
+            }
+        }
+    for (int i = 0; i < n; ++i) {
+        double s = b[i];
+        for (int t = 0; t < i; ++t) s -= L[i][t] * b[t];
+        b[i] = s / L[i][i];
+    }
+    for (int i = n - 1; i >= 0; --i) {
+        double s = b[i];
+        for (int t = i + 1; t < n; ++t) s -= L[t][i] * b[t];
+        b[i] = s / L[i][i];
+    }
+    for (int k = 0; k < K; ++k) z[k] = gamma;
+    for (int i = 0; i < n; ++i) z[idx[i]] = b[i];
+    return true;
+}
+
+__global__ __launch_bounds__(64) void gem_solve_kernel(const double* __restrict__ gem_sums, float* __restrict__ gem_state, int K,
+                                                       float gamma_f, float eps_f) {
+    __shared__ double P[GEM_MAX][GEM_MAX], L[GEM_MAX][GEM_MAX], d[GEM_MAX], v[GEM_MAX], z[GEM_MAX];
+    if (threadIdx.x != 0) return;
+    const double gamma = (double)gamma_f;
+    bool finite = true, violated = false;
+    double scale = 0.0;
+    for (int k = 0; k < K; ++k) {
+        d[k] = gem_sums[GEM_D + k];
+        finite = finite && isfinite(d[k]);
+        violated = violated || d[k] < 0.0;
+        scale = fmax(scale, fabs(d[k]));
+        double row = 0.0;
+        for (int j = 0; j < K; ++j) {
+            P[k][j] = gem_sums[GEM_GRAM + k * GEM_MAX + j] + (j == k ? (double)eps_f : 0.0);
+            finite = finite && isfinite(P[k][j]);
+            row += fabs(P[k][j]);
+        }
+        scale = fmax(scale, row * fmax(gamma, 1.0));
+    }
+    int iterations = 0, active = 0;
+    bool solved = finite;
+    violated = violated && finite;
+    for (int k = 0; k < GEM_MAX; ++k) v[k] = 0.0;
+    if (violated) {
+        const double tol = 1e-12 * scale;          // on a multiplier: what its own fp64 evaluation cannot resolve
+        unsigned free_set = 0, refused = 0;        // refused: the face's minimiser did not take it inside; not offered again here
+        for (int k = 0; k < K; ++k) v[k] = gamma;
+        solved = false;
+        bool ok = true;
+        while (ok && iterations < GEM_SOLVE_CAP) {
+            int j = -1;
+            double worst = -tol;
+            for (int k = 0; k < K; ++k) {
+                if ((free_set | refused) >> k & 1u) continue;
+                double lam = d[k];
+                for (int t = 0; t < K; ++t) lam += P[k][t] * v[t];
+                if (lam < worst) { worst = lam; j = k; }
+            }
+            if (j < 0) { solved = true; break; }
+            free_set |= 1u << j;
+            bool first = true;
+            while (free_set && iterations < GEM_SOLVE_CAP) {
+                ++iterations;
+                ok = gem_face_minimiser(P, L, d, K, free_set, gamma, z);
+                if (!ok) break;
+                if (first && !(z[j] > gamma)) {     // in exact arithmetic a negative multiplier always moves inside
+                    free_set &= ~(1u << j);
+                    refused |= 1u << j;
+                    break;
+                }
+                if (first) refused = 0;
+                first = false;
+                int kb = -1;
+                double alpha = 1.0;
+                for (int k = 0; k < K; ++k)
+                    if ((free_set >> k & 1u) && !(z[k] > gamma)) {
+                        const double room = v[k] - gamma, a = room <= 0.0 ? 0.0 : room / (v[k] - z[k]);
+                        if (a <= alpha) { alpha = a; kb = k; }
+                    }
+                if (kb < 0) {                       // the minimiser of the face lies inside the bounds: take it whole
+                    for (int k = 0; k < K; ++k) v[k] = z[k];
+                    break;
+                }
+                for (int k = 0; k < K; ++k)
+                    if (free_set >> k & 1u) {
+                        v[k] += alpha * (z[k] - v[k]);
+                        if (k == kb || !(v[k] > gamma)) { v[k] = gamma; free_set &= ~(1u << k); }
+                    }
+            }
+        }
+        for (int k = 0; k < K; ++k) solved = solved && isfinite((double)(float)v[k]);
+        if (!solved) {
+            violated = false;
+            for (int k = 0; k < K; ++k) v[k] = 0.0;
+        }
+        for (int k = 0; k < K; ++k) active += v[k] > gamma ? 1 : 0;
+    }
+    for (int k = 0; k < GEM_MAX; ++k) gem_state[GEM_V + k] = (float)v[k];
+    gem_state[GEM_VIOLATED] = violated ? 1.f : 0.f;
+    gem_state[GEM_ACTIVE] = (float)active;
+    gem_state[GEM_ITERATIONS] = (float)iterations;
+    gem_state[GEM_SOLVED] = solved ? 1.f : 0.f;
+}
+
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+
+// acc = g * s, then acc += v_k * r_k for k ascending over the rows with v_k != 0: every product and sum rounded on its own
+__device__ __forceinline__ float4 gem_grad4(float4 g, const float* __restrict__ refs, int64_t stride, int K, int64_t q4,
+                                            const float* sh_v, float grad_scale) {
+    float4 a = make_float4(mul_rn(g.x, grad_scale), mul_rn(g.y, grad_scale), mul_rn(g.z, grad_scale), mul_rn(g.w, grad_scale));
+    for (int k = 0; k < K; ++k) {
+        const float vk = sh_v[k];
+        if (vk == 0.f) continue;                 // workgroup-uniform: the row is not read
+        const float4 r = reinterpret_cast<const float4*>(refs + (int64_t)k * stride)[q4];
+        a.x = add_rn(a.x, mul_rn(vk, r.x)); a.y = add_rn(a.y, mul_rn(vk, r.y));
+        a.z = add_rn(a.z, mul_rn(vk, r.z)); a.w = add_rn(a.w, mul_rn(vk, r.w));
+    }
+    return a;
+}
+
+__device__ __forceinline__ float gem_grad1(float g, const float* __restrict__ refs, int64_t stride, int K, int64_t i,
+                                           const float* sh_v, float grad_scale) {
+    float a = mul_rn(g, grad_scale);
+    for (int k = 0; k < K; ++k) {
+        const float vk = sh_v[k];
+        if (vk != 0.f) a = add_rn(a, mul_rn(vk, refs[(int64_t)k * stride + i]));
+    }
+    return a;
+}
+
+// proj_norm_kernel for GEM: un-projected, the raw sum of g^2 over every chunk (ia_grad_norm's first pass bit for bit);
+// projected, the sum of G^2 over the chunks of live tensors, a dead tensor's chunk storing 0.
+__global__ __launch_bounds__(CL_THREADS) void gem_norm_kernel(const float* __restrict__ g, const float* __restrict__ refs,
+                                                              int64_t stride, int K, const int4* __restrict__ table, int nchunks,
+                                                              const int* __restrict__ seg_active,
+                                                              const float* __restrict__ gem_state, float grad_scale,
+                                                              float* __restrict__ chunk_sumsq) {
+    __shared__ float sh[CL_THREADS / 64];
+    __shared__ float sh_v[GEM_MAX];
+    const bool violated = gem_state[GEM_VIOLATED] != 0.f;
+    if (threadIdx.x < GEM_MAX) sh_v[threadIdx.x] = gem_state[GEM_V + threadIdx.x];
+    __syncthreads();
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const int4 e = table[c];
+        const int off = e.x, cnt = e.y, n4 = cnt >> 2;
+        float ss = 0.f;
+        if (!violated) {
+            for (int q = threadIdx.x; q < n4; q += CL_THREADS) {
+                const float4 x = reinterpret_cast<const float4*>(g + off)[q];
+                ss = sumsq4_rn(ss, x.x, x.y, x.z, x.w);
+            }
+            for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) ss = __builtin_fmaf(g[off + i], g[off + i], ss);
+        } else if (!seg_active || seg_active[e.z]) {
+            for (int q = threadIdx.x; q < n4; q += CL_THREADS) {
+                const float4 G = gem_grad4(reinterpret_cast<const float4*>(g + off)[q], refs, stride, K, (off >> 2) + q, sh_v,
+                                           grad_scale);
+                ss = sumsq4_rn(ss, G.x, G.y, G.z, G.w);
+            }
+            for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) {
+                const float G = gem_grad1(g[off + i], refs, stride, K, off + i, sh_v, grad_scale);
+                ss = __builtin_fmaf(G, G, ss);
+            }
+        }
+        const float t = block_sum(ss, sh);
+        if (threadIdx.x == 0) chunk_sumsq[c] = t;
+    }
+}
+
+__global__ __launch_bounds__(GN_THREADS) void grad_norm_finish_gem_kernel(const float* __restrict__ chunk_sumsq,
+                                                                          const int* __restrict__ seg_chunk_begin, int nseg,
+                                                                          float abs_scale, float max_norm,
+                                                                          float* __restrict__ seg_norm,
+                                                                          float* __restrict__ norm_state,
+                                                                          const float* __restrict__ gem_state) {
+    grad_norm_finish(chunk_sumsq, seg_chunk_begin, nseg, gem_state[GEM_VIOLATED] != 0.f ? 1.f : abs_scale, max_norm, seg_norm,
+                     norm_state);
+}
+
+// adamw_seg_proj_kernel with the K-row gradient: an un-projected step reads no row and is adamw_seg_kernel bit for bit
+template <bool CLIP>
+__global__ __launch_bounds__(CL_THREADS) void adamw_seg_gem_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                                   float* __restrict__ m, float* __restrict__ v,
+                                                                   const int4* __restrict__ table, int nchunks,
+                                                                   const int* __restrict__ seg_active,
+                                                                   const int* __restrict__ seg_step, const group_table groups,
+                                                                   const int* __restrict__ seg_group, float b1, float b2, float eps,
+                                                                   float grad_scale,
+                                                                   unsigned short* __restrict__ shadow_bf16,
+                                                                   const float* __restrict__ norm_state, int skip_nonfinite,
+                                                                   const float* __restrict__ refs, int64_t stride, int ntasks,
+                                                                   const float* __restrict__ gem_state) {
+    __shared__ float sh_c[2];
+    __shared__ float sh_v[GEM_MAX];
+    float coef = 1.f;
+    if (CLIP) {
+        if (skip_nonfinite && norm_state[2] != 0.f) return;
+        coef = norm_state[1];
+    }
+    const int K = gem_state[GEM_VIOLATED] != 0.f ? ntasks : 0;      // uniform over the launch; 0: no row is read
+    if (threadIdx.x < GEM_MAX) sh_v[threadIdx.x] = gem_state[GEM_V + threadIdx.x];
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const int4 e = table[c];
+        if (!seg_active[e.z]) {           // workgroup-uniform: no task gradient -- untouched whatever the rows hold there
+            if (shadow_bf16)
+                for (int i = threadIdx.x; i < e.y; i += CL_THREADS) {
+                    __hip_bfloat16 a = __float2bfloat16(p[e.x + i]);
+                    shadow_bf16[e.x + i] = *reinterpret_cast<unsigned short*>(&a);
+                }
+            continue;
+        }
+        const int gi = group_of(seg_group, e.z, groups.n);      // workgroup-uniform
+        const float lr = groups.lr[gi], wd = groups.weight_decay[gi];
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const double step = (double)(seg_step[e.z] + 1);
+            sh_c[0] = (float)((double)lr / (1.0 - pow((double)b1, step)));
+            sh_c[1] = (float)(1.0 / sqrt(1.0 - pow((double)b2, step)));
+        }
+        __syncthreads();
+        const si_consts k = {__builtin_fmaf(-lr, wd, 1.f), 1.f - b1, b2, 1.f - b2, eps, sh_c[0], sh_c[1], grad_scale, coef, 0.f};
+        const int off = e.x, cnt = e.y, n4 = cnt >> 2;
+        for (int q = threadIdx.x; q < n4; q += CL_THREADS) {
+            float4 P = reinterpret_cast<float4*>(p + off)[q];
+            float4 G = gem_grad4(reinterpret_cast<const float4*>(g + off)[q], refs, stride, K, (off >> 2) + q, sh_v, grad_scale);
+            float4 M = reinterpret_cast<float4*>(m + off)[q];
+            float4 V = reinterpret_cast<float4*>(v + off)[q];
+            if (CLIP) { G.x = mul_rn(G.x, coef); G.y = mul_rn(G.y, coef); G.z = mul_rn(G.z, coef); G.w = mul_rn(G.w, coef); }
+            adamw1_rn<false>(P.x, G.x, M.x, V.x, k.decay, k.omb1, k.b2, k.omb2, k.eps, k.step_size, k.inv_bc2_sqrt);
+            adamw1_rn<false>(P.y, G.y, M.y, V.y, k.decay, k.omb1, k.b2, k.omb2, k.eps, k.step_size, k.inv_bc2_sqrt);
+            adamw1_rn<false>(P.z, G.z, M.z, V.z, k.decay, k.omb1, k.b2, k.omb2, k.eps, k.step_size, k.inv_bc2_sqrt);
+            adamw1_rn<false>(P.w, G.w, M.w, V.w, k.decay, k.omb1, k.b2, k.omb2, k.eps, k.step_size, k.inv_bc2_sqrt);
+            reinterpret_cast<float4*>(p + off)[q] = P;
+            reinterpret_cast<float4*>(m + off)[q] = M;
+            reinterpret_cast<float4*>(v + off)[q] = V;
+            if (shadow_bf16) {
+                __hip_bfloat16 a = __float2bfloat16(P.x), b = __float2bfloat16(P.y), cc = __float2bfloat16(P.z),
+                               d = __float2bfloat16(P.w);
+                ushort4 o;
+                o.x = *reinterpret_cast<unsigned short*>(&a); o.y = *reinterpret_cast<unsigned short*>(&b);
+                o.z = *reinterpret_cast<unsigned short*>(&cc); o.w = *reinterpret_cast<unsigned short*>(&d);
+                reinterpret_cast<ushort4*>(shadow_bf16 + off)[q] = o;
+            }
+        }
+        for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) {
+            float P = p[off + i], M = m[off + i], V = v[off + i];
+            float G = gem_grad1(g[off + i], refs, stride, K, off + i, sh_v, grad_scale);
+            if (CLIP) G = mul_rn(G, coef);
+            adamw1_rn<true>(P, G, M, V, k.decay, k.omb1, k.b2, k.omb2, k.eps, k.step_size, k.inv_bc2_sqrt);
+            p[off + i] = P; m[off + i] = M; v[off + i] = V;
+            if (shadow_bf16) { __hip_bfloat16 a = __float2bfloat16(P); shadow_bf16[off + i] = *reinterpret_cast<unsigned short*>(&a); }
+        }
+    }
+}
+
+// ... after a GEM step: gem_counters = {projected steps, unsolved steps}; a skipped step does not count as projected, and a
+// step whose program could not be solved counts as unsolved whether or not it was skipped
+__global__ void seg_step_advance_gem_kernel(int* __restrict__ seg_active, int* __restrict__ seg_step, int nseg,
+                                            const float* __restrict__ norm_state, int skip_nonfinite,
+                                            int* __restrict__ counters, const float* __restrict__ gem_state,
+                                            int* __restrict__ gem_counters) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool skipped = norm_state && skip_nonfinite && norm_state[2] != 0.f;
+    if (s < nseg) { seg_step[s] += (!skipped && seg_active[s]) ? 1 : 0; seg_active[s] = 0; }
+    if (s == 0) {
+        if (skipped) counters[1] += 1;
+        else if (norm_state && norm_state[1] < 1.f) counters[0] += 1;
+        if (!skipped && gem_state[GEM_VIOLATED] != 0.f) gem_counters[0] += 1;
+        if (gem_state[GEM_SOLVED] == 0.f) gem_counters[1] += 1;
+    }
+}
+
 inline int cap_grid(int64_t work_items, int per_block) {
     int64_t b = (work_items + per_block - 1) / per_block;
     return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
@@ -865,6 +1271,26 @@ int run_step_projected(const step_head& h, const group_table& gt, const int32_t*
                        skip_nonfinite, ref, proj_state);
     hipLaunchKernelGGL(seg_step_advance_projected_kernel, dim3((h.nseg + 255) / 256), dim3(256), 0, st, h.seg_active, h.seg_step,
                        h.nseg, norm_state, skip_nonfinite, counters, proj_state, proj_counters);
+    IA_RETURN_IF_LAUNCH_FAILED();
+    return IA_OK;
+}
+
+inline bool gem_operands_ok(const float* refs, int64_t stride, int ntasks, const float* gem_state) {
+    if (!refs || !gem_state || ntasks < 1 || ntasks > GEM_MAX || stride <= 0 || (stride & 3)) return false;
+    return ia_is_aligned(refs, 16) && ia_is_aligned(gem_state, 4);
+}
+
+int run_step_gem(const step_head& h, const group_table& gt, const int32_t* seg_group, const float* norm_state, int skip_nonfinite,
+                 int32_t* counters, const float* refs, int64_t stride, int ntasks, const float* gem_state, int32_t* gem_counters,
+                 hipStream_t st) {
+    if (h.all_active)   // otherwise ia_gem_dots has set the flags from the task gradient
+        if (!mark_all_active(h, st)) return IA_LAUNCH_FAILED;
+    auto kernel = norm_state ? adamw_seg_gem_kernel<true> : adamw_seg_gem_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(step_grid(h)), dim3(CL_THREADS), 0, st, h.theta, h.grad, h.exp_avg, h.exp_avg_sq, h.table,
+                       h.nchunks, h.seg_active, h.seg_step, gt, seg_group, h.b1, h.b2, h.eps, h.grad_scale, h.shadow, norm_state,
+                       skip_nonfinite, refs, stride, ntasks, gem_state);
+    hipLaunchKernelGGL(seg_step_advance_gem_kernel, dim3((h.nseg + 255) / 256), dim3(256), 0, st, h.seg_active, h.seg_step,
+                       h.nseg, norm_state, skip_nonfinite, counters, gem_state, gem_counters);
     IA_RETURN_IF_LAUNCH_FAILED();
     return IA_OK;
 }
@@ -1071,4 +1497,80 @@ extern "C" int ia_adamw_step_segmented_grouped(float* theta, const float* grad, 
     if (si)
         return run_step_si(h, gt, seg_group, norm_state, skip_nonfinite, counters, path_w, omega, theta_star, penalty_coef, st);
     return run_step(h, gt, seg_group, norm_state, skip_nonfinite, counters, st);
+}
+
+extern "C" size_t ia_gem_workspace_bytes(int nchunks, int max_tasks) {
+    return nchunks > 0 && max_tasks >= 1 && max_tasks <= GEM_MAX ? (size_t)nchunks * max_tasks * sizeof(float) : 0;
+}
+
+extern "C" int ia_gem_dots(const float* x, const float* refs, int64_t stride, int ntasks, const int32_t* chunk_table, int nchunks,
+                           int nseg, float grad_scale, int32_t* seg_active, int gram_row, double* gem_sums, void* workspace,
+                           size_t workspace_bytes, ia_stream_t stream) {
+    if (!x || !chunk_table || !workspace || !gem_sums || nchunks <= 0 || nseg <= 0 || gram_row >= ntasks || stride <= 0 ||
+        (stride & 3) || !refs || ntasks < 1 || ntasks > GEM_MAX)
+        return IA_INVALID_VALUE;
+    if (!ia_is_aligned(refs, 16) || !ia_is_aligned(gem_sums, 8)) return IA_INVALID_VALUE;
+    if (!ia_is_aligned(x, 16) || !ia_is_aligned(chunk_table, 16) || !ia_is_aligned(workspace, 4)) return IA_INVALID_VALUE;
+    if (workspace_bytes < ia_gem_workspace_bytes(nchunks, ntasks)) return IA_WORKSPACE_TOO_SMALL;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(gem_dots_kernel, dim3(nchunks < 2048 ? nchunks : 2048), dim3(CL_THREADS), 0, st, x, refs, stride, ntasks,
+                       (const int4*)chunk_table, nchunks, gram_row < 0 ? seg_active : (int32_t*)nullptr, (float*)workspace);
+    hipLaunchKernelGGL(gem_finish_kernel, dim3(1), dim3(GN_THREADS), 0, st, (const float*)workspace, nchunks, ntasks, grad_scale,
+                       gram_row, gem_sums);
+    IA_RETURN_IF_LAUNCH_FAILED();
+    return IA_OK;
+}
+
+extern "C" int ia_gem_solve(const double* gem_sums, float* gem_state, int ntasks, float memory_strength, float eps,
+                            ia_stream_t stream) {
+    if (!gem_state || !gem_sums || ntasks < 1 || ntasks > GEM_MAX || !(memory_strength >= 0.f) || !(eps >= 0.f) ||
+        !isfinite(memory_strength) || !isfinite(eps))
+        return IA_INVALID_VALUE;
+    if (!ia_is_aligned(gem_state, 4) || !ia_is_aligned(gem_sums, 8)) return IA_INVALID_VALUE;
+    hipLaunchKernelGGL(gem_solve_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, gem_sums, gem_state, ntasks, memory_strength,
+                       eps);
+    IA_RETURN_IF_LAUNCH_FAILED();
+    return IA_OK;
+}
+
+extern "C" int ia_grad_norm_gem(const float* grad, const int32_t* chunk_table, int nchunks, const int32_t* seg_chunk_begin, int nseg,
+                                float grad_scale, float max_norm, const int32_t* seg_active, float* seg_norm, float* norm_state,
+                                void* workspace, size_t workspace_bytes, const float* refs, int64_t stride, int ntasks,
+                                const float* gem_state, ia_stream_t stream) {
+    if (!grad || !chunk_table || !seg_chunk_begin || !seg_norm || !norm_state || !workspace || nchunks <= 0 || nseg <= 0 ||
+        !gem_operands_ok(refs, stride, ntasks, gem_state))
+        return IA_INVALID_VALUE;
+    if (!ia_is_aligned(grad, 16) || !ia_is_aligned(chunk_table, 16) || !ia_is_aligned(workspace, 4)) return IA_INVALID_VALUE;
+    if (workspace_bytes < ia_grad_norm_workspace_bytes(nchunks)) return IA_WORKSPACE_TOO_SMALL;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(gem_norm_kernel, dim3(nchunks < 2048 ? nchunks : 2048), dim3(CL_THREADS), 0, st, grad, refs, stride, ntasks,
+                       (const int4*)chunk_table, nchunks, seg_active, gem_state, grad_scale, (float*)workspace);
+    hipLaunchKernelGGL(grad_norm_finish_gem_kernel, dim3(1), dim3(GN_THREADS), 0, st, (const float*)workspace, seg_chunk_begin,
+                       nseg, fabsf(grad_scale), max_norm, seg_norm, norm_state, gem_state);
+    IA_RETURN_IF_LAUNCH_FAILED();
+    return IA_OK;
+}
+
+extern "C" int ia_adamw_step_segmented_gem(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq,
+                                           const int32_t* chunk_table, int nchunks, int32_t* seg_active, int32_t* seg_step, int nseg,
+                                           int all_active, float beta1, float beta2, float eps, float grad_scale, void* shadow_bf16,
+                                           const int32_t* seg_group, int ngroups, const float* group_lr,
+                                           const float* group_weight_decay, const float* norm_state, int skip_nonfinite,
+                                           int32_t* counters, const float* refs, int64_t stride, int ntasks, const float* gem_state,
+                                           int32_t* gem_counters, ia_stream_t stream) {
+    if (!step_head_ok(theta, grad, exp_avg, exp_avg_sq, chunk_table, nchunks, seg_active, seg_step, nseg, shadow_bf16))
+        return IA_INVALID_VALUE;
+    if (ngroups < 1 || ngroups > IA_MAX_PARAM_GROUPS || !group_lr || !group_weight_decay || (ngroups > 1 && !seg_group) ||
+        (seg_group && !ia_is_aligned(seg_group, 4)))
+        return IA_INVALID_VALUE;
+    if ((norm_state == nullptr) != (counters == nullptr) || !gem_counters || !ia_is_aligned(gem_counters, 4) ||
+        !gem_operands_ok(refs, stride, ntasks, gem_state))
+        return IA_INVALID_VALUE;
+    group_table gt = {};
+    gt.n = ngroups;
+    for (int k = 0; k < ngroups; ++k) { gt.lr[k] = group_lr[k]; gt.weight_decay[k] = group_weight_decay[k]; }
+    const step_head h = {theta, grad, exp_avg, exp_avg_sq, (const int4*)chunk_table, nchunks, seg_active, seg_step, nseg, all_active,
+                         beta1, beta2, eps, grad_scale, (unsigned short*)shadow_bf16};
+    return run_step_gem(h, gt, seg_group, norm_state, skip_nonfinite, counters, refs, stride, ntasks, gem_state, gem_counters,
+                        (hipStream_t)stream);
 }
