@@ -934,6 +934,45 @@ int ia_adamw_step_segmented_grouped(float* theta, const float* grad, float* exp_
                                     int32_t* counters, float* path_w, const float* omega, const float* theta_star,
                                     float penalty_coef, const float* ref, const float* proj_state, int32_t* proj_counters,
                                     ia_stream_t stream);
+/* Piggyback (Mallya, Davis, Lazebnik 2018): per-language binary masks over a fixed backbone, trained inside the AdamW launch.
+ * seg_kind: int32[nseg] on the device, the kind of tensor k.  base and scores are flat fp32 buffers laid out as theta.
+ *   IA_MASK_FREE    plain AdamW on theta, exactly the arithmetic of ia_adamw_step_segmented[_clipped / _grouped]
+ *   IA_MASK_MASKED  theta = base * 1[score >= threshold]; the scores are what AdamW trains.  Per element of a live tensor, every
+ *                   product rounded to fp32 on its own:
+ *                     ge = grad * grad_scale [* coef when clipping];   gs = ge * base   (straight-through gradient of the score)
+ *                     score, exp_avg, exp_avg_sq = AdamW(score, gs) with the group's lr and weight decay 0
+ *                     theta = score >= threshold ? base : +0.0f;   shadow = bf16(theta)
+ *   IA_MASK_FROZEN  never written: theta, moments and step counter stay whatever the gradient holds; only the shadow is refreshed
+ * A tensor that received no gradient only has its shadow kept in step, whatever its kind.
+ * ia_adamw_step_segmented_masked  one AdamW launch over the chunk table, 38 B per masked element (reads grad, base, score and the
+ *                          two moments; writes score, the moments, theta and the bf16 image), 30 B per free element, 6 B per
+ *                          frozen or idle one.  Group table as ia_adamw_step_segmented_gem takes it.  norm_state and counters:
+ *                          both NULL (the liveness pass runs here unless all_active) or both set (ia_grad_norm has measured the
+ *                          gradient and set the flags: clip by norm_state[1]; with skip_nonfinite a flagged norm writes nothing).
+ *                          Step counters advance for live free and masked tensors only.
+ * ia_mask_pack             scores -> bits: bit i of 64-bit word j is scores[64 * j + i] >= threshold inside masked tensors, 0 in
+ *                          the alignment gaps and in every other tensor.  Tensors start on 64-float boundaries and chunks hold
+ *                          4096 elements, so no word straddles a chunk; nwords = flat length / 64 bounds every store.  seg_kept
+ *                          (optional, int32[nseg], zeroed here) receives the number of set bits per tensor.  4 B read per
+ *                          masked element, 1 bit written.
+ * ia_mask_apply            bits -> weights: theta = bit ? base : +0.0f inside masked tensors, then shadow = bf16(theta) for every
+ *                          tensor when a shadow is given (so one launch leaves the whole bf16 image consistent).
+ * IA_INVALID_VALUE before any device work: a NULL required pointer, counts <= 0, counters without norm_state (or the reverse),
+ * the group conditions of ia_adamw_step_segmented_grouped, misaligned buffers (16 bytes for the flat buffers and the chunk table,
+ * 8 for bits and the shadow, 4 for seg_kind and seg_kept). */
+#define IA_MASK_FREE 0
+#define IA_MASK_MASKED 1
+#define IA_MASK_FROZEN 2
+int ia_adamw_step_segmented_masked(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq, const int32_t* chunk_table,
+                                   int nchunks, int32_t* seg_active, int32_t* seg_step, int nseg, int all_active, float beta1,
+                                   float beta2, float eps, float grad_scale, void* shadow_bf16, const int32_t* seg_group,
+                                   int ngroups, const float* group_lr, const float* group_weight_decay, const float* norm_state,
+                                   int skip_nonfinite, int32_t* counters, const float* base, float* scores,
+                                   const int32_t* seg_kind, float threshold, ia_stream_t stream);
+int ia_mask_pack(const float* scores, const int32_t* chunk_table, int nchunks, const int32_t* seg_kind, int nseg, float threshold,
+                 uint64_t* bits, int64_t nwords, int32_t* seg_kept, ia_stream_t stream);
+int ia_mask_apply(float* theta, const float* base, const uint64_t* bits, int64_t nwords, const int32_t* chunk_table, int nchunks,
+                  const int32_t* seg_kind, int nseg, void* shadow_bf16, ia_stream_t stream);
 
 /* ---- CTC head + loss on RAW logits (ConvASRDecoder.forward + CTCLoss.forward, A/modules/conv_asr.py:459-490 and
  * A/losses/ctc.py:68-82, without the [B,T,V] log-prob tensor and without a softmax backward pass): logits [B*T, ld] f32 with V

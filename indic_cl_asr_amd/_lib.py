@@ -220,6 +220,10 @@ SIGNATURES = {
                                          _vp, _i, _vp, _vp, _i64, _i, _vp, _vp, _vp]),
     "ia_adamw_step_segmented_grouped": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _f, _vp, _vp, _i, _vp, _vp,
                                              _vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
+    "ia_adamw_step_segmented_masked": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _f, _vp, _vp, _i, _vp, _vp,
+                                            _vp, _i, _vp, _vp, _vp, _vp, _f, _vp]),
+    "ia_mask_pack": (_i, [_vp, _vp, _i, _vp, _i, _f, _vp, _i64, _vp, _vp]),
+    "ia_mask_apply": (_i, [_vp, _vp, _vp, _i64, _vp, _i, _vp, _i, _vp, _vp]),
 }
 
 _lib = None

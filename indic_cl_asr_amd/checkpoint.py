@@ -175,3 +175,15 @@ def load_memory(memory, path):
     """Inverse of save_memory: the loaded memory holds the same utterances and continues the same sequence of draws."""
     memory.load_state_dict(torch.load(path, map_location="cpu"))
     return memory
+
+
+def save_masks(masks, path):
+    """Persist cl.Piggyback.state_dict(): kinds, base, scores and every saved language's bits, free tensors and buffers."""
+    torch.save(masks.state_dict(), path)
+
+
+def load_masks(masks, path):
+    """Inverse of save_masks, in place; refuses a file whose tensor table differs from the model's.  The weights follow with
+    masks.activate(lang) or masks.begin_language(lang)."""
+    masks.load_state_dict(torch.load(path, map_location="cpu"), source=path)
+    return masks

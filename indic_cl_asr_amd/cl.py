@@ -16,6 +16,7 @@ The dict-of-tensors API of the reference is kept: the dicts handed out are `Flat
 import ctypes
 import math
 import re
+import weakref
 from contextlib import contextmanager
 from typing import Dict, List, Optional
 
@@ -628,6 +629,229 @@ class EpisodicMemory:
         self.items = {lang: [(x.clone(), t.clone()) for x, t in kept] for lang, kept in sd["items"].items()}
 
 
+# ----------------------------------------------------------------------------- Piggyback
+MASK_FREE, MASK_MASKED, MASK_FROZEN = 0, 1, 2      # IA_MASK_* of include/indicasr.h
+_KIND_NAMES = ("free", "masked", "frozen")
+_HEAD_RE = re.compile(r"^(joint\.joint_net\.[^.]+\.[^.]+\.[^.]+|ctc_decoder\.decoder_layers\.0\.(weight|bias))$")
+
+
+def _select_names(flat: FlatParams, spec, what: str) -> List[str]:
+    """`spec` is a list of parameter names or one regular expression (re.search on the name, as "match" of param_groups)."""
+    if isinstance(spec, str):
+        names = [n for n in flat.names if re.search(spec, n)]
+        if not names:
+            raise ValueError(f"Piggyback: {what} '{spec}' matches no trainable tensor")
+        return names
+    names, known = list(spec), set(flat.names)
+    for n in names:
+        if n not in known:
+            raise ValueError(f"Piggyback: {what}: '{n}' is not a trainable tensor of this FlatParams")
+    return names
+
+
+class Piggyback:
+    """Piggyback (Mallya, Davis, Lazebnik, ECCV 2018): parameter isolation.  One fixed backbone `base` and, per language, a binary
+    mask over its weights, trained through real-valued `scores` with the straight-through estimator: the network sees
+    `base * 1[score >= threshold]`.  Nothing a language learns touches what another language uses, so forgetting is exactly zero
+    and the order of the languages does not matter; a language costs 1 bit per trainable weight plus its own heads.
+
+    Every trainable tensor has a kind, fixed here:
+      masked  `flat.theta` holds base * mask; the optimizer trains the scores.  Default: tensors with dim() >= 2 that are not heads.
+      free    plain AdamW as without masks, snapshotted per language.  Default: the per-language heads `joint.joint_net.*.<lang>.*`
+              and the CTC head `ctc_decoder.decoder_layers.0.{weight,bias}` (one tensor with every language's rows: the
+              per-language snapshot is what keeps weight decay from eroding the other languages' rows).
+      frozen  never written.  Default: everything else (biases, LayerNorm / BatchNorm affine parameters).
+    `masked=` / `frozen=` replace the default sets: a list of parameter names or one regular expression.  A tensor named by one
+    of them leaves the other's default set; a tensor both name raises ValueError; what neither holds is free.
+
+    Attach it with `FusedAdamW(..., masks=pb)`: the step is then ia_adamw_step_segmented_masked, one launch.  Two flat fp32 buffers
+    over the layout (8 B per parameter) while training; per saved language numel / 8 bytes of bits, the free tensors and the
+    module buffers (BatchNorm running statistics: frozen layers still update them in train mode).
+
+    Limits: one language is active at a time -- `flat.theta`, `get_params`, `save_trainable` and the bf16 images show the ACTIVE
+    language's masked weights, and a batch that mixes languages is out of scope.  `activate` is for evaluation: it restores the
+    bits, not the scores, so training continues only after `begin_language`."""
+
+    def __init__(self, model_or_flat, masked=None, frozen=None, threshold=5e-3, init=1e-2):
+        self.flat = _as_flat(model_or_flat)
+        self.threshold, self.init = float(threshold), float(init)
+        if not self.init >= self.threshold:
+            raise ValueError(f"Piggyback: init ({init}) must be >= threshold ({threshold}): a new language starts with every bit on")
+        f = self.flat
+        heads = {n for n in f.names if _HEAD_RE.search(n)}
+        default_masked = [n for n, p in zip(f.names, f.params) if p.dim() >= 2 and n not in heads]
+        given_m = None if masked is None else _select_names(f, masked, "masked=")
+        given_f = None if frozen is None else _select_names(f, frozen, "frozen=")
+        both = sorted(set(given_m or ()) & set(given_f or ()))
+        if both:
+            raise ValueError(f"Piggyback: '{both[0]}' is claimed by masked= and by frozen=")
+        m_set = set(default_masked if given_m is None else given_m) - set(given_f or ())
+        f_set = (set(f.names) - heads - set(default_masked) if given_f is None else set(given_f)) - m_set
+        self._kinds = [MASK_MASKED if n in m_set else MASK_FROZEN if n in f_set else MASK_FREE for n in f.names]
+        dev = f.theta.device
+        self.seg_kind = torch.tensor(self._kinds, dtype=torch.int32, device=dev)
+        flush_pending_updates()
+        self.base = FlatDict(f, f.theta.clone())
+        self.scores = f.zeros()
+        self._fill_scores()
+        self.current: Optional[str] = None
+        self.records: Dict[str, dict] = {}    # lang -> {"bits": int64 [numel / 64], "free": {name: tensor}, "buffers": {name: tensor}}
+        self._scores_lang: Optional[str] = None    # the language the scores describe (None: nobody's yet)
+        self._stale = False                    # True while theta shows a language the scores do not describe
+        self._optimizer = None                 # weak reference to the FusedAdamW that holds the bf16 shadow
+        self._scratch = None
+
+    # -- kinds -----------------------------------------------------------------------------------------------------
+    def kinds(self) -> Dict[str, str]:
+        return {n: _KIND_NAMES[k] for n, k in zip(self.flat.names, self._kinds)}
+
+    def _names_of(self, kind):
+        return [n for n, k in zip(self.flat.names, self._kinds) if k == kind]
+
+    def languages(self) -> List[str]:
+        return list(self.records)
+
+    def _fill_scores(self):
+        for n in self._names_of(MASK_MASKED):
+            self.scores[n].fill_(self.init)
+
+    def _shadow(self):
+        opt = self._optimizer() if self._optimizer is not None else None
+        return opt, (opt.shadow if opt is not None else None)
+
+    # -- bits <-> weights ------------------------------------------------------------------------------------------
+    def _pack(self, out=None, kept=None) -> torch.Tensor:
+        f = self.flat
+        if out is None:
+            out = torch.empty(f.numel // 64, dtype=torch.int64, device=f.theta.device)
+        st = _lib.lib().ia_mask_pack(_lib.ptr(self.scores.flat), _lib.ptr(f.chunk_table), f.chunk_table.shape[0],
+                                     _lib.ptr(self.seg_kind), len(f.entries), self.threshold, _lib.ptr(out), out.numel(),
+                                     _lib.ptr(kept), _lib.stream_ptr())
+        _lib.check(st, "ia_mask_pack")
+        return out
+
+    def _apply_bits(self, bits):
+        """theta = bit ? base : 0 on masked tensors and the bf16 image of every tensor, one launch; then what
+        FusedAdamW._after_update does: the weight epoch moves and the flat shadow views are handed to the shadow cache."""
+        f = self.flat
+        opt, shadow = self._shadow()
+        st = _lib.lib().ia_mask_apply(_lib.ptr(f.theta), _lib.ptr(self.base.flat), _lib.ptr(bits), bits.numel(),
+                                      _lib.ptr(f.chunk_table), f.chunk_table.shape[0], _lib.ptr(self.seg_kind), len(f.entries),
+                                      _lib.ptr(shadow), _lib.stream_ptr())
+        _lib.check(st, "ia_mask_apply")
+        if opt is not None:
+            opt._after_update()
+        else:
+            from .ops import fast
+            fast.bump_weight_epoch()
+
+    # -- the per-language loop ---------------------------------------------------------------------------------------
+    def save_language(self, lang: Optional[str] = None):
+        """Record `lang` (default: the current language): the bits of the scores, the free tensors and every module buffer.
+        Before any masked training every bit is on: this is how the language the backbone was trained on is recorded."""
+        lang = self.current if lang is None else lang
+        if lang is None:
+            raise ValueError("Piggyback.save_language: no language is current; name one")
+        if self._stale:
+            raise RuntimeError(f"Piggyback.save_language: the weights show '{self.current}' as activate() restored it, but the "
+                               "scores belong to another language; call begin_language() before training and saving")
+        flush_pending_updates()
+        f = self.flat
+        self.records[lang] = {
+            "bits": self._pack(),
+            "free": {n: f._theta_views[n].detach().clone() for n in self._names_of(MASK_FREE)},
+            "buffers": {n: b.detach().clone() for n, b in f.model.named_buffers()}}
+        self.current = self._scores_lang = lang
+
+    def begin_language(self, lang: str, optimizer: Optional["FusedAdamW"] = None):
+        """Start training `lang`: scores = init, so every bit is on and theta equals base on the masked tensors; the free tensors
+        and buffers continue from where they are.  With an optimizer, the moments and step counters of every tensor that is not
+        frozen are zeroed (a frozen tensor's are never read)."""
+        flush_pending_updates()
+        self._fill_scores()
+        if optimizer is not None:
+            if optimizer.flat is not self.flat:
+                raise ValueError("optimizer belongs to another FlatParams")
+            for k, (n, o, cnt, shape) in enumerate(self.flat.entries):
+                if self._kinds[k] != MASK_FROZEN:
+                    optimizer.exp_avg[o:o + cnt].zero_()
+                    optimizer.exp_avg_sq[o:o + cnt].zero_()
+            optimizer.seg_step.mul_((self.seg_kind == MASK_FROZEN).to(torch.int32))
+        self._apply_bits(self._pack())
+        self.current, self._scores_lang, self._stale = lang, lang, False
+
+    def activate(self, lang: str):
+        """Show `lang` to the network: its free tensors and buffers come back, then one launch rewrites the masked weights from
+        its bits and the whole bf16 image; every cached derived weight image is re-made on its next use.  Progress of the
+        current language that save_language() has not recorded is lost (its heads are overwritten); after save_language(x),
+        activate(other), ..., activate(x) training x continues where it was."""
+        if lang not in self.records:
+            raise ValueError(f"Piggyback.activate: unknown language '{lang}' (saved: {', '.join(self.records) or 'none'})")
+        flush_pending_updates()
+        rec, f = self.records[lang], self.flat
+        with torch.no_grad():
+            for n, t in rec["free"].items():
+                f._theta_views[n].copy_(t)
+            buffers = dict(f.model.named_buffers())
+            for n, t in rec["buffers"].items():
+                buffers[n].copy_(t)
+        self._apply_bits(rec["bits"])
+        self.current, self._stale = lang, lang != self._scores_lang
+
+    # -- reports ---------------------------------------------------------------------------------------------------
+    def sparsity(self) -> Dict[str, float]:
+        """name -> fraction of bits ON, for the masked tensors, from the scores as they are now: one pack into scratch and one
+        small device-to-host read."""
+        flush_pending_updates()
+        f = self.flat
+        if self._scratch is None:
+            self._scratch = (torch.empty(f.numel // 64, dtype=torch.int64, device=f.theta.device),
+                             torch.zeros(len(f.entries), dtype=torch.int32, device=f.theta.device))
+        self._pack(*self._scratch)
+        kept = self._scratch[1].tolist()
+        return {e[0]: kept[k] / e[2] for k, e in enumerate(f.entries) if self._kinds[k] == MASK_MASKED}
+
+    def bytes_per_language(self) -> dict:
+        """Bytes one saved language holds: the bits (1 per flat element), the free tensors and the module buffers."""
+        f = self.flat
+        free = sum(e[2] * 4 for k, e in enumerate(f.entries) if self._kinds[k] == MASK_FREE)
+        buffers = sum(b.numel() * b.element_size() for b in f.model.buffers())
+        mask = f.numel // 64 * 8
+        return {"mask": mask, "free": free, "buffers": buffers, "total": mask + free + buffers}
+
+    # -- resumable state -------------------------------------------------------------------------------------------
+    def state_dict(self) -> dict:
+        flush_pending_updates()
+        cpu = lambda t: t.detach().to("cpu", copy=True)
+        return {"entries": list(self.flat.entries), "kinds": [_KIND_NAMES[k] for k in self._kinds], "threshold": self.threshold,
+                "init": self.init, "base": cpu(self.base.flat), "scores": cpu(self.scores.flat), "current": self.current,
+                "scores_language": self._scores_lang,
+                "languages": {lang: {"bits": cpu(r["bits"]), "free": {n: cpu(t) for n, t in r["free"].items()},
+                                     "buffers": {n: cpu(t) for n, t in r["buffers"].items()}}
+                              for lang, r in self.records.items()}}
+
+    def load_state_dict(self, sd: dict, source="state dict"):
+        """In place: base, scores and the kind table keep their addresses (an attached optimizer keeps pointing at them).  The
+        weights are not part of this state: `activate(lang)` or `begin_language(lang)` puts them in step with it."""
+        if [tuple(e[:3]) + (tuple(e[3]),) for e in sd["entries"]] != list(self.flat.entries):
+            raise ValueError(f"{source}: 'masks' was saved for a different set of trainable tensors")
+        kinds = [_KIND_NAMES.index(k) for k in sd["kinds"]]
+        if not float(sd["init"]) >= float(sd["threshold"]):
+            raise ValueError(f"{source}: init must be >= threshold")
+        flush_pending_updates()
+        dev = self.flat.theta.device
+        self.base.flat.copy_(sd["base"])
+        self.scores.flat.copy_(sd["scores"])
+        self._kinds = kinds
+        self.seg_kind.copy_(torch.tensor(kinds, dtype=torch.int32))
+        self.threshold, self.init = float(sd["threshold"]), float(sd["init"])
+        self.current, self._scores_lang = sd["current"], sd["scores_language"]
+        self._stale = False                    # the weights are the caller's to restore
+        self.records = {lang: {"bits": r["bits"].to(dev), "free": {n: t.to(dev) for n, t in r["free"].items()},
+                               "buffers": {n: t.to(dev) for n, t in r["buffers"].items()}}
+                        for lang, r in sd["languages"].items()}
+
+
 # ----------------------------------------------------------------------------- LwF
 def lwf_kd_loss(loss, prob, prob_, pred_store_list, store_list, knowledge_distillation: float, kd_ctx: float):
     """R/cl_baseline_lwf.py:242-264.  Returns (total loss, rnnt_kd, ctc_kd) -- device tensors."""
@@ -777,7 +1001,7 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def __init__(self, model_or_flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, group=None,
                  bf16_shadow=None, defer_update=True, grad_exchange_dtype=None, max_grad_norm=None, skip_nonfinite=False,
-                 track_grad_norm=False, path_integral=None, projection=None, param_groups=None):
+                 track_grad_norm=False, path_integral=None, projection=None, param_groups=None, masks=None):
         """`max_grad_norm=c`: torch.nn.utils.clip_grad_norm_(parameters, c) applied inside the step, to the gradient the
         update consumes -- after the data-parallel all-reduce, so every rank clips the AVERAGED gradient by the same factor
         (the torch call between backward() and step() would clip each rank's local gradient: the exchange happens in here).
@@ -808,8 +1032,21 @@ class FusedAdamW(torch.optim.Optimizer):
         "weight_decay", and may carry a "name".  Every trainable tensor nobody claims stays in group 0, which carries this
         constructor's values; `no_decay_groups` and `layerwise_lr_groups` build such lists.  All groups go through ONE launch
         (ia_adamw_step_segmented_grouped; clipping, the non-finite skip, path_integral and projection included).  A deferred
-        update applies the lr / weight_decay its step() saw, whatever a scheduler has written since."""
+        update applies the lr / weight_decay its step() saw, whatever a scheduler has written since.
+
+        `masks=pb` (a `Piggyback` on the same FlatParams): the step is ia_adamw_step_segmented_masked for one or many groups,
+        after ia_grad_norm when the norm is measured (the norm is that of the task gradient, as without masks).  A masked tensor's
+        scores are trained with its group's `lr`; its `weight_decay` is IGNORED (a score is not a weight, and decaying it towards
+        zero would switch bits off by itself).  A free tensor takes the plain step, a frozen one is never written.  `exp_avg`,
+        `exp_avg_sq` and the step counters of a masked tensor are those of its scores.  Not combinable with `path_integral` or
+        `projection`.  The masks are not optimizer state: `pb.state_dict()` / `checkpoint.save_masks`."""
         self.flat = model_or_flat if isinstance(model_or_flat, FlatParams) else flat_of(model_or_flat)
+        if masks is not None and (path_integral is not None or projection is not None):
+            raise ValueError("masks cannot be combined with path_integral or projection: the masked weights do not move along "
+                             "the gradient those methods constrain")
+        if masks is not None and masks.flat is not self.flat:
+            raise ValueError("masks belongs to another FlatParams")
+        self.masks = masks
         if path_integral is not None and path_integral.flat is not self.flat:
             raise ValueError("path_integral belongs to another FlatParams")
         if projection is not None and path_integral is not None:
@@ -878,6 +1115,8 @@ class FusedAdamW(torch.optim.Optimizer):
         self._seg_norm = self._norm_ws = None
         self.defer_update = defer_update   # data parallel only: overlap the gradient all-reduce with the next forward
         self._pending, self._zero_after_flush = None, False
+        if masks is not None:
+            masks._optimizer = weakref.ref(self)      # activate() / begin_language() rewrite this optimizer's bf16 shadow
 
     def add_param_group(self, param_group):
         if self._layout_fixed:
@@ -1031,6 +1270,16 @@ class FusedAdamW(torch.optim.Optimizer):
                 _lib.ptr(self._seg_norm), _lib.ptr(self._norm_state), _lib.ptr(self._norm_ws), self._norm_ws.numel(),
                 _lib.stream_ptr())
             _lib.check(st, "ia_grad_norm")
+        if self.masks is not None:
+            pb, n = self.masks, len(lrs)
+            st = L.ia_adamw_step_segmented_masked(
+                _lib.ptr(f.theta), _lib.ptr(f.grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), _lib.ptr(f.chunk_table),
+                nchunks, _lib.ptr(self.seg_active), _lib.ptr(self.seg_step), nseg, int(all_live), b1, b2, eps, float(scale),
+                _lib.ptr(self.shadow), _lib.ptr(self.seg_group), n, (ctypes.c_float * n)(*lrs), (ctypes.c_float * n)(*wds),
+                _lib.ptr(self._norm_state) if measured else None, int(skip), _lib.ptr(self._counters) if measured else None,
+                _lib.ptr(pb.base.flat), _lib.ptr(pb.scores.flat), _lib.ptr(pb.seg_kind), pb.threshold, _lib.stream_ptr())
+            _lib.check(st, "ia_adamw_step_segmented_masked")
+            return self._after_update()
         head = (_lib.ptr(f.theta), _lib.ptr(f.grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), _lib.ptr(f.chunk_table),
                 nchunks, _lib.ptr(self.seg_active), _lib.ptr(self.seg_step), nseg, int(all_live))
         if len(lrs) > 1:           # every kind of step through the one grouped entry point: the operands select the kernel

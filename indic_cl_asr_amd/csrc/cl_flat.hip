@@ -19,6 +19,9 @@
 //                              bound-constrained quadratic program in fp64, and norm and AdamW on g * s + sum_k v_k * r_k
 //   ia_adamw_step_segmented_grouped .... any of the four segmented steps with lr and weight_decay per parameter group
 //                              (torch.optim.AdamW's param_groups): the same kernels, the group table by value in their arguments
+//   ia_adamw_step_segmented_masked, ia_mask_pack, ia_mask_apply .. Piggyback (Mallya, Davis, Lazebnik 2018): per tensor a kind --
+//                              masked (scores trained on g * base, theta = score >= threshold ? base : 0), free (the plain step),
+//                              frozen (untouched) --, the scores as one bit per weight, and the bits back to weights
 // All are HBM-streaming kernels: 16-byte accesses, grid capped at 2048 workgroups, fp32 math.
 #include "ia_common.h"
 
@@ -1161,6 +1164,210 @@ __global__ void seg_step_advance_gem_kernel(int* __restrict__ seg_active, int* _
     }
 }
 
+// ---- Piggyback (Mallya, Davis, Lazebnik 2018): a fixed backbone `base` and, per language, a binary mask over it that is
+// trained through real-valued scores.  Per tensor a kind (workgroup-uniform per chunk, read inside the chunk loop as group_of is):
+//   free    adamw_seg_kernel's arithmetic on theta (adamw1_rn restates it), so a free tensor moves as under the plain step
+//   masked  ge = g * grad_scale [* coef];  gs = ge * base;  score, m, v = AdamW(score, gs) with weight decay 0 (decay factor 1);
+//           theta = score >= threshold ? base : +0;  every product rounded on its own
+//   frozen  nothing but the bf16 image
+// A masked element moves 38 B (g, base, score, m, v in; score, m, v, theta and the bf16 image out), a free one 30 B.
+constexpr int KIND_MASKED = IA_MASK_MASKED, KIND_FROZEN = IA_MASK_FROZEN;      // anything else is IA_MASK_FREE
+
+__device__ __forceinline__ unsigned short bf16_bits(float x) {
+    __hip_bfloat16 a = __float2bfloat16(x);
+    return *reinterpret_cast<unsigned short*>(&a);
+}
+
+template <bool CLIP, bool TAIL>
+__device__ __forceinline__ float adamw_mask1(float& s, float g, float base, float& m, float& v, float threshold,
+                                             const si_consts& k) {
+    const float ge = mul_rn(g, k.grad_scale);
+    const float eff = CLIP ? mul_rn(ge, k.coef) : ge;           // eff_grad<true>'s two products
+    adamw1_rn<TAIL>(s, mul_rn(eff, base), m, v, 1.f, k.omb1, k.b2, k.omb2, k.eps, k.step_size, k.inv_bc2_sqrt);
+    return s >= threshold ? base : 0.f;
+}
+
+template <bool CLIP>
+__global__ __launch_bounds__(CL_THREADS) void adamw_seg_masked_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                                      float* __restrict__ m, float* __restrict__ v,
+                                                                      const int4* __restrict__ table, int nchunks,
+                                                                      const int* __restrict__ seg_active,
+                                                                      const int* __restrict__ seg_step, const group_table groups,
+                                                                      const int* __restrict__ seg_group, float b1, float b2,
+                                                                      float eps, float grad_scale,
+                                                                      unsigned short* __restrict__ shadow_bf16,
+                                                                      const float* __restrict__ norm_state, int skip_nonfinite,
+                                                                      const float* __restrict__ base, float* __restrict__ scores,
+                                                                      const int* __restrict__ seg_kind, float threshold) {
+    __shared__ float sh_c[2];
+    float coef = 1.f;
+    if (CLIP) {
+        if (skip_nonfinite && norm_state[2] != 0.f) return;
+        coef = norm_state[1];
+    }
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const int4 e = table[c];
+        const int kind = seg_kind[e.z];                          // workgroup-uniform
+        if (kind == KIND_FROZEN || !seg_active[e.z]) {           // never written / untouched: only the bf16 image is kept in step
+            if (shadow_bf16)
+                for (int i = threadIdx.x; i < e.y; i += CL_THREADS) shadow_bf16[e.x + i] = bf16_bits(p[e.x + i]);
+            continue;
+        }
+        const int gi = group_of(seg_group, e.z, groups.n);      // workgroup-uniform
+        const float lr = groups.lr[gi], wd = groups.weight_decay[gi];
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const double step = (double)(seg_step[e.z] + 1);
+            sh_c[0] = (float)((double)lr / (1.0 - pow((double)b1, step)));
+            sh_c[1] = (float)(1.0 / sqrt(1.0 - pow((double)b2, step)));
+        }
+        __syncthreads();
+        const si_consts k = {__builtin_fmaf(-lr, wd, 1.f), 1.f - b1, b2, 1.f - b2, eps, sh_c[0], sh_c[1], grad_scale, coef, 0.f};
+        const int off = e.x, cnt = e.y, n4 = cnt >> 2;
+        if (kind == KIND_MASKED) {
+            for (int q = threadIdx.x; q < n4; q += CL_THREADS) {
+                const float4 G = reinterpret_cast<const float4*>(g + off)[q];
+                const float4 B = reinterpret_cast<const float4*>(base + off)[q];
+                float4 S = reinterpret_cast<float4*>(scores + off)[q];
+                float4 M = reinterpret_cast<float4*>(m + off)[q];
+                float4 V = reinterpret_cast<float4*>(v + off)[q];
+                float4 P;
+                P.x = adamw_mask1<CLIP, false>(S.x, G.x, B.x, M.x, V.x, threshold, k);
+                P.y = adamw_mask1<CLIP, false>(S.y, G.y, B.y, M.y, V.y, threshold, k);
+                P.z = adamw_mask1<CLIP, false>(S.z, G.z, B.z, M.z, V.z, threshold, k);
+                P.w = adamw_mask1<CLIP, false>(S.w, G.w, B.w, M.w, V.w, threshold, k);
+                reinterpret_cast<float4*>(scores + off)[q] = S;
+                reinterpret_cast<float4*>(m + off)[q] = M;
+                reinterpret_cast<float4*>(v + off)[q] = V;
+                reinterpret_cast<float4*>(p + off)[q] = P;
+                if (shadow_bf16) {
+                    ushort4 o;
+                    o.x = bf16_bits(P.x); o.y = bf16_bits(P.y); o.z = bf16_bits(P.z); o.w = bf16_bits(P.w);
+                    reinterpret_cast<ushort4*>(shadow_bf16 + off)[q] = o;
+                }
+            }
+            for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) {
+                float S = scores[off + i], M = m[off + i], V = v[off + i];
+                const float P = adamw_mask1<CLIP, true>(S, g[off + i], base[off + i], M, V, threshold, k);
+                scores[off + i] = S; m[off + i] = M; v[off + i] = V; p[off + i] = P;
+                if (shadow_bf16) shadow_bf16[off + i] = bf16_bits(P);
+            }
+            continue;
+        }
+        for (int q = threadIdx.x; q < n4; q += CL_THREADS) {    // free: adamw_seg_gem_kernel's un-projected path
+            float4 P = reinterpret_cast<float4*>(p + off)[q];
+            float4 G = reinterpret_cast<const float4*>(g + off)[q];
+            float4 M = reinterpret_cast<float4*>(m + off)[q];
+            float4 V = reinterpret_cast<float4*>(v + off)[q];
+            G.x = mul_rn(G.x, grad_scale); G.y = mul_rn(G.y, grad_scale); G.z = mul_rn(G.z, grad_scale); G.w = mul_rn(G.w, grad_scale);
+            if (CLIP) { G.x = mul_rn(G.x, coef); G.y = mul_rn(G.y, coef); G.z = mul_rn(G.z, coef); G.w = mul_rn(G.w, coef); }
+            adamw1_rn<false>(P.x, G.x, M.x, V.x, k.decay, k.omb1, k.b2, k.omb2, k.eps, k.step_size, k.inv_bc2_sqrt);
+            adamw1_rn<false>(P.y, G.y, M.y, V.y, k.decay, k.omb1, k.b2, k.omb2, k.eps, k.step_size, k.inv_bc2_sqrt);
+            adamw1_rn<false>(P.z, G.z, M.z, V.z, k.decay, k.omb1, k.b2, k.omb2, k.eps, k.step_size, k.inv_bc2_sqrt);
+            adamw1_rn<false>(P.w, G.w, M.w, V.w, k.decay, k.omb1, k.b2, k.omb2, k.eps, k.step_size, k.inv_bc2_sqrt);
+            reinterpret_cast<float4*>(p + off)[q] = P;
+            reinterpret_cast<float4*>(m + off)[q] = M;
+            reinterpret_cast<float4*>(v + off)[q] = V;
+            if (shadow_bf16) {
+                ushort4 o;
+                o.x = bf16_bits(P.x); o.y = bf16_bits(P.y); o.z = bf16_bits(P.z); o.w = bf16_bits(P.w);
+                reinterpret_cast<ushort4*>(shadow_bf16 + off)[q] = o;
+            }
+        }
+        for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) {
+            float P = p[off + i], M = m[off + i], V = v[off + i];
+            float G = mul_rn(g[off + i], grad_scale);
+            if (CLIP) G = mul_rn(G, coef);
+            adamw1_rn<true>(P, G, M, V, k.decay, k.omb1, k.b2, k.omb2, k.eps, k.step_size, k.inv_bc2_sqrt);
+            p[off + i] = P; m[off + i] = M; v[off + i] = V;
+            if (shadow_bf16) shadow_bf16[off + i] = bf16_bits(P);
+        }
+    }
+}
+
+// ... after a masked step: a frozen tensor's counter never moves; norm_state / counters may both be NULL (nothing measured)
+__global__ void seg_step_advance_masked_kernel(int* __restrict__ seg_active, int* __restrict__ seg_step, int nseg,
+                                               const float* __restrict__ norm_state, int skip_nonfinite,
+                                               int* __restrict__ counters, const int* __restrict__ seg_kind) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool skipped = norm_state && skip_nonfinite && norm_state[2] != 0.f;
+    if (s < nseg) { seg_step[s] += (!skipped && seg_active[s] && seg_kind[s] != KIND_FROZEN) ? 1 : 0; seg_active[s] = 0; }
+    if (s == 0 && norm_state) {
+        if (skipped) counters[1] += 1;
+        else if (norm_state[1] < 1.f) counters[0] += 1;
+    }
+}
+
+// Scores -> bits.  A chunk starts on a 64-float boundary of the flat buffer and holds at most 4096 elements = 64 words; wave w of
+// the workgroup takes words w, w + 4, ... (a wave-uniform trip count), lane i votes for element 64 * j + i and the 64-bit ballot IS
+// word j.  Lanes past the chunk's count and every lane of a tensor that is not masked vote 0, so gaps and other tensors read 0.
+__global__ __launch_bounds__(CL_THREADS) void mask_pack_kernel(const float* __restrict__ scores, const int4* __restrict__ table,
+                                                               int nchunks, const int* __restrict__ seg_kind, float threshold,
+                                                               unsigned long long* __restrict__ bits, int64_t nwords,
+                                                               int* __restrict__ seg_kept) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const int4 e = table[c];
+        const int off = e.x, cnt = e.y, words = (cnt + 63) >> 6;
+        const bool masked = seg_kind[e.z] == KIND_MASKED;        // workgroup-uniform
+        const int64_t word0 = (int64_t)(off >> 6);
+        int kept = 0;
+        for (int j = wave; j < words; j += CL_THREADS / 64) {
+            const int i = (j << 6) + lane;
+            const bool on = masked && i < cnt && scores[off + i] >= threshold;
+            const unsigned long long word = __ballot(on);
+            if (lane == 0 && word0 + j < nwords) bits[word0 + j] = word;
+            kept += __popcll(word);
+        }
+        if (seg_kept && lane == 0 && kept) atomicAdd(seg_kept + e.z, kept);
+    }
+}
+
+// Bits -> weights: theta = bit ? base : +0 inside masked tensors; the bf16 image of every tensor follows theta.
+__global__ __launch_bounds__(CL_THREADS) void mask_apply_kernel(float* __restrict__ p, const float* __restrict__ base,
+                                                                const unsigned long long* __restrict__ bits, int64_t nwords,
+                                                                const int4* __restrict__ table, int nchunks,
+                                                                const int* __restrict__ seg_kind,
+                                                                unsigned short* __restrict__ shadow_bf16) {
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const int4 e = table[c];
+        const int off = e.x, cnt = e.y, n4 = cnt >> 2;
+        const bool masked = seg_kind[e.z] == KIND_MASKED;        // workgroup-uniform
+        if (!masked && !shadow_bf16) continue;
+        const int64_t word0 = (int64_t)(off >> 6);
+        for (int q = threadIdx.x; q < n4; q += CL_THREADS) {
+            float4 P;
+            if (masked) {
+                const int64_t wi = word0 + (q >> 4);             // 16 float4 per word
+                const unsigned long long word = wi < nwords ? bits[wi] : 0ull;
+                const unsigned nib = (unsigned)(word >> ((q & 15) << 2)) & 15u;
+                const float4 B = reinterpret_cast<const float4*>(base + off)[q];
+                P = make_float4(nib & 1u ? B.x : 0.f, nib & 2u ? B.y : 0.f, nib & 4u ? B.z : 0.f, nib & 8u ? B.w : 0.f);
+                reinterpret_cast<float4*>(p + off)[q] = P;
+            } else {
+                P = reinterpret_cast<const float4*>(p + off)[q];
+            }
+            if (shadow_bf16) {
+                ushort4 o;
+                o.x = bf16_bits(P.x); o.y = bf16_bits(P.y); o.z = bf16_bits(P.z); o.w = bf16_bits(P.w);
+                reinterpret_cast<ushort4*>(shadow_bf16 + off)[q] = o;
+            }
+        }
+        for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) {
+            float P;
+            if (masked) {
+                const int64_t wi = word0 + (i >> 6);
+                const unsigned long long word = wi < nwords ? bits[wi] : 0ull;
+                P = (word >> (i & 63)) & 1ull ? base[off + i] : 0.f;
+                p[off + i] = P;
+            } else {
+                P = p[off + i];
+            }
+            if (shadow_bf16) shadow_bf16[off + i] = bf16_bits(P);
+        }
+    }
+}
+
 inline int cap_grid(int64_t work_items, int per_block) {
     int64_t b = (work_items + per_block - 1) / per_block;
     return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
@@ -1573,4 +1780,67 @@ extern "C" int ia_adamw_step_segmented_gem(float* theta, const float* grad, floa
                          beta1, beta2, eps, grad_scale, (unsigned short*)shadow_bf16};
     return run_step_gem(h, gt, seg_group, norm_state, skip_nonfinite, counters, refs, stride, ntasks, gem_state, gem_counters,
                         (hipStream_t)stream);
+}
+
+extern "C" int ia_adamw_step_segmented_masked(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq,
+                                              const int32_t* chunk_table, int nchunks, int32_t* seg_active, int32_t* seg_step,
+                                              int nseg, int all_active, float beta1, float beta2, float eps, float grad_scale,
+                                              void* shadow_bf16, const int32_t* seg_group, int ngroups, const float* group_lr,
+                                              const float* group_weight_decay, const float* norm_state, int skip_nonfinite,
+                                              int32_t* counters, const float* base, float* scores, const int32_t* seg_kind,
+                                              float threshold, ia_stream_t stream) {
+    if (!step_head_ok(theta, grad, exp_avg, exp_avg_sq, chunk_table, nchunks, seg_active, seg_step, nseg, shadow_bf16))
+        return IA_INVALID_VALUE;
+    if (ngroups < 1 || ngroups > IA_MAX_PARAM_GROUPS || !group_lr || !group_weight_decay || (ngroups > 1 && !seg_group) ||
+        (seg_group && !ia_is_aligned(seg_group, 4)))
+        return IA_INVALID_VALUE;
+    if ((norm_state == nullptr) != (counters == nullptr) || !base || !scores || !seg_kind || !ia_is_aligned(base, 16) ||
+        !ia_is_aligned(scores, 16) || !ia_is_aligned(seg_kind, 4))
+        return IA_INVALID_VALUE;
+    group_table gt = {};
+    gt.n = ngroups;
+    for (int k = 0; k < ngroups; ++k) { gt.lr[k] = group_lr[k]; gt.weight_decay[k] = group_weight_decay[k]; }
+    const step_head h = {theta, grad, exp_avg, exp_avg_sq, (const int4*)chunk_table, nchunks, seg_active, seg_step, nseg, all_active,
+                         beta1, beta2, eps, grad_scale, (unsigned short*)shadow_bf16};
+    hipStream_t st = (hipStream_t)stream;
+    if (h.all_active) {
+        if (!mark_all_active(h, st)) return IA_LAUNCH_FAILED;
+    } else if (!norm_state) {   // with norm_state, ia_grad_norm's first pass has set the flags
+        launch_activity(h, st);
+    }
+    auto kernel = norm_state ? adamw_seg_masked_kernel<true> : adamw_seg_masked_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(step_grid(h)), dim3(CL_THREADS), 0, st, h.theta, h.grad, h.exp_avg, h.exp_avg_sq, h.table,
+                       h.nchunks, h.seg_active, h.seg_step, gt, seg_group, h.b1, h.b2, h.eps, h.grad_scale, h.shadow, norm_state,
+                       skip_nonfinite, base, scores, seg_kind, threshold);
+    hipLaunchKernelGGL(seg_step_advance_masked_kernel, dim3((h.nseg + 255) / 256), dim3(256), 0, st, h.seg_active, h.seg_step,
+                       h.nseg, norm_state, skip_nonfinite, counters, seg_kind);
+    IA_RETURN_IF_LAUNCH_FAILED();
+    return IA_OK;
+}
+
+extern "C" int ia_mask_pack(const float* scores, const int32_t* chunk_table, int nchunks, const int32_t* seg_kind, int nseg,
+                            float threshold, uint64_t* bits, int64_t nwords, int32_t* seg_kept, ia_stream_t stream) {
+    if (!scores || !chunk_table || !seg_kind || !bits || nchunks <= 0 || nseg <= 0 || nwords <= 0) return IA_INVALID_VALUE;
+    if (!ia_is_aligned(scores, 16) || !ia_is_aligned(chunk_table, 16) || !ia_is_aligned(seg_kind, 4) || !ia_is_aligned(bits, 8) ||
+        (seg_kept && !ia_is_aligned(seg_kept, 4)))
+        return IA_INVALID_VALUE;
+    hipStream_t st = (hipStream_t)stream;
+    if (seg_kept && hipMemsetAsync(seg_kept, 0, (size_t)nseg * sizeof(int32_t), st) != hipSuccess) return IA_LAUNCH_FAILED;
+    hipLaunchKernelGGL(mask_pack_kernel, dim3(nchunks < 2048 ? nchunks : 2048), dim3(CL_THREADS), 0, st, scores,
+                       (const int4*)chunk_table, nchunks, seg_kind, threshold, (unsigned long long*)bits, nwords, seg_kept);
+    IA_RETURN_IF_LAUNCH_FAILED();
+    return IA_OK;
+}
+
+extern "C" int ia_mask_apply(float* theta, const float* base, const uint64_t* bits, int64_t nwords, const int32_t* chunk_table,
+                             int nchunks, const int32_t* seg_kind, int nseg, void* shadow_bf16, ia_stream_t stream) {
+    if (!theta || !base || !bits || !chunk_table || !seg_kind || nchunks <= 0 || nseg <= 0 || nwords <= 0) return IA_INVALID_VALUE;
+    if (!ia_is_aligned(theta, 16) || !ia_is_aligned(base, 16) || !ia_is_aligned(bits, 8) || !ia_is_aligned(chunk_table, 16) ||
+        !ia_is_aligned(seg_kind, 4) || (shadow_bf16 && !ia_is_aligned(shadow_bf16, 8)))
+        return IA_INVALID_VALUE;
+    hipLaunchKernelGGL(mask_apply_kernel, dim3(nchunks < 2048 ? nchunks : 2048), dim3(CL_THREADS), 0, (hipStream_t)stream, theta,
+                       base, (const unsigned long long*)bits, nwords, (const int4*)chunk_table, nchunks, seg_kind,
+                       (unsigned short*)shadow_bf16);
+    IA_RETURN_IF_LAUNCH_FAILED();
+    return IA_OK;
 }
