@@ -1009,6 +1009,8 @@ class FusedAdamW(torch.optim.Optimizer):
         and is counted.  `track_grad_norm=True`: measure the norms without clipping.  Norm, coefficient and counters stay
         on the device: `last_grad_norm`, `stats()`, `grad_norms()`.  With all three at their defaults the step is the plain
         ia_adamw_step_segmented.  `max_grad_norm` / `skip_nonfinite` live in param_groups[0] and are read per step, as lr is.
+        The entry points named here and below are reached through ia_adamw_step_segmented_grouped (one group or many), whose
+        operands select the same step; only masks and GEM have entry points of their own.
 
         `grad_exchange_dtype="bf16"` ("fp32 or bf16"): the data-parallel exchange all-reduces a bf16 image of the
         flat gradient (half the bytes over xGMI: 80 instead of 160 MB per step at 40 M trainable parameters); every rank
@@ -1232,117 +1234,63 @@ class FusedAdamW(torch.optim.Optimizer):
         return dict(zip(self.flat.names, self._seg_norm.tolist()))
 
     def _apply(self, scale, all_live=False, hyper=None):
+        """Dots (A-GEM / GEM: they also set the liveness flags) -> norm of the gradient the step consumes (when measured) ->
+        the step, all on the device.  One entry point per family of variants, for one or many parameter groups."""
         self.step_count += 1
         g = self.param_groups[0]
         lrs, wds = self._group_hyper() if hyper is None else hyper
-        f = self.flat
-        L = _lib.lib()
+        f, L, ptr, stream = self.flat, _lib.lib(), _lib.ptr, _lib.stream_ptr()
         max_norm, skip = g.get("max_grad_norm"), bool(g.get("skip_nonfinite", False))
-        si = self.path_integral
+        si, pb = self.path_integral, self.masks
         measured = max_norm is not None or skip or self.track_grad_norm
         penalised = si is not None and si.tasks_consolidated > 0
         all_live = bool(all_live) or penalised       # autograd on loss + surrogate gives every trainable tensor a gradient
-        nchunks, nseg = f.chunk_table.shape[0], len(f.entries)
-        b1, b2, eps = float(g["betas"][0]), float(g["betas"][1]), float(g["eps"])
-        agem = self.projection if self.projection is not None and self.projection.has_reference else None
+        scale, nchunks, nseg, n = float(scale), f.chunk_table.shape[0], len(f.entries), len(lrs)
+        proj = self.projection if self.projection is not None and self.projection.has_reference else None
+        gem, agem = (proj, None) if isinstance(proj, GEM) else (None, proj)
         if measured and self._seg_norm is None:
             self._seg_norm = torch.zeros(nseg, dtype=torch.float32, device=f.theta.device)
             self._norm_ws = torch.empty(L.ia_grad_norm_workspace_bytes(nchunks), dtype=torch.uint8, device=f.theta.device)
-        if isinstance(agem, GEM):
-            return self._apply_gem(agem, float(scale), all_live, lrs, wds, measured, max_norm, skip)
-        if agem is not None:       # dots (and the liveness flags) -> norm of the projected gradient -> projected step
-            ws = agem.workspace(nchunks)
-            st = L.ia_agem_dots(_lib.ptr(f.grad), _lib.ptr(agem.ref.flat), _lib.ptr(f.chunk_table), nchunks, nseg, float(scale),
-                                None if all_live else _lib.ptr(self.seg_active), _lib.ptr(agem.proj_state), _lib.ptr(ws),
-                                ws.numel(), _lib.stream_ptr())
-            _lib.check(st, "ia_agem_dots")
+        live = None if all_live else ptr(self.seg_active)
+        # what every step takes: head, betas, eps, scale, shadow, the group arrays, norm / skip / counters
+        common = (ptr(f.theta), ptr(f.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), ptr(f.chunk_table), nchunks,
+                  ptr(self.seg_active), ptr(self.seg_step), nseg, int(all_live), float(g["betas"][0]), float(g["betas"][1]),
+                  float(g["eps"]), scale, ptr(self.shadow), ptr(self.seg_group), n, (ctypes.c_float * n)(*lrs),
+                  (ctypes.c_float * n)(*wds), ptr(self._norm_state) if measured else None, int(skip),
+                  ptr(self._counters) if measured else None)
+        # ... and every norm: ia_grad_norm, or that of the projected gradient with the variant's rows behind it
+        norm = (ptr(f.grad), ptr(f.chunk_table), nchunks, ptr(f.seg_chunk_begin), nseg, scale,
+                0.0 if max_norm is None else float(max_norm), live, ptr(self._seg_norm), ptr(self._norm_state),
+                ptr(self._norm_ws), self._norm_ws.numel()) if measured else None
+        if gem is not None:
+            k, ws = len(gem.tasks()), gem.workspace(nchunks)
+            rows = (ptr(gem.refs), gem.stride, k, ptr(gem.state))
+            _lib.check(L.ia_gem_dots(ptr(f.grad), ptr(gem.refs), gem.stride, k, ptr(f.chunk_table), nchunks, nseg, scale, live, -1,
+                                     ptr(gem.sums), ptr(ws), ws.numel(), stream), "ia_gem_dots")
+            _lib.check(L.ia_gem_solve(ptr(gem.sums), ptr(gem.state), k, gem.memory_strength, gem.eps, stream), "ia_gem_solve")
             if measured:
-                st = L.ia_grad_norm_projected(
-                    _lib.ptr(f.grad), _lib.ptr(f.chunk_table), nchunks, _lib.ptr(f.seg_chunk_begin), nseg, float(scale),
-                    0.0 if max_norm is None else float(max_norm), None if all_live else _lib.ptr(self.seg_active),
-                    _lib.ptr(self._seg_norm), _lib.ptr(self._norm_state), _lib.ptr(self._norm_ws), self._norm_ws.numel(),
-                    _lib.ptr(agem.ref.flat), _lib.ptr(agem.proj_state), _lib.stream_ptr())
-                _lib.check(st, "ia_grad_norm_projected")
-        elif measured:
-            st = L.ia_grad_norm(
-                _lib.ptr(f.grad), _lib.ptr(f.chunk_table), nchunks, _lib.ptr(f.seg_chunk_begin), nseg, float(scale),
-                0.0 if max_norm is None else float(max_norm), None if all_live else _lib.ptr(self.seg_active),
-                _lib.ptr(self._seg_norm), _lib.ptr(self._norm_state), _lib.ptr(self._norm_ws), self._norm_ws.numel(),
-                _lib.stream_ptr())
-            _lib.check(st, "ia_grad_norm")
-        if self.masks is not None:
-            pb, n = self.masks, len(lrs)
-            st = L.ia_adamw_step_segmented_masked(
-                _lib.ptr(f.theta), _lib.ptr(f.grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), _lib.ptr(f.chunk_table),
-                nchunks, _lib.ptr(self.seg_active), _lib.ptr(self.seg_step), nseg, int(all_live), b1, b2, eps, float(scale),
-                _lib.ptr(self.shadow), _lib.ptr(self.seg_group), n, (ctypes.c_float * n)(*lrs), (ctypes.c_float * n)(*wds),
-                _lib.ptr(self._norm_state) if measured else None, int(skip), _lib.ptr(self._counters) if measured else None,
-                _lib.ptr(pb.base.flat), _lib.ptr(pb.scores.flat), _lib.ptr(pb.seg_kind), pb.threshold, _lib.stream_ptr())
-            _lib.check(st, "ia_adamw_step_segmented_masked")
+                _lib.check(L.ia_grad_norm_gem(*norm, *rows, stream), "ia_grad_norm_gem")
+            _lib.check(L.ia_adamw_step_segmented_gem(*common, *rows, ptr(gem.counters), stream), "ia_adamw_step_segmented_gem")
             return self._after_update()
-        head = (_lib.ptr(f.theta), _lib.ptr(f.grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), _lib.ptr(f.chunk_table),
-                nchunks, _lib.ptr(self.seg_active), _lib.ptr(self.seg_step), nseg, int(all_live))
-        if len(lrs) > 1:           # every kind of step through the one grouped entry point: the operands select the kernel
-            n = len(lrs)
-            st = L.ia_adamw_step_segmented_grouped(
-                *head, b1, b2, eps, float(scale), _lib.ptr(self.shadow), _lib.ptr(self.seg_group), n,
-                (ctypes.c_float * n)(*lrs), (ctypes.c_float * n)(*wds),
-                _lib.ptr(self._norm_state) if measured else None, int(skip), _lib.ptr(self._counters) if measured else None,
-                _lib.ptr(si.w.flat) if si is not None else None, _lib.ptr(si.omega.flat) if penalised else None,
-                _lib.ptr(si.theta_star.flat) if penalised else None, float(si.si_c) if si is not None else 0.0,
-                _lib.ptr(agem.ref.flat) if agem is not None else None, _lib.ptr(agem.proj_state) if agem is not None else None,
-                _lib.ptr(agem.proj_counters) if agem is not None else None, _lib.stream_ptr())
-            _lib.check(st, "ia_adamw_step_segmented_grouped")
-            return self._after_update()
-        head += (lrs[0], b1, b2, eps, wds[0], float(scale), _lib.ptr(self.shadow))
         if agem is not None:
-            st = L.ia_adamw_step_segmented_projected(
-                *head, _lib.ptr(self._norm_state) if measured else None, int(skip), _lib.ptr(self._counters) if measured else None,
-                _lib.ptr(agem.ref.flat), _lib.ptr(agem.proj_state), _lib.ptr(agem.proj_counters), _lib.stream_ptr())
-            _lib.check(st, "ia_adamw_step_segmented_projected")
-        elif si is not None:
-            st = L.ia_adamw_step_segmented_si(
-                *head, _lib.ptr(self._norm_state) if measured else None, int(skip), _lib.ptr(self._counters) if measured else None,
-                _lib.ptr(si.w.flat), _lib.ptr(si.omega.flat) if penalised else None,
-                _lib.ptr(si.theta_star.flat) if penalised else None, float(si.si_c), _lib.stream_ptr())
-            _lib.check(st, "ia_adamw_step_segmented_si")
+            ws = agem.workspace(nchunks)
+            _lib.check(L.ia_agem_dots(ptr(f.grad), ptr(agem.ref.flat), ptr(f.chunk_table), nchunks, nseg, scale, live,
+                                      ptr(agem.proj_state), ptr(ws), ws.numel(), stream), "ia_agem_dots")
+            if measured:
+                _lib.check(L.ia_grad_norm_projected(*norm, ptr(agem.ref.flat), ptr(agem.proj_state), stream),
+                           "ia_grad_norm_projected")
         elif measured:
-            st = L.ia_adamw_step_segmented_clipped(*head, _lib.ptr(self._norm_state), int(skip), _lib.ptr(self._counters),
-                                                   _lib.stream_ptr())
-            _lib.check(st, "ia_adamw_step_segmented_clipped")
-        else:
-            st = L.ia_adamw_step_segmented(*head, _lib.stream_ptr())
-            _lib.check(st, "ia_adamw_step_segmented")
-        self._after_update()
-
-    def _apply_gem(self, gem, scale, all_live, lrs, wds, measured, max_norm, skip):
-        """K dots (and the liveness flags) -> the program -> norm of the projected gradient -> projected step, all on the
-        device; one entry point for one or many parameter groups."""
-        f, L = self.flat, _lib.lib()
-        g = self.param_groups[0]
-        nchunks, nseg, k, n = f.chunk_table.shape[0], len(f.entries), len(gem.tasks()), len(lrs)
-        ws = gem.workspace(nchunks)
-        rows = (_lib.ptr(gem.refs), gem.stride, k, _lib.ptr(gem.state))
-        st = L.ia_gem_dots(_lib.ptr(f.grad), _lib.ptr(gem.refs), gem.stride, k, _lib.ptr(f.chunk_table), nchunks, nseg, scale,
-                           None if all_live else _lib.ptr(self.seg_active), -1, _lib.ptr(gem.sums), _lib.ptr(ws), ws.numel(),
-                           _lib.stream_ptr())
-        _lib.check(st, "ia_gem_dots")
-        st = L.ia_gem_solve(_lib.ptr(gem.sums), _lib.ptr(gem.state), k, gem.memory_strength, gem.eps, _lib.stream_ptr())
-        _lib.check(st, "ia_gem_solve")
-        if measured:
-            st = L.ia_grad_norm_gem(
-                _lib.ptr(f.grad), _lib.ptr(f.chunk_table), nchunks, _lib.ptr(f.seg_chunk_begin), nseg, scale,
-                0.0 if max_norm is None else float(max_norm), None if all_live else _lib.ptr(self.seg_active),
-                _lib.ptr(self._seg_norm), _lib.ptr(self._norm_state), _lib.ptr(self._norm_ws), self._norm_ws.numel(), *rows,
-                _lib.stream_ptr())
-            _lib.check(st, "ia_grad_norm_gem")
-        st = L.ia_adamw_step_segmented_gem(
-            _lib.ptr(f.theta), _lib.ptr(f.grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), _lib.ptr(f.chunk_table),
-            nchunks, _lib.ptr(self.seg_active), _lib.ptr(self.seg_step), nseg, int(all_live), float(g["betas"][0]),
-            float(g["betas"][1]), float(g["eps"]), scale, _lib.ptr(self.shadow), _lib.ptr(self.seg_group), n,
-            (ctypes.c_float * n)(*lrs), (ctypes.c_float * n)(*wds), _lib.ptr(self._norm_state) if measured else None, int(skip),
-            _lib.ptr(self._counters) if measured else None, *rows, _lib.ptr(gem.counters), _lib.stream_ptr())
-        _lib.check(st, "ia_adamw_step_segmented_gem")
+            _lib.check(L.ia_grad_norm(*norm, stream), "ia_grad_norm")
+        if pb is not None:
+            _lib.check(L.ia_adamw_step_segmented_masked(*common, ptr(pb.base.flat), ptr(pb.scores.flat), ptr(pb.seg_kind),
+                                                        pb.threshold, stream), "ia_adamw_step_segmented_masked")
+            return self._after_update()
+        # plain, clipped, SI or projected: the operands that are present select the variant
+        _lib.check(L.ia_adamw_step_segmented_grouped(
+            *common, ptr(si.w.flat) if si is not None else None, ptr(si.omega.flat) if penalised else None,
+            ptr(si.theta_star.flat) if penalised else None, float(si.si_c) if si is not None else 0.0,
+            ptr(agem.ref.flat) if agem is not None else None, ptr(agem.proj_state) if agem is not None else None,
+            ptr(agem.proj_counters) if agem is not None else None, stream), "ia_adamw_step_segmented_grouped")
         self._after_update()
 
     def _after_update(self):

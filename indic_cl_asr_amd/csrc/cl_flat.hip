@@ -5,29 +5,60 @@
 //   ia_cl_fisher_accumulate .. R/cl_baseline_ewc.py:245-255  F += mean(loss) * g^2
 //   ia_cl_abs_accumulate ..... R/cl_baseline_mas.py:267-270  omega += |g|
 //   ia_adamw_step ............ torch.optim.AdamW single-tensor update (R/cl_baseline.py:137 defaults)
-//   ia_grad_norm ............. torch.nn.utils.clip_grad_norm_'s norm and coefficient of the flat gradient, on the device
-//   ia_adamw_step_segmented_clipped .. the per-tensor AdamW on (g * grad_scale) * coef, skipped when the norm is not finite
-//   ia_adamw_step_segmented_si ....... the same step with Synaptic Intelligence's path integral w -= ge * (theta' - theta) and,
-//                              from the second task on, the surrogate's gradient 2c*omega*(theta-theta*) added after the clip
 //   ia_si_consolidate ........ end of a task: omega += max(0, w / ((theta-theta*)^2 + xi)), w = 0, theta* = theta
-//   ia_agem_dots ............. Averaged GEM (Chaudhry et al. 2019): g.r and r.r of the flat gradient and the episodic-memory
-//                              reference gradient, the decision g.r < 0 and alpha = g.r / r.r left on the device
-//   ia_grad_norm_projected ... ia_grad_norm of the gradient the projected step consumes (g - alpha * r when the flag is set)
-//   ia_adamw_step_segmented_projected .. the per-tensor AdamW on that gradient, r as one more operand of the launch
-//   ia_gem_dots, ia_gem_solve, ia_grad_norm_gem, ia_adamw_step_segmented_gem .. GEM (Lopez-Paz, Ranzato 2017): the K dots of the
-//                              flat gradient with one reference row per earlier task (and the rows' Gram matrix), the
-//                              bound-constrained quadratic program in fp64, and norm and AdamW on g * s + sum_k v_k * r_k
-//   ia_adamw_step_segmented_grouped .... any of the four segmented steps with lr and weight_decay per parameter group
-//                              (torch.optim.AdamW's param_groups): the same kernels, the group table by value in their arguments
-//   ia_adamw_step_segmented_masked, ia_mask_pack, ia_mask_apply .. Piggyback (Mallya, Davis, Lazebnik 2018): per tensor a kind --
-//                              masked (scores trained on g * base, theta = score >= threshold ? base : 0), free (the plain step),
-//                              frozen (untouched) --, the scores as one bit per weight, and the bits back to weights
+//   ia_mask_pack, ia_mask_apply .. Piggyback's scores as one bit per weight, and the bits back to weights
+//
+// The per-tensor ("segmented") AdamW step, ia_adamw_step_segmented*, is ONE kernel, ONE update rule and ONE host routine:
+//   adamw_seg_kernel<CLIP, Variant>   the chunk walker.  It owns the skip on a non-finite norm, the chunk loop, the refresh of
+//                              the bf16 image of a tensor that is dead (no gradient) or frozen, the group lookup, the fp64
+//                              bias-correction constants, the float4 body / scalar tail split and the stores of theta, the
+//                              moments and the bf16 image.
+//   adamw1_rn<TAIL>            the arithmetic of one element, every rounding written out.
+//   a variant                  a small struct passed by value: its extra operands and its rule for one access of W elements
+//                              (W = 4 in the body, 1 in the tail).  A rule forms the gradient AdamW consumes, calls adamw1_rn and
+//                              loads / stores what is its own:
+//       plain_step             consumed_step<scaled_grad>: g * grad_scale [* coef]           ia_adamw_step_segmented[_clipped]
+//       si_step<PEN>           Synaptic Intelligence: [+ 2c*omega*(theta-theta*)] after the clip, and the path integral
+//                              w -= ge * (theta' - theta)                                     ia_adamw_step_segmented_si
+//       agem_step              consumed_step<agem_source>: g * s - alpha * r when g.r < 0     ia_adamw_step_segmented_projected
+//       gem_step               consumed_step<gem_source>: g * s + sum_k v_k * r_k             ia_adamw_step_segmented_gem
+//       masked_step            Piggyback, per tensor a kind: masked (the scores are trained on g * base and
+//                              theta = score >= threshold ? base : 0), free (the plain rule), frozen    ia_adamw_step_segmented_masked
+//                              ia_adamw_step_segmented_grouped is the first four with lr and weight_decay per parameter group.
+//   consumed_norm_kernel<Source>   the clip norm of the gradient a consumed_step consumes, from the SAME gradient functor
+//                              (ia_grad_norm_projected, ia_grad_norm_gem); ia_grad_norm measures the raw gradient in the
+//                              liveness pass.  grad_norm_finish_kernel adds the chunk sums of all three in a fixed order.
+//   seg_step_advance_kernel    the per-tensor step counters and the clip / skip / projected / unsolved counters of every variant.
+//   run_step                   liveness (activity pass or mark-all), the walker, the advance: three launches for every variant.
+// The dots of A-GEM (ia_agem_dots) and GEM (ia_gem_dots, ia_gem_solve) run before their step and leave the decision on the device.
 // All are HBM-streaming kernels: 16-byte accesses, grid capped at 2048 workgroups, fp32 math.
 #include "ia_common.h"
+#include <type_traits>
 
 namespace {
 constexpr int CL_THREADS = 256;
 constexpr int CL_CHUNK = 4096;  // elements per chunk-table entry (host builds the table with this size)
+
+__device__ __forceinline__ unsigned short bf16_bits(float x) {
+    __hip_bfloat16 a = __float2bfloat16(x);
+    return *reinterpret_cast<unsigned short*>(&a);
+}
+
+__device__ __forceinline__ ushort4 bf16_bits(float4 x) {
+    ushort4 o;
+    o.x = bf16_bits(x.x); o.y = bf16_bits(x.y); o.z = bf16_bits(x.z); o.w = bf16_bits(x.w);
+    return o;
+}
+
+// W floats moved as one access: W = 4 in a chunk's float4 body (16 bytes), W = 1 in its tail
+template <int W>
+struct alignas(4 * W) vecf {
+    float a[W];
+    __device__ __forceinline__ float& operator[](int j) { return a[j]; }
+    __device__ __forceinline__ float operator[](int j) const { return a[j]; }
+};
+template <int W> __device__ __forceinline__ vecf<W> ldv(const float* p, int64_t at) { return *reinterpret_cast<const vecf<W>*>(p + at); }
+template <int W> __device__ __forceinline__ void stv(float* p, int64_t at, const vecf<W>& x) { *reinterpret_cast<vecf<W>*>(p + at) = x; }
 
 __device__ __forceinline__ float block_sum(float v, float* sh) {
     v = ia_wave_sum_dpp(v);
@@ -100,6 +131,7 @@ __global__ __launch_bounds__(CL_THREADS) void cl_accumulate_kernel(float* __rest
             acc[i] += (MODE == 0) ? s * g[i] * g[i] : fabsf(g[i]);
 }
 
+// The unsegmented step (ia_adamw_step) only; the segmented steps use adamw1_rn
 __device__ __forceinline__ void adamw1(float& p, float g, float& m, float& v, float lr, float b1, float b2, float eps,
                                        float wd, float step_size, float inv_bc2_sqrt) {
     p *= (1.f - lr * wd);
@@ -127,21 +159,14 @@ __global__ __launch_bounds__(CL_THREADS) void adamw_kernel(float* __restrict__ p
         reinterpret_cast<float4*>(p)[q] = P;
         reinterpret_cast<float4*>(m)[q] = M;
         reinterpret_cast<float4*>(v)[q] = V;
-        if (shadow_bf16) {
-            __hip_bfloat16 a = __float2bfloat16(P.x), b = __float2bfloat16(P.y), c = __float2bfloat16(P.z),
-                           d = __float2bfloat16(P.w);
-            ushort4 o;
-            o.x = *reinterpret_cast<unsigned short*>(&a); o.y = *reinterpret_cast<unsigned short*>(&b);
-            o.z = *reinterpret_cast<unsigned short*>(&c); o.w = *reinterpret_cast<unsigned short*>(&d);
-            reinterpret_cast<ushort4*>(shadow_bf16)[q] = o;
-        }
+        if (shadow_bf16) reinterpret_cast<ushort4*>(shadow_bf16)[q] = bf16_bits(P);
     }
     if (blockIdx.x == 0)
         for (int64_t i = (n4 << 2) + threadIdx.x; i < n; i += CL_THREADS) {
             float P = p[i], M = m[i], V = v[i];
             adamw1(P, g[i] * grad_scale, M, V, lr, b1, b2, eps, wd, step_size, inv_bc2_sqrt);
             p[i] = P; m[i] = M; v[i] = V;
-            if (shadow_bf16) { __hip_bfloat16 a = __float2bfloat16(P); shadow_bf16[i] = *reinterpret_cast<unsigned short*>(&a); }
+            if (shadow_bf16) shadow_bf16[i] = bf16_bits(P);
         }
 }
 
@@ -188,12 +213,16 @@ __global__ __launch_bounds__(CL_THREADS) void seg_activity_kernel(const float* _
 // Second half: ONE workgroup of GN_THREADS adds the chunk sums in fp64 in a fixed order -- wave w takes segments w, w + 16,
 // ...; its lanes stride over the segment's chunks (contiguous in the table: seg_chunk_begin), then a butterfly over the
 // lanes; the wave keeps a running fp64 total of its segments and thread 0 adds the 16 wave totals in order.
-// norm_state = {total_norm, coef, non-finite flag (0 / 1), max_norm}.
+// norm_state = {total_norm, coef, non-finite flag (0 / 1), max_norm}.  `projected` (NULL, proj_state + 3 or gem_state +
+// GEM_VIOLATED): a projected gradient already carries grad_scale, so the roots are scaled only when the step did not project.
 constexpr int GN_THREADS = 1024;
-__device__ __forceinline__ void grad_norm_finish(const float* __restrict__ chunk_sumsq, const int* __restrict__ seg_chunk_begin,
-                                                 int nseg, float abs_scale, float max_norm, float* __restrict__ seg_norm,
-                                                 float* __restrict__ norm_state) {
+__global__ __launch_bounds__(GN_THREADS) void grad_norm_finish_kernel(const float* __restrict__ chunk_sumsq,
+                                                                      const int* __restrict__ seg_chunk_begin, int nseg,
+                                                                      float abs_scale, float max_norm,
+                                                                      float* __restrict__ seg_norm, float* __restrict__ norm_state,
+                                                                      const float* __restrict__ projected) {
     __shared__ double sh_w[GN_THREADS / 64];
+    if (projected && projected[0] != 0.f) abs_scale = 1.f;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double wave_total = 0.0;
     for (int s = wave; s < nseg; s += GN_THREADS / 64) {
@@ -223,13 +252,6 @@ __device__ __forceinline__ void grad_norm_finish(const float* __restrict__ chunk
     }
 }
 
-__global__ __launch_bounds__(GN_THREADS) void grad_norm_finish_kernel(const float* __restrict__ chunk_sumsq,
-                                                                      const int* __restrict__ seg_chunk_begin, int nseg,
-                                                                      float abs_scale, float max_norm,
-                                                                      float* __restrict__ seg_norm, float* __restrict__ norm_state) {
-    grad_norm_finish(chunk_sumsq, seg_chunk_begin, nseg, abs_scale, max_norm, seg_norm, norm_state);
-}
-
 // Parameter groups: learning rate and weight decay per group, by value in the kernel arguments (the host fills them from two host
 // arrays at every call: no copy, no staging buffer).  seg_group[k] is tensor k's group (NULL: group 0), so the lookup is
 // workgroup-uniform per chunk: a scalar load of the index and two scalar loads from the argument segment.  It has to sit INSIDE
@@ -245,99 +267,101 @@ __device__ __forceinline__ int group_of(const int* __restrict__ seg_group, int s
     return gi < 0 ? 0 : (gi >= n ? n - 1 : gi);      // the argument segment is never indexed outside the table
 }
 
-// CLIP: the gradient is (g * grad_scale) * coef with coef = norm_state[1] read from the device, each product rounded to
-// fp32 on its own (never fused into the moment update), so that with grad_scale == 1 it is torch's g.mul_(coef) bit for
-// bit; when norm_state[2] flags a non-finite norm and skip_nonfinite is set the launch writes nothing at all.
-template <bool CLIP>
-__device__ __forceinline__ float eff_grad(float g, float grad_scale, float coef) {
-    if constexpr (!CLIP) {
-        return g * grad_scale;
-    } else {
-#pragma clang fp contract(off)
-        const float gs = g * grad_scale;
-        return gs * coef;
-    }
-}
-
-template <bool CLIP>
-__global__ __launch_bounds__(CL_THREADS) void adamw_seg_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                               float* __restrict__ m, float* __restrict__ v,
-                                                               const int4* __restrict__ table, int nchunks,
-                                                               const int* __restrict__ seg_active,
-                                                               const int* __restrict__ seg_step, const group_table groups,
-                                                               const int* __restrict__ seg_group, float b1, float b2, float eps,
-                                                               float grad_scale,
-                                                               unsigned short* __restrict__ shadow_bf16,
-                                                               const float* __restrict__ norm_state, int skip_nonfinite) {
-    __shared__ float sh_c[2];
-    float coef = 1.f;
-    if (CLIP) {
-        if (skip_nonfinite && norm_state[2] != 0.f) return;
-        coef = norm_state[1];
-    }
-    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
-        const int4 e = table[c];
-        if (!seg_active[e.z]) {           // workgroup-uniform: untouched tensor -- only keep its bf16 image in step
-            if (shadow_bf16)
-                for (int i = threadIdx.x; i < e.y; i += CL_THREADS) {
-                    __hip_bfloat16 a = __float2bfloat16(p[e.x + i]);
-                    shadow_bf16[e.x + i] = *reinterpret_cast<unsigned short*>(&a);
-                }
-            continue;
-        }
-        const int gi = group_of(seg_group, e.z, groups.n);      // workgroup-uniform
-        const float lr = groups.lr[gi], wd = groups.weight_decay[gi];
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const double step = (double)(seg_step[e.z] + 1);
-            sh_c[0] = (float)((double)lr / (1.0 - pow((double)b1, step)));
-            sh_c[1] = (float)(1.0 / sqrt(1.0 - pow((double)b2, step)));
-        }
-        __syncthreads();
-        const float step_size = sh_c[0], inv_bc2_sqrt = sh_c[1];
-        const int off = e.x, cnt = e.y, n4 = cnt >> 2;
-        for (int q = threadIdx.x; q < n4; q += CL_THREADS) {
-            float4 P = reinterpret_cast<float4*>(p + off)[q];
-            const float4 G = reinterpret_cast<const float4*>(g + off)[q];
-            float4 M = reinterpret_cast<float4*>(m + off)[q];
-            float4 V = reinterpret_cast<float4*>(v + off)[q];
-            adamw1(P.x, eff_grad<CLIP>(G.x, grad_scale, coef), M.x, V.x, lr, b1, b2, eps, wd, step_size, inv_bc2_sqrt);
-            adamw1(P.y, eff_grad<CLIP>(G.y, grad_scale, coef), M.y, V.y, lr, b1, b2, eps, wd, step_size, inv_bc2_sqrt);
-            adamw1(P.z, eff_grad<CLIP>(G.z, grad_scale, coef), M.z, V.z, lr, b1, b2, eps, wd, step_size, inv_bc2_sqrt);
-            adamw1(P.w, eff_grad<CLIP>(G.w, grad_scale, coef), M.w, V.w, lr, b1, b2, eps, wd, step_size, inv_bc2_sqrt);
-            reinterpret_cast<float4*>(p + off)[q] = P;
-            reinterpret_cast<float4*>(m + off)[q] = M;
-            reinterpret_cast<float4*>(v + off)[q] = V;
-            if (shadow_bf16) {
-                __hip_bfloat16 a = __float2bfloat16(P.x), b = __float2bfloat16(P.y), cc = __float2bfloat16(P.z),
-                               d = __float2bfloat16(P.w);
-                ushort4 o;
-                o.x = *reinterpret_cast<unsigned short*>(&a); o.y = *reinterpret_cast<unsigned short*>(&b);
-                o.z = *reinterpret_cast<unsigned short*>(&cc); o.w = *reinterpret_cast<unsigned short*>(&d);
-                reinterpret_cast<ushort4*>(shadow_bf16 + off)[q] = o;
-            }
-        }
-        for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) {
-            float P = p[off + i], M = m[off + i], V = v[off + i];
-            adamw1(P, eff_grad<CLIP>(g[off + i], grad_scale, coef), M, V, lr, b1, b2, eps, wd, step_size, inv_bc2_sqrt);
-            p[off + i] = P; m[off + i] = M; v[off + i] = V;
-            if (shadow_bf16) { __hip_bfloat16 a = __float2bfloat16(P); shadow_bf16[off + i] = *reinterpret_cast<unsigned short*>(&a); }
-        }
-    }
-}
-
-// ---- Synaptic Intelligence (Zenke, Poole, Ganguli 2017) inside the AdamW launch.  Per element of a live tensor:
-//   ge = g * grad_scale                      the task gradient (before the clip coefficient, without the penalty)
-//   G  = ge [* coef] [+ (c2 * omega) * (theta - theta_star)]      the gradient AdamW consumes (PEN: a penalty is attached)
-//   theta', m, v = adamw1(theta, G, ...)
-//   w  = w - ge * (theta' - theta)           the path integral, on the fp32 weight that is stored (weight decay included)
-// Every product, difference and sum of these lines is rounded to fp32 on its own (contraction off), so that one torch op
-// per rounding reproduces G and w bit for bit; adamw1 itself is the routine of the plain kernel.
+// ---- the update rule of every segmented step.  Each product, difference and sum that forms the gradient AdamW consumes is
+// rounded to fp32 on its own (contraction off), so that one torch op per rounding reproduces it bit for bit.
 __device__ __forceinline__ float mul_rn(float a, float b) {
 #pragma clang fp contract(off)
     return a * b;
 }
 
+__device__ __forceinline__ float sub_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
+
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+
+struct chunk_consts {   // workgroup-uniform operands of one chunk
+    float decay, omb1, b2, omb2, eps, step_size, inv_bc2_sqrt, grad_scale, coef;
+};
+
+// CLIP: ge = g * grad_scale is multiplied by coef = norm_state[1], read from the device: two products, never fused with each
+// other or into the moment update, so that with grad_scale == 1 the gradient is torch's g.mul_(coef) bit for bit.
+template <bool CLIP>
+__device__ __forceinline__ float eff_grad(float ge, const chunk_consts& k) {
+    return CLIP ? mul_rn(ge, k.coef) : ge;
+}
+
+// torch.optim.AdamW's single-tensor update of one element, the definition for every segmented step:
+//   v = b2 * v + (1 - b2) * g * g       as fma(g, (1-b2)*g, b2*v) in a chunk's float4 body and as fma(b2, v, ((1-b2)*g)*g) in its
+//                                       scalar tail (TAIL): an element is in the body under every variant or in the tail under
+//                                       every variant, so all of them move it alike
+//   m = m + (1 - b1) * (g - m)          one fma on the separately rounded difference
+//   p = decay * p - step_size * (m / (sqrt(v) * inv_bc2_sqrt + eps))     decay = 1 - lr * wd; denominator and result one fma each
+// Nothing here is left to the compiler's contraction, which chose differently from kernel to kernel.
+template <bool TAIL>
+__device__ __forceinline__ void adamw1_rn(float& p, float g, float& m, float& v, float decay, const chunk_consts& k) {
+#pragma clang fp contract(off)
+    const float t = k.omb2 * g;
+    if constexpr (TAIL) {
+        const float tg = t * g;
+        v = __builtin_fmaf(k.b2, v, tg);
+    } else {
+        const float vb = k.b2 * v;
+        v = __builtin_fmaf(g, t, vb);
+    }
+    const float gm = g - m;
+    m = __builtin_fmaf(k.omb1, gm, m);
+    const float denom = __builtin_fmaf(k.inv_bc2_sqrt, sqrtf(v), k.eps);
+    const float q = m / denom;
+    const float u = k.step_size * q;
+    p = __builtin_fmaf(decay, p, -u);
+}
+
+// A gradient functor maps W raw gradient elements at flat offset `at` to the gradient before the clip.  Its source is what the
+// host passes; begin() reads the launch-uniform decision from the device once per workgroup.  The plain gradient: g * grad_scale.
+struct scaled_grad {
+    __device__ __forceinline__ scaled_grad begin() const { return *this; }
+    __device__ __forceinline__ bool projecting() const { return false; }
+    template <int W>
+    __device__ __forceinline__ vecf<W> operator()(const vecf<W>& G, int64_t at, float grad_scale) const {
+        vecf<W> a;
+#pragma unroll
+        for (int j = 0; j < W; ++j) a[j] = mul_rn(G[j], grad_scale);
+        return a;
+    }
+};
+
+// The rule of the steps that only change the gradient (plain, A-GEM, GEM): AdamW on grad(g) [* coef]
+template <class Grad>
+struct consumed_rule {
+    Grad grad;
+    static constexpr bool reads_theta = true;
+    template <bool CLIP, int W>
+    __device__ __forceinline__ void apply(vecf<W>& P, const vecf<W>& G, vecf<W>& M, vecf<W>& V, int64_t at,
+                                          const chunk_consts& k) const {
+        const vecf<W> E = grad(G, at, k.grad_scale);
+#pragma unroll
+        for (int j = 0; j < W; ++j) adamw1_rn<W == 1>(P[j], eff_grad<CLIP>(E[j], k), M[j], V[j], k.decay, k);
+    }
+};
+
+template <class Source>
+struct consumed_step {
+    Source src;
+    __device__ __forceinline__ auto begin() const { return consumed_rule<decltype(src.begin())>{src.begin()}; }
+};
+using plain_step = consumed_step<scaled_grad>;
+
+// ---- Synaptic Intelligence (Zenke, Poole, Ganguli 2017) inside the AdamW launch.  Per element of a live tensor:
+//   ge = g * grad_scale                      the task gradient (before the clip coefficient, without the penalty)
+//   G  = ge [* coef] [+ (c2 * omega) * (theta - theta_star)]      the gradient AdamW consumes (PEN: a penalty is attached)
+//   theta', m, v = adamw1_rn(theta, G, ...)
+//   w  = w - ge * (theta' - theta)           the path integral, on the fp32 weight that is stored (weight decay included)
+// A dead tensor's w stays.
 template <bool PEN>
 __device__ __forceinline__ float si_grad(float eff, float theta, float omega, float star, float c2) {
 #pragma clang fp contract(off)
@@ -358,122 +382,25 @@ __device__ __forceinline__ float si_path(float w, float ge, float p_new, float p
     return w - t;
 }
 
-// adamw1 with every rounding written out.  Left to the compiler, the contraction of adamw1 depends on the code around it: in
-// adamw_seg_kernel (both instantiations) it comes out as below, the second moment as fma(g, (1-b2)*g, b2*v) in the float4 body
-// and as fma(b2, v, ((1-b2)*g)*g) in the scalar tail; inside this kernel the same source lost some of the fmas.  The SI step has
-// to move the weights exactly as the plain step does on the same gradient (an element is in the body of both kernels or in the
-// tail of both), so it restates that arithmetic with explicit fmas; tests/test_si_gpu.py compares the two bit for bit.
-template <bool TAIL>
-__device__ __forceinline__ void adamw1_rn(float& p, float g, float& m, float& v, float decay, float omb1, float b2, float omb2,
-                                          float eps, float step_size, float inv_bc2_sqrt) {
-#pragma clang fp contract(off)
-    const float t = omb2 * g;
-    if constexpr (TAIL) {
-        const float tg = t * g;
-        v = __builtin_fmaf(b2, v, tg);
-    } else {
-        const float vb = b2 * v;
-        v = __builtin_fmaf(g, t, vb);
+template <bool PEN>
+struct si_step {
+    float* path_w; const float* omega; const float* star; float c2;
+    static constexpr bool reads_theta = true;
+    __device__ __forceinline__ si_step begin() const { return *this; }
+    template <bool CLIP, int W>
+    __device__ __forceinline__ void apply(vecf<W>& P, const vecf<W>& G, vecf<W>& M, vecf<W>& V, int64_t at,
+                                          const chunk_consts& k) const {
+        vecf<W> Pw = ldv<W>(path_w, at), O = {}, S = {};
+        if constexpr (PEN) { O = ldv<W>(omega, at); S = ldv<W>(star, at); }
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            const float ge = mul_rn(G[j], k.grad_scale), p_old = P[j];
+            adamw1_rn<W == 1>(P[j], si_grad<PEN>(eff_grad<CLIP>(ge, k), p_old, O[j], S[j], c2), M[j], V[j], k.decay, k);
+            Pw[j] = si_path(Pw[j], ge, P[j], p_old);
+        }
+        stv<W>(path_w, at, Pw);
     }
-    const float gm = g - m;
-    m = __builtin_fmaf(omb1, gm, m);
-    const float denom = __builtin_fmaf(inv_bc2_sqrt, sqrtf(v), eps);
-    const float q = m / denom;
-    const float u = step_size * q;
-    p = __builtin_fmaf(decay, p, -u);
-}
-
-struct si_consts {   // workgroup-uniform operands of one chunk
-    float decay, omb1, b2, omb2, eps, step_size, inv_bc2_sqrt, grad_scale, coef, c2;
 };
-
-template <bool CLIP, bool PEN, bool TAIL>
-__device__ __forceinline__ void adamw_si1(float& p, float g, float& m, float& v, float& w, float omega, float star,
-                                          const si_consts& k) {
-    const float ge = mul_rn(g, k.grad_scale);
-    const float eff = CLIP ? mul_rn(ge, k.coef) : ge;           // eff_grad<true>'s two products
-    const float p_old = p;
-    adamw1_rn<TAIL>(p, si_grad<PEN>(eff, p_old, omega, star, k.c2), m, v, k.decay, k.omb1, k.b2, k.omb2, k.eps, k.step_size,
-                    k.inv_bc2_sqrt);
-    w = si_path(w, ge, p, p_old);
-}
-
-template <bool CLIP, bool PEN>
-__global__ __launch_bounds__(CL_THREADS) void adamw_seg_si_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                                  float* __restrict__ m, float* __restrict__ v,
-                                                                  const int4* __restrict__ table, int nchunks,
-                                                                  const int* __restrict__ seg_active,
-                                                                  const int* __restrict__ seg_step, const group_table groups,
-                                                                  const int* __restrict__ seg_group, float b1, float b2, float eps,
-                                                                  float grad_scale,
-                                                                  unsigned short* __restrict__ shadow_bf16,
-                                                                  const float* __restrict__ norm_state, int skip_nonfinite,
-                                                                  float* __restrict__ path_w, const float* __restrict__ omega,
-                                                                  const float* __restrict__ star, float c2) {
-    __shared__ float sh_c[2];
-    float coef = 1.f;
-    if (CLIP) {
-        if (skip_nonfinite && norm_state[2] != 0.f) return;
-        coef = norm_state[1];
-    }
-    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
-        const int4 e = table[c];
-        if (!seg_active[e.z]) {           // workgroup-uniform: untouched tensor -- its w stays, only the bf16 image is kept in step
-            if (shadow_bf16)
-                for (int i = threadIdx.x; i < e.y; i += CL_THREADS) {
-                    __hip_bfloat16 a = __float2bfloat16(p[e.x + i]);
-                    shadow_bf16[e.x + i] = *reinterpret_cast<unsigned short*>(&a);
-                }
-            continue;
-        }
-        const int gi = group_of(seg_group, e.z, groups.n);      // workgroup-uniform
-        const float lr = groups.lr[gi], wd = groups.weight_decay[gi];
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const double step = (double)(seg_step[e.z] + 1);
-            sh_c[0] = (float)((double)lr / (1.0 - pow((double)b1, step)));
-            sh_c[1] = (float)(1.0 / sqrt(1.0 - pow((double)b2, step)));
-        }
-        __syncthreads();
-        const si_consts k = {__builtin_fmaf(-lr, wd, 1.f), 1.f - b1, b2, 1.f - b2, eps, sh_c[0], sh_c[1], grad_scale, coef, c2};
-        const int off = e.x, cnt = e.y, n4 = cnt >> 2;
-        for (int q = threadIdx.x; q < n4; q += CL_THREADS) {
-            float4 P = reinterpret_cast<float4*>(p + off)[q];
-            const float4 G = reinterpret_cast<const float4*>(g + off)[q];
-            float4 M = reinterpret_cast<float4*>(m + off)[q];
-            float4 V = reinterpret_cast<float4*>(v + off)[q];
-            float4 W = reinterpret_cast<float4*>(path_w + off)[q];
-            float4 O = make_float4(0.f, 0.f, 0.f, 0.f), S = O;
-            if constexpr (PEN) {
-                O = reinterpret_cast<const float4*>(omega + off)[q];
-                S = reinterpret_cast<const float4*>(star + off)[q];
-            }
-            adamw_si1<CLIP, PEN, false>(P.x, G.x, M.x, V.x, W.x, O.x, S.x, k);
-            adamw_si1<CLIP, PEN, false>(P.y, G.y, M.y, V.y, W.y, O.y, S.y, k);
-            adamw_si1<CLIP, PEN, false>(P.z, G.z, M.z, V.z, W.z, O.z, S.z, k);
-            adamw_si1<CLIP, PEN, false>(P.w, G.w, M.w, V.w, W.w, O.w, S.w, k);
-            reinterpret_cast<float4*>(p + off)[q] = P;
-            reinterpret_cast<float4*>(m + off)[q] = M;
-            reinterpret_cast<float4*>(v + off)[q] = V;
-            reinterpret_cast<float4*>(path_w + off)[q] = W;
-            if (shadow_bf16) {
-                __hip_bfloat16 a = __float2bfloat16(P.x), b = __float2bfloat16(P.y), cc = __float2bfloat16(P.z),
-                               d = __float2bfloat16(P.w);
-                ushort4 o;
-                o.x = *reinterpret_cast<unsigned short*>(&a); o.y = *reinterpret_cast<unsigned short*>(&b);
-                o.z = *reinterpret_cast<unsigned short*>(&cc); o.w = *reinterpret_cast<unsigned short*>(&d);
-                reinterpret_cast<ushort4*>(shadow_bf16 + off)[q] = o;
-            }
-        }
-        for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) {
-            float P = p[off + i], M = m[off + i], V = v[off + i], W = path_w[off + i];
-            const float O = PEN ? omega[off + i] : 0.f, S = PEN ? star[off + i] : 0.f;
-            adamw_si1<CLIP, PEN, true>(P, g[off + i], M, V, W, O, S, k);
-            p[off + i] = P; m[off + i] = M; v[off + i] = V; path_w[off + i] = W;
-            if (shadow_bf16) { __hip_bfloat16 a = __float2bfloat16(P); shadow_bf16[off + i] = *reinterpret_cast<unsigned short*>(&a); }
-        }
-    }
-}
 
 // End of a task: omega += max(0, w / ((theta - theta_star)^2 + xi)); w = 0; theta_star = theta.  One pass, 28 B per element.
 __device__ __forceinline__ void si_consolidate1(float t, float& s, float& w, float& o, float xi) {
@@ -515,7 +442,8 @@ __global__ __launch_bounds__(CL_THREADS) void si_consolidate_kernel(const float*
 //                        seg_activity_kernel<true>) in chunk_dots[c] and sets the liveness flags from g as that kernel does
 //   agem_finish_kernel   one workgroup adds the partials in fp64 (thread t takes chunks t, t + 1024, ...; butterfly over the
 //                        lanes; thread 0 adds the 16 wave totals in order) and writes proj_state = {dot, ref_sq, alpha, violated}
-//   proj_norm_kernel     the chunk sums of squares of the gradient the step will consume, branching on the device flag
+//   consumed_norm_kernel<agem_source>   the chunk sums of squares of the gradient the step will consume, branching on the
+//                        device flag
 __global__ __launch_bounds__(CL_THREADS) void agem_dots_kernel(const float* __restrict__ g, const float* __restrict__ r,
                                                                const int4* __restrict__ table, int nchunks,
                                                                int* __restrict__ seg_active, float2* __restrict__ chunk_dots) {
@@ -572,194 +500,30 @@ __global__ __launch_bounds__(GN_THREADS) void agem_finish_kernel(const float2* _
     }
 }
 
-__device__ __forceinline__ float sub_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a - b;
-}
-
-// (g * grad_scale) - (alpha * r): both products and the difference rounded to fp32 on their own
-__device__ __forceinline__ float proj_grad(float g, float r, float grad_scale, float alpha) {
-    return sub_rn(mul_rn(g, grad_scale), mul_rn(alpha, r));
-}
-
-// seg_activity_kernel<true>'s sum as the compiler emits it there, written out so that an un-projected step measures the norm
-// ia_grad_norm measures bit for bit (tests/test_agem_gpu.py compares them): in the float4 body four separately rounded squares
-// added left to right and then to the running sum, in the scalar tail one fma.
-__device__ __forceinline__ float sumsq4_rn(float ss, float a, float b, float c, float d) {
-#pragma clang fp contract(off)
-    const float aa = a * a, bb = b * b, cc = c * c, dd = d * d;
-    const float t = ((aa + bb) + cc) + dd;
-    return ss + t;
-}
-
-// violated == 0: the raw sum of g^2 over every chunk, as ia_grad_norm's first pass.  violated == 1: the sum of G^2 with
-// G = g * grad_scale - alpha * r over the chunks of live tensors; a dead tensor's chunk stores 0 (its .grad is None for torch's
-// clip norm) and is not read.  seg_active is read only (NULL: every tensor live): agem_dots_kernel has set it.
-__global__ __launch_bounds__(CL_THREADS) void proj_norm_kernel(const float* __restrict__ g, const float* __restrict__ r,
-                                                               const int4* __restrict__ table, int nchunks,
-                                                               const int* __restrict__ seg_active,
-                                                               const float* __restrict__ proj_state, float grad_scale,
-                                                               float* __restrict__ chunk_sumsq) {
-    __shared__ float sh[CL_THREADS / 64];
-    const bool violated = proj_state[3] != 0.f;
-    const float alpha = proj_state[2];
-    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
-        const int4 e = table[c];
-        const int off = e.x, cnt = e.y, n4 = cnt >> 2;
-        float ss = 0.f;
-        if (!violated) {
-            for (int q = threadIdx.x; q < n4; q += CL_THREADS) {
-                const float4 x = reinterpret_cast<const float4*>(g + off)[q];
-                ss = sumsq4_rn(ss, x.x, x.y, x.z, x.w);
-            }
-            for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) ss = __builtin_fmaf(g[off + i], g[off + i], ss);
-        } else if (!seg_active || seg_active[e.z]) {
-            for (int q = threadIdx.x; q < n4; q += CL_THREADS) {
-                const float4 x = reinterpret_cast<const float4*>(g + off)[q];
-                const float4 y = reinterpret_cast<const float4*>(r + off)[q];
-                ss = sumsq4_rn(ss, proj_grad(x.x, y.x, grad_scale, alpha), proj_grad(x.y, y.y, grad_scale, alpha),
-                               proj_grad(x.z, y.z, grad_scale, alpha), proj_grad(x.w, y.w, grad_scale, alpha));
-            }
-            for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) {
-                const float G = proj_grad(g[off + i], r[off + i], grad_scale, alpha);
-                ss = __builtin_fmaf(G, G, ss);
-            }
+// (g * grad_scale) - (alpha * r) when the step projects: both products and the difference rounded to fp32 on their own.  An
+// un-projected step does not read r.  Liveness is that of the task gradient g, whatever r holds.
+struct agem_grad {
+    const float* ref; float alpha; bool violated;      // violated: uniform over the launch
+    __device__ __forceinline__ bool projecting() const { return violated; }
+    template <int W>
+    __device__ __forceinline__ vecf<W> operator()(const vecf<W>& G, int64_t at, float grad_scale) const {
+        vecf<W> a, R = {};
+        if (violated) R = ldv<W>(ref, at);
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            const float ge = mul_rn(G[j], grad_scale);
+            a[j] = violated ? sub_rn(ge, mul_rn(alpha, R[j])) : ge;
         }
-        const float t = block_sum(ss, sh);
-        if (threadIdx.x == 0) chunk_sumsq[c] = t;
+        return a;
     }
-}
+};
 
-// ... the projected gradient already carries grad_scale: the root is scaled only when the step did not project
-__global__ __launch_bounds__(GN_THREADS) void grad_norm_finish_projected_kernel(const float* __restrict__ chunk_sumsq,
-                                                                                const int* __restrict__ seg_chunk_begin, int nseg,
-                                                                                float abs_scale, float max_norm,
-                                                                                float* __restrict__ seg_norm,
-                                                                                float* __restrict__ norm_state,
-                                                                                const float* __restrict__ proj_state) {
-    grad_norm_finish(chunk_sumsq, seg_chunk_begin, nseg, proj_state[3] != 0.f ? 1.f : abs_scale, max_norm, seg_norm, norm_state);
-}
+struct agem_source {
+    const float* ref; const float* proj_state;
+    __device__ __forceinline__ agem_grad begin() const { return {ref, proj_state[2], proj_state[3] != 0.f}; }
+};
+using agem_step = consumed_step<agem_source>;
 
-// The segmented AdamW on the projected gradient.  Per element of a live tensor (liveness is that of the task gradient g):
-//   ge = g * grad_scale;   gp = violated ? ge - (alpha * r) : ge;   G = CLIP ? gp * coef : gp;   theta, m, v = AdamW(theta, G)
-// with the explicit roundings of adamw1_rn, so that an un-projected step moves weights, moments, counters and the bf16 image
-// exactly as adamw_seg_kernel does (r is then not read at all).
-template <bool CLIP, bool TAIL>
-__device__ __forceinline__ void adamw_proj1(float& p, float g, float r, float& m, float& v, bool violated, float alpha,
-                                            const si_consts& k) {
-    const float ge = mul_rn(g, k.grad_scale);
-    const float gp = violated ? sub_rn(ge, mul_rn(alpha, r)) : ge;
-    const float G = CLIP ? mul_rn(gp, k.coef) : gp;
-    adamw1_rn<TAIL>(p, G, m, v, k.decay, k.omb1, k.b2, k.omb2, k.eps, k.step_size, k.inv_bc2_sqrt);
-}
-
-template <bool CLIP>
-__global__ __launch_bounds__(CL_THREADS) void adamw_seg_proj_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                                    float* __restrict__ m, float* __restrict__ v,
-                                                                    const int4* __restrict__ table, int nchunks,
-                                                                    const int* __restrict__ seg_active,
-                                                                    const int* __restrict__ seg_step, const group_table groups,
-                                                                    const int* __restrict__ seg_group, float b1, float b2, float eps,
-                                                                    float grad_scale,
-                                                                    unsigned short* __restrict__ shadow_bf16,
-                                                                    const float* __restrict__ norm_state, int skip_nonfinite,
-                                                                    const float* __restrict__ ref,
-                                                                    const float* __restrict__ proj_state) {
-    __shared__ float sh_c[2];
-    float coef = 1.f;
-    if (CLIP) {
-        if (skip_nonfinite && norm_state[2] != 0.f) return;
-        coef = norm_state[1];
-    }
-    const bool violated = proj_state[3] != 0.f;      // uniform over the launch
-    const float alpha = proj_state[2];
-    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
-        const int4 e = table[c];
-        if (!seg_active[e.z]) {           // workgroup-uniform: no task gradient -- untouched whatever r holds there
-            if (shadow_bf16)
-                for (int i = threadIdx.x; i < e.y; i += CL_THREADS) {
-                    __hip_bfloat16 a = __float2bfloat16(p[e.x + i]);
-                    shadow_bf16[e.x + i] = *reinterpret_cast<unsigned short*>(&a);
-                }
-            continue;
-        }
-        const int gi = group_of(seg_group, e.z, groups.n);      // workgroup-uniform
-        const float lr = groups.lr[gi], wd = groups.weight_decay[gi];
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const double step = (double)(seg_step[e.z] + 1);
-            sh_c[0] = (float)((double)lr / (1.0 - pow((double)b1, step)));
-            sh_c[1] = (float)(1.0 / sqrt(1.0 - pow((double)b2, step)));
-        }
-        __syncthreads();
-        const si_consts k = {__builtin_fmaf(-lr, wd, 1.f), 1.f - b1, b2, 1.f - b2, eps, sh_c[0], sh_c[1], grad_scale, coef, 0.f};
-        const int off = e.x, cnt = e.y, n4 = cnt >> 2;
-        for (int q = threadIdx.x; q < n4; q += CL_THREADS) {
-            float4 P = reinterpret_cast<float4*>(p + off)[q];
-            const float4 G = reinterpret_cast<const float4*>(g + off)[q];
-            float4 M = reinterpret_cast<float4*>(m + off)[q];
-            float4 V = reinterpret_cast<float4*>(v + off)[q];
-            float4 R = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (violated) R = reinterpret_cast<const float4*>(ref + off)[q];
-            adamw_proj1<CLIP, false>(P.x, G.x, R.x, M.x, V.x, violated, alpha, k);
-            adamw_proj1<CLIP, false>(P.y, G.y, R.y, M.y, V.y, violated, alpha, k);
-            adamw_proj1<CLIP, false>(P.z, G.z, R.z, M.z, V.z, violated, alpha, k);
-            adamw_proj1<CLIP, false>(P.w, G.w, R.w, M.w, V.w, violated, alpha, k);
-            reinterpret_cast<float4*>(p + off)[q] = P;
-            reinterpret_cast<float4*>(m + off)[q] = M;
-            reinterpret_cast<float4*>(v + off)[q] = V;
-            if (shadow_bf16) {
-                __hip_bfloat16 a = __float2bfloat16(P.x), b = __float2bfloat16(P.y), cc = __float2bfloat16(P.z),
-                               d = __float2bfloat16(P.w);
-                ushort4 o;
-                o.x = *reinterpret_cast<unsigned short*>(&a); o.y = *reinterpret_cast<unsigned short*>(&b);
-                o.z = *reinterpret_cast<unsigned short*>(&cc); o.w = *reinterpret_cast<unsigned short*>(&d);
-                reinterpret_cast<ushort4*>(shadow_bf16 + off)[q] = o;
-            }
-        }
-        for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) {
-            float P = p[off + i], M = m[off + i], V = v[off + i];
-            const float R = violated ? ref[off + i] : 0.f;
-            adamw_proj1<CLIP, true>(P, g[off + i], R, M, V, violated, alpha, k);
-            p[off + i] = P; m[off + i] = M; v[off + i] = V;
-            if (shadow_bf16) { __hip_bfloat16 a = __float2bfloat16(P); shadow_bf16[off + i] = *reinterpret_cast<unsigned short*>(&a); }
-        }
-    }
-}
-
-__global__ void seg_step_advance_kernel(int* __restrict__ seg_active, int* __restrict__ seg_step, int nseg) {
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s < nseg) { seg_step[s] += seg_active[s] ? 1 : 0; seg_active[s] = 0; }
-}
-
-// ... after a clipped step: a skipped step only clears the flags; counters = {clipped steps, skipped steps}
-__global__ void seg_step_advance_clipped_kernel(int* __restrict__ seg_active, int* __restrict__ seg_step, int nseg,
-                                                const float* __restrict__ norm_state, int skip_nonfinite,
-                                                int* __restrict__ counters) {
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool skipped = skip_nonfinite && norm_state[2] != 0.f;
-    if (s < nseg) { seg_step[s] += (!skipped && seg_active[s]) ? 1 : 0; seg_active[s] = 0; }
-    if (s == 0) {
-        if (skipped) counters[1] += 1;
-        else if (norm_state[1] < 1.f) counters[0] += 1;
-    }
-}
-
-// ... after a projected step: norm_state / counters may both be NULL (nothing measured); proj_counters[0] counts the steps that
-// projected, a skipped step not among them
-__global__ void seg_step_advance_projected_kernel(int* __restrict__ seg_active, int* __restrict__ seg_step, int nseg,
-                                                  const float* __restrict__ norm_state, int skip_nonfinite,
-                                                  int* __restrict__ counters, const float* __restrict__ proj_state,
-                                                  int* __restrict__ proj_counters) {
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool skipped = norm_state && skip_nonfinite && norm_state[2] != 0.f;
-    if (s < nseg) { seg_step[s] += (!skipped && seg_active[s]) ? 1 : 0; seg_active[s] = 0; }
-    if (s == 0) {
-        if (skipped) counters[1] += 1;
-        else if (norm_state && norm_state[1] < 1.f) counters[0] += 1;
-        if (!skipped && proj_state[3] != 0.f) proj_counters[0] += 1;
-    }
-}
 
 // ---- GEM (Lopez-Paz, Ranzato 2017): one constraint per earlier task.  refs is [max_tasks, stride] fp32, row k the reference
 // gradient of task k laid out as grad; K = ntasks rows are in use.  gem_sums (IA_GEM_SUMS_DOUBLES doubles) = d[16], then the
@@ -771,7 +535,7 @@ __global__ void seg_step_advance_projected_kernel(int* __restrict__ seg_active, 
 //   gem_finish_kernel    one workgroup adds the partials in fp64 (agem_finish_kernel's order) and writes d, or row and column
 //                        gram_row of the Gram matrix
 //   gem_solve_kernel     the bound-constrained QP in fp64, by an active-set method
-//   gem_norm_kernel, adamw_seg_gem_kernel   proj_norm_kernel / adamw_seg_proj_kernel with g * s + sum_k v_k * r_k
+//   consumed_norm_kernel<gem_source>, adamw_seg_kernel<CLIP, gem_step>   norm and step on g * s + sum_k v_k * r_k
 constexpr int GEM_MAX = IA_GEM_MAX_TASKS;
 constexpr int GEM_V = 0, GEM_VIOLATED = GEM_MAX, GEM_ACTIVE = GEM_VIOLATED + 1, GEM_ITERATIONS = GEM_VIOLATED + 2,
               GEM_SOLVED = GEM_VIOLATED + 3;
@@ -994,65 +758,74 @@ __global__ __launch_bounds__(64) void gem_solve_kernel(const double* __restrict_
     gem_state[GEM_SOLVED] = solved ? 1.f : 0.f;
 }
 
-__device__ __forceinline__ float add_rn(float a, float b) {
+// acc = g * s, then acc += v_k * r_k for k ascending over the rows with v_k != 0: every product and sum rounded on its own.
+// K = 0 when the step does not project: no row is read.
+struct gem_grad {
+    const float* refs; int64_t stride; int K; const float* sh_v;     // K: uniform over the launch
+    __device__ __forceinline__ bool projecting() const { return K > 0; }
+    template <int W>
+    __device__ __forceinline__ vecf<W> operator()(const vecf<W>& G, int64_t at, float grad_scale) const {
+        vecf<W> a;
+#pragma unroll
+        for (int j = 0; j < W; ++j) a[j] = mul_rn(G[j], grad_scale);
+        for (int k = 0; k < K; ++k) {
+            const float vk = sh_v[k];
+            if (vk == 0.f) continue;                 // workgroup-uniform: the row is not read
+            const vecf<W> R = ldv<W>(refs + (int64_t)k * stride, at);
+#pragma unroll
+            for (int j = 0; j < W; ++j) a[j] = add_rn(a[j], mul_rn(vk, R[j]));
+        }
+        return a;
+    }
+};
+
+struct gem_source {
+    const float* refs; int64_t stride; int ntasks; const float* gem_state;
+    __device__ __forceinline__ gem_grad begin() const {
+        __shared__ float sh_v[GEM_MAX];
+        if (threadIdx.x < GEM_MAX) sh_v[threadIdx.x] = gem_state[GEM_V + threadIdx.x];
+        __syncthreads();
+        return {refs, stride, gem_state[GEM_VIOLATED] != 0.f ? ntasks : 0, sh_v};
+    }
+};
+using gem_step = consumed_step<gem_source>;
+
+// ---- the clip norm of the gradient a consumed_step consumes, from the step's own gradient functor.
+// seg_activity_kernel<true>'s sum as the compiler emits it there, written out so that an un-projected step measures the norm
+// ia_grad_norm measures bit for bit (tests/test_agem_gpu.py compares them): in the float4 body four separately rounded squares
+// added left to right and then to the running sum, in the scalar tail one fma.
+__device__ __forceinline__ float sumsq4_rn(float ss, const vecf<4>& x) {
 #pragma clang fp contract(off)
-    return a + b;
+    const float aa = x[0] * x[0], bb = x[1] * x[1], cc = x[2] * x[2], dd = x[3] * x[3];
+    const float t = ((aa + bb) + cc) + dd;
+    return ss + t;
 }
 
-// acc = g * s, then acc += v_k * r_k for k ascending over the rows with v_k != 0: every product and sum rounded on its own
-__device__ __forceinline__ float4 gem_grad4(float4 g, const float* __restrict__ refs, int64_t stride, int K, int64_t q4,
-                                            const float* sh_v, float grad_scale) {
-    float4 a = make_float4(mul_rn(g.x, grad_scale), mul_rn(g.y, grad_scale), mul_rn(g.z, grad_scale), mul_rn(g.w, grad_scale));
-    for (int k = 0; k < K; ++k) {
-        const float vk = sh_v[k];
-        if (vk == 0.f) continue;                 // workgroup-uniform: the row is not read
-        const float4 r = reinterpret_cast<const float4*>(refs + (int64_t)k * stride)[q4];
-        a.x = add_rn(a.x, mul_rn(vk, r.x)); a.y = add_rn(a.y, mul_rn(vk, r.y));
-        a.z = add_rn(a.z, mul_rn(vk, r.z)); a.w = add_rn(a.w, mul_rn(vk, r.w));
-    }
-    return a;
-}
-
-__device__ __forceinline__ float gem_grad1(float g, const float* __restrict__ refs, int64_t stride, int K, int64_t i,
-                                           const float* sh_v, float grad_scale) {
-    float a = mul_rn(g, grad_scale);
-    for (int k = 0; k < K; ++k) {
-        const float vk = sh_v[k];
-        if (vk != 0.f) a = add_rn(a, mul_rn(vk, refs[(int64_t)k * stride + i]));
-    }
-    return a;
-}
-
-// proj_norm_kernel for GEM: un-projected, the raw sum of g^2 over every chunk (ia_grad_norm's first pass bit for bit);
-// projected, the sum of G^2 over the chunks of live tensors, a dead tensor's chunk storing 0.
-__global__ __launch_bounds__(CL_THREADS) void gem_norm_kernel(const float* __restrict__ g, const float* __restrict__ refs,
-                                                              int64_t stride, int K, const int4* __restrict__ table, int nchunks,
-                                                              const int* __restrict__ seg_active,
-                                                              const float* __restrict__ gem_state, float grad_scale,
-                                                              float* __restrict__ chunk_sumsq) {
+// Not projecting: the raw sum of g^2 over every chunk, as ia_grad_norm's first pass.  Projecting: the sum of G^2, G the functor's
+// gradient, over the chunks of live tensors; a dead tensor's chunk stores 0 (its .grad is None for torch's clip norm) and is not
+// read.  seg_active is read only (NULL: every tensor live): the variant's dots kernel has set it.
+template <class Source>
+__global__ __launch_bounds__(CL_THREADS) void consumed_norm_kernel(const float* __restrict__ g, const int4* __restrict__ table,
+                                                                   int nchunks, const int* __restrict__ seg_active,
+                                                                   const Source src, float grad_scale,
+                                                                   float* __restrict__ chunk_sumsq) {
     __shared__ float sh[CL_THREADS / 64];
-    __shared__ float sh_v[GEM_MAX];
-    const bool violated = gem_state[GEM_VIOLATED] != 0.f;
-    if (threadIdx.x < GEM_MAX) sh_v[threadIdx.x] = gem_state[GEM_V + threadIdx.x];
-    __syncthreads();
+    const auto grad = src.begin();
+    const bool projecting = grad.projecting();
     for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
         const int4 e = table[c];
         const int off = e.x, cnt = e.y, n4 = cnt >> 2;
         float ss = 0.f;
-        if (!violated) {
-            for (int q = threadIdx.x; q < n4; q += CL_THREADS) {
-                const float4 x = reinterpret_cast<const float4*>(g + off)[q];
-                ss = sumsq4_rn(ss, x.x, x.y, x.z, x.w);
-            }
+        if (!projecting) {
+            for (int q = threadIdx.x; q < n4; q += CL_THREADS) ss = sumsq4_rn(ss, ldv<4>(g, off + (q << 2)));
             for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) ss = __builtin_fmaf(g[off + i], g[off + i], ss);
         } else if (!seg_active || seg_active[e.z]) {
             for (int q = threadIdx.x; q < n4; q += CL_THREADS) {
-                const float4 G = gem_grad4(reinterpret_cast<const float4*>(g + off)[q], refs, stride, K, (off >> 2) + q, sh_v,
-                                           grad_scale);
-                ss = sumsq4_rn(ss, G.x, G.y, G.z, G.w);
+                const int at = off + (q << 2);
+                ss = sumsq4_rn(ss, grad(ldv<4>(g, at), at, grad_scale));
             }
             for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) {
-                const float G = gem_grad1(g[off + i], refs, stride, K, off + i, sh_v, grad_scale);
+                const float G = grad(ldv<1>(g, off + i), off + i, grad_scale)[0];
                 ss = __builtin_fmaf(G, G, ss);
             }
         }
@@ -1061,154 +834,95 @@ __global__ __launch_bounds__(CL_THREADS) void gem_norm_kernel(const float* __res
     }
 }
 
-__global__ __launch_bounds__(GN_THREADS) void grad_norm_finish_gem_kernel(const float* __restrict__ chunk_sumsq,
-                                                                          const int* __restrict__ seg_chunk_begin, int nseg,
-                                                                          float abs_scale, float max_norm,
-                                                                          float* __restrict__ seg_norm,
-                                                                          float* __restrict__ norm_state,
-                                                                          const float* __restrict__ gem_state) {
-    grad_norm_finish(chunk_sumsq, seg_chunk_begin, nseg, gem_state[GEM_VIOLATED] != 0.f ? 1.f : abs_scale, max_norm, seg_norm,
-                     norm_state);
-}
-
-// adamw_seg_proj_kernel with the K-row gradient: an un-projected step reads no row and is adamw_seg_kernel bit for bit
-template <bool CLIP>
-__global__ __launch_bounds__(CL_THREADS) void adamw_seg_gem_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                                   float* __restrict__ m, float* __restrict__ v,
-                                                                   const int4* __restrict__ table, int nchunks,
-                                                                   const int* __restrict__ seg_active,
-                                                                   const int* __restrict__ seg_step, const group_table groups,
-                                                                   const int* __restrict__ seg_group, float b1, float b2, float eps,
-                                                                   float grad_scale,
-                                                                   unsigned short* __restrict__ shadow_bf16,
-                                                                   const float* __restrict__ norm_state, int skip_nonfinite,
-                                                                   const float* __restrict__ refs, int64_t stride, int ntasks,
-                                                                   const float* __restrict__ gem_state) {
-    __shared__ float sh_c[2];
-    __shared__ float sh_v[GEM_MAX];
-    float coef = 1.f;
-    if (CLIP) {
-        if (skip_nonfinite && norm_state[2] != 0.f) return;
-        coef = norm_state[1];
-    }
-    const int K = gem_state[GEM_VIOLATED] != 0.f ? ntasks : 0;      // uniform over the launch; 0: no row is read
-    if (threadIdx.x < GEM_MAX) sh_v[threadIdx.x] = gem_state[GEM_V + threadIdx.x];
-    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
-        const int4 e = table[c];
-        if (!seg_active[e.z]) {           // workgroup-uniform: no task gradient -- untouched whatever the rows hold there
-            if (shadow_bf16)
-                for (int i = threadIdx.x; i < e.y; i += CL_THREADS) {
-                    __hip_bfloat16 a = __float2bfloat16(p[e.x + i]);
-                    shadow_bf16[e.x + i] = *reinterpret_cast<unsigned short*>(&a);
-                }
-            continue;
-        }
-        const int gi = group_of(seg_group, e.z, groups.n);      // workgroup-uniform
-        const float lr = groups.lr[gi], wd = groups.weight_decay[gi];
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const double step = (double)(seg_step[e.z] + 1);
-            sh_c[0] = (float)((double)lr / (1.0 - pow((double)b1, step)));
-            sh_c[1] = (float)(1.0 / sqrt(1.0 - pow((double)b2, step)));
-        }
-        __syncthreads();
-        const si_consts k = {__builtin_fmaf(-lr, wd, 1.f), 1.f - b1, b2, 1.f - b2, eps, sh_c[0], sh_c[1], grad_scale, coef, 0.f};
-        const int off = e.x, cnt = e.y, n4 = cnt >> 2;
-        for (int q = threadIdx.x; q < n4; q += CL_THREADS) {
-            float4 P = reinterpret_cast<float4*>(p + off)[q];
-            float4 G = gem_grad4(reinterpret_cast<const float4*>(g + off)[q], refs, stride, K, (off >> 2) + q, sh_v, grad_scale);
-            float4 M = reinterpret_cast<float4*>(m + off)[q];
-            float4 V = reinterpret_cast<float4*>(v + off)[q];
-            if (CLIP) { G.x = mul_rn(G.x, coef); G.y = mul_rn(G.y, coef); G.z = mul_rn(G.z, coef); G.w = mul_rn(G.w, coef); }
-            adamw1_rn<false>(P.x, G.x, M.x, V.x, k.decay, k.omb1, k.b2, k.omb2, k.eps, k.step_size, k.inv_bc2_sqrt);
-            adamw1_rn<false>(P.y, G.y, M.y, V.y, k.decay, k.omb1, k.b2, k.omb2, k.eps, k.step_size, k.inv_bc2_sqrt);
-            adamw1_rn<false>(P.z, G.z, M.z, V.z, k.decay, k.omb1, k.b2, k.omb2, k.eps, k.step_size, k.inv_bc2_sqrt);
-            adamw1_rn<false>(P.w, G.w, M.w, V.w, k.decay, k.omb1, k.b2, k.omb2, k.eps, k.step_size, k.inv_bc2_sqrt);
-            reinterpret_cast<float4*>(p + off)[q] = P;
-            reinterpret_cast<float4*>(m + off)[q] = M;
-            reinterpret_cast<float4*>(v + off)[q] = V;
-            if (shadow_bf16) {
-                __hip_bfloat16 a = __float2bfloat16(P.x), b = __float2bfloat16(P.y), cc = __float2bfloat16(P.z),
-                               d = __float2bfloat16(P.w);
-                ushort4 o;
-                o.x = *reinterpret_cast<unsigned short*>(&a); o.y = *reinterpret_cast<unsigned short*>(&b);
-                o.z = *reinterpret_cast<unsigned short*>(&cc); o.w = *reinterpret_cast<unsigned short*>(&d);
-                reinterpret_cast<ushort4*>(shadow_bf16 + off)[q] = o;
-            }
-        }
-        for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) {
-            float P = p[off + i], M = m[off + i], V = v[off + i];
-            float G = gem_grad1(g[off + i], refs, stride, K, off + i, sh_v, grad_scale);
-            if (CLIP) G = mul_rn(G, coef);
-            adamw1_rn<true>(P, G, M, V, k.decay, k.omb1, k.b2, k.omb2, k.eps, k.step_size, k.inv_bc2_sqrt);
-            p[off + i] = P; m[off + i] = M; v[off + i] = V;
-            if (shadow_bf16) { __hip_bfloat16 a = __float2bfloat16(P); shadow_bf16[off + i] = *reinterpret_cast<unsigned short*>(&a); }
-        }
-    }
-}
-
-// ... after a GEM step: gem_counters = {projected steps, unsolved steps}; a skipped step does not count as projected, and a
-// step whose program could not be solved counts as unsolved whether or not it was skipped
-__global__ void seg_step_advance_gem_kernel(int* __restrict__ seg_active, int* __restrict__ seg_step, int nseg,
-                                            const float* __restrict__ norm_state, int skip_nonfinite,
-                                            int* __restrict__ counters, const float* __restrict__ gem_state,
-                                            int* __restrict__ gem_counters) {
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool skipped = norm_state && skip_nonfinite && norm_state[2] != 0.f;
-    if (s < nseg) { seg_step[s] += (!skipped && seg_active[s]) ? 1 : 0; seg_active[s] = 0; }
-    if (s == 0) {
-        if (skipped) counters[1] += 1;
-        else if (norm_state && norm_state[1] < 1.f) counters[0] += 1;
-        if (!skipped && gem_state[GEM_VIOLATED] != 0.f) gem_counters[0] += 1;
-        if (gem_state[GEM_SOLVED] == 0.f) gem_counters[1] += 1;
-    }
-}
-
 // ---- Piggyback (Mallya, Davis, Lazebnik 2018): a fixed backbone `base` and, per language, a binary mask over it that is
 // trained through real-valued scores.  Per tensor a kind (workgroup-uniform per chunk, read inside the chunk loop as group_of is):
-//   free    adamw_seg_kernel's arithmetic on theta (adamw1_rn restates it), so a free tensor moves as under the plain step
+//   free    the plain rule on theta, so a free tensor moves as under the plain step
 //   masked  ge = g * grad_scale [* coef];  gs = ge * base;  score, m, v = AdamW(score, gs) with weight decay 0 (decay factor 1);
 //           theta = score >= threshold ? base : +0;  every product rounded on its own
 //   frozen  nothing but the bf16 image
 // A masked element moves 38 B (g, base, score, m, v in; score, m, v, theta and the bf16 image out), a free one 30 B.
-constexpr int KIND_MASKED = IA_MASK_MASKED, KIND_FROZEN = IA_MASK_FROZEN;      // anything else is IA_MASK_FREE
+constexpr int KIND_FREE = IA_MASK_FREE, KIND_MASKED = IA_MASK_MASKED, KIND_FROZEN = IA_MASK_FROZEN;   // anything else is free
 
-__device__ __forceinline__ unsigned short bf16_bits(float x) {
-    __hip_bfloat16 a = __float2bfloat16(x);
-    return *reinterpret_cast<unsigned short*>(&a);
+struct score_rule {
+    const float* base; float* scores; float threshold;
+    static constexpr bool reads_theta = false;       // theta is an output only
+    template <bool CLIP, int W>
+    __device__ __forceinline__ void apply(vecf<W>& P, const vecf<W>& G, vecf<W>& M, vecf<W>& V, int64_t at,
+                                          const chunk_consts& k) const {
+        const vecf<W> B = ldv<W>(base, at);
+        vecf<W> S = ldv<W>(scores, at);
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            const float eff = eff_grad<CLIP>(mul_rn(G[j], k.grad_scale), k);
+            adamw1_rn<W == 1>(S[j], mul_rn(eff, B[j]), M[j], V[j], 1.f, k);
+            P[j] = S[j] >= threshold ? B[j] : 0.f;
+        }
+        stv<W>(scores, at, S);
+    }
+};
+
+struct masked_step {
+    const float* base; float* scores; const int* seg_kind; float threshold;
+    __device__ __forceinline__ masked_step begin() const { return *this; }
+};
+
+// ---- the chunk walker.  One access of W elements: the common operands in, the variant's rule, the common operands out.
+template <bool CLIP, int W, class Rule>
+__device__ __forceinline__ void step_vec(const Rule& rule, float* __restrict__ p, const float* __restrict__ g,
+                                         float* __restrict__ m, float* __restrict__ v,
+                                         unsigned short* __restrict__ shadow_bf16, int at, const chunk_consts& k) {
+    vecf<W> P;
+    if constexpr (Rule::reads_theta) P = ldv<W>(p, at);
+    const vecf<W> G = ldv<W>(g, at);
+    vecf<W> M = ldv<W>(m, at), V = ldv<W>(v, at);
+    rule.template apply<CLIP, W>(P, G, M, V, at, k);
+    stv<W>(p, at, P);
+    stv<W>(m, at, M);
+    stv<W>(v, at, V);
+    if (shadow_bf16) {
+        if constexpr (W == 4) *reinterpret_cast<ushort4*>(shadow_bf16 + at) = bf16_bits(make_float4(P[0], P[1], P[2], P[3]));
+        else shadow_bf16[at] = bf16_bits(P[0]);
+    }
 }
 
-template <bool CLIP, bool TAIL>
-__device__ __forceinline__ float adamw_mask1(float& s, float g, float base, float& m, float& v, float threshold,
-                                             const si_consts& k) {
-    const float ge = mul_rn(g, k.grad_scale);
-    const float eff = CLIP ? mul_rn(ge, k.coef) : ge;           // eff_grad<true>'s two products
-    adamw1_rn<TAIL>(s, mul_rn(eff, base), m, v, 1.f, k.omb1, k.b2, k.omb2, k.eps, k.step_size, k.inv_bc2_sqrt);
-    return s >= threshold ? base : 0.f;
+// One live chunk under one rule: the float4 body and the scalar tail, split at cnt >> 2
+template <bool CLIP, class Rule>
+__device__ __forceinline__ void walk_chunk(const Rule& rule, float* __restrict__ p, const float* __restrict__ g,
+                                           float* __restrict__ m, float* __restrict__ v,
+                                           unsigned short* __restrict__ shadow_bf16, int off, int cnt, const chunk_consts& k) {
+    const int n4 = cnt >> 2;
+    for (int q = threadIdx.x; q < n4; q += CL_THREADS) step_vec<CLIP, 4>(rule, p, g, m, v, shadow_bf16, off + (q << 2), k);
+    for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) step_vec<CLIP, 1>(rule, p, g, m, v, shadow_bf16, off + i, k);
 }
 
-template <bool CLIP>
-__global__ __launch_bounds__(CL_THREADS) void adamw_seg_masked_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                                      float* __restrict__ m, float* __restrict__ v,
-                                                                      const int4* __restrict__ table, int nchunks,
-                                                                      const int* __restrict__ seg_active,
-                                                                      const int* __restrict__ seg_step, const group_table groups,
-                                                                      const int* __restrict__ seg_group, float b1, float b2,
-                                                                      float eps, float grad_scale,
-                                                                      unsigned short* __restrict__ shadow_bf16,
-                                                                      const float* __restrict__ norm_state, int skip_nonfinite,
-                                                                      const float* __restrict__ base, float* __restrict__ scores,
-                                                                      const int* __restrict__ seg_kind, float threshold) {
+// The segmented AdamW of every variant.  CLIP: norm_state = {norm, coef, non-finite flag, max_norm} is read from the device; when
+// the flag is set and skip_nonfinite is given the launch writes nothing at all.
+template <bool CLIP, class Variant>
+__global__ __launch_bounds__(CL_THREADS) void adamw_seg_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                               float* __restrict__ m, float* __restrict__ v,
+                                                               const int4* __restrict__ table, int nchunks,
+                                                               const int* __restrict__ seg_active,
+                                                               const int* __restrict__ seg_step, const group_table groups,
+                                                               const int* __restrict__ seg_group, float b1, float b2, float eps,
+                                                               float grad_scale, unsigned short* __restrict__ shadow_bf16,
+                                                               const float* __restrict__ norm_state, int skip_nonfinite,
+                                                               const Variant variant) {
     __shared__ float sh_c[2];
     float coef = 1.f;
     if (CLIP) {
         if (skip_nonfinite && norm_state[2] != 0.f) return;
         coef = norm_state[1];
     }
+    // The variant's launch-uniform state (violated, alpha, K and v).  begin() may contain a barrier (gem_source fills shared
+    // memory): it has to stay in control flow that is uniform over the workgroup, as it is after the launch-uniform return above.
+    const auto rule = variant.begin();
+    using Rule = std::remove_cv_t<decltype(rule)>;
+    constexpr bool MASKED_STEP = std::is_same_v<Rule, masked_step>;      // the only variant with per-tensor kinds
     for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
-        const int4 e = table[c];
-        const int kind = seg_kind[e.z];                          // workgroup-uniform
-        if (kind == KIND_FROZEN || !seg_active[e.z]) {           // never written / untouched: only the bf16 image is kept in step
+        const int4 e = table[c];           // x = offset (multiple of 4), y = count, z = segment id
+        int kind = KIND_FREE;                                    // workgroup-uniform
+        if constexpr (MASKED_STEP) kind = rule.seg_kind[e.z];
+        if (kind == KIND_FROZEN || !seg_active[e.z]) {           // never written / no gradient: only the bf16 image is kept in step
             if (shadow_bf16)
                 for (int i = threadIdx.x; i < e.y; i += CL_THREADS) shadow_bf16[e.x + i] = bf16_bits(p[e.x + i]);
             continue;
@@ -1222,79 +936,39 @@ __global__ __launch_bounds__(CL_THREADS) void adamw_seg_masked_kernel(float* __r
             sh_c[1] = (float)(1.0 / sqrt(1.0 - pow((double)b2, step)));
         }
         __syncthreads();
-        const si_consts k = {__builtin_fmaf(-lr, wd, 1.f), 1.f - b1, b2, 1.f - b2, eps, sh_c[0], sh_c[1], grad_scale, coef, 0.f};
-        const int off = e.x, cnt = e.y, n4 = cnt >> 2;
-        if (kind == KIND_MASKED) {
-            for (int q = threadIdx.x; q < n4; q += CL_THREADS) {
-                const float4 G = reinterpret_cast<const float4*>(g + off)[q];
-                const float4 B = reinterpret_cast<const float4*>(base + off)[q];
-                float4 S = reinterpret_cast<float4*>(scores + off)[q];
-                float4 M = reinterpret_cast<float4*>(m + off)[q];
-                float4 V = reinterpret_cast<float4*>(v + off)[q];
-                float4 P;
-                P.x = adamw_mask1<CLIP, false>(S.x, G.x, B.x, M.x, V.x, threshold, k);
-                P.y = adamw_mask1<CLIP, false>(S.y, G.y, B.y, M.y, V.y, threshold, k);
-                P.z = adamw_mask1<CLIP, false>(S.z, G.z, B.z, M.z, V.z, threshold, k);
-                P.w = adamw_mask1<CLIP, false>(S.w, G.w, B.w, M.w, V.w, threshold, k);
-                reinterpret_cast<float4*>(scores + off)[q] = S;
-                reinterpret_cast<float4*>(m + off)[q] = M;
-                reinterpret_cast<float4*>(v + off)[q] = V;
-                reinterpret_cast<float4*>(p + off)[q] = P;
-                if (shadow_bf16) {
-                    ushort4 o;
-                    o.x = bf16_bits(P.x); o.y = bf16_bits(P.y); o.z = bf16_bits(P.z); o.w = bf16_bits(P.w);
-                    reinterpret_cast<ushort4*>(shadow_bf16 + off)[q] = o;
-                }
-            }
-            for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) {
-                float S = scores[off + i], M = m[off + i], V = v[off + i];
-                const float P = adamw_mask1<CLIP, true>(S, g[off + i], base[off + i], M, V, threshold, k);
-                scores[off + i] = S; m[off + i] = M; v[off + i] = V; p[off + i] = P;
-                if (shadow_bf16) shadow_bf16[off + i] = bf16_bits(P);
-            }
-            continue;
-        }
-        for (int q = threadIdx.x; q < n4; q += CL_THREADS) {    // free: adamw_seg_gem_kernel's un-projected path
-            float4 P = reinterpret_cast<float4*>(p + off)[q];
-            float4 G = reinterpret_cast<const float4*>(g + off)[q];
-            float4 M = reinterpret_cast<float4*>(m + off)[q];
-            float4 V = reinterpret_cast<float4*>(v + off)[q];
-            G.x = mul_rn(G.x, grad_scale); G.y = mul_rn(G.y, grad_scale); G.z = mul_rn(G.z, grad_scale); G.w = mul_rn(G.w, grad_scale);
-            if (CLIP) { G.x = mul_rn(G.x, coef); G.y = mul_rn(G.y, coef); G.z = mul_rn(G.z, coef); G.w = mul_rn(G.w, coef); }
-            adamw1_rn<false>(P.x, G.x, M.x, V.x, k.decay, k.omb1, k.b2, k.omb2, k.eps, k.step_size, k.inv_bc2_sqrt);
-            adamw1_rn<false>(P.y, G.y, M.y, V.y, k.decay, k.omb1, k.b2, k.omb2, k.eps, k.step_size, k.inv_bc2_sqrt);
-            adamw1_rn<false>(P.z, G.z, M.z, V.z, k.decay, k.omb1, k.b2, k.omb2, k.eps, k.step_size, k.inv_bc2_sqrt);
-            adamw1_rn<false>(P.w, G.w, M.w, V.w, k.decay, k.omb1, k.b2, k.omb2, k.eps, k.step_size, k.inv_bc2_sqrt);
-            reinterpret_cast<float4*>(p + off)[q] = P;
-            reinterpret_cast<float4*>(m + off)[q] = M;
-            reinterpret_cast<float4*>(v + off)[q] = V;
-            if (shadow_bf16) {
-                ushort4 o;
-                o.x = bf16_bits(P.x); o.y = bf16_bits(P.y); o.z = bf16_bits(P.z); o.w = bf16_bits(P.w);
-                reinterpret_cast<ushort4*>(shadow_bf16 + off)[q] = o;
-            }
-        }
-        for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) {
-            float P = p[off + i], M = m[off + i], V = v[off + i];
-            float G = mul_rn(g[off + i], grad_scale);
-            if (CLIP) G = mul_rn(G, coef);
-            adamw1_rn<true>(P, G, M, V, k.decay, k.omb1, k.b2, k.omb2, k.eps, k.step_size, k.inv_bc2_sqrt);
-            p[off + i] = P; m[off + i] = M; v[off + i] = V;
-            if (shadow_bf16) shadow_bf16[off + i] = bf16_bits(P);
+        const chunk_consts k = {__builtin_fmaf(-lr, wd, 1.f), 1.f - b1, b2, 1.f - b2, eps, sh_c[0], sh_c[1], grad_scale, coef};
+        if constexpr (MASKED_STEP) {
+            if (kind == KIND_MASKED)
+                walk_chunk<CLIP>(score_rule{rule.base, rule.scores, rule.threshold}, p, g, m, v, shadow_bf16, e.x, e.y, k);
+            else
+                walk_chunk<CLIP>(consumed_rule<scaled_grad>{}, p, g, m, v, shadow_bf16, e.x, e.y, k);
+        } else {
+            walk_chunk<CLIP>(rule, p, g, m, v, shadow_bf16, e.x, e.y, k);
         }
     }
 }
 
-// ... after a masked step: a frozen tensor's counter never moves; norm_state / counters may both be NULL (nothing measured)
-__global__ void seg_step_advance_masked_kernel(int* __restrict__ seg_active, int* __restrict__ seg_step, int nseg,
-                                               const float* __restrict__ norm_state, int skip_nonfinite,
-                                               int* __restrict__ counters, const int* __restrict__ seg_kind) {
+// After a step: a live tensor's counter moves unless the step was skipped or the tensor is frozen, and every flag is cleared.
+// counters = {clipped steps, skipped steps}, with norm_state or both NULL (nothing measured).  projected (proj_state + 3 or
+// gem_state + GEM_VIOLATED) with its counter: a skipped step is not counted as projected.  solved (gem_state + GEM_SOLVED) with
+// its counter: an unsolved program is counted whether or not the step was skipped.  Each of the three and seg_kind may be NULL.
+__global__ void seg_step_advance_kernel(int* __restrict__ seg_active, int* __restrict__ seg_step, int nseg,
+                                        const float* __restrict__ norm_state, int skip_nonfinite, int* __restrict__ counters,
+                                        const float* __restrict__ projected, int* __restrict__ projected_count,
+                                        const float* __restrict__ solved, int* __restrict__ unsolved_count,
+                                        const int* __restrict__ seg_kind) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     const bool skipped = norm_state && skip_nonfinite && norm_state[2] != 0.f;
-    if (s < nseg) { seg_step[s] += (!skipped && seg_active[s] && seg_kind[s] != KIND_FROZEN) ? 1 : 0; seg_active[s] = 0; }
-    if (s == 0 && norm_state) {
+    if (s < nseg) {
+        const bool frozen = seg_kind && seg_kind[s] == KIND_FROZEN;
+        seg_step[s] += (!skipped && seg_active[s] && !frozen) ? 1 : 0;
+        seg_active[s] = 0;
+    }
+    if (s == 0) {
         if (skipped) counters[1] += 1;
-        else if (norm_state[1] < 1.f) counters[0] += 1;
+        else if (norm_state && norm_state[1] < 1.f) counters[0] += 1;
+        if (projected && !skipped && projected[0] != 0.f) projected_count[0] += 1;
+        if (solved && solved[0] == 0.f) unsolved_count[0] += 1;
     }
 }
 
@@ -1347,11 +1021,7 @@ __global__ __launch_bounds__(CL_THREADS) void mask_apply_kernel(float* __restric
             } else {
                 P = reinterpret_cast<const float4*>(p + off)[q];
             }
-            if (shadow_bf16) {
-                ushort4 o;
-                o.x = bf16_bits(P.x); o.y = bf16_bits(P.y); o.z = bf16_bits(P.z); o.w = bf16_bits(P.w);
-                reinterpret_cast<ushort4*>(shadow_bf16 + off)[q] = o;
-            }
+            if (shadow_bf16) reinterpret_cast<ushort4*>(shadow_bf16 + off)[q] = bf16_bits(P);
         }
         for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) {
             float P;
@@ -1373,113 +1043,55 @@ inline int cap_grid(int64_t work_items, int per_block) {
     return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
 }
 
-inline group_table one_group(float lr, float weight_decay) {
+inline int chunk_grid(int nchunks) { return nchunks < 2048 ? nchunks : 2048; }
+
+inline bool groups_ok(const int32_t* seg_group, int ngroups, const float* group_lr, const float* group_weight_decay) {
+    return ngroups >= 1 && ngroups <= IA_MAX_PARAM_GROUPS && group_lr && group_weight_decay && (ngroups == 1 || seg_group) &&
+           (!seg_group || ia_is_aligned(seg_group, 4));
+}
+
+inline group_table make_group_table(int ngroups, const float* group_lr, const float* group_weight_decay) {
     group_table t = {};
-    t.n = 1;
-    t.lr[0] = lr;
-    t.weight_decay[0] = weight_decay;
+    t.n = ngroups;
+    for (int k = 0; k < ngroups; ++k) { t.lr[k] = group_lr[k]; t.weight_decay[k] = group_weight_decay[k]; }
     return t;
 }
 
-// The launches of the four kinds of segmented step, shared by their entry points (one group, seg_group NULL) and by
-// ia_adamw_step_segmented_grouped.  Arguments are validated by the callers.
+inline group_table one_group(float lr, float weight_decay) { return make_group_table(1, &lr, &weight_decay); }
+
+// The operands every segmented step shares.  seg_group NULL: every tensor in group 0.  norm_state and counters: both (the clip
+// coefficient and the non-finite flag are read from the device) or neither.
 struct step_head {
     float *theta; const float* grad; float *exp_avg, *exp_avg_sq;
     const int4* table; int nchunks; int32_t *seg_active, *seg_step; int nseg, all_active;
     float b1, b2, eps, grad_scale; unsigned short* shadow;
+    const int32_t* seg_group; const float* norm_state; int skip_nonfinite; int32_t* counters;
 };
 
-inline bool step_head_ok(const float* theta, const float* grad, const float* exp_avg, const float* exp_avg_sq,
-                         const int32_t* chunk_table, int nchunks, const int32_t* seg_active, const int32_t* seg_step, int nseg,
-                         const void* shadow_bf16) {
-    if (!theta || !grad || !exp_avg || !exp_avg_sq || !chunk_table || !seg_active || !seg_step || nchunks <= 0 || nseg <= 0)
-        return false;
-    return ia_is_aligned(theta, 16) && ia_is_aligned(grad, 16) && ia_is_aligned(exp_avg, 16) && ia_is_aligned(exp_avg_sq, 16) &&
-           ia_is_aligned(chunk_table, 16) && (!shadow_bf16 || ia_is_aligned(shadow_bf16, 8));
+inline step_head make_head(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq, const int32_t* chunk_table,
+                           int nchunks, int32_t* seg_active, int32_t* seg_step, int nseg, int all_active, float beta1, float beta2,
+                           float eps, float grad_scale, void* shadow_bf16, const int32_t* seg_group, const float* norm_state,
+                           int skip_nonfinite, int32_t* counters) {
+    return {theta, grad, exp_avg, exp_avg_sq, (const int4*)chunk_table, nchunks, seg_active, seg_step, nseg, all_active,
+            beta1, beta2, eps, grad_scale, (unsigned short*)shadow_bf16, seg_group, norm_state, skip_nonfinite, counters};
 }
 
-inline bool si_operands_ok(const float* norm_state, const int32_t* counters, const float* path_w, const float* omega,
-                           const float* theta_star) {
-    if (!path_w || (norm_state == nullptr) != (counters == nullptr) || (omega == nullptr) != (theta_star == nullptr)) return false;
+inline bool head_ok(const step_head& h) {
+    if (!h.theta || !h.grad || !h.exp_avg || !h.exp_avg_sq || !h.table || !h.seg_active || !h.seg_step || h.nchunks <= 0 ||
+        h.nseg <= 0 || (h.norm_state == nullptr) != (h.counters == nullptr))
+        return false;
+    return ia_is_aligned(h.theta, 16) && ia_is_aligned(h.grad, 16) && ia_is_aligned(h.exp_avg, 16) &&
+           ia_is_aligned(h.exp_avg_sq, 16) && ia_is_aligned(h.table, 16) && (!h.shadow || ia_is_aligned(h.shadow, 8));
+}
+
+inline bool si_operands_ok(const float* path_w, const float* omega, const float* theta_star) {
+    if (!path_w || (omega == nullptr) != (theta_star == nullptr)) return false;
     return ia_is_aligned(path_w, 16) && (!omega || (ia_is_aligned(omega, 16) && ia_is_aligned(theta_star, 16)));
 }
 
-inline bool proj_operands_ok(const float* norm_state, const int32_t* counters, const float* ref, const float* proj_state,
-                             const int32_t* proj_counters) {
-    if (!ref || !proj_state || !proj_counters || (norm_state == nullptr) != (counters == nullptr)) return false;
+inline bool proj_operands_ok(const float* ref, const float* proj_state, const int32_t* proj_counters) {
+    if (!ref || !proj_state || !proj_counters) return false;
     return ia_is_aligned(ref, 16) && ia_is_aligned(proj_state, 4) && ia_is_aligned(proj_counters, 4);
-}
-
-inline int step_grid(const step_head& h) { return h.nchunks < 2048 ? h.nchunks : 2048; }
-
-inline bool mark_all_active(const step_head& h, hipStream_t st) {   // 0x01010101: non-zero
-    return hipMemsetAsync(h.seg_active, 1, (size_t)h.nseg * sizeof(int32_t), st) == hipSuccess;
-}
-
-inline void launch_activity(const step_head& h, hipStream_t st) {
-    hipLaunchKernelGGL(seg_activity_kernel<false>, dim3(step_grid(h)), dim3(CL_THREADS), 0, st, h.grad, h.table, h.nchunks,
-                       h.seg_active, (float*)nullptr);
-}
-
-inline void launch_advance(const step_head& h, const float* norm_state, int skip_nonfinite, int32_t* counters, hipStream_t st) {
-    const dim3 grid((h.nseg + 255) / 256), block(256);
-    if (norm_state)
-        hipLaunchKernelGGL(seg_step_advance_clipped_kernel, grid, block, 0, st, h.seg_active, h.seg_step, h.nseg, norm_state,
-                           skip_nonfinite, counters);
-    else
-        hipLaunchKernelGGL(seg_step_advance_kernel, grid, block, 0, st, h.seg_active, h.seg_step, h.nseg);
-}
-
-// plain (norm_state NULL: the activity pass runs here unless all_active) or clipped (ia_grad_norm has set the flags)
-int run_step(const step_head& h, const group_table& gt, const int32_t* seg_group, const float* norm_state, int skip_nonfinite,
-             int32_t* counters, hipStream_t st) {
-    if (h.all_active) {
-        if (!mark_all_active(h, st)) return IA_LAUNCH_FAILED;
-    } else if (!norm_state) {
-        launch_activity(h, st);
-    }
-    auto kernel = norm_state ? adamw_seg_kernel<true> : adamw_seg_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3(step_grid(h)), dim3(CL_THREADS), 0, st, h.theta, h.grad, h.exp_avg, h.exp_avg_sq, h.table,
-                       h.nchunks, h.seg_active, h.seg_step, gt, seg_group, h.b1, h.b2, h.eps, h.grad_scale, h.shadow, norm_state,
-                       skip_nonfinite);
-    launch_advance(h, norm_state, skip_nonfinite, counters, st);
-    IA_RETURN_IF_LAUNCH_FAILED();
-    return IA_OK;
-}
-
-int run_step_si(const step_head& h, const group_table& gt, const int32_t* seg_group, const float* norm_state, int skip_nonfinite,
-                int32_t* counters, float* path_w, const float* omega, const float* theta_star, float penalty_coef,
-                hipStream_t st) {
-    const bool clip = norm_state != nullptr, pen = omega != nullptr;
-    if (h.all_active) {
-        if (!mark_all_active(h, st)) return IA_LAUNCH_FAILED;
-    } else if (!clip) {   // with norm_state, ia_grad_norm's first pass has set the flags
-        launch_activity(h, st);
-    }
-    const float c2 = 2.f * penalty_coef;
-    auto kernel = clip ? (pen ? adamw_seg_si_kernel<true, true> : adamw_seg_si_kernel<true, false>)
-                       : (pen ? adamw_seg_si_kernel<false, true> : adamw_seg_si_kernel<false, false>);
-    hipLaunchKernelGGL(kernel, dim3(step_grid(h)), dim3(CL_THREADS), 0, st, h.theta, h.grad, h.exp_avg, h.exp_avg_sq, h.table,
-                       h.nchunks, h.seg_active, h.seg_step, gt, seg_group, h.b1, h.b2, h.eps, h.grad_scale, h.shadow, norm_state,
-                       skip_nonfinite, path_w, omega, theta_star, c2);
-    launch_advance(h, norm_state, skip_nonfinite, counters, st);
-    IA_RETURN_IF_LAUNCH_FAILED();
-    return IA_OK;
-}
-
-int run_step_projected(const step_head& h, const group_table& gt, const int32_t* seg_group, const float* norm_state,
-                       int skip_nonfinite, int32_t* counters, const float* ref, const float* proj_state, int32_t* proj_counters,
-                       hipStream_t st) {
-    if (h.all_active)   // otherwise ia_agem_dots has set the flags from the task gradient
-        if (!mark_all_active(h, st)) return IA_LAUNCH_FAILED;
-    auto kernel = norm_state ? adamw_seg_proj_kernel<true> : adamw_seg_proj_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3(step_grid(h)), dim3(CL_THREADS), 0, st, h.theta, h.grad, h.exp_avg, h.exp_avg_sq, h.table,
-                       h.nchunks, h.seg_active, h.seg_step, gt, seg_group, h.b1, h.b2, h.eps, h.grad_scale, h.shadow, norm_state,
-                       skip_nonfinite, ref, proj_state);
-    hipLaunchKernelGGL(seg_step_advance_projected_kernel, dim3((h.nseg + 255) / 256), dim3(256), 0, st, h.seg_active, h.seg_step,
-                       h.nseg, norm_state, skip_nonfinite, counters, proj_state, proj_counters);
-    IA_RETURN_IF_LAUNCH_FAILED();
-    return IA_OK;
 }
 
 inline bool gem_operands_ok(const float* refs, int64_t stride, int ntasks, const float* gem_state) {
@@ -1487,17 +1099,68 @@ inline bool gem_operands_ok(const float* refs, int64_t stride, int ntasks, const
     return ia_is_aligned(refs, 16) && ia_is_aligned(gem_state, 4);
 }
 
-int run_step_gem(const step_head& h, const group_table& gt, const int32_t* seg_group, const float* norm_state, int skip_nonfinite,
-                 int32_t* counters, const float* refs, int64_t stride, int ntasks, const float* gem_state, int32_t* gem_counters,
-                 hipStream_t st) {
-    if (h.all_active)   // otherwise ia_gem_dots has set the flags from the task gradient
-        if (!mark_all_active(h, st)) return IA_LAUNCH_FAILED;
-    auto kernel = norm_state ? adamw_seg_gem_kernel<true> : adamw_seg_gem_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3(step_grid(h)), dim3(CL_THREADS), 0, st, h.theta, h.grad, h.exp_avg, h.exp_avg_sq, h.table,
-                       h.nchunks, h.seg_active, h.seg_step, gt, seg_group, h.b1, h.b2, h.eps, h.grad_scale, h.shadow, norm_state,
-                       skip_nonfinite, refs, stride, ntasks, gem_state);
-    hipLaunchKernelGGL(seg_step_advance_gem_kernel, dim3((h.nseg + 255) / 256), dim3(256), 0, st, h.seg_active, h.seg_step,
-                       h.nseg, norm_state, skip_nonfinite, counters, gem_state, gem_counters);
+// What the host and the advance kernel need to know of a variant beyond its kernel operands
+struct step_extras {
+    bool flags_preset;       // the variant's dots kernel has set seg_active from the task gradient: never an activity pass here
+    const float* projected; int32_t* projected_count; const float* solved; int32_t* unsolved_count;
+    const int32_t* seg_kind;  // the masked step only: the SAME array as masked_step::seg_kind, so that walker and advance agree
+};
+
+// Every segmented step: liveness, the walker, the advance.  Arguments are validated by the callers.  Liveness: all_active marks
+// every tensor; otherwise the flags are those of ia_grad_norm's first pass (norm_state given) or of the variant's dots kernel,
+// or an activity pass over the gradient runs here.
+template <class Variant>
+int run_step(const step_head& h, const group_table& gt, const Variant& variant, const step_extras& x, hipStream_t st) {
+    if (h.all_active) {    // 0x01010101: non-zero
+        if (hipMemsetAsync(h.seg_active, 1, (size_t)h.nseg * sizeof(int32_t), st) != hipSuccess) return IA_LAUNCH_FAILED;
+    } else if (!h.norm_state && !x.flags_preset) {
+        hipLaunchKernelGGL(seg_activity_kernel<false>, dim3(chunk_grid(h.nchunks)), dim3(CL_THREADS), 0, st, h.grad, h.table,
+                           h.nchunks, h.seg_active, (float*)nullptr);
+    }
+    auto kernel = h.norm_state ? adamw_seg_kernel<true, Variant> : adamw_seg_kernel<false, Variant>;
+    hipLaunchKernelGGL(kernel, dim3(chunk_grid(h.nchunks)), dim3(CL_THREADS), 0, st, h.theta, h.grad, h.exp_avg, h.exp_avg_sq,
+                       h.table, h.nchunks, h.seg_active, h.seg_step, gt, h.seg_group, h.b1, h.b2, h.eps, h.grad_scale, h.shadow,
+                       h.norm_state, h.skip_nonfinite, variant);
+    hipLaunchKernelGGL(seg_step_advance_kernel, dim3((h.nseg + 255) / 256), dim3(256), 0, st, h.seg_active, h.seg_step, h.nseg,
+                       h.norm_state, h.skip_nonfinite, h.counters, x.projected, x.projected_count, x.solved, x.unsolved_count,
+                       x.seg_kind);
+    IA_RETURN_IF_LAUNCH_FAILED();
+    return IA_OK;
+}
+
+int run_step_si(const step_head& h, const group_table& gt, float* path_w, const float* omega, const float* theta_star,
+                float penalty_coef, hipStream_t st) {
+    const float c2 = 2.f * penalty_coef;
+    return omega ? run_step(h, gt, si_step<true>{path_w, omega, theta_star, c2}, step_extras{}, st)
+                 : run_step(h, gt, si_step<false>{path_w, omega, theta_star, c2}, step_extras{}, st);
+}
+
+int run_step_agem(const step_head& h, const group_table& gt, const float* ref, const float* proj_state, int32_t* proj_counters,
+                  hipStream_t st) {
+    step_extras x = {};
+    x.flags_preset = true;
+    x.projected = proj_state + 3;
+    x.projected_count = proj_counters;
+    return run_step(h, gt, agem_step{{ref, proj_state}}, x, st);
+}
+
+// The clip norm of ia_grad_norm_projected / ia_grad_norm_gem: chunk sums of the consumed gradient, then the finisher, which
+// leaves the root unscaled when the step projects (`projected` set on the device)
+inline bool norm_operands_ok(const float* grad, const int32_t* chunk_table, int nchunks, const int32_t* seg_chunk_begin, int nseg,
+                             const float* seg_norm, const float* norm_state, const void* workspace) {
+    if (!grad || !chunk_table || !seg_chunk_begin || !seg_norm || !norm_state || !workspace || nchunks <= 0 || nseg <= 0)
+        return false;
+    return ia_is_aligned(grad, 16) && ia_is_aligned(chunk_table, 16) && ia_is_aligned(workspace, 4);
+}
+
+template <class Source>
+int run_consumed_norm(const float* grad, const int32_t* chunk_table, int nchunks, const int32_t* seg_chunk_begin, int nseg,
+                      float grad_scale, float max_norm, const int32_t* seg_active, float* seg_norm, float* norm_state,
+                      void* workspace, const Source& src, const float* projected, hipStream_t st) {
+    hipLaunchKernelGGL(consumed_norm_kernel<Source>, dim3(chunk_grid(nchunks)), dim3(CL_THREADS), 0, st, grad,
+                       (const int4*)chunk_table, nchunks, seg_active, src, grad_scale, (float*)workspace);
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(GN_THREADS), 0, st, (const float*)workspace, seg_chunk_begin, nseg,
+                       fabsf(grad_scale), max_norm, seg_norm, norm_state, projected);
     IA_RETURN_IF_LAUNCH_FAILED();
     return IA_OK;
 }
@@ -1558,11 +1221,10 @@ extern "C" int ia_adamw_step_segmented(float* theta, const float* grad, float* e
                                        const int32_t* chunk_table, int nchunks, int32_t* seg_active, int32_t* seg_step, int nseg,
                                        int all_active, float lr, float beta1, float beta2, float eps, float weight_decay,
                                        float grad_scale, void* shadow_bf16, ia_stream_t stream) {
-    if (!step_head_ok(theta, grad, exp_avg, exp_avg_sq, chunk_table, nchunks, seg_active, seg_step, nseg, shadow_bf16))
-        return IA_INVALID_VALUE;
-    const step_head h = {theta, grad, exp_avg, exp_avg_sq, (const int4*)chunk_table, nchunks, seg_active, seg_step, nseg, all_active,
-                         beta1, beta2, eps, grad_scale, (unsigned short*)shadow_bf16};
-    return run_step(h, one_group(lr, weight_decay), nullptr, nullptr, 0, nullptr, (hipStream_t)stream);
+    const step_head h = make_head(theta, grad, exp_avg, exp_avg_sq, chunk_table, nchunks, seg_active, seg_step, nseg, all_active,
+                                  beta1, beta2, eps, grad_scale, shadow_bf16, nullptr, nullptr, 0, nullptr);
+    if (!head_ok(h)) return IA_INVALID_VALUE;
+    return run_step(h, one_group(lr, weight_decay), plain_step{}, step_extras{}, (hipStream_t)stream);
 }
 
 extern "C" size_t ia_grad_norm_workspace_bytes(int nchunks) { return nchunks > 0 ? (size_t)nchunks * sizeof(float) : 0; }
@@ -1570,15 +1232,14 @@ extern "C" size_t ia_grad_norm_workspace_bytes(int nchunks) { return nchunks > 0
 extern "C" int ia_grad_norm(const float* grad, const int32_t* chunk_table, int nchunks, const int32_t* seg_chunk_begin, int nseg,
                             float grad_scale, float max_norm, int32_t* seg_active, float* seg_norm, float* norm_state,
                             void* workspace, size_t workspace_bytes, ia_stream_t stream) {
-    if (!grad || !chunk_table || !seg_chunk_begin || !seg_norm || !norm_state || !workspace || nchunks <= 0 || nseg <= 0)
+    if (!norm_operands_ok(grad, chunk_table, nchunks, seg_chunk_begin, nseg, seg_norm, norm_state, workspace))
         return IA_INVALID_VALUE;
-    if (!ia_is_aligned(grad, 16) || !ia_is_aligned(chunk_table, 16) || !ia_is_aligned(workspace, 4)) return IA_INVALID_VALUE;
     if (workspace_bytes < ia_grad_norm_workspace_bytes(nchunks)) return IA_WORKSPACE_TOO_SMALL;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(seg_activity_kernel<true>, dim3(nchunks < 2048 ? nchunks : 2048), dim3(CL_THREADS), 0, st, grad,
+    hipLaunchKernelGGL(seg_activity_kernel<true>, dim3(chunk_grid(nchunks)), dim3(CL_THREADS), 0, st, grad,
                        (const int4*)chunk_table, nchunks, seg_active, (float*)workspace);
     hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(GN_THREADS), 0, st, (const float*)workspace, seg_chunk_begin, nseg,
-                       fabsf(grad_scale), max_norm, seg_norm, norm_state);
+                       fabsf(grad_scale), max_norm, seg_norm, norm_state, (const float*)nullptr);
     IA_RETURN_IF_LAUNCH_FAILED();
     return IA_OK;
 }
@@ -1588,12 +1249,10 @@ extern "C" int ia_adamw_step_segmented_clipped(float* theta, const float* grad, 
                                                int nseg, int all_active, float lr, float beta1, float beta2, float eps,
                                                float weight_decay, float grad_scale, void* shadow_bf16, const float* norm_state,
                                                int skip_nonfinite, int32_t* counters, ia_stream_t stream) {
-    if (!norm_state || !counters ||
-        !step_head_ok(theta, grad, exp_avg, exp_avg_sq, chunk_table, nchunks, seg_active, seg_step, nseg, shadow_bf16))
-        return IA_INVALID_VALUE;
-    const step_head h = {theta, grad, exp_avg, exp_avg_sq, (const int4*)chunk_table, nchunks, seg_active, seg_step, nseg, all_active,
-                         beta1, beta2, eps, grad_scale, (unsigned short*)shadow_bf16};
-    return run_step(h, one_group(lr, weight_decay), nullptr, norm_state, skip_nonfinite, counters, (hipStream_t)stream);
+    const step_head h = make_head(theta, grad, exp_avg, exp_avg_sq, chunk_table, nchunks, seg_active, seg_step, nseg, all_active,
+                                  beta1, beta2, eps, grad_scale, shadow_bf16, nullptr, norm_state, skip_nonfinite, counters);
+    if (!norm_state || !counters || !head_ok(h)) return IA_INVALID_VALUE;
+    return run_step(h, one_group(lr, weight_decay), plain_step{}, step_extras{}, (hipStream_t)stream);
 }
 
 extern "C" int ia_adamw_step_segmented_si(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq,
@@ -1602,13 +1261,10 @@ extern "C" int ia_adamw_step_segmented_si(float* theta, const float* grad, float
                                           float grad_scale, void* shadow_bf16, const float* norm_state, int skip_nonfinite,
                                           int32_t* counters, float* path_w, const float* omega, const float* theta_star,
                                           float penalty_coef, ia_stream_t stream) {
-    if (!step_head_ok(theta, grad, exp_avg, exp_avg_sq, chunk_table, nchunks, seg_active, seg_step, nseg, shadow_bf16) ||
-        !si_operands_ok(norm_state, counters, path_w, omega, theta_star))
-        return IA_INVALID_VALUE;
-    const step_head h = {theta, grad, exp_avg, exp_avg_sq, (const int4*)chunk_table, nchunks, seg_active, seg_step, nseg, all_active,
-                         beta1, beta2, eps, grad_scale, (unsigned short*)shadow_bf16};
-    return run_step_si(h, one_group(lr, weight_decay), nullptr, norm_state, skip_nonfinite, counters, path_w, omega, theta_star,
-                       penalty_coef, (hipStream_t)stream);
+    const step_head h = make_head(theta, grad, exp_avg, exp_avg_sq, chunk_table, nchunks, seg_active, seg_step, nseg, all_active,
+                                  beta1, beta2, eps, grad_scale, shadow_bf16, nullptr, norm_state, skip_nonfinite, counters);
+    if (!head_ok(h) || !si_operands_ok(path_w, omega, theta_star)) return IA_INVALID_VALUE;
+    return run_step_si(h, one_group(lr, weight_decay), path_w, omega, theta_star, penalty_coef, (hipStream_t)stream);
 }
 
 extern "C" int ia_si_consolidate(const float* theta, float* theta_star, float* path_w, float* omega, float xi, int64_t n,
@@ -1645,20 +1301,12 @@ extern "C" int ia_grad_norm_projected(const float* grad, const int32_t* chunk_ta
                                       int nseg, float grad_scale, float max_norm, const int32_t* seg_active, float* seg_norm,
                                       float* norm_state, void* workspace, size_t workspace_bytes, const float* ref,
                                       const float* proj_state, ia_stream_t stream) {
-    if (!grad || !chunk_table || !seg_chunk_begin || !seg_norm || !norm_state || !workspace || !ref || !proj_state ||
-        nchunks <= 0 || nseg <= 0)
-        return IA_INVALID_VALUE;
-    if (!ia_is_aligned(grad, 16) || !ia_is_aligned(ref, 16) || !ia_is_aligned(chunk_table, 16) || !ia_is_aligned(workspace, 4) ||
-        !ia_is_aligned(proj_state, 4))
+    if (!norm_operands_ok(grad, chunk_table, nchunks, seg_chunk_begin, nseg, seg_norm, norm_state, workspace) || !ref ||
+        !proj_state || !ia_is_aligned(ref, 16) || !ia_is_aligned(proj_state, 4))
         return IA_INVALID_VALUE;
     if (workspace_bytes < ia_grad_norm_workspace_bytes(nchunks)) return IA_WORKSPACE_TOO_SMALL;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(proj_norm_kernel, dim3(nchunks < 2048 ? nchunks : 2048), dim3(CL_THREADS), 0, st, grad, ref,
-                       (const int4*)chunk_table, nchunks, seg_active, proj_state, grad_scale, (float*)workspace);
-    hipLaunchKernelGGL(grad_norm_finish_projected_kernel, dim3(1), dim3(GN_THREADS), 0, st, (const float*)workspace,
-                       seg_chunk_begin, nseg, fabsf(grad_scale), max_norm, seg_norm, norm_state, proj_state);
-    IA_RETURN_IF_LAUNCH_FAILED();
-    return IA_OK;
+    return run_consumed_norm(grad, chunk_table, nchunks, seg_chunk_begin, nseg, grad_scale, max_norm, seg_active, seg_norm,
+                             norm_state, workspace, agem_source{ref, proj_state}, proj_state + 3, (hipStream_t)stream);
 }
 
 extern "C" int ia_adamw_step_segmented_projected(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq,
@@ -1667,16 +1315,13 @@ extern "C" int ia_adamw_step_segmented_projected(float* theta, const float* grad
                                                  float weight_decay, float grad_scale, void* shadow_bf16, const float* norm_state,
                                                  int skip_nonfinite, int32_t* counters, const float* ref, const float* proj_state,
                                                  int32_t* proj_counters, ia_stream_t stream) {
-    if (!step_head_ok(theta, grad, exp_avg, exp_avg_sq, chunk_table, nchunks, seg_active, seg_step, nseg, shadow_bf16) ||
-        !proj_operands_ok(norm_state, counters, ref, proj_state, proj_counters))
-        return IA_INVALID_VALUE;
-    const step_head h = {theta, grad, exp_avg, exp_avg_sq, (const int4*)chunk_table, nchunks, seg_active, seg_step, nseg, all_active,
-                         beta1, beta2, eps, grad_scale, (unsigned short*)shadow_bf16};
-    return run_step_projected(h, one_group(lr, weight_decay), nullptr, norm_state, skip_nonfinite, counters, ref, proj_state,
-                              proj_counters, (hipStream_t)stream);
+    const step_head h = make_head(theta, grad, exp_avg, exp_avg_sq, chunk_table, nchunks, seg_active, seg_step, nseg, all_active,
+                                  beta1, beta2, eps, grad_scale, shadow_bf16, nullptr, norm_state, skip_nonfinite, counters);
+    if (!head_ok(h) || !proj_operands_ok(ref, proj_state, proj_counters)) return IA_INVALID_VALUE;
+    return run_step_agem(h, one_group(lr, weight_decay), ref, proj_state, proj_counters, (hipStream_t)stream);
 }
 
-// Any of the four steps with per-group lr / weight_decay: the operands that are present select the step.
+// The plain, clipped, SI or projected step with per-group lr / weight_decay: the operands that are present select the variant.
 extern "C" int ia_adamw_step_segmented_grouped(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq,
                                                const int32_t* chunk_table, int nchunks, int32_t* seg_active, int32_t* seg_step,
                                                int nseg, int all_active, float beta1, float beta2, float eps, float grad_scale,
@@ -1685,25 +1330,17 @@ extern "C" int ia_adamw_step_segmented_grouped(float* theta, const float* grad, 
                                                int32_t* counters, float* path_w, const float* omega, const float* theta_star,
                                                float penalty_coef, const float* ref, const float* proj_state,
                                                int32_t* proj_counters, ia_stream_t stream) {
-    if (!step_head_ok(theta, grad, exp_avg, exp_avg_sq, chunk_table, nchunks, seg_active, seg_step, nseg, shadow_bf16))
-        return IA_INVALID_VALUE;
-    if (ngroups < 1 || ngroups > IA_MAX_PARAM_GROUPS || !group_lr || !group_weight_decay || (ngroups > 1 && !seg_group) ||
-        (seg_group && !ia_is_aligned(seg_group, 4)))
-        return IA_INVALID_VALUE;
+    const step_head h = make_head(theta, grad, exp_avg, exp_avg_sq, chunk_table, nchunks, seg_active, seg_step, nseg, all_active,
+                                  beta1, beta2, eps, grad_scale, shadow_bf16, seg_group, norm_state, skip_nonfinite, counters);
     const bool si = path_w || omega || theta_star, proj = ref || proj_state || proj_counters;
-    if ((si && proj) || (norm_state == nullptr) != (counters == nullptr)) return IA_INVALID_VALUE;
-    if (si && !si_operands_ok(norm_state, counters, path_w, omega, theta_star)) return IA_INVALID_VALUE;
-    if (proj && !proj_operands_ok(norm_state, counters, ref, proj_state, proj_counters)) return IA_INVALID_VALUE;
-    group_table gt = {};
-    gt.n = ngroups;
-    for (int k = 0; k < ngroups; ++k) { gt.lr[k] = group_lr[k]; gt.weight_decay[k] = group_weight_decay[k]; }
-    const step_head h = {theta, grad, exp_avg, exp_avg_sq, (const int4*)chunk_table, nchunks, seg_active, seg_step, nseg, all_active,
-                         beta1, beta2, eps, grad_scale, (unsigned short*)shadow_bf16};
+    if (!head_ok(h) || !groups_ok(seg_group, ngroups, group_lr, group_weight_decay) || (si && proj) ||
+        (si && !si_operands_ok(path_w, omega, theta_star)) || (proj && !proj_operands_ok(ref, proj_state, proj_counters)))
+        return IA_INVALID_VALUE;
+    const group_table gt = make_group_table(ngroups, group_lr, group_weight_decay);
     hipStream_t st = (hipStream_t)stream;
-    if (proj) return run_step_projected(h, gt, seg_group, norm_state, skip_nonfinite, counters, ref, proj_state, proj_counters, st);
-    if (si)
-        return run_step_si(h, gt, seg_group, norm_state, skip_nonfinite, counters, path_w, omega, theta_star, penalty_coef, st);
-    return run_step(h, gt, seg_group, norm_state, skip_nonfinite, counters, st);
+    if (proj) return run_step_agem(h, gt, ref, proj_state, proj_counters, st);
+    if (si) return run_step_si(h, gt, path_w, omega, theta_star, penalty_coef, st);
+    return run_step(h, gt, plain_step{}, step_extras{}, st);
 }
 
 extern "C" size_t ia_gem_workspace_bytes(int nchunks, int max_tasks) {
@@ -1744,18 +1381,13 @@ extern "C" int ia_grad_norm_gem(const float* grad, const int32_t* chunk_table, i
                                 float grad_scale, float max_norm, const int32_t* seg_active, float* seg_norm, float* norm_state,
                                 void* workspace, size_t workspace_bytes, const float* refs, int64_t stride, int ntasks,
                                 const float* gem_state, ia_stream_t stream) {
-    if (!grad || !chunk_table || !seg_chunk_begin || !seg_norm || !norm_state || !workspace || nchunks <= 0 || nseg <= 0 ||
+    if (!norm_operands_ok(grad, chunk_table, nchunks, seg_chunk_begin, nseg, seg_norm, norm_state, workspace) ||
         !gem_operands_ok(refs, stride, ntasks, gem_state))
         return IA_INVALID_VALUE;
-    if (!ia_is_aligned(grad, 16) || !ia_is_aligned(chunk_table, 16) || !ia_is_aligned(workspace, 4)) return IA_INVALID_VALUE;
     if (workspace_bytes < ia_grad_norm_workspace_bytes(nchunks)) return IA_WORKSPACE_TOO_SMALL;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(gem_norm_kernel, dim3(nchunks < 2048 ? nchunks : 2048), dim3(CL_THREADS), 0, st, grad, refs, stride, ntasks,
-                       (const int4*)chunk_table, nchunks, seg_active, gem_state, grad_scale, (float*)workspace);
-    hipLaunchKernelGGL(grad_norm_finish_gem_kernel, dim3(1), dim3(GN_THREADS), 0, st, (const float*)workspace, seg_chunk_begin,
-                       nseg, fabsf(grad_scale), max_norm, seg_norm, norm_state, gem_state);
-    IA_RETURN_IF_LAUNCH_FAILED();
-    return IA_OK;
+    return run_consumed_norm(grad, chunk_table, nchunks, seg_chunk_begin, nseg, grad_scale, max_norm, seg_active, seg_norm,
+                             norm_state, workspace, gem_source{refs, stride, ntasks, gem_state}, gem_state + GEM_VIOLATED,
+                             (hipStream_t)stream);
 }
 
 extern "C" int ia_adamw_step_segmented_gem(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq,
@@ -1765,21 +1397,19 @@ extern "C" int ia_adamw_step_segmented_gem(float* theta, const float* grad, floa
                                            const float* group_weight_decay, const float* norm_state, int skip_nonfinite,
                                            int32_t* counters, const float* refs, int64_t stride, int ntasks, const float* gem_state,
                                            int32_t* gem_counters, ia_stream_t stream) {
-    if (!step_head_ok(theta, grad, exp_avg, exp_avg_sq, chunk_table, nchunks, seg_active, seg_step, nseg, shadow_bf16))
+    const step_head h = make_head(theta, grad, exp_avg, exp_avg_sq, chunk_table, nchunks, seg_active, seg_step, nseg, all_active,
+                                  beta1, beta2, eps, grad_scale, shadow_bf16, seg_group, norm_state, skip_nonfinite, counters);
+    if (!head_ok(h) || !groups_ok(seg_group, ngroups, group_lr, group_weight_decay) || !gem_counters ||
+        !ia_is_aligned(gem_counters, 4) || !gem_operands_ok(refs, stride, ntasks, gem_state))
         return IA_INVALID_VALUE;
-    if (ngroups < 1 || ngroups > IA_MAX_PARAM_GROUPS || !group_lr || !group_weight_decay || (ngroups > 1 && !seg_group) ||
-        (seg_group && !ia_is_aligned(seg_group, 4)))
-        return IA_INVALID_VALUE;
-    if ((norm_state == nullptr) != (counters == nullptr) || !gem_counters || !ia_is_aligned(gem_counters, 4) ||
-        !gem_operands_ok(refs, stride, ntasks, gem_state))
-        return IA_INVALID_VALUE;
-    group_table gt = {};
-    gt.n = ngroups;
-    for (int k = 0; k < ngroups; ++k) { gt.lr[k] = group_lr[k]; gt.weight_decay[k] = group_weight_decay[k]; }
-    const step_head h = {theta, grad, exp_avg, exp_avg_sq, (const int4*)chunk_table, nchunks, seg_active, seg_step, nseg, all_active,
-                         beta1, beta2, eps, grad_scale, (unsigned short*)shadow_bf16};
-    return run_step_gem(h, gt, seg_group, norm_state, skip_nonfinite, counters, refs, stride, ntasks, gem_state, gem_counters,
-                        (hipStream_t)stream);
+    step_extras x = {};
+    x.flags_preset = true;
+    x.projected = gem_state + GEM_VIOLATED;
+    x.projected_count = gem_counters;          // gem_counters = {projected steps, unsolved steps}
+    x.solved = gem_state + GEM_SOLVED;
+    x.unsolved_count = gem_counters + 1;
+    return run_step(h, make_group_table(ngroups, group_lr, group_weight_decay), gem_step{{refs, stride, ntasks, gem_state}}, x,
+                    (hipStream_t)stream);
 }
 
 extern "C" int ia_adamw_step_segmented_masked(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq,
@@ -1789,33 +1419,15 @@ extern "C" int ia_adamw_step_segmented_masked(float* theta, const float* grad, f
                                               const float* group_weight_decay, const float* norm_state, int skip_nonfinite,
                                               int32_t* counters, const float* base, float* scores, const int32_t* seg_kind,
                                               float threshold, ia_stream_t stream) {
-    if (!step_head_ok(theta, grad, exp_avg, exp_avg_sq, chunk_table, nchunks, seg_active, seg_step, nseg, shadow_bf16))
+    const step_head h = make_head(theta, grad, exp_avg, exp_avg_sq, chunk_table, nchunks, seg_active, seg_step, nseg, all_active,
+                                  beta1, beta2, eps, grad_scale, shadow_bf16, seg_group, norm_state, skip_nonfinite, counters);
+    if (!head_ok(h) || !groups_ok(seg_group, ngroups, group_lr, group_weight_decay) || !base || !scores || !seg_kind ||
+        !ia_is_aligned(base, 16) || !ia_is_aligned(scores, 16) || !ia_is_aligned(seg_kind, 4))
         return IA_INVALID_VALUE;
-    if (ngroups < 1 || ngroups > IA_MAX_PARAM_GROUPS || !group_lr || !group_weight_decay || (ngroups > 1 && !seg_group) ||
-        (seg_group && !ia_is_aligned(seg_group, 4)))
-        return IA_INVALID_VALUE;
-    if ((norm_state == nullptr) != (counters == nullptr) || !base || !scores || !seg_kind || !ia_is_aligned(base, 16) ||
-        !ia_is_aligned(scores, 16) || !ia_is_aligned(seg_kind, 4))
-        return IA_INVALID_VALUE;
-    group_table gt = {};
-    gt.n = ngroups;
-    for (int k = 0; k < ngroups; ++k) { gt.lr[k] = group_lr[k]; gt.weight_decay[k] = group_weight_decay[k]; }
-    const step_head h = {theta, grad, exp_avg, exp_avg_sq, (const int4*)chunk_table, nchunks, seg_active, seg_step, nseg, all_active,
-                         beta1, beta2, eps, grad_scale, (unsigned short*)shadow_bf16};
-    hipStream_t st = (hipStream_t)stream;
-    if (h.all_active) {
-        if (!mark_all_active(h, st)) return IA_LAUNCH_FAILED;
-    } else if (!norm_state) {   // with norm_state, ia_grad_norm's first pass has set the flags
-        launch_activity(h, st);
-    }
-    auto kernel = norm_state ? adamw_seg_masked_kernel<true> : adamw_seg_masked_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3(step_grid(h)), dim3(CL_THREADS), 0, st, h.theta, h.grad, h.exp_avg, h.exp_avg_sq, h.table,
-                       h.nchunks, h.seg_active, h.seg_step, gt, seg_group, h.b1, h.b2, h.eps, h.grad_scale, h.shadow, norm_state,
-                       skip_nonfinite, base, scores, seg_kind, threshold);
-    hipLaunchKernelGGL(seg_step_advance_masked_kernel, dim3((h.nseg + 255) / 256), dim3(256), 0, st, h.seg_active, h.seg_step,
-                       h.nseg, norm_state, skip_nonfinite, counters, seg_kind);
-    IA_RETURN_IF_LAUNCH_FAILED();
-    return IA_OK;
+    step_extras x = {};
+    x.seg_kind = seg_kind;
+    return run_step(h, make_group_table(ngroups, group_lr, group_weight_decay), masked_step{base, scores, seg_kind, threshold}, x,
+                    (hipStream_t)stream);
 }
 
 extern "C" int ia_mask_pack(const float* scores, const int32_t* chunk_table, int nchunks, const int32_t* seg_kind, int nseg,

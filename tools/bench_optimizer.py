@@ -1,11 +1,13 @@
 """FusedAdamW._apply on the flat buffers of BASELINE configs[1]'s trainable set (Conformer-medium, freeze_layer(m, 12)):
 plain, with max_grad_norm=1.0 (live-segment detection on / every segment live), and with a Synaptic Intelligence path integral
 attached (first task: w only; later tasks: omega and theta* read as well, every segment live), and `grouped`: the plain step
-with layerwise_lr_groups + no-decay parameter groups (ia_adamw_step_segmented_grouped).  Per leg: `<leg>_us` device time of one
+with layerwise_lr_groups + no-decay parameter groups (ia_adamw_step_segmented_grouped), and `masked`: Piggyback on its default
+kinds without clipping (ia_adamw_step_segmented_masked: matrices masked, heads free, the rest frozen).  Per leg: `<leg>_us` device time of one
 _apply between two events, `<leg>_host_us` host wall-clock of one step() call with no synchronisation inside the timed loop
 (what the training loop's thread pays: Python, ctypes and the launches).  Developer tool; one JSON line.
 
-`--legs plain` uses nothing newer than the segmented AdamW itself, so the same file times an older checkout."""
+`--legs plain` uses nothing newer than the segmented AdamW itself, so the same file times an older checkout; every other leg
+touches its own method only when it is asked for."""
 import argparse
 import json
 import os
@@ -45,7 +47,7 @@ def host_timeit(fn, warmup=5, n=50):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--legs", default="plain,clip,clip_all_live,si_first_task,si_penalty,grouped")
+    ap.add_argument("--legs", default="plain,clip,clip_all_live,si_first_task,si_penalty,grouped,masked")
     args = ap.parse_args()
     from indic_cl_asr_amd import cl
     from indic_cl_asr_amd.config import model_config
@@ -59,7 +61,7 @@ def main():
     for leg in args.legs.split(","):
         kw, live = {"plain": ({}, False), "clip": ({"max_grad_norm": 1.0}, False),
                     "clip_all_live": ({"max_grad_norm": 1.0}, True), "si_first_task": ({}, False),
-                    "si_penalty": ({}, True), "grouped": ({}, False)}[leg]
+                    "si_penalty": ({}, True), "grouped": ({}, False), "masked": ({}, False)}[leg]
         if leg == "grouped":
             kw["param_groups"] = cl.layerwise_lr_groups(flat, 1e-4, 0.9)
         if leg.startswith("si_"):
@@ -67,6 +69,8 @@ def main():
             if leg == "si_penalty":                  # a consolidated task: the step reads omega and theta* and adds the penalty
                 si.omega.flat.uniform_(0.0, 1.0)
                 si.tasks_consolidated = 1
+        if leg == "masked":
+            kw["masks"] = cl.Piggyback(flat)
         opt = cl.FusedAdamW(flat, lr=1e-4, **kw)
         flat.grad.copy_(grad)
         if leg == "grouped":
