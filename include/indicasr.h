@@ -973,6 +973,58 @@ int ia_mask_pack(const float* scores, const int32_t* chunk_table, int nchunks, c
                  uint64_t* bits, int64_t nwords, int32_t* seg_kept, ia_stream_t stream);
 int ia_mask_apply(float* theta, const float* base, const uint64_t* bits, int64_t nwords, const int32_t* chunk_table, int nchunks,
                   const int32_t* seg_kind, int nseg, void* shadow_bf16, ia_stream_t stream);
+/* PackNet (Mallya, Lazebnik 2018): all languages share one weight buffer and every weight has one owner.  After a language is
+ * trained the smallest-magnitude fraction of the weights it used is released; the rest are its property and never move again.
+ * owner: uint8[flat length] on the device, laid out as theta: 0 free, t >= 1 owned by the t-th language (up to 255), 0 in the
+ * alignment gaps.  seg_kind: the kinds of Piggyback with the same numbering, `packed` in the IA_MASK_MASKED slot.
+ *   IA_MASK_MASKED (packed)  per element of a live tensor: owner == train_owner -> exactly the plain rule, AdamW on
+ *                   grad * grad_scale [* coef when clipping] with the group's lr and weight decay; otherwise theta, exp_avg and
+ *                   exp_avg_sq keep their bit patterns (a -0.0f stays -0.0f).  shadow = bf16(theta) for every element.
+ *   IA_MASK_FREE    the plain step, bit for bit;   IA_MASK_FROZEN  never written, only the shadow is refreshed
+ * A tensor that received no gradient only has its shadow kept in step.  Step counters advance for live free and packed tensors.
+ * train_owner: 0 while a language trains (the free weights learn beside everything the earlier languages own), t while language
+ * t retrains after its pruning, and a value no element carries (-1) when no language is open: every packed tensor is frozen then.
+ * ia_adamw_step_segmented_packed  one AdamW launch, 31 B per packed element (reads grad, theta, the moments and the owner byte;
+ *                          writes theta, the moments and the bf16 image), 30 B per free one.  Operands as
+ *                          ia_adamw_step_segmented_masked; norm_state from ia_grad_norm_packed.
+ * ia_grad_norm_packed      ia_grad_norm (same outputs, same workspace) of the gradient the step consumes: the trainable elements of
+ *                          packed tensors and every element of free tensors; +0 where owner != train_owner and in frozen tensors.
+ *                          Liveness is the raw gradient's: seg_active (NULL: every tensor live) is set here, from any non-zero
+ *                          gradient element, as `grad is not None` is in torch.
+ * ia_pack_prune            for every packed tensor on its own: F = its elements with owner == 0, n = |F|, r = floor((double)fraction
+ *                          * n) computed on the device from the float `fraction`.  r == 0: nothing is released.  Otherwise the
+ *                          cutoff c is the r-th smallest (1-based) |theta| over F; the elements of F with |theta| <= c are released
+ *                          (theta = +0.0f, owner stays 0: ties at the cutoff all go, as kthvalue followed by abs().le(cutoff) has
+ *                          it); every other element of F gets owner = task.  For every element of a packed tensor exp_avg =
+ *                          exp_avg_sq = +0 (the retraining starts with fresh moments; the step counters are the caller's).
+ *                          shadow = bf16(theta) for every tensor when a shadow is given.  seg_counts: int32[2 * nseg], zeroed
+ *                          here, {released, newly owned} per tensor.  The order is that of the 31-bit pattern of |theta|: exact for
+ *                          finite values, and what it says for infinities and NaNs (above every finite value) is the definition.
+ *                          An exact radix select (digits of 8, 8, 8 and 7 bits): per digit one streaming pass over theta and owner
+ *                          (5 B per packed element) with integer atomics only, so the result does not depend on scheduling; no
+ *                          host synchronisation, no allocation: workspace of ia_pack_prune_workspace_bytes(nseg), caller-owned.
+ * ia_pack_apply            owner map -> weights: theta = (lo <= owner && owner <= hi) ? base : +0.0f inside packed tensors, then
+ *                          shadow = bf16(theta) for every tensor when a shadow is given.  One launch.
+ * IA_INVALID_VALUE before any device work: a NULL required pointer, counts <= 0, task outside 1..255, fraction outside [0, 1) (NaN
+ * included), counters without norm_state (or the reverse), the group conditions of ia_adamw_step_segmented_grouped, misaligned
+ * buffers (16 bytes for the flat buffers, owner, the chunk table and the prune workspace, 8 for the shadow, 4 for seg_kind and
+ * seg_counts). */
+int ia_adamw_step_segmented_packed(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq, const int32_t* chunk_table,
+                                   int nchunks, int32_t* seg_active, int32_t* seg_step, int nseg, int all_active, float beta1,
+                                   float beta2, float eps, float grad_scale, void* shadow_bf16, const int32_t* seg_group,
+                                   int ngroups, const float* group_lr, const float* group_weight_decay, const float* norm_state,
+                                   int skip_nonfinite, int32_t* counters, const uint8_t* owner, const int32_t* seg_kind,
+                                   int train_owner, ia_stream_t stream);
+int ia_grad_norm_packed(const float* grad, const int32_t* chunk_table, int nchunks, const int32_t* seg_chunk_begin, int nseg,
+                        float grad_scale, float max_norm, int32_t* seg_active, float* seg_norm, float* norm_state,
+                        void* workspace, size_t workspace_bytes, const uint8_t* owner, const int32_t* seg_kind, int train_owner,
+                        ia_stream_t stream);
+size_t ia_pack_prune_workspace_bytes(int nseg);
+int ia_pack_prune(float* theta, float* exp_avg, float* exp_avg_sq, uint8_t* owner, const int32_t* chunk_table, int nchunks,
+                  const int32_t* seg_kind, int nseg, float fraction, int task, void* shadow_bf16, int32_t* seg_counts,
+                  void* workspace, size_t workspace_bytes, ia_stream_t stream);
+int ia_pack_apply(float* theta, const float* base, const uint8_t* owner, const int32_t* chunk_table, int nchunks,
+                  const int32_t* seg_kind, int nseg, int lo, int hi, void* shadow_bf16, ia_stream_t stream);
 
 /* ---- CTC head + loss on RAW logits (ConvASRDecoder.forward + CTCLoss.forward, A/modules/conv_asr.py:459-490 and
  * A/losses/ctc.py:68-82, without the [B,T,V] log-prob tensor and without a softmax backward pass): logits [B*T, ld] f32 with V

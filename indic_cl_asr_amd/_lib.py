@@ -224,6 +224,12 @@ SIGNATURES = {
                                             _vp, _i, _vp, _vp, _vp, _vp, _f, _vp]),
     "ia_mask_pack": (_i, [_vp, _vp, _i, _vp, _i, _f, _vp, _i64, _vp, _vp]),
     "ia_mask_apply": (_i, [_vp, _vp, _vp, _i64, _vp, _i, _vp, _i, _vp, _vp]),
+    "ia_adamw_step_segmented_packed": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _f, _vp, _vp, _i, _vp, _vp,
+                                            _vp, _i, _vp, _vp, _vp, _i, _vp]),
+    "ia_grad_norm_packed": (_i, [_vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _i, _vp]),
+    "ia_pack_prune_workspace_bytes": (_sz, [_i]),
+    "ia_pack_prune": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _f, _i, _vp, _vp, _vp, _sz, _vp]),
+    "ia_pack_apply": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp]),
 }
 
 _lib = None

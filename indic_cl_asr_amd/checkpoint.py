@@ -178,7 +178,9 @@ def load_memory(memory, path):
 
 
 def save_masks(masks, path):
-    """Persist cl.Piggyback.state_dict(): kinds, base, scores and every saved language's bits, free tensors and buffers."""
+    """Persist cl.Piggyback.state_dict() (kinds, base, scores and every saved language's bits, free tensors and buffers) or
+    cl.PackNet.state_dict() (kinds, base, the owner map, the open language and its phase, every finished language's free tensors
+    and buffers)."""
     torch.save(masks.state_dict(), path)
 
 

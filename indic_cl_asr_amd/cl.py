@@ -635,18 +635,35 @@ _KIND_NAMES = ("free", "masked", "frozen")
 _HEAD_RE = re.compile(r"^(joint\.joint_net\.[^.]+\.[^.]+\.[^.]+|ctc_decoder\.decoder_layers\.0\.(weight|bias))$")
 
 
-def _select_names(flat: FlatParams, spec, what: str) -> List[str]:
+def _select_names(flat: FlatParams, spec, what: str, who: str = "Piggyback") -> List[str]:
     """`spec` is a list of parameter names or one regular expression (re.search on the name, as "match" of param_groups)."""
     if isinstance(spec, str):
         names = [n for n in flat.names if re.search(spec, n)]
         if not names:
-            raise ValueError(f"Piggyback: {what} '{spec}' matches no trainable tensor")
+            raise ValueError(f"{who}: {what} '{spec}' matches no trainable tensor")
         return names
     names, known = list(spec), set(flat.names)
     for n in names:
         if n not in known:
-            raise ValueError(f"Piggyback: {what}: '{n}' is not a trainable tensor of this FlatParams")
+            raise ValueError(f"{who}: {what}: '{n}' is not a trainable tensor of this FlatParams")
     return names
+
+
+def _select_kinds(flat: FlatParams, special, frozen, who: str, special_name: str) -> List[int]:
+    """The kind of every trainable tensor, for Piggyback (`special` is masked=) and PackNet (packed=).  Defaults: special = tensors
+    with dim() >= 2 that are not heads, free = the per-language heads, frozen = everything else.  `special` / `frozen` replace the
+    default sets; a tensor named by one of them leaves the other's default set; one both name raises; what neither holds is free."""
+    f = flat
+    heads = {n for n in f.names if _HEAD_RE.search(n)}
+    default_special = [n for n, p in zip(f.names, f.params) if p.dim() >= 2 and n not in heads]
+    given_s = None if special is None else _select_names(f, special, f"{special_name}=", who)
+    given_f = None if frozen is None else _select_names(f, frozen, "frozen=", who)
+    both = sorted(set(given_s or ()) & set(given_f or ()))
+    if both:
+        raise ValueError(f"{who}: '{both[0]}' is claimed by {special_name}= and by frozen=")
+    s_set = set(default_special if given_s is None else given_s) - set(given_f or ())
+    f_set = (set(f.names) - heads - set(default_special) if given_f is None else set(given_f)) - s_set
+    return [MASK_MASKED if n in s_set else MASK_FROZEN if n in f_set else MASK_FREE for n in f.names]
 
 
 class Piggyback:
@@ -678,16 +695,7 @@ class Piggyback:
         if not self.init >= self.threshold:
             raise ValueError(f"Piggyback: init ({init}) must be >= threshold ({threshold}): a new language starts with every bit on")
         f = self.flat
-        heads = {n for n in f.names if _HEAD_RE.search(n)}
-        default_masked = [n for n, p in zip(f.names, f.params) if p.dim() >= 2 and n not in heads]
-        given_m = None if masked is None else _select_names(f, masked, "masked=")
-        given_f = None if frozen is None else _select_names(f, frozen, "frozen=")
-        both = sorted(set(given_m or ()) & set(given_f or ()))
-        if both:
-            raise ValueError(f"Piggyback: '{both[0]}' is claimed by masked= and by frozen=")
-        m_set = set(default_masked if given_m is None else given_m) - set(given_f or ())
-        f_set = (set(f.names) - heads - set(default_masked) if given_f is None else set(given_f)) - m_set
-        self._kinds = [MASK_MASKED if n in m_set else MASK_FROZEN if n in f_set else MASK_FREE for n in f.names]
+        self._kinds = _select_kinds(f, masked, frozen, "Piggyback", "masked")
         dev = f.theta.device
         self.seg_kind = torch.tensor(self._kinds, dtype=torch.int32, device=dev)
         flush_pending_updates()
@@ -852,6 +860,256 @@ class Piggyback:
                         for lang, r in sd["languages"].items()}
 
 
+# ----------------------------------------------------------------------------- PackNet
+_PACK_KIND_NAMES = ("free", "packed", "frozen")       # the numbering of _KIND_NAMES, `packed` in the masked slot
+_PACK_PHASES = (None, "train", "retrain", "finished")
+
+
+class PackNet:
+    """PackNet (Mallya, Lazebnik, CVPR 2018): parameter isolation by weight ownership.  All languages share `flat.theta`; one byte
+    per weight (`owner`) says whose it is: 0 free, t >= 1 the t-th language's.  A language trains the free weights beside
+    everything the earlier languages own, then `prune` releases the smallest-magnitude fraction of the weights it used (they are
+    set to +0 and stay free) and the rest become its property; a short retraining moves only those.  Nothing a later language
+    does touches an owned weight, so forgetting is exactly zero; unlike Piggyback every language trains weights of its own.
+
+    The kinds are Piggyback's, with the same defaults and overrides (`packed=` in the place of `masked=`):
+      packed  the owner map decides per element.  Default: tensors with dim() >= 2 that are not heads.
+      free    plain AdamW, snapshotted per language.  Default: the per-language heads.
+      frozen  never written.  Default: everything else.
+
+        pn  = PackNet(model_or_flat, prune=0.5)
+        opt = FusedAdamW(flat, ..., masks=pn)     # the step is ia_adamw_step_segmented_packed, one launch
+        pn.begin_language("hi", opt)              # task t = number of languages + 1; train_owner = 0
+        ...train...
+        pn.prune(opt)                             # ia_pack_prune on the device; train_owner = t
+        ...retrain...                             # only language t's weights move; the released ones stay +0
+        pn.finish_language()                      # base <- theta, heads and module buffers recorded; train_owner = -1
+        pn.activate("hi")                         # theta = 1 <= owner <= task("hi") ? base : 0, heads and buffers restored
+
+    State: the owner map (1 B per flat element) and `base`, the weights as the latest finished language left them (4 B), against
+    Piggyback's two fp32 buffers (8 B) while training; per language only its free tensors and the module buffers.  While no
+    language is open train_owner is -1 and a step moves no packed weight.
+
+    Limits: one language is active at a time, as with Piggyback; a language sees the weights of the languages before it, so the
+    order matters; at most 255 languages."""
+
+    def __init__(self, model_or_flat, packed=None, frozen=None, prune=0.5):
+        self.flat = _as_flat(model_or_flat)
+        self.prune_fraction = self._checked_fraction(prune)
+        f = self.flat
+        self._kinds = _select_kinds(f, packed, frozen, "PackNet", "packed")
+        dev = f.theta.device
+        self.seg_kind = torch.tensor(self._kinds, dtype=torch.int32, device=dev)
+        flush_pending_updates()
+        self.base = FlatDict(f, f.theta.clone())
+        self.owner = torch.zeros(f.numel, dtype=torch.uint8, device=dev)
+        self.seg_counts = torch.zeros(len(f.entries), 2, dtype=torch.int32, device=dev)    # {released, newly owned} of the last prune
+        self.current: Optional[str] = None
+        self.phase: Optional[str] = None       # None | "train" | "retrain" | "finished"
+        self.train_owner = -1
+        self.tasks: Dict[str, int] = {}        # lang -> task index, in language order (the open language included)
+        self.records: Dict[str, dict] = {}     # finished lang -> {"task": int, "free": {name: tensor}, "buffers": {name: tensor}}
+        self._optimizer = None                 # weak reference to the FusedAdamW that holds the moments and the bf16 shadow
+        self._workspace = None
+
+    @staticmethod
+    def _checked_fraction(fraction) -> float:
+        fraction = float(fraction)
+        if not 0.0 <= fraction < 1.0:
+            raise ValueError(f"PackNet: prune fraction {fraction} is outside [0, 1)")
+        return fraction
+
+    # -- kinds -----------------------------------------------------------------------------------------------------
+    def kinds(self) -> Dict[str, str]:
+        return {n: _PACK_KIND_NAMES[k] for n, k in zip(self.flat.names, self._kinds)}
+
+    def _names_of(self, kind):
+        return [n for n, k in zip(self.flat.names, self._kinds) if k == kind]
+
+    def _packed_entries(self):
+        return [e for k, e in enumerate(self.flat.entries) if self._kinds[k] == MASK_MASKED]
+
+    def languages(self) -> List[str]:
+        return list(self.records)
+
+    def _attached(self, optimizer=None):
+        opt = optimizer if optimizer is not None else (self._optimizer() if self._optimizer is not None else None)
+        if opt is not None and opt.flat is not self.flat:
+            raise ValueError("optimizer belongs to another FlatParams")
+        return opt
+
+    def _weights_changed(self, opt):
+        """What FusedAdamW._after_update does: the weight epoch moves and the flat shadow views go to the shadow cache."""
+        if opt is not None:
+            opt._after_update()
+        else:
+            from .ops import fast
+            fast.bump_weight_epoch()
+
+    def _apply_owners(self, lo, hi):
+        """theta = lo <= owner <= hi ? base : +0 on packed tensors and the bf16 image of every tensor, one launch."""
+        f, opt = self.flat, self._attached()
+        st = _lib.lib().ia_pack_apply(_lib.ptr(f.theta), _lib.ptr(self.base.flat), _lib.ptr(self.owner), _lib.ptr(f.chunk_table),
+                                      f.chunk_table.shape[0], _lib.ptr(self.seg_kind), len(f.entries), int(lo), int(hi),
+                                      _lib.ptr(opt.shadow if opt is not None else None), _lib.stream_ptr())
+        _lib.check(st, "ia_pack_apply")
+        self._weights_changed(opt)
+
+    # -- the per-language loop ---------------------------------------------------------------------------------------
+    def begin_language(self, lang: str, optimizer: Optional["FusedAdamW"] = None):
+        """Open `lang` as task number of languages + 1 and train the free weights (train_owner = 0).  The first language keeps
+        theta as it is: it prunes the pretrained network.  Later ones start from `owner >= 1 ? base : +0`.  With an optimizer
+        (given, or attached through masks=) the moments and step counters of every tensor that is not frozen are zeroed."""
+        if self.phase in ("train", "retrain"):
+            raise RuntimeError(f"PackNet.begin_language: '{self.current}' is still open (phase '{self.phase}'); prune() and "
+                               "finish_language() first")
+        if lang in self.tasks:
+            raise ValueError(f"PackNet.begin_language: '{lang}' has been trained already; activate() shows it")
+        task = len(self.records) + 1
+        if task > 255:
+            raise ValueError("PackNet: the owner map holds at most 255 languages")
+        opt = self._attached(optimizer)
+        flush_pending_updates()
+        packed = self._packed_entries()
+        free = torch.stack([(self.owner[o:o + k] == 0).sum() for _, o, k, _ in packed]).sum() if packed else None
+        if free is None or int(free) == 0:          # one small device read per language
+            raise RuntimeError(f"PackNet.begin_language: no packed tensor has a free weight left for '{lang}'")
+        if optimizer is not None:
+            self._optimizer = weakref.ref(optimizer)
+        if self.records:
+            self._apply_owners(1, 255)
+        if opt is not None:
+            for k, (n, o, cnt, shape) in enumerate(self.flat.entries):
+                if self._kinds[k] != MASK_FROZEN:
+                    opt.exp_avg[o:o + cnt].zero_()
+                    opt.exp_avg_sq[o:o + cnt].zero_()
+            opt.seg_step.mul_((self.seg_kind == MASK_FROZEN).to(torch.int32))
+        self.tasks[lang] = task
+        self.current, self.phase, self.train_owner = lang, "train", 0
+
+    def prune(self, optimizer: Optional["FusedAdamW"] = None, fraction: Optional[float] = None):
+        """Per packed tensor, release the `fraction` (default: the constructor's) of its free weights with the smallest magnitude
+        and give the rest to the open language; the moments of the packed tensors are zeroed and their step counters with them.
+        From here on only the language's own weights move (train_owner = its task).  No host synchronisation."""
+        if self.phase != "train":
+            raise RuntimeError("PackNet.prune: " + ("no language is open; call begin_language() first" if self.phase != "retrain"
+                                                    else f"'{self.current}' has been pruned already"))
+        fraction = self.prune_fraction if fraction is None else self._checked_fraction(fraction)
+        opt = self._attached(optimizer)
+        if opt is None:
+            raise RuntimeError("PackNet.prune: no optimizer is attached (FusedAdamW(..., masks=pn)) and none was given: the "
+                               "pruning resets its moments")
+        flush_pending_updates()
+        f, L, task = self.flat, _lib.lib(), self.tasks[self.current]
+        nseg = len(f.entries)
+        if self._workspace is None:
+            self._workspace = torch.empty(L.ia_pack_prune_workspace_bytes(nseg), dtype=torch.uint8, device=f.theta.device)
+        st = L.ia_pack_prune(_lib.ptr(f.theta), _lib.ptr(opt.exp_avg), _lib.ptr(opt.exp_avg_sq), _lib.ptr(self.owner),
+                             _lib.ptr(f.chunk_table), f.chunk_table.shape[0], _lib.ptr(self.seg_kind), nseg, fraction, task,
+                             _lib.ptr(opt.shadow), _lib.ptr(self.seg_counts), _lib.ptr(self._workspace), self._workspace.numel(),
+                             _lib.stream_ptr())
+        _lib.check(st, "ia_pack_prune")
+        opt.seg_step.mul_((self.seg_kind != MASK_MASKED).to(torch.int32))
+        self._weights_changed(opt)
+        self.phase, self.train_owner = "retrain", task
+
+    def finish_language(self):
+        """Close the open language after its retraining: base <- theta, its free tensors and every module buffer are recorded, and
+        train_owner = -1, so that no packed weight moves until the next begin_language()."""
+        if self.phase != "retrain":
+            raise RuntimeError("PackNet.finish_language: " + (f"'{self.current}' has not been pruned; call prune() first"
+                                                              if self.phase == "train" else "no language is open"))
+        flush_pending_updates()
+        f = self.flat
+        self.base.flat.copy_(f.theta)
+        self.records[self.current] = {
+            "task": self.tasks[self.current],
+            "free": {n: f._theta_views[n].detach().clone() for n in self._names_of(MASK_FREE)},
+            "buffers": {n: b.detach().clone() for n, b in f.model.named_buffers()}}
+        self.phase, self.train_owner = "finished", -1
+
+    def activate(self, lang: str):
+        """Show finished language `lang` to the network: its free tensors and buffers come back, then one launch rewrites the
+        packed weights as `1 <= owner <= task(lang) ? base : +0` and the whole bf16 image."""
+        if lang not in self.records:
+            raise ValueError(f"PackNet.activate: unknown language '{lang}' (finished: {', '.join(self.records) or 'none'})")
+        if self.phase in ("train", "retrain"):
+            raise RuntimeError(f"PackNet.activate: '{self.current}' is still open; finish_language() first")
+        flush_pending_updates()
+        rec, f = self.records[lang], self.flat
+        with torch.no_grad():
+            for n, t in rec["free"].items():
+                f._theta_views[n].copy_(t)
+            buffers = dict(f.model.named_buffers())
+            for n, t in rec["buffers"].items():
+                buffers[n].copy_(t)
+        self._apply_owners(1, rec["task"])
+        self.current = lang
+
+    # -- reports ---------------------------------------------------------------------------------------------------
+    def usage(self) -> Dict[str, dict]:
+        """name -> {"owned": {language: fraction of the tensor it owns, in language order}, "free": fraction still free} for the
+        packed tensors: plain torch ops and one device-to-host read."""
+        flush_pending_updates()
+        packed = self._packed_entries()
+        if not packed:
+            return {}
+        counts = torch.stack([torch.bincount(self.owner[o:o + k].to(torch.int64), minlength=256) for _, o, k, _ in packed]).tolist()
+        return {n: {"owned": {lang: row[t] / k for lang, t in self.tasks.items()}, "free": row[0] / k}
+                for (n, o, k, _), row in zip(packed, counts)}
+
+    def free_fraction(self) -> float:
+        """Fraction of all packed weights that no language owns."""
+        flush_pending_updates()
+        packed = self._packed_entries()
+        total = sum(e[2] for e in packed)
+        return float(torch.stack([(self.owner[o:o + k] == 0).sum() for _, o, k, _ in packed]).sum()) / total if total else 0.0
+
+    def bytes_per_language(self) -> dict:
+        """Bytes one finished language holds (its free tensors and the module buffers), beside what all languages share: the
+        owner map (1 B per flat element) and base (4 B)."""
+        f = self.flat
+        free = sum(e[2] * 4 for k, e in enumerate(f.entries) if self._kinds[k] == MASK_FREE)
+        buffers = sum(b.numel() * b.element_size() for b in f.model.buffers())
+        return {"free": free, "buffers": buffers, "total": free + buffers, "shared_owner_map": f.numel, "shared_base": 4 * f.numel}
+
+    # -- resumable state -------------------------------------------------------------------------------------------
+    def state_dict(self) -> dict:
+        flush_pending_updates()
+        cpu = lambda t: t.detach().to("cpu", copy=True)
+        return {"entries": list(self.flat.entries), "kinds": [_PACK_KIND_NAMES[k] for k in self._kinds],
+                "prune": self.prune_fraction, "owner": cpu(self.owner), "base": cpu(self.base.flat), "current": self.current,
+                "phase": self.phase, "tasks": dict(self.tasks),
+                "languages": {lang: {"task": r["task"], "free": {n: cpu(t) for n, t in r["free"].items()},
+                                     "buffers": {n: cpu(t) for n, t in r["buffers"].items()}}
+                              for lang, r in self.records.items()}}
+
+    def load_state_dict(self, sd: dict, source="state dict"):
+        """In place: owner map, base and the kind table keep their addresses (an attached optimizer keeps pointing at them).  The
+        weights are not part of this state: `activate(lang)` puts them in step with it, or the weights of a checkpoint taken at
+        the same moment when a language was open."""
+        if [tuple(e[:3]) + (tuple(e[3]),) for e in sd["entries"]] != list(self.flat.entries):
+            raise ValueError(f"{source}: 'masks' was saved for a different set of trainable tensors")
+        if "owner" not in sd:
+            raise ValueError(f"{source}: 'masks' does not hold a PackNet owner map")
+        kinds = [_PACK_KIND_NAMES.index(k) for k in sd["kinds"]]
+        fraction = self._checked_fraction(sd["prune"])
+        if sd["phase"] not in _PACK_PHASES:
+            raise ValueError(f"{source}: unknown phase '{sd['phase']}'")
+        flush_pending_updates()
+        dev = self.flat.theta.device
+        self.owner.copy_(sd["owner"])
+        self.base.flat.copy_(sd["base"])
+        self._kinds = kinds
+        self.seg_kind.copy_(torch.tensor(kinds, dtype=torch.int32))
+        self.prune_fraction = fraction
+        self.current, self.phase, self.tasks = sd["current"], sd["phase"], {k: int(v) for k, v in sd["tasks"].items()}
+        self.train_owner = {"train": 0, "retrain": self.tasks.get(self.current, -1)}.get(self.phase, -1)
+        self.records = {lang: {"task": int(r["task"]), "free": {n: t.to(dev) for n, t in r["free"].items()},
+                               "buffers": {n: t.to(dev) for n, t in r["buffers"].items()}}
+                        for lang, r in sd["languages"].items()}
+
+
 # ----------------------------------------------------------------------------- LwF
 def lwf_kd_loss(loss, prob, prob_, pred_store_list, store_list, knowledge_distillation: float, kd_ctx: float):
     """R/cl_baseline_lwf.py:242-264.  Returns (total loss, rnnt_kd, ctc_kd) -- device tensors."""
@@ -1010,7 +1268,7 @@ class FusedAdamW(torch.optim.Optimizer):
         on the device: `last_grad_norm`, `stats()`, `grad_norms()`.  With all three at their defaults the step is the plain
         ia_adamw_step_segmented.  `max_grad_norm` / `skip_nonfinite` live in param_groups[0] and are read per step, as lr is.
         The entry points named here and below are reached through ia_adamw_step_segmented_grouped (one group or many), whose
-        operands select the same step; only masks and GEM have entry points of their own.
+        operands select the same step; only masks (Piggyback, PackNet) and GEM have entry points of their own.
 
         `grad_exchange_dtype="bf16"` ("fp32 or bf16"): the data-parallel exchange all-reduces a bf16 image of the
         flat gradient (half the bytes over xGMI: 80 instead of 160 MB per step at 40 M trainable parameters); every rank
@@ -1041,7 +1299,12 @@ class FusedAdamW(torch.optim.Optimizer):
         scores are trained with its group's `lr`; its `weight_decay` is IGNORED (a score is not a weight, and decaying it towards
         zero would switch bits off by itself).  A free tensor takes the plain step, a frozen one is never written.  `exp_avg`,
         `exp_avg_sq` and the step counters of a masked tensor are those of its scores.  Not combinable with `path_integral` or
-        `projection`.  The masks are not optimizer state: `pb.state_dict()` / `checkpoint.save_masks`."""
+        `projection`.  The masks are not optimizer state: `pb.state_dict()` / `checkpoint.save_masks`.
+
+        `masks=pn` (a `PackNet`): the step is ia_adamw_step_segmented_packed, after ia_grad_norm_packed when the norm is measured
+        -- the norm of the gradient the step consumes: the trainable elements of packed tensors and the free tensors.  In a packed
+        tensor the elements whose owner is `pn.train_owner` take the plain rule with the group's `lr` and `weight_decay`; every
+        other element keeps its weight and moments.  The same refusals and the same place outside the optimizer state."""
         self.flat = model_or_flat if isinstance(model_or_flat, FlatParams) else flat_of(model_or_flat)
         if masks is not None and (path_integral is not None or projection is not None):
             raise ValueError("masks cannot be combined with path_integral or projection: the masked weights do not move along "
@@ -1279,8 +1542,15 @@ class FusedAdamW(torch.optim.Optimizer):
             if measured:
                 _lib.check(L.ia_grad_norm_projected(*norm, ptr(agem.ref.flat), ptr(agem.proj_state), stream),
                            "ia_grad_norm_projected")
+        elif measured and isinstance(pb, PackNet):
+            _lib.check(L.ia_grad_norm_packed(*norm, ptr(pb.owner), ptr(pb.seg_kind), int(pb.train_owner), stream),
+                       "ia_grad_norm_packed")
         elif measured:
             _lib.check(L.ia_grad_norm(*norm, stream), "ia_grad_norm")
+        if isinstance(pb, PackNet):
+            _lib.check(L.ia_adamw_step_segmented_packed(*common, ptr(pb.owner), ptr(pb.seg_kind), int(pb.train_owner), stream),
+                       "ia_adamw_step_segmented_packed")
+            return self._after_update()
         if pb is not None:
             _lib.check(L.ia_adamw_step_segmented_masked(*common, ptr(pb.base.flat), ptr(pb.scores.flat), ptr(pb.seg_kind),
                                                         pb.threshold, stream), "ia_adamw_step_segmented_masked")

@@ -24,16 +24,20 @@
 //       gem_step               consumed_step<gem_source>: g * s + sum_k v_k * r_k             ia_adamw_step_segmented_gem
 //       masked_step            Piggyback, per tensor a kind: masked (the scores are trained on g * base and
 //                              theta = score >= threshold ? base : 0), free (the plain rule), frozen    ia_adamw_step_segmented_masked
+//       packed_step            PackNet, per tensor a kind: packed (the plain rule where owner == train_owner, nothing
+//                              elsewhere), free, frozen                                          ia_adamw_step_segmented_packed
 //                              ia_adamw_step_segmented_grouped is the first four with lr and weight_decay per parameter group.
 //   consumed_norm_kernel<Source>   the clip norm of the gradient a consumed_step consumes, from the SAME gradient functor
-//                              (ia_grad_norm_projected, ia_grad_norm_gem); ia_grad_norm measures the raw gradient in the
+//                              (ia_grad_norm_projected, ia_grad_norm_gem, ia_grad_norm_packed); ia_grad_norm measures the raw gradient in the
 //                              liveness pass.  grad_norm_finish_kernel adds the chunk sums of all three in a fixed order.
 //   seg_step_advance_kernel    the per-tensor step counters and the clip / skip / projected / unsolved counters of every variant.
 //   run_step                   liveness (activity pass or mark-all), the walker, the advance: three launches for every variant.
+//   ia_pack_prune, ia_pack_apply   PackNet's pruning (an exact per-tensor radix select on |theta|) and owner map -> weights.
 // The dots of A-GEM (ia_agem_dots) and GEM (ia_gem_dots, ia_gem_solve) run before their step and leave the decision on the device.
 // All are HBM-streaming kernels: 16-byte accesses, grid capped at 2048 workgroups, fp32 math.
 #include "ia_common.h"
 #include <type_traits>
+#include <utility>
 
 namespace {
 constexpr int CL_THREADS = 256;
@@ -804,6 +808,18 @@ __device__ __forceinline__ float sumsq4_rn(float ss, const vecf<4>& x) {
 // Not projecting: the raw sum of g^2 over every chunk, as ia_grad_norm's first pass.  Projecting: the sum of G^2, G the functor's
 // gradient, over the chunks of live tensors; a dead tensor's chunk stores 0 (its .grad is None for torch's clip norm) and is not
 // read.  seg_active is read only (NULL: every tensor live): the variant's dots kernel has set it.
+// A gradient functor whose answer depends on the tensor (packed_grad: the tensor's kind) has for_segment(seg); every other one is
+// used as it is.
+template <class Grad, class = void> struct grad_per_segment : std::false_type {};
+template <class Grad>
+struct grad_per_segment<Grad, std::void_t<decltype(std::declval<const Grad&>().for_segment(0))>> : std::true_type {};
+
+template <class Grad>
+__device__ __forceinline__ decltype(auto) at_segment(const Grad& grad, int seg) {
+    if constexpr (grad_per_segment<Grad>::value) return grad.for_segment(seg);
+    else return (grad);
+}
+
 template <class Source>
 __global__ __launch_bounds__(CL_THREADS) void consumed_norm_kernel(const float* __restrict__ g, const int4* __restrict__ table,
                                                                    int nchunks, const int* __restrict__ seg_active,
@@ -820,12 +836,13 @@ __global__ __launch_bounds__(CL_THREADS) void consumed_norm_kernel(const float* 
             for (int q = threadIdx.x; q < n4; q += CL_THREADS) ss = sumsq4_rn(ss, ldv<4>(g, off + (q << 2)));
             for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) ss = __builtin_fmaf(g[off + i], g[off + i], ss);
         } else if (!seg_active || seg_active[e.z]) {
+            decltype(auto) seg_grad = at_segment(grad, e.z);     // workgroup-uniform
             for (int q = threadIdx.x; q < n4; q += CL_THREADS) {
                 const int at = off + (q << 2);
-                ss = sumsq4_rn(ss, grad(ldv<4>(g, at), at, grad_scale));
+                ss = sumsq4_rn(ss, seg_grad(ldv<4>(g, at), at, grad_scale));
             }
             for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) {
-                const float G = grad(ldv<1>(g, off + i), off + i, grad_scale)[0];
+                const float G = seg_grad(ldv<1>(g, off + i), off + i, grad_scale)[0];
                 ss = __builtin_fmaf(G, G, ss);
             }
         }
@@ -864,6 +881,75 @@ struct score_rule {
 struct masked_step {
     const float* base; float* scores; const int* seg_kind; float threshold;
     __device__ __forceinline__ masked_step begin() const { return *this; }
+    __device__ __forceinline__ score_rule kind_rule() const { return {base, scores, threshold}; }
+};
+
+// ---- PackNet (Mallya, Lazebnik 2018): all languages share theta, and one byte per weight says whose it is: 0 free, t >= 1 the
+// t-th language's.  The kinds are Piggyback's, with `packed` in the masked slot:
+//   packed  per element: owner == train_owner -> the plain rule (ge = g * grad_scale [* coef], the group's lr and weight decay);
+//           otherwise theta and both moments keep their bit patterns.  The bf16 image follows theta for every element.
+//   free    the plain rule;   frozen  nothing but the bf16 image
+// A packed element moves 31 B (g, theta, m, v and the owner byte in; theta, m, v and the bf16 image out), one more than a free one.
+__device__ __forceinline__ void ld_owner(const unsigned char* __restrict__ owner, int64_t at, unsigned char (&o)[4]) {
+    const uchar4 q = *reinterpret_cast<const uchar4*>(owner + at);      // at is a multiple of 4 in a chunk's body
+    o[0] = q.x; o[1] = q.y; o[2] = q.z; o[3] = q.w;
+}
+__device__ __forceinline__ void ld_owner(const unsigned char* __restrict__ owner, int64_t at, unsigned char (&o)[1]) {
+    o[0] = owner[at];
+}
+
+struct owner_rule {
+    const unsigned char* owner; int train_owner;
+    static constexpr bool reads_theta = true;
+    template <bool CLIP, int W>
+    __device__ __forceinline__ void apply(vecf<W>& P, const vecf<W>& G, vecf<W>& M, vecf<W>& V, int64_t at,
+                                          const chunk_consts& k) const {
+        unsigned char o[W];
+        ld_owner(owner, at, o);
+#pragma unroll
+        for (int j = 0; j < W; ++j)
+            if ((int)o[j] == train_owner)
+                adamw1_rn<W == 1>(P[j], eff_grad<CLIP>(mul_rn(G[j], k.grad_scale), k), M[j], V[j], k.decay, k);
+    }
+};
+
+struct packed_step {
+    const unsigned char* owner; const int* seg_kind; int train_owner;
+    __device__ __forceinline__ packed_step begin() const { return *this; }
+    __device__ __forceinline__ owner_rule kind_rule() const { return {owner, train_owner}; }
+};
+
+// A variant with per-tensor kinds has seg_kind and kind_rule(), the rule of its KIND_MASKED slot; its free tensors take the plain
+// rule and its frozen ones are never written.
+template <class Rule, class = void> struct has_kinds : std::false_type {};
+template <class Rule>
+struct has_kinds<Rule, std::void_t<decltype(std::declval<const Rule&>().kind_rule())>> : std::true_type {};
+
+// The clip norm of the packed step: the raw gradient (the finisher scales the roots, as for ia_grad_norm) where the step consumes
+// it, +0 elsewhere -- in a frozen tensor and where owner != train_owner in a packed one.
+struct packed_grad {
+    const unsigned char* owner; const int* seg_kind; int train_owner, kind;
+    __device__ __forceinline__ bool projecting() const { return true; }      // never the raw sum over every chunk
+    __device__ __forceinline__ packed_grad for_segment(int seg) const { return {owner, seg_kind, train_owner, seg_kind[seg]}; }
+    template <int W>
+    __device__ __forceinline__ vecf<W> operator()(const vecf<W>& G, int64_t at, float) const {
+        vecf<W> a = G;
+        if (kind == KIND_FROZEN) {
+#pragma unroll
+            for (int j = 0; j < W; ++j) a[j] = 0.f;
+        } else if (kind == KIND_MASKED) {
+            unsigned char o[W];
+            ld_owner(owner, at, o);
+#pragma unroll
+            for (int j = 0; j < W; ++j) a[j] = (int)o[j] == train_owner ? G[j] : 0.f;
+        }
+        return a;
+    }
+};
+
+struct packed_source {
+    const unsigned char* owner; const int* seg_kind; int train_owner;
+    __device__ __forceinline__ packed_grad begin() const { return {owner, seg_kind, train_owner, KIND_FREE}; }
 };
 
 // ---- the chunk walker.  One access of W elements: the common operands in, the variant's rule, the common operands out.
@@ -917,11 +1003,11 @@ __global__ __launch_bounds__(CL_THREADS) void adamw_seg_kernel(float* __restrict
     // memory): it has to stay in control flow that is uniform over the workgroup, as it is after the launch-uniform return above.
     const auto rule = variant.begin();
     using Rule = std::remove_cv_t<decltype(rule)>;
-    constexpr bool MASKED_STEP = std::is_same_v<Rule, masked_step>;      // the only variant with per-tensor kinds
+    constexpr bool KINDS = has_kinds<Rule>::value;               // masked_step, packed_step: per-tensor kinds
     for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
         const int4 e = table[c];           // x = offset (multiple of 4), y = count, z = segment id
         int kind = KIND_FREE;                                    // workgroup-uniform
-        if constexpr (MASKED_STEP) kind = rule.seg_kind[e.z];
+        if constexpr (KINDS) kind = rule.seg_kind[e.z];
         if (kind == KIND_FROZEN || !seg_active[e.z]) {           // never written / no gradient: only the bf16 image is kept in step
             if (shadow_bf16)
                 for (int i = threadIdx.x; i < e.y; i += CL_THREADS) shadow_bf16[e.x + i] = bf16_bits(p[e.x + i]);
@@ -937,9 +1023,9 @@ __global__ __launch_bounds__(CL_THREADS) void adamw_seg_kernel(float* __restrict
         }
         __syncthreads();
         const chunk_consts k = {__builtin_fmaf(-lr, wd, 1.f), 1.f - b1, b2, 1.f - b2, eps, sh_c[0], sh_c[1], grad_scale, coef};
-        if constexpr (MASKED_STEP) {
+        if constexpr (KINDS) {
             if (kind == KIND_MASKED)
-                walk_chunk<CLIP>(score_rule{rule.base, rule.scores, rule.threshold}, p, g, m, v, shadow_bf16, e.x, e.y, k);
+                walk_chunk<CLIP>(rule.kind_rule(), p, g, m, v, shadow_bf16, e.x, e.y, k);
             else
                 walk_chunk<CLIP>(consumed_rule<scaled_grad>{}, p, g, m, v, shadow_bf16, e.x, e.y, k);
         } else {
@@ -1038,6 +1124,214 @@ __global__ __launch_bounds__(CL_THREADS) void mask_apply_kernel(float* __restric
     }
 }
 
+// ---- PackNet's pruning: per packed tensor, the r-th smallest |theta| among its free elements (owner == 0), r = floor(fraction * n),
+// by an exact radix select on the 31-bit pattern of |theta| (the order of finite magnitudes), most significant digit first:
+//   pack_hist_kernel    one pass per digit (8, 8, 8 and 7 bits).  A workgroup counts the digit of the free elements whose higher
+//                       digits equal the tensor's prefix into a histogram in LDS and adds it to hist[seg][bin] with integer
+//                       atomics: the sums do not depend on the order of arrival.  With more than 2048 chunks a workgroup visits
+//                       chunks of different tensors, so the histogram is flushed whenever the tensor changes, and at the end.
+//                       Only elements below a chunk's count are read: never a float4 over a short tail, never an alignment gap.
+//   pack_pick_kernel    one workgroup per tensor: the first pass fixes n (the histogram's total) and r; every pass picks the bin
+//                       that holds the rank, extends the prefix, reduces the rank to one inside that bin and clears the histogram.
+//                       The last pass also knows the counts: released = the free elements at or below the cutoff = r - rank +
+//                       the bin's inclusive sum, newly owned = n - released; no pass over the data counts them.
+//   pack_prune_kernel   free elements at or below the cutoff are released (theta = +0, owner stays 0), the other free ones get
+//                       owner = task; both moments of every element of a packed tensor become +0; the bf16 image of every tensor
+//                       is rewritten.
+constexpr int PK_BINS = 256, PK_PASSES = 4;
+static_assert(PK_BINS == CL_THREADS, "one histogram bin per thread");
+__host__ __device__ constexpr int pk_shift(int pass) { return pass == 0 ? 23 : pass == 1 ? 15 : pass == 2 ? 7 : 0; }
+__host__ __device__ constexpr int pk_width(int pass) { return pass == 3 ? 7 : 8; }
+
+struct alignas(16) pack_sel {     // per tensor, in the workspace (zeroed by the host before the first pass)
+    unsigned prefix;              // the digits chosen so far, in place; after the last pass the cutoff's pattern
+    unsigned rank;                // 1-based rank of the cutoff among the elements that share the prefix
+    unsigned r;                   // floor(fraction * n); 0: nothing is released
+    unsigned n;                   // free elements of the tensor
+};
+
+__device__ __forceinline__ void pk_flush(unsigned* sh, unsigned* __restrict__ hist, int seg) {
+    __syncthreads();
+    const unsigned h = sh[threadIdx.x];
+    if (h) atomicAdd(hist + (int64_t)seg * PK_BINS + threadIdx.x, h);
+    sh[threadIdx.x] = 0;
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(CL_THREADS) void pack_hist_kernel(const float* __restrict__ p, const unsigned char* __restrict__ owner,
+                                                               const int4* __restrict__ table, int nchunks,
+                                                               const int* __restrict__ seg_kind, const pack_sel* __restrict__ sel,
+                                                               int pass, unsigned* __restrict__ hist) {
+    __shared__ unsigned sh[PK_BINS];
+    sh[threadIdx.x] = 0;
+    __syncthreads();
+    const int shift = pk_shift(pass), up = shift + pk_width(pass);      // up == 31 in the first pass: every pattern matches
+    const unsigned digit_mask = (1u << pk_width(pass)) - 1u;
+    int cur = -1;                                                        // the tensor the LDS histogram belongs to
+    unsigned prefix_up = 0;
+    bool counted = true;                                                 // false: r == 0, nothing to select in this tensor
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const int4 e = table[c];
+        if (seg_kind[e.z] != KIND_MASKED) continue;                      // workgroup-uniform, as everything up to the counting
+        if (e.z != cur) {
+            if (cur >= 0) pk_flush(sh, hist, cur);
+            cur = e.z;
+            if (pass > 0) {
+                const pack_sel s = sel[e.z];
+                prefix_up = s.prefix >> up;
+                counted = s.r != 0;
+            }
+        }
+        if (!counted) continue;
+        const int off = e.x, cnt = e.y, n4 = cnt >> 2;
+        for (int q = threadIdx.x; q < n4; q += CL_THREADS) {
+            const uint4 x = reinterpret_cast<const uint4*>(p + off)[q];
+            const uchar4 o = reinterpret_cast<const uchar4*>(owner + off)[q];
+            const unsigned k0 = x.x & 0x7FFFFFFFu, k1 = x.y & 0x7FFFFFFFu, k2 = x.z & 0x7FFFFFFFu, k3 = x.w & 0x7FFFFFFFu;
+            if (o.x == 0 && k0 >> up == prefix_up) atomicAdd(sh + ((k0 >> shift) & digit_mask), 1u);
+            if (o.y == 0 && k1 >> up == prefix_up) atomicAdd(sh + ((k1 >> shift) & digit_mask), 1u);
+            if (o.z == 0 && k2 >> up == prefix_up) atomicAdd(sh + ((k2 >> shift) & digit_mask), 1u);
+            if (o.w == 0 && k3 >> up == prefix_up) atomicAdd(sh + ((k3 >> shift) & digit_mask), 1u);
+        }
+        for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) {
+            const unsigned k = __float_as_uint(p[off + i]) & 0x7FFFFFFFu;
+            if (owner[off + i] == 0 && k >> up == prefix_up) atomicAdd(sh + ((k >> shift) & digit_mask), 1u);
+        }
+    }
+    if (cur >= 0) pk_flush(sh, hist, cur);
+}
+
+__global__ __launch_bounds__(PK_BINS) void pack_pick_kernel(unsigned* __restrict__ hist, pack_sel* __restrict__ sel,
+                                                            const int* __restrict__ seg_kind, int pass, float fraction,
+                                                            int* __restrict__ seg_counts) {
+    __shared__ unsigned sc[PK_BINS];
+    const int seg = blockIdx.x, t = threadIdx.x;
+    if (seg_kind[seg] != KIND_MASKED) return;
+    const pack_sel s = sel[seg];
+    if (pass > 0 && !s.r) return;                                        // workgroup-uniform
+    const unsigned h = hist[(int64_t)seg * PK_BINS + t];
+    hist[(int64_t)seg * PK_BINS + t] = 0;                                // for the next pass
+    sc[t] = h;
+    __syncthreads();
+    for (int d = 1; d < PK_BINS; d <<= 1) {                              // inclusive scan
+        const unsigned a = t >= d ? sc[t - d] : 0u;
+        __syncthreads();
+        sc[t] += a;
+        __syncthreads();
+    }
+    const unsigned incl = sc[t], excl = incl - h;
+    unsigned rank = s.rank, r = s.r, n = s.n;
+    if (pass == 0) {
+        n = sc[PK_BINS - 1];
+        rank = r = (unsigned)floor((double)fraction * (double)n);        // fraction < 1, so r < n
+        if (r == 0) {
+            if (t == 0) {
+                sel[seg] = {0u, 0u, 0u, n};
+                seg_counts[2 * seg] = 0;
+                seg_counts[2 * seg + 1] = (int)n;                        // everything free is taken
+            }
+            return;
+        }
+    }
+    if (h && excl < rank && rank <= incl) {                              // one thread
+        sel[seg] = {s.prefix | ((unsigned)t << pk_shift(pass)), rank - excl, r, n};
+        if (pass == PK_PASSES - 1) {
+            const unsigned released = r - rank + incl;                   // r - rank lie below the prefix, incl at or below the cutoff
+            seg_counts[2 * seg] = (int)released;
+            seg_counts[2 * seg + 1] = (int)(n - released);
+        }
+    }
+}
+
+// One element: a free one is released, or taken by `task`
+__device__ __forceinline__ void pk_release(float& P, unsigned char& o, bool active, unsigned cutoff, unsigned char task) {
+    if (o != 0) return;
+    if (active && (__float_as_uint(P) & 0x7FFFFFFFu) <= cutoff) P = 0.f;
+    else o = task;
+}
+
+__global__ __launch_bounds__(CL_THREADS) void pack_prune_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
+                                                                unsigned char* __restrict__ owner, const int4* __restrict__ table,
+                                                                int nchunks, const int* __restrict__ seg_kind,
+                                                                const pack_sel* __restrict__ sel, int task,
+                                                                unsigned short* __restrict__ shadow_bf16) {
+    const unsigned char mine = (unsigned char)task;
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const int4 e = table[c];
+        const int off = e.x, cnt = e.y, n4 = cnt >> 2;
+        if (seg_kind[e.z] != KIND_MASKED) {                              // workgroup-uniform: only the bf16 image
+            if (shadow_bf16)
+                for (int i = threadIdx.x; i < cnt; i += CL_THREADS) shadow_bf16[off + i] = bf16_bits(p[off + i]);
+            continue;
+        }
+        const pack_sel s = sel[e.z];
+        const bool active = s.r != 0;
+        const unsigned cutoff = s.prefix;
+        const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int q = threadIdx.x; q < n4; q += CL_THREADS) {
+            float4 P = reinterpret_cast<float4*>(p + off)[q];
+            uchar4 o = reinterpret_cast<uchar4*>(owner + off)[q];
+            pk_release(P.x, o.x, active, cutoff, mine);
+            pk_release(P.y, o.y, active, cutoff, mine);
+            pk_release(P.z, o.z, active, cutoff, mine);
+            pk_release(P.w, o.w, active, cutoff, mine);
+            reinterpret_cast<float4*>(p + off)[q] = P;
+            reinterpret_cast<uchar4*>(owner + off)[q] = o;
+            reinterpret_cast<float4*>(m + off)[q] = zero;
+            reinterpret_cast<float4*>(v + off)[q] = zero;
+            if (shadow_bf16) reinterpret_cast<ushort4*>(shadow_bf16 + off)[q] = bf16_bits(P);
+        }
+        for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) {
+            float P = p[off + i];
+            unsigned char o = owner[off + i];
+            pk_release(P, o, active, cutoff, mine);
+            p[off + i] = P;
+            owner[off + i] = o;
+            m[off + i] = 0.f;
+            v[off + i] = 0.f;
+            if (shadow_bf16) shadow_bf16[off + i] = bf16_bits(P);
+        }
+    }
+}
+
+// Owner map -> weights: theta = lo <= owner <= hi ? base : +0 inside packed tensors; the bf16 image of every tensor follows theta.
+__global__ __launch_bounds__(CL_THREADS) void pack_apply_kernel(float* __restrict__ p, const float* __restrict__ base,
+                                                                const unsigned char* __restrict__ owner,
+                                                                const int4* __restrict__ table, int nchunks,
+                                                                const int* __restrict__ seg_kind, int lo, int hi,
+                                                                unsigned short* __restrict__ shadow_bf16) {
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const int4 e = table[c];
+        const int off = e.x, cnt = e.y, n4 = cnt >> 2;
+        const bool packed = seg_kind[e.z] == KIND_MASKED;        // workgroup-uniform
+        if (!packed && !shadow_bf16) continue;
+        for (int q = threadIdx.x; q < n4; q += CL_THREADS) {
+            float4 P;
+            if (packed) {
+                const float4 B = reinterpret_cast<const float4*>(base + off)[q];
+                const uchar4 o = reinterpret_cast<const uchar4*>(owner + off)[q];
+                P = make_float4(lo <= o.x && o.x <= hi ? B.x : 0.f, lo <= o.y && o.y <= hi ? B.y : 0.f,
+                                lo <= o.z && o.z <= hi ? B.z : 0.f, lo <= o.w && o.w <= hi ? B.w : 0.f);
+                reinterpret_cast<float4*>(p + off)[q] = P;
+            } else {
+                P = reinterpret_cast<const float4*>(p + off)[q];
+            }
+            if (shadow_bf16) reinterpret_cast<ushort4*>(shadow_bf16 + off)[q] = bf16_bits(P);
+        }
+        for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS) {
+            float P;
+            if (packed) {
+                const int o = owner[off + i];
+                P = lo <= o && o <= hi ? base[off + i] : 0.f;
+                p[off + i] = P;
+            } else {
+                P = p[off + i];
+            }
+            if (shadow_bf16) shadow_bf16[off + i] = bf16_bits(P);
+        }
+    }
+}
+
 inline int cap_grid(int64_t work_items, int per_block) {
     int64_t b = (work_items + per_block - 1) / per_block;
     return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
@@ -1103,7 +1397,7 @@ inline bool gem_operands_ok(const float* refs, int64_t stride, int ntasks, const
 struct step_extras {
     bool flags_preset;       // the variant's dots kernel has set seg_active from the task gradient: never an activity pass here
     const float* projected; int32_t* projected_count; const float* solved; int32_t* unsolved_count;
-    const int32_t* seg_kind;  // the masked step only: the SAME array as masked_step::seg_kind, so that walker and advance agree
+    const int32_t* seg_kind;  // the masked and packed steps: the SAME array as the variant's seg_kind, so that walker and advance agree
 };
 
 // Every segmented step: liveness, the walker, the advance.  Arguments are validated by the callers.  Liveness: all_active marks
@@ -1453,6 +1747,87 @@ extern "C" int ia_mask_apply(float* theta, const float* base, const uint64_t* bi
     hipLaunchKernelGGL(mask_apply_kernel, dim3(nchunks < 2048 ? nchunks : 2048), dim3(CL_THREADS), 0, (hipStream_t)stream, theta,
                        base, (const unsigned long long*)bits, nwords, (const int4*)chunk_table, nchunks, seg_kind,
                        (unsigned short*)shadow_bf16);
+    IA_RETURN_IF_LAUNCH_FAILED();
+    return IA_OK;
+}
+
+extern "C" int ia_grad_norm_packed(const float* grad, const int32_t* chunk_table, int nchunks, const int32_t* seg_chunk_begin,
+                                   int nseg, float grad_scale, float max_norm, int32_t* seg_active, float* seg_norm,
+                                   float* norm_state, void* workspace, size_t workspace_bytes, const uint8_t* owner,
+                                   const int32_t* seg_kind, int train_owner, ia_stream_t stream) {
+    if (!norm_operands_ok(grad, chunk_table, nchunks, seg_chunk_begin, nseg, seg_norm, norm_state, workspace) || !owner ||
+        !seg_kind || !ia_is_aligned(owner, 16) || !ia_is_aligned(seg_kind, 4))
+        return IA_INVALID_VALUE;
+    if (workspace_bytes < ia_grad_norm_workspace_bytes(nchunks)) return IA_WORKSPACE_TOO_SMALL;
+    hipStream_t st = (hipStream_t)stream;
+    if (seg_active)      // liveness is the raw gradient's, as in ia_grad_norm's first pass
+        hipLaunchKernelGGL(seg_activity_kernel<false>, dim3(chunk_grid(nchunks)), dim3(CL_THREADS), 0, st, grad,
+                           (const int4*)chunk_table, nchunks, seg_active, (float*)nullptr);
+    return run_consumed_norm(grad, chunk_table, nchunks, seg_chunk_begin, nseg, grad_scale, max_norm, seg_active, seg_norm,
+                             norm_state, workspace, packed_source{owner, seg_kind, train_owner}, (const float*)nullptr, st);
+}
+
+extern "C" int ia_adamw_step_segmented_packed(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq,
+                                              const int32_t* chunk_table, int nchunks, int32_t* seg_active, int32_t* seg_step,
+                                              int nseg, int all_active, float beta1, float beta2, float eps, float grad_scale,
+                                              void* shadow_bf16, const int32_t* seg_group, int ngroups, const float* group_lr,
+                                              const float* group_weight_decay, const float* norm_state, int skip_nonfinite,
+                                              int32_t* counters, const uint8_t* owner, const int32_t* seg_kind, int train_owner,
+                                              ia_stream_t stream) {
+    const step_head h = make_head(theta, grad, exp_avg, exp_avg_sq, chunk_table, nchunks, seg_active, seg_step, nseg, all_active,
+                                  beta1, beta2, eps, grad_scale, shadow_bf16, seg_group, norm_state, skip_nonfinite, counters);
+    if (!head_ok(h) || !groups_ok(seg_group, ngroups, group_lr, group_weight_decay) || !owner || !seg_kind ||
+        !ia_is_aligned(owner, 16) || !ia_is_aligned(seg_kind, 4))
+        return IA_INVALID_VALUE;
+    step_extras x = {};
+    x.seg_kind = seg_kind;
+    return run_step(h, make_group_table(ngroups, group_lr, group_weight_decay), packed_step{owner, seg_kind, train_owner}, x,
+                    (hipStream_t)stream);
+}
+
+// workspace: pack_sel[nseg], then the histograms unsigned[nseg][PK_BINS]
+extern "C" size_t ia_pack_prune_workspace_bytes(int nseg) {
+    return nseg > 0 ? (size_t)nseg * (sizeof(pack_sel) + PK_BINS * sizeof(unsigned)) : 0;
+}
+
+extern "C" int ia_pack_prune(float* theta, float* exp_avg, float* exp_avg_sq, uint8_t* owner, const int32_t* chunk_table,
+                             int nchunks, const int32_t* seg_kind, int nseg, float fraction, int task, void* shadow_bf16,
+                             int32_t* seg_counts, void* workspace, size_t workspace_bytes, ia_stream_t stream) {
+    if (!theta || !exp_avg || !exp_avg_sq || !owner || !chunk_table || !seg_kind || !seg_counts || !workspace || nchunks <= 0 ||
+        nseg <= 0 || task < 1 || task > 255 || !(fraction >= 0.f && fraction < 1.f))
+        return IA_INVALID_VALUE;
+    if (!ia_is_aligned(theta, 16) || !ia_is_aligned(exp_avg, 16) || !ia_is_aligned(exp_avg_sq, 16) || !ia_is_aligned(owner, 16) ||
+        !ia_is_aligned(chunk_table, 16) || !ia_is_aligned(seg_kind, 4) || !ia_is_aligned(seg_counts, 4) ||
+        !ia_is_aligned(workspace, 16) || (shadow_bf16 && !ia_is_aligned(shadow_bf16, 8)))
+        return IA_INVALID_VALUE;
+    const size_t need = ia_pack_prune_workspace_bytes(nseg);
+    if (workspace_bytes < need) return IA_WORKSPACE_TOO_SMALL;
+    hipStream_t st = (hipStream_t)stream;
+    pack_sel* sel = (pack_sel*)workspace;
+    unsigned* hist = (unsigned*)(sel + nseg);
+    if (hipMemsetAsync(workspace, 0, need, st) != hipSuccess ||
+        hipMemsetAsync(seg_counts, 0, (size_t)nseg * 2 * sizeof(int32_t), st) != hipSuccess)
+        return IA_LAUNCH_FAILED;
+    for (int pass = 0; pass < PK_PASSES; ++pass) {
+        hipLaunchKernelGGL(pack_hist_kernel, dim3(chunk_grid(nchunks)), dim3(CL_THREADS), 0, st, theta, owner,
+                           (const int4*)chunk_table, nchunks, seg_kind, sel, pass, hist);
+        hipLaunchKernelGGL(pack_pick_kernel, dim3(nseg), dim3(PK_BINS), 0, st, hist, sel, seg_kind, pass, fraction,
+                           seg_counts);
+    }
+    hipLaunchKernelGGL(pack_prune_kernel, dim3(chunk_grid(nchunks)), dim3(CL_THREADS), 0, st, theta, exp_avg, exp_avg_sq, owner,
+                       (const int4*)chunk_table, nchunks, seg_kind, sel, task, (unsigned short*)shadow_bf16);
+    IA_RETURN_IF_LAUNCH_FAILED();
+    return IA_OK;
+}
+
+extern "C" int ia_pack_apply(float* theta, const float* base, const uint8_t* owner, const int32_t* chunk_table, int nchunks,
+                             const int32_t* seg_kind, int nseg, int lo, int hi, void* shadow_bf16, ia_stream_t stream) {
+    if (!theta || !base || !owner || !chunk_table || !seg_kind || nchunks <= 0 || nseg <= 0) return IA_INVALID_VALUE;
+    if (!ia_is_aligned(theta, 16) || !ia_is_aligned(base, 16) || !ia_is_aligned(owner, 16) || !ia_is_aligned(chunk_table, 16) ||
+        !ia_is_aligned(seg_kind, 4) || (shadow_bf16 && !ia_is_aligned(shadow_bf16, 8)))
+        return IA_INVALID_VALUE;
+    hipLaunchKernelGGL(pack_apply_kernel, dim3(chunk_grid(nchunks)), dim3(CL_THREADS), 0, (hipStream_t)stream, theta, base, owner,
+                       (const int4*)chunk_table, nchunks, seg_kind, lo, hi, (unsigned short*)shadow_bf16);
     IA_RETURN_IF_LAUNCH_FAILED();
     return IA_OK;
 }

@@ -2,7 +2,10 @@
 plain, with max_grad_norm=1.0 (live-segment detection on / every segment live), and with a Synaptic Intelligence path integral
 attached (first task: w only; later tasks: omega and theta* read as well, every segment live), and `grouped`: the plain step
 with layerwise_lr_groups + no-decay parameter groups (ia_adamw_step_segmented_grouped), and `masked`: Piggyback on its default
-kinds without clipping (ia_adamw_step_segmented_masked: matrices masked, heads free, the rest frozen).  Per leg: `<leg>_us` device time of one
+kinds without clipping (ia_adamw_step_segmented_masked: matrices masked, heads free, the rest frozen), and `packed`: PackNet on the
+same kinds (ia_adamw_step_segmented_packed with every packed weight free and trained; `prune_us`: one ia_pack_prune at fraction
+0.5, each call from a zeroed owner map and the same weights, between its own two events; `packed_retrain_us`: the step after the
+pruning, when half of the packed weights move).  Per leg: `<leg>_us` device time of one
 _apply between two events, `<leg>_host_us` host wall-clock of one step() call with no synchronisation inside the timed loop
 (what the training loop's thread pays: Python, ctypes and the launches).  Developer tool; one JSON line.
 
@@ -47,7 +50,7 @@ def host_timeit(fn, warmup=5, n=50):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--legs", default="plain,clip,clip_all_live,si_first_task,si_penalty,grouped,masked")
+    ap.add_argument("--legs", default="plain,clip,clip_all_live,si_first_task,si_penalty,grouped,masked,packed")
     args = ap.parse_args()
     from indic_cl_asr_amd import cl
     from indic_cl_asr_amd.config import model_config
@@ -61,7 +64,7 @@ def main():
     for leg in args.legs.split(","):
         kw, live = {"plain": ({}, False), "clip": ({"max_grad_norm": 1.0}, False),
                     "clip_all_live": ({"max_grad_norm": 1.0}, True), "si_first_task": ({}, False),
-                    "si_penalty": ({}, True), "grouped": ({}, False), "masked": ({}, False)}[leg]
+                    "si_penalty": ({}, True), "grouped": ({}, False), "masked": ({}, False), "packed": ({}, False)}[leg]
         if leg == "grouped":
             kw["param_groups"] = cl.layerwise_lr_groups(flat, 1e-4, 0.9)
         if leg.startswith("si_"):
@@ -71,14 +74,34 @@ def main():
                 si.tasks_consolidated = 1
         if leg == "masked":
             kw["masks"] = cl.Piggyback(flat)
+        if leg == "packed":
+            kw["masks"] = pn = cl.PackNet(flat, prune=0.5)
         opt = cl.FusedAdamW(flat, lr=1e-4, **kw)
         flat.grad.copy_(grad)
+        if leg == "packed":
+            pn.begin_language("bench", opt)
         if leg == "grouped":
             out["groups"] = len(opt.param_groups)
         out[leg + "_us"] = round(timeit(lambda: opt._apply(1.0, live)), 2)
         flat.all_grads_live = live
         out[leg + "_host_us"] = round(host_timeit(opt.step), 2)
         flat.all_grads_live = False
+        if leg == "packed":
+            theta0, total = flat.theta.clone(), 0.0
+            for i in range(8):                       # the first three calls are warm-up
+                pn.owner.zero_()
+                flat.theta.copy_(theta0)
+                pn.phase = "train"
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                pn.prune(opt)
+                b.record()
+                torch.cuda.synchronize()
+                total += a.elapsed_time(b) * 1e3 if i >= 3 else 0.0
+            out["prune_us"] = round(total / 5, 2)
+            out["packed_elements"] = sum(e[2] for e in pn._packed_entries())
+            out["packed_free_after_prune"] = round(pn.free_fraction(), 4)
+            out["packed_retrain_us"] = round(timeit(lambda: opt._apply(1.0, live)), 2)
         del opt
     print(json.dumps(out), flush=True)
 
