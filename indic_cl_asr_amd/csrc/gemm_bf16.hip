@@ -23,10 +23,8 @@ int ia_gemm_big_launch(const void* gemm_args, hipStream_t st);
 
 namespace {
 
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-
 constexpr int G_BK = 64;
-constexpr int G_ROWB = G_BK * 2 + 16;  // LDS bytes per tile row (padded)
+constexpr int G_ROWB = GEMM_ROWB;      // LDS bytes per tile row (padded)
 constexpr int G_THREADS = GEMM_THREADS;
 struct ConvRow { int b, t2, f2; };  // output pixel of a tile row (t2 < 0: row past M)
 
@@ -46,7 +44,6 @@ __global__ __launch_bounds__(G_THREADS, (BN == 256 ? 2 : (BM == 128 ? 3 : 4))) v
     static_assert(BM == 64 || BM == 96 || BM == 128, "row tiles of 64, 96 or 128");
     constexpr int WM = BM / 2, WN = BN / 2, TI = WM / 16, TJ = WN / 16;
     constexpr int A_BYTES = BM * G_ROWB;
-    constexpr int AV = BM * 8 / G_THREADS, BV = BN * 8 / G_THREADS;  // 16-byte vectors per thread per stage
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 15, q = lane >> 4;
@@ -54,102 +51,39 @@ __global__ __launch_bounds__(G_THREADS, (BN == 256 ? 2 : (BM == 128 ? 3 : 4))) v
     int m0, n0;
     if (!gemm_xcd_tile<BM, BN>(a.M, a.N, m0, n0)) return;
 
-    static_assert((BV == 4 || BV == 8) && (AV == 2 || AV == 3 || AV == 4), "staging registers are named (arrays end up in scratch)");
-    ConvRow crow[4];
+    GemmRegTile<BM> ra;
+    GemmRegTile<BN> rb;
+    constexpr int AV = GemmRegTile<BM>::NV;
+    ConvRow crow[AV];   // CONV: the output pixels of this thread's A vectors
     if constexpr (CONV) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
+        for (int i = 0; i < AV; ++i) {
             const int m = m0 + ((tid + i * G_THREADS) >> 3);
             const int f2 = m % a.cF2, bt = m / a.cF2;
             crow[i].f2 = f2; crow[i].t2 = (m < a.M) ? (bt % a.cT2) : -1; crow[i].b = bt / a.cT2;
         }
     }
-    uint4 ra0, ra1, ra2 = make_uint4(0, 0, 0, 0), ra3 = make_uint4(0, 0, 0, 0), rb0, rb1, rb2, rb3;
-    uint4 rb4 = make_uint4(0, 0, 0, 0), rb5 = rb4, rb6 = rb4, rb7 = rb4;   // BN = 256
-    // 16-byte vector at column k_ of a K-contiguous row; columns >= K read as zero (K % 8 == 0: d_model = 144 -> K = 144 is two
-    // 64-wide k-tiles and a 16-wide tail).  The address is clamped, the select applied to the value: no branch around the load.
-#define G_LDK(rowp_, k_) ([&]() { const int kk_ = (k_); const uint4 v_ = *reinterpret_cast<const uint4*>((rowp_) + (kk_ < a.K ? kk_ : 0)); \
-                                  return kk_ < a.K ? v_ : make_uint4(0, 0, 0, 0); }())
-#define G_LOAD(k0_) \
-    do { \
-        { const int idx_ = tid + 0 * G_THREADS, kv_ = idx_ & 7; if constexpr (CONV) { ra0 = conv_a_load(a, crow[0], (k0_), kv_); } else { const int row_ = idx_ >> 3; const int gr_ = (m0 + row_ < a.M) ? (m0 + row_) : (a.M - 1); ra0 = G_LDK(a.A + (size_t)gr_ * a.lda, (k0_) + kv_ * 8); } } \
-        { const int idx_ = tid + 1 * G_THREADS, kv_ = idx_ & 7; if constexpr (CONV) { ra1 = conv_a_load(a, crow[1], (k0_), kv_); } else { const int row_ = idx_ >> 3; const int gr_ = (m0 + row_ < a.M) ? (m0 + row_) : (a.M - 1); ra1 = G_LDK(a.A + (size_t)gr_ * a.lda, (k0_) + kv_ * 8); } } \
-        if constexpr (AV >= 3) { \
-        { const int idx_ = tid + 2 * G_THREADS, kv_ = idx_ & 7; if constexpr (CONV) { ra2 = conv_a_load(a, crow[2], (k0_), kv_); } else { const int row_ = idx_ >> 3; const int gr_ = (m0 + row_ < a.M) ? (m0 + row_) : (a.M - 1); ra2 = G_LDK(a.A + (size_t)gr_ * a.lda, (k0_) + kv_ * 8); } } \
-        } \
-        if constexpr (AV == 4) { \
-        { const int idx_ = tid + 3 * G_THREADS, kv_ = idx_ & 7; if constexpr (CONV) { ra3 = conv_a_load(a, crow[3], (k0_), kv_); } else { const int row_ = idx_ >> 3; const int gr_ = (m0 + row_ < a.M) ? (m0 + row_) : (a.M - 1); ra3 = G_LDK(a.A + (size_t)gr_ * a.lda, (k0_) + kv_ * 8); } } \
-        } \
-        { const int idx_ = tid + 0 * G_THREADS, row_ = idx_ >> 3, kv_ = idx_ & 7; const int gr_ = (n0 + row_ < a.N) ? (n0 + row_) : (a.N - 1); rb0 = G_LDK(a.W + (size_t)gr_ * a.ldw, (k0_) + kv_ * 8); } \
-        { const int idx_ = tid + 1 * G_THREADS, row_ = idx_ >> 3, kv_ = idx_ & 7; const int gr_ = (n0 + row_ < a.N) ? (n0 + row_) : (a.N - 1); rb1 = G_LDK(a.W + (size_t)gr_ * a.ldw, (k0_) + kv_ * 8); } \
-        { const int idx_ = tid + 2 * G_THREADS, row_ = idx_ >> 3, kv_ = idx_ & 7; const int gr_ = (n0 + row_ < a.N) ? (n0 + row_) : (a.N - 1); rb2 = G_LDK(a.W + (size_t)gr_ * a.ldw, (k0_) + kv_ * 8); } \
-        { const int idx_ = tid + 3 * G_THREADS, row_ = idx_ >> 3, kv_ = idx_ & 7; const int gr_ = (n0 + row_ < a.N) ? (n0 + row_) : (a.N - 1); rb3 = G_LDK(a.W + (size_t)gr_ * a.ldw, (k0_) + kv_ * 8); } \
-        if constexpr (BV == 8) { \
-        { const int idx_ = tid + 4 * G_THREADS, row_ = idx_ >> 3, kv_ = idx_ & 7; const int gr_ = (n0 + row_ < a.N) ? (n0 + row_) : (a.N - 1); rb4 = G_LDK(a.W + (size_t)gr_ * a.ldw, (k0_) + kv_ * 8); } \
-        { const int idx_ = tid + 5 * G_THREADS, row_ = idx_ >> 3, kv_ = idx_ & 7; const int gr_ = (n0 + row_ < a.N) ? (n0 + row_) : (a.N - 1); rb5 = G_LDK(a.W + (size_t)gr_ * a.ldw, (k0_) + kv_ * 8); } \
-        { const int idx_ = tid + 6 * G_THREADS, row_ = idx_ >> 3, kv_ = idx_ & 7; const int gr_ = (n0 + row_ < a.N) ? (n0 + row_) : (a.N - 1); rb6 = G_LDK(a.W + (size_t)gr_ * a.ldw, (k0_) + kv_ * 8); } \
-        { const int idx_ = tid + 7 * G_THREADS, row_ = idx_ >> 3, kv_ = idx_ & 7; const int gr_ = (n0 + row_ < a.N) ? (n0 + row_) : (a.N - 1); rb7 = G_LDK(a.W + (size_t)gr_ * a.ldw, (k0_) + kv_ * 8); } \
-        } \
-    } while (0)
-#define G_STORE(buf_) \
-    do { \
-        unsigned char* sa_ = smem; (void)(buf_); \
-        unsigned char* sb_ = sa_ + A_BYTES; \
-        { const int idx_ = tid + 0 * G_THREADS; *reinterpret_cast<uint4*>(sa_ + (idx_ >> 3) * G_ROWB + (idx_ & 7) * 16) = ra0; } \
-        { const int idx_ = tid + 1 * G_THREADS; *reinterpret_cast<uint4*>(sa_ + (idx_ >> 3) * G_ROWB + (idx_ & 7) * 16) = ra1; } \
-        if constexpr (AV >= 3) { \
-        { const int idx_ = tid + 2 * G_THREADS; *reinterpret_cast<uint4*>(sa_ + (idx_ >> 3) * G_ROWB + (idx_ & 7) * 16) = ra2; } \
-        } \
-        if constexpr (AV == 4) { \
-        { const int idx_ = tid + 3 * G_THREADS; *reinterpret_cast<uint4*>(sa_ + (idx_ >> 3) * G_ROWB + (idx_ & 7) * 16) = ra3; } \
-        } \
-        { const int idx_ = tid + 0 * G_THREADS; *reinterpret_cast<uint4*>(sb_ + (idx_ >> 3) * G_ROWB + (idx_ & 7) * 16) = rb0; } \
-        { const int idx_ = tid + 1 * G_THREADS; *reinterpret_cast<uint4*>(sb_ + (idx_ >> 3) * G_ROWB + (idx_ & 7) * 16) = rb1; } \
-        { const int idx_ = tid + 2 * G_THREADS; *reinterpret_cast<uint4*>(sb_ + (idx_ >> 3) * G_ROWB + (idx_ & 7) * 16) = rb2; } \
-        { const int idx_ = tid + 3 * G_THREADS; *reinterpret_cast<uint4*>(sb_ + (idx_ >> 3) * G_ROWB + (idx_ & 7) * 16) = rb3; } \
-        if constexpr (BV == 8) { \
-        { const int idx_ = tid + 4 * G_THREADS; *reinterpret_cast<uint4*>(sb_ + (idx_ >> 3) * G_ROWB + (idx_ & 7) * 16) = rb4; } \
-        { const int idx_ = tid + 5 * G_THREADS; *reinterpret_cast<uint4*>(sb_ + (idx_ >> 3) * G_ROWB + (idx_ & 7) * 16) = rb5; } \
-        { const int idx_ = tid + 6 * G_THREADS; *reinterpret_cast<uint4*>(sb_ + (idx_ >> 3) * G_ROWB + (idx_ & 7) * 16) = rb6; } \
-        { const int idx_ = tid + 7 * G_THREADS; *reinterpret_cast<uint4*>(sb_ + (idx_ >> 3) * G_ROWB + (idx_ & 7) * 16) = rb7; } \
-        } \
-    } while (0)
-    // (rows past M / N are clamped to the last valid row: their products land in output rows/columns that the
-    //  epilogue never stores)
-
     f4 acc[TI][TJ];
 #pragma unroll
     for (int i = 0; i < TI; ++i)
 #pragma unroll
         for (int j = 0; j < TJ; ++j) acc[i][j] = (f4){0.f, 0.f, 0.f, 0.f};
 
-    const int nk = (a.K + G_BK - 1) / G_BK;
-    G_LOAD(0);
-    G_STORE(0);
-    __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-        if (kt + 1 < nk) G_LOAD((kt + 1) * G_BK);
-        const unsigned char* sa = smem + (wm * WM + c) * G_ROWB + q * 16;
-        const unsigned char* sb = smem + A_BYTES + (wn * WN + c) * G_ROWB + q * 16;
+    const unsigned char* sa = smem + (wm * WM + c) * G_ROWB + q * 16;
+    const unsigned char* sb = smem + A_BYTES + (wn * WN + c) * G_ROWB + q * 16;
+    gemm_staged_loop(
+        (a.K + G_BK - 1) / G_BK,
+        [&](int kt) {
+            if constexpr (CONV) {
 #pragma unroll
-        for (int ks = 0; ks < G_BK / 32; ++ks) {
-            bf8 af[TI], bfr[TJ];
-#pragma unroll
-            for (int i = 0; i < TI; ++i) af[i] = *reinterpret_cast<const bf8*>(sa + i * 16 * G_ROWB + ks * 64);
-#pragma unroll
-            for (int j = 0; j < TJ; ++j) bfr[j] = *reinterpret_cast<const bf8*>(sb + j * 16 * G_ROWB + ks * 64);
-#pragma unroll
-            for (int i = 0; i < TI; ++i)
-#pragma unroll
-                for (int j = 0; j < TJ; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-        }
-        __syncthreads();
-        if (kt + 1 < nk) {
-            G_STORE((kt + 1) & 1);
-            __syncthreads();
-        }
-    }
+                for (int i = 0; i < AV; ++i) ra.v[i] = conv_a_load(a, crow[i], kt * G_BK, tid & 7);
+            } else {
+                ra.load(a.A, a.lda, m0, a.M, kt * G_BK, a.K);
+            }
+            rb.load(a.W, a.ldw, n0, a.N, kt * G_BK, a.K);
+        },
+        [&](int) { ra.store(smem); rb.store(smem + A_BYTES); },
+        [&](int) { gemm_mfma_bf16_ktile(sa, sb, acc); });
 
     gemm_tile_epilogue<BM, BN>(a, acc, smem, m0, n0);
 }
@@ -178,10 +112,10 @@ __global__ __launch_bounds__(G_THREADS, 2) void gemm_bf16_nt_dma_kernel(GemmArgs
     int m0, n0;
     if (!gemm_xcd_tile<BM, BN>(a.M, a.N, m0, n0)) return;
 
-    // one LDS-DMA instruction = 8 rows x 8 chunks of 16 B, lane l at position l: lane l fetches row 8 blk + (l >> 3), logical
-    // chunk (l & 7) ^ (l >> 3).  Wave w issues A blocks 2 w, 2 w + 1 and B blocks 4 w .. 4 w + 3.  Rows past M / N: clamped.
-    const int lrow = lane >> 3;
-    const unsigned lsw = (unsigned)(((lane & 7) ^ lrow) * 16);
+    // 8-row blocks by LDS-DMA (gemm_glds_lane): wave w issues A blocks 2 w, 2 w + 1 and B blocks 4 w .. 4 w + 3.  Rows past M / N:
+    // clamped.
+    int lrow;
+    const unsigned lsw = gemm_glds_lane(lane, lrow);
     unsigned aoff[2], boff[4];
     unsigned avalid[2] = {0u, 0u};   // CONV: bits 0-2 = tap rows dt in bounds, bits 3-5 = tap columns df in bounds (0 for rows past M)
 #pragma unroll
@@ -234,13 +168,10 @@ __global__ __launch_bounds__(G_THREADS, 2) void gemm_bf16_nt_dma_kernel(GemmArgs
             // first row / column: signed 32-bit, the image is < 2 GB)
             const unsigned char* src = CONV ? ak + (long long)(int)aoff[i] : ak + aoff[i];
             if constexpr (CONV) src = ((avalid[i] & tapbits) == tapbits) ? src : zpage;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)(dA + i * 1024), 16, 0, 0);
+            gemm_glds16(src, dA + i * 1024);
         }
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wk + boff[i]),
-                                             (__attribute__((address_space(3))) void*)(dB + i * 1024), 16, 0, 0);
+        for (int i = 0; i < 4; ++i) gemm_glds16(wk + boff[i], dB + i * 1024);
     };
 
     f4 acc[BM / 32][BN / 32];

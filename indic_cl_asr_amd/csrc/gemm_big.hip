@@ -26,7 +26,6 @@
 
 namespace {
 
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
 typedef float f16v __attribute__((ext_vector_type(16)));
 
 constexpr int GB_T = 256;                   // tile rows and columns
@@ -46,12 +45,10 @@ __global__ __launch_bounds__(GEMM_THREADS, 1) void gemm_big_kernel(GemmArgs a) {
     int m0, n0;
     if (!gemm_xcd_tile<GB_T, GB_T>(a.M, a.N, m0, n0)) return;
 
-    // ---- stage loader.  One LDS-DMA instruction moves 1 KB = 8 rows x 8 chunks with lane l at position l: lane l fetches,
-    // for row 8 blk + (l >> 3), the chunk that belongs at position l & 7, i.e. logical chunk (l & 7) ^ (l >> 3).  Wave w
-    // issues blocks 8 w .. 8 w + 7 of both operand tiles (rows 64 w .. 64 w + 63).  Rows of A beyond M are fetched from row
-    // M - 1 (finite values, never stored).
-    const int lrow = lane >> 3;
-    const unsigned lsw = (unsigned)(((lane & 7) ^ lrow) * 16);
+    // ---- stage loader: 8-row blocks by LDS-DMA (gemm_glds_lane).  Wave w issues blocks 8 w .. 8 w + 7 of both operand tiles
+    // (rows 64 w .. 64 w + 63).  Rows of A beyond M are fetched from row M - 1 (finite values, never stored).
+    int lrow;
+    const unsigned lsw = gemm_glds_lane(lane, lrow);
     unsigned aoff[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -68,13 +65,9 @@ __global__ __launch_bounds__(GEMM_THREADS, 1) void gemm_big_kernel(GemmArgs a) {
         unsigned char* dA = smem + buf * GB_STAGE + wave * 8192;
         unsigned char* dW = dA + GB_TILE;
 #pragma unroll
-        for (int i = 0; i < 8; ++i)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ak + aoff[i]),
-                                             (__attribute__((address_space(3))) void*)(dA + i * 1024), 16, 0, 0);
+        for (int i = 0; i < 8; ++i) gemm_glds16(ak + aoff[i], dA + i * 1024);
 #pragma unroll
-        for (int i = 0; i < 8; ++i)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wk + woff + (unsigned)(i * 8 * a.ldw * 2)),
-                                             (__attribute__((address_space(3))) void*)(dW + i * 1024), 16, 0, 0);
+        for (int i = 0; i < 8; ++i) gemm_glds16(wk + woff + (unsigned)(i * 8 * a.ldw * 2), dW + i * 1024);
     };
 
     // ---- fragment addresses: lane (row l31 of a 32-row tile, k half hh) reads the 16 bytes of logical chunk 2 ks + hh,

@@ -18,10 +18,8 @@
 
 namespace {
 
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-
 constexpr int BS_BM = 64, BS_BN = 128, BS_BK = 64;
-constexpr int BS_ROWB = BS_BK * 2 + 16;   // LDS bytes per tile row (padded: conflict-free 16-byte fragment reads)
+constexpr int BS_ROWB = GEMM_ROWB;        // LDS bytes per tile row (padded: conflict-free 16-byte fragment reads)
 constexpr int BS_THREADS = GEMM_THREADS;
 constexpr int BS_MAIN = (BS_BM + BS_BN) * BS_ROWB;          // 27 648 B
 constexpr int BS_EPI = gemm_epi_bytes(BS_BM, BS_BN);        // 33 792 B
@@ -73,59 +71,6 @@ __global__ __launch_bounds__(BS_THREADS, 4) void gemm_bnsilu_kernel(BsArgs a) {
     int m0, n0;   // (padding workgroups leave after the running-statistics update of workgroup 0, which is row tile 0)
     if (!gemm_xcd_tile<BS_BM, BS_BN>(a.M, a.N, m0, n0)) return;
 
-    // ---- staging: A = 64 rows x 64 k fp32 (4 float4 per thread), W = 128 rows x 64 k bf16 (4 uint4 per thread)
-    float4 fa0, fa1, fa2, fa3;
-    uint4 rb0, rb1, rb2, rb3;
-#define BS_LDA(i_, k0_)                                                                                   \
-    ([&]() {                                                                                              \
-        const int idx_ = tid + (i_) * BS_THREADS, row_ = idx_ >> 4, kq_ = idx_ & 15;                      \
-        const int gr_ = (m0 + row_ < a.M) ? (m0 + row_) : (a.M - 1);                                      \
-        const int kk_ = (k0_) + kq_ * 4;                                                                  \
-        const float4 v_ = *reinterpret_cast<const float4*>(a.z + (size_t)gr_ * a.ldz + (kk_ < a.K ? kk_ : 0)); \
-        return v_;                                                                                        \
-    }())
-#define BS_LDB(i_, k0_)                                                                                   \
-    ([&]() {                                                                                              \
-        const int idx_ = tid + (i_) * BS_THREADS, row_ = idx_ >> 3, kv_ = idx_ & 7;                       \
-        const int gr_ = (n0 + row_ < a.N) ? (n0 + row_) : (a.N - 1);                                      \
-        const int kk_ = (k0_) + kv_ * 8;                                                                  \
-        const uint4 v_ = *reinterpret_cast<const uint4*>(a.W + (size_t)gr_ * a.ldw + (kk_ < a.K ? kk_ : 0)); \
-        return kk_ < a.K ? v_ : make_uint4(0, 0, 0, 0);                                                   \
-    }())
-#define BS_LOAD(k0_)                                                                                      \
-    do {                                                                                                  \
-        fa0 = BS_LDA(0, k0_); fa1 = BS_LDA(1, k0_); fa2 = BS_LDA(2, k0_); fa3 = BS_LDA(3, k0_);           \
-        rb0 = BS_LDB(0, k0_); rb1 = BS_LDB(1, k0_); rb2 = BS_LDB(2, k0_); rb3 = BS_LDB(3, k0_);           \
-    } while (0)
-    // SiLU(BN(z)) rounded to bf16: four k-consecutive values of one row -> 8 bytes of the A tile
-#define BS_STA(i_, v_, k0_)                                                                               \
-    do {                                                                                                  \
-        const int idx_ = tid + (i_) * BS_THREADS, row_ = idx_ >> 4, kq_ = idx_ & 15;                      \
-        const int kk_ = (k0_) + kq_ * 4;                                                                  \
-        union { uint2 u; __bf16 h[4]; } o_;                                                               \
-        if (kk_ < a.K) {                                                                                  \
-            const float4 sc_ = *reinterpret_cast<const float4*>(s_scale + kk_);                           \
-            const float4 sh_ = *reinterpret_cast<const float4*>(s_shift + kk_);                           \
-            o_.h[0] = (__bf16)ia_bn_silu_value((v_).x, sc_.x, sh_.x); o_.h[1] = (__bf16)ia_bn_silu_value((v_).y, sc_.y, sh_.y); \
-            o_.h[2] = (__bf16)ia_bn_silu_value((v_).z, sc_.z, sh_.z); o_.h[3] = (__bf16)ia_bn_silu_value((v_).w, sc_.w, sh_.w); \
-        } else {                                                                                          \
-            o_.u = make_uint2(0, 0);                                                                      \
-        }                                                                                                 \
-        *reinterpret_cast<uint2*>(smem + row_ * BS_ROWB + kq_ * 8) = o_.u;                                \
-        if (KEEP && n0 == 0 && m0 + row_ < a.M && kk_ < a.K)                                              \
-            *reinterpret_cast<uint2*>(a.outA + (size_t)(m0 + row_) * a.ldoa + kk_) = o_.u;                \
-    } while (0)
-#define BS_STB(i_, v_)                                                                                    \
-    do {                                                                                                  \
-        const int idx_ = tid + (i_) * BS_THREADS;                                                         \
-        *reinterpret_cast<uint4*>(smem + BS_BM * BS_ROWB + (idx_ >> 3) * BS_ROWB + (idx_ & 7) * 16) = (v_); \
-    } while (0)
-#define BS_STORE(k0_)                                                                                     \
-    do {                                                                                                  \
-        BS_STA(0, fa0, k0_); BS_STA(1, fa1, k0_); BS_STA(2, fa2, k0_); BS_STA(3, fa3, k0_);               \
-        BS_STB(0, rb0); BS_STB(1, rb1); BS_STB(2, rb2); BS_STB(3, rb3);                                   \
-    } while (0)
-
     constexpr int WM = BS_BM / 2, WN = BS_BN / 2, TI = WM / 16, TJ = WN / 16;
     f4 acc[TI][TJ];
 #pragma unroll
@@ -133,40 +78,48 @@ __global__ __launch_bounds__(BS_THREADS, 4) void gemm_bnsilu_kernel(BsArgs a) {
 #pragma unroll
         for (int j = 0; j < TJ; ++j) acc[i][j] = (f4){0.f, 0.f, 0.f, 0.f};
 
-    const int nk = (a.K + BS_BK - 1) / BS_BK;
-    BS_LOAD(0);
-    __syncthreads();                 // scale / shift visible
-    BS_STORE(0);
-    __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-        if (kt + 1 < nk) BS_LOAD((kt + 1) * BS_BK);
-        const unsigned char* sa = smem + (wm * WM + c) * BS_ROWB + q * 16;
-        const unsigned char* sb = smem + BS_BM * BS_ROWB + (wn * WN + c) * BS_ROWB + q * 16;
+    // ---- staging: A = 64 rows x 64 k fp32 (4 float4 per thread: row (tid + 256 i) >> 4, k-quad (tid & 15)), W = 128 rows x 64 k bf16
+    float4 fa[4];
+    GemmRegTile<BS_BN> rb;
+    const int kq = tid & 15;
+    unsigned char* const sw = smem + BS_BM * BS_ROWB;
+    const unsigned char* sa = smem + (wm * WM + c) * BS_ROWB + q * 16;
+    const unsigned char* sb = sw + (wn * WN + c) * BS_ROWB + q * 16;
+    gemm_staged_loop(
+        (a.K + BS_BK - 1) / BS_BK,
+        [&](int kt) {
+            const int kk = kt * BS_BK + kq * 4;
 #pragma unroll
-        for (int ks = 0; ks < BS_BK / 32; ++ks) {
-            bf8 af[TI], bfr[TJ];
+            for (int i = 0; i < 4; ++i) {
+                const int row = (tid + i * BS_THREADS) >> 4;
+                const int gr = (m0 + row < a.M) ? (m0 + row) : (a.M - 1);
+                fa[i] = *reinterpret_cast<const float4*>(a.z + (size_t)gr * a.ldz + (kk < a.K ? kk : 0));   // (zeroed in the store)
+            }
+            rb.load(a.W, a.ldw, n0, a.N, kt * BS_BK, a.K);
+            if (kt == 0) __syncthreads();   // scale / shift visible before the first store (the first tile's loads are in flight)
+        },
+        [&](int kt) {
+            // SiLU(BN(z)) rounded to bf16: four k-consecutive values of one row -> 8 bytes of the A tile
+            const int kk = kt * BS_BK + kq * 4;
 #pragma unroll
-            for (int i = 0; i < TI; ++i) af[i] = *reinterpret_cast<const bf8*>(sa + i * 16 * BS_ROWB + ks * 64);
-#pragma unroll
-            for (int j = 0; j < TJ; ++j) bfr[j] = *reinterpret_cast<const bf8*>(sb + j * 16 * BS_ROWB + ks * 64);
-#pragma unroll
-            for (int i = 0; i < TI; ++i)
-#pragma unroll
-                for (int j = 0; j < TJ; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-        }
-        __syncthreads();
-        if (kt + 1 < nk) {
-            BS_STORE((kt + 1) * BS_BK);
-            __syncthreads();
-        }
-    }
-#undef BS_LDA
-#undef BS_LDB
-#undef BS_LOAD
-#undef BS_STA
-#undef BS_STB
-#undef BS_STORE
+            for (int i = 0; i < 4; ++i) {
+                const int row = (tid + i * BS_THREADS) >> 4;
+                union { uint2 u; __bf16 h[4]; } o;
+                if (kk < a.K) {
+                    const float4 sc = *reinterpret_cast<const float4*>(s_scale + kk);
+                    const float4 sh = *reinterpret_cast<const float4*>(s_shift + kk);
+                    o.h[0] = (__bf16)ia_bn_silu_value(fa[i].x, sc.x, sh.x); o.h[1] = (__bf16)ia_bn_silu_value(fa[i].y, sc.y, sh.y);
+                    o.h[2] = (__bf16)ia_bn_silu_value(fa[i].z, sc.z, sh.z); o.h[3] = (__bf16)ia_bn_silu_value(fa[i].w, sc.w, sh.w);
+                } else {
+                    o.u = make_uint2(0, 0);
+                }
+                *reinterpret_cast<uint2*>(smem + row * BS_ROWB + kq * 8) = o.u;
+                if (KEEP && n0 == 0 && m0 + row < a.M && kk < a.K)
+                    *reinterpret_cast<uint2*>(a.outA + (size_t)(m0 + row) * a.ldoa + kk) = o.u;
+            }
+            rb.store(sw);
+        },
+        [&](int) { gemm_mfma_bf16_ktile(sa, sb, acc); });
 
     gemm_tile_epilogue<BS_BM, BS_BN>(a, acc, smem, m0, n0);   // bias, dropout, alpha, residual, fp32 / bf16 outputs
 }

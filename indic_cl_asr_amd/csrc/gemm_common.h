@@ -1,8 +1,11 @@
 // What the projection GEMM family shares (gemm_bf16.hip: 64 / 96 / 128-row tiles on 16x16x32 MFMAs; gemm_big.hip: 256 x 256
 // tiles on 32x32x16 MFMAs; gemm_bnsilu.hip: BatchNorm + SiLU on the A operand; gemm_fp8.hip / gemm_mxfp8.hip: row-scaled and
 // block-scaled e4m3 operands): the epilogue arguments and the per-vector epilogue, the two tile epilogues through LDS, the
-// XCD-aware tile order with its grid size, and the operand checks of the extern "C" entries.  Only the operand staging and the
-// MFMA loop are a kernel's own.
+// XCD-aware tile order with its grid size, the operand checks of the extern "C" entries, and the main loop of the
+// register-staged kernels (clamped 16-byte loads, the per-thread register tile, the load / MFMA / store skeleton, the 16x16x32
+// bf16 MFMA step) with the two LDS-DMA helpers of the others.  A kernel's own: what it stages that is not a plain K-contiguous
+// tile (the implicit-GEMM gather, the BatchNorm + SiLU on the way into LDS, the MX scale words), the fp8 MFMAs, and the stage
+// rings of the LDS-DMA kernels.
 #pragma once
 #include <hip/hip_bf16.h>
 
@@ -131,6 +134,103 @@ __device__ __forceinline__ bool gemm_xcd_tile(int M, int N, int& m0, int& n0) {
 inline int gemm_xcd_grid(int M, int N, int BM, int BN) {
     const int ntm = (M + BM - 1) / BM, ntn = (N + BN - 1) / BN;
     return 8 * ((ntm + 7) / 8) * ntn;
+}
+
+// ---- Register-staged operand tiles: ONE LDS stage of 144-byte rows (a 128-byte k-tile = 64 bf16 or 128 e4m3, + 16 bytes of
+// padding: conflict-free 16-byte fragment reads), the next k-tile prefetched in registers while the MFMAs run on the current one.
+// The staging registers are plain arrays indexed by fully unrolled loops and captured by the kernels' lambdas: they stay in
+// VGPRs (0 bytes of scratch in every kernel that uses them, profiles/gemm_staging_refactor.md).
+constexpr int GEMM_ROWB = 128 + 16;
+
+// 16 bytes at element k of a K-contiguous row; elements at and past K read as zero (K % 8 == 0 for bf16, % 16 for e4m3: d_model =
+// 144 is two 64-wide k-tiles and a 16-wide tail).  The address is clamped, the select applied to the value: no branch around the load.
+template <class T>
+__device__ __forceinline__ uint4 gemm_load16_k(const T* row, int k, int K) {
+    const uint4 v = *reinterpret_cast<const uint4*>(row + (k < K ? k : 0));
+    return k < K ? v : make_uint4(0, 0, 0, 0);
+}
+
+// A thread's share of a ROWS-row operand tile: vector i = tile row (tid + i * GEMM_THREADS) >> 3, 16-byte column (tid & 7).  Rows
+// past the limit are clamped to the last valid one (their products land in output rows / columns that the epilogue never stores).
+// K_TAIL = false: the caller guarantees whole k-tiles; the loads are then unconditional (the compiler turns the k-tail select into
+// a branch around each load, which the kernel of the double-rate MFMA cannot hide).  Every vector is assigned from a by-value
+// temporary: a whole-struct copy `v[i] = *ptr` straight from memory is what leaves the array in scratch.
+template <int ROWS, bool K_TAIL = true>
+struct GemmRegTile {
+    static constexpr int NV = ROWS * 8 / GEMM_THREADS;
+    static_assert(NV * GEMM_THREADS == ROWS * 8, "whole vectors per thread");
+    uint4 v[NV];
+    template <class T>
+    __device__ __forceinline__ void load(const T* base, int ld, int row0, int row_limit, int k0, int K) {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int idx = threadIdx.x + i * GEMM_THREADS, row = idx >> 3, k = k0 + (idx & 7) * (16 / (int)sizeof(T));
+            const T* rowp = base + (size_t)((row0 + row < row_limit) ? (row0 + row) : (row_limit - 1)) * ld;
+            if constexpr (K_TAIL) {
+                v[i] = gemm_load16_k(rowp, k, K);
+            } else {
+                const uint4 t = *reinterpret_cast<const uint4*>(rowp + k);
+                v[i] = make_uint4(t.x, t.y, t.z, t.w);
+            }
+        }
+    }
+    __device__ __forceinline__ void store(unsigned char* tile) const {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int idx = threadIdx.x + i * GEMM_THREADS;
+            *reinterpret_cast<uint4*>(tile + (idx >> 3) * GEMM_ROWB + (idx & 7) * 16) = v[i];
+        }
+    }
+};
+
+// The main loop of the register-staged kernels.  load(kt): k-tile kt global -> registers; store(kt): those registers -> the LDS
+// stage; compute(kt): the MFMAs on the stage.  Called by all threads of the workgroup.
+template <class Load, class Store, class Compute>
+__device__ __forceinline__ void gemm_staged_loop(int nk, Load load, Store store, Compute compute) {
+    load(0);
+    store(0);
+    __syncthreads();
+    for (int kt = 0; kt < nk; ++kt) {
+        if (kt + 1 < nk) load(kt + 1);
+        compute(kt);
+        __syncthreads();
+        if (kt + 1 < nk) {
+            store(kt + 1);
+            __syncthreads();
+        }
+    }
+}
+
+// 16x16x32 bf16 MFMAs over one 64-deep k-tile of the stage: TI x TJ accumulator tiles of a wave.  sa / sb = the lane's fragment
+// address in the first of its TI / TJ 16-row groups: tile + (first row + (lane & 15)) * GEMM_ROWB + (lane >> 4) * 16.
+typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
+template <int TI, int TJ>
+__device__ __forceinline__ void gemm_mfma_bf16_ktile(const unsigned char* sa, const unsigned char* sb, f4 (&acc)[TI][TJ]) {
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+        bf8 af[TI], bfr[TJ];
+#pragma unroll
+        for (int i = 0; i < TI; ++i) af[i] = *reinterpret_cast<const bf8*>(sa + i * 16 * GEMM_ROWB + ks * 64);
+#pragma unroll
+        for (int j = 0; j < TJ; ++j) bfr[j] = *reinterpret_cast<const bf8*>(sb + j * 16 * GEMM_ROWB + ks * 64);
+#pragma unroll
+        for (int i = 0; i < TI; ++i)
+#pragma unroll
+            for (int j = 0; j < TJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+    }
+}
+
+// ---- LDS-DMA staging (gemm_bf16_nt_dma_kernel, gemm_big_kernel).  One instruction moves 1 KB = 8 rows x 8 chunks of 16 bytes
+// into unpadded 128-byte LDS rows, lane l's 16 bytes to dst + 16 l (dst is wave-uniform).  The conflict-free placement (chunk c
+// of row r at position c ^ (r & 7)) is produced on the SOURCE side: lane l fetches row l >> 3 of the block, logical chunk
+// (l & 7) ^ (l >> 3), whose byte offset inside the row is returned.
+__device__ __forceinline__ unsigned gemm_glds_lane(int lane, int& row) {
+    row = lane >> 3;
+    return (unsigned)(((lane & 7) ^ row) * 16);
+}
+__device__ __forceinline__ void gemm_glds16(const unsigned char* src, unsigned char* dst) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)dst,
+                                     16, 0, 0);
 }
 
 // sum over the 32 lanes of a half wave (as csrc/ffn_fused.hip): every lane of the half wave gets the total

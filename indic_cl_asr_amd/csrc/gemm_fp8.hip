@@ -20,7 +20,7 @@
 namespace {
 
 constexpr int F8_BM = GEMM_T_BM, F8_BN = GEMM_T_BN, F8_BK = 128;
-constexpr int F8_ROWB = F8_BK + 16;
+constexpr int F8_ROWB = GEMM_ROWB;
 constexpr int F8_STAGE = (F8_BM + F8_BN) * F8_ROWB;          // 36 864 B
 constexpr int F8_LDS = F8_STAGE > GEMM_T_EPI ? F8_STAGE : GEMM_T_EPI;
 constexpr float F8_MAX = 448.f;
@@ -38,63 +38,36 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_fp8_nt_kernel(F8Args a) 
     int m0, n0;
     if (!gemm_xcd_tile<F8_BM, F8_BN>(a.M, a.N, m0, n0)) return;
 
-    uint4 ra[4], rb[4];
-    // 16-byte vector (16 k-elements) at byte k_ of a K-contiguous row; bytes >= K read as zero (K % 16 == 0)
-    auto ldk = [&](const unsigned char* rowp, int k) {
-        const uint4 v = *reinterpret_cast<const uint4*>(rowp + (k < a.K ? k : 0));
-        return k < a.K ? v : make_uint4(0, 0, 0, 0);
-    };
-    auto load = [&](int k0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int idx = tid + i * GEMM_THREADS, row = idx >> 3, kv = idx & 7;
-            const int gm = (m0 + row < a.M) ? (m0 + row) : (a.M - 1);
-            const int gn = (n0 + row < a.N) ? (n0 + row) : (a.N - 1);
-            ra[i] = ldk(a.A + (size_t)gm * a.lda, k0 + kv * 16);
-            rb[i] = ldk(a.W + (size_t)gn * a.ldw, k0 + kv * 16);
-        }
-    };
-    auto store = [&]() {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int idx = tid + i * GEMM_THREADS, row = idx >> 3, kv = idx & 7;
-            *reinterpret_cast<uint4*>(smem + row * F8_ROWB + kv * 16) = ra[i];
-            *reinterpret_cast<uint4*>(smem + F8_BM * F8_ROWB + row * F8_ROWB + kv * 16) = rb[i];
-        }
-    };
+    GemmRegTile<F8_BM> ra;   // (bytes >= K read as zero, K % 16 == 0)
+    GemmRegTile<F8_BN> rb;
     f4 acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = (f4){0.f, 0.f, 0.f, 0.f};
 
-    const int nk = (a.K + F8_BK - 1) / F8_BK;
-    load(0);
-    store();
-    __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-        if (kt + 1 < nk) load((kt + 1) * F8_BK);
-        const unsigned char* sa_ = smem + (wm * 64 + c) * F8_ROWB + q * 8;
-        const unsigned char* sb_ = smem + F8_BM * F8_ROWB + (wn * 64 + c) * F8_ROWB + q * 8;
+    unsigned char* const sw = smem + F8_BM * F8_ROWB;
+    const unsigned char* sa_ = smem + (wm * 64 + c) * F8_ROWB + q * 8;
+    const unsigned char* sb_ = sw + (wn * 64 + c) * F8_ROWB + q * 8;
+    gemm_staged_loop(
+        (a.K + F8_BK - 1) / F8_BK,
+        [&](int kt) { ra.load(a.A, a.lda, m0, a.M, kt * F8_BK, a.K); rb.load(a.W, a.ldw, n0, a.N, kt * F8_BK, a.K); },
+        [&](int) { ra.store(smem); rb.store(sw); },
+        [&](int) {
 #pragma unroll
-        for (int ks = 0; ks < F8_BK / 32; ++ks) {
-            long af[4], wf[4];
+            for (int ks = 0; ks < F8_BK / 32; ++ks) {
+                long af[4], wf[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) af[i] = *reinterpret_cast<const long*>(sa_ + i * 16 * F8_ROWB + ks * 32);
+                for (int i = 0; i < 4; ++i) af[i] = *reinterpret_cast<const long*>(sa_ + i * 16 * F8_ROWB + ks * 32);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) wf[j] = *reinterpret_cast<const long*>(sb_ + j * 16 * F8_ROWB + ks * 32);
+                for (int j = 0; j < 4; ++j) wf[j] = *reinterpret_cast<const long*>(sb_ + j * 16 * F8_ROWB + ks * 32);
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
+                for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int j = 0; j < 4; ++j)   // transposed product: rows of the MFMA result = output columns
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(wf[j], af[i], acc[i][j], 0, 0, 0);
-        }
-        __syncthreads();
-        if (kt + 1 < nk) {
-            store();
-            __syncthreads();
-        }
-    }
+                    for (int j = 0; j < 4; ++j)   // transposed product: rows of the MFMA result = output columns
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(wf[j], af[i], acc[i][j], 0, 0, 0);
+            }
+        });
     gemm_tile_epilogue_t<true>(a, acc, smem, m0, n0, a.sa, a.sw);
 }
 

@@ -26,7 +26,7 @@ namespace {
 typedef int v8i __attribute__((ext_vector_type(8)));
 
 constexpr int MX_BM = GEMM_T_BM, MX_BN = GEMM_T_BN, MX_BK = 128;
-constexpr int MX_ROWB = MX_BK + 16;
+constexpr int MX_ROWB = GEMM_ROWB;
 constexpr int MX_STAGE = (MX_BM + MX_BN) * MX_ROWB;
 constexpr int MX_LDS = MX_STAGE > GEMM_T_EPI ? MX_STAGE : GEMM_T_EPI;
 
@@ -44,40 +44,11 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_mxfp8_nt_kernel(MxArgs a
     if (!gemm_xcd_tile<MX_BM, MX_BN>(a.M, a.N, m0, n0)) return;
     const int bsh = 8 * (2 * (kg & 1) + (kg >> 1));           // this lane's 32-block inside a k-tile -> byte of the scale word
 
-    // staging (named scalars / fully unrolled arrays only: pointer arrays captured by lambdas end up in scratch memory)
-    uint4 ra0, ra1, ra2, ra3, rb0, rb1, rb2, rb3;
-    const int row_l = tid >> 3, kv_l = (tid & 7) * 16;     // rows row_l + 32 i, i = 0..3
-    size_t a_off[4], w_off[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int row = row_l + 32 * i;
-        const int gm = (m0 + row < a.M) ? (m0 + row) : (a.M - 1);
-        const int gn = (n0 + row < a.N) ? (n0 + row) : (a.N - 1);
-        a_off[i] = (size_t)gm * a.lda + kv_l;
-        w_off[i] = (size_t)gn * a.ldw + kv_l;
-    }
-#define MX_LOAD(k0_)                                                                   \
-    do {                                                                               \
-        ra0 = *reinterpret_cast<const uint4*>(a.A + a_off[0] + (k0_));                 \
-        ra1 = *reinterpret_cast<const uint4*>(a.A + a_off[1] + (k0_));                 \
-        ra2 = *reinterpret_cast<const uint4*>(a.A + a_off[2] + (k0_));                 \
-        ra3 = *reinterpret_cast<const uint4*>(a.A + a_off[3] + (k0_));                 \
-        rb0 = *reinterpret_cast<const uint4*>(a.W + w_off[0] + (k0_));                 \
-        rb1 = *reinterpret_cast<const uint4*>(a.W + w_off[1] + (k0_));                 \
-        rb2 = *reinterpret_cast<const uint4*>(a.W + w_off[2] + (k0_));                 \
-        rb3 = *reinterpret_cast<const uint4*>(a.W + w_off[3] + (k0_));                 \
-    } while (0)
-#define MX_STORE()                                                                                     \
-    do {                                                                                               \
-        unsigned char* sa2_ = smem + row_l * MX_ROWB + kv_l;                                           \
-        unsigned char* sb2_ = sa2_ + MX_BM * MX_ROWB;                                                  \
-        *reinterpret_cast<uint4*>(sa2_) = ra0; *reinterpret_cast<uint4*>(sa2_ + 32 * MX_ROWB) = ra1;   \
-        *reinterpret_cast<uint4*>(sa2_ + 64 * MX_ROWB) = ra2; *reinterpret_cast<uint4*>(sa2_ + 96 * MX_ROWB) = ra3; \
-        *reinterpret_cast<uint4*>(sb2_) = rb0; *reinterpret_cast<uint4*>(sb2_ + 32 * MX_ROWB) = rb1;   \
-        *reinterpret_cast<uint4*>(sb2_ + 64 * MX_ROWB) = rb2; *reinterpret_cast<uint4*>(sb2_ + 96 * MX_ROWB) = rb3; \
-    } while (0)
-    // scale words (4 e8m0 bytes = the 4 blocks of one k-tile) of this lane's 4 + 4 fragment rows: byte offsets of the rows
-    unsigned sa_off[4], sw_off[4];
+    GemmRegTile<MX_BM, false> ra;   // (K % 128 == 0: whole k-tiles)
+    GemmRegTile<MX_BN, false> rb;
+    // scale words (4 e8m0 bytes = the 4 blocks of one k-tile) of this lane's 4 + 4 fragment rows: byte offsets of the rows, the
+    // prefetched k-tile's words and the staged k-tile's bytes
+    unsigned sa_off[4], sw_off[4], nxt_a[4], nxt_w[4], cur_a[4], cur_w[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         int gm = m0 + wm * 64 + i * 16 + c; gm = gm < a.M ? gm : a.M - 1;
@@ -85,53 +56,51 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_mxfp8_nt_kernel(MxArgs a
         sa_off[i] = (unsigned)gm * (unsigned)a.ldsa;
         sw_off[i] = (unsigned)gn * (unsigned)a.ldsw;
     }
-    unsigned sca[4], scw[4];
-#define MX_LOAD_SCALES(kt_)                                                                            \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                    \
-        sca[i] = *reinterpret_cast<const unsigned*>(a.sa + sa_off[i] + 4 * (kt_));                     \
-        scw[i] = *reinterpret_cast<const unsigned*>(a.sw + sw_off[i] + 4 * (kt_));                     \
-    }
+    // the prefetched words become the current bytes behind a k-tile's MFMAs, never in the store: the words are the last loads a
+    // k-step issues, and the LDS stores must wait for the tile loads only
+    auto take_scales = [&]() {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { cur_a[i] = (nxt_a[i] >> bsh) & 0xFFu; cur_w[i] = (nxt_w[i] >> bsh) & 0xFFu; }
+    };
     f4 acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = (f4){0.f, 0.f, 0.f, 0.f};
 
-    const int nk = a.K / MX_BK;
-    MX_LOAD(0);
-    MX_LOAD_SCALES(0);
-    MX_STORE();
-    __syncthreads();
     const int koff = 64 * (kg >> 1) + 16 * (kg & 1);
+    unsigned char* const sw = smem + MX_BM * MX_ROWB;
     const unsigned char* sa_ = smem + (wm * 64 + c) * MX_ROWB + koff;
-    const unsigned char* sb_ = smem + MX_BM * MX_ROWB + (wn * 64 + c) * MX_ROWB + koff;
-    for (int kt = 0; kt < nk; ++kt) {
-        unsigned cur_a[4], cur_w[4];
+    const unsigned char* sb_ = sw + (wn * 64 + c) * MX_ROWB + koff;
+    gemm_staged_loop(
+        a.K / MX_BK,
+        [&](int kt) {
+            ra.load(a.A, a.lda, m0, a.M, kt * MX_BK, a.K);
+            rb.load(a.W, a.ldw, n0, a.N, kt * MX_BK, a.K);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) { cur_a[i] = (sca[i] >> bsh) & 0xFFu; cur_w[i] = (scw[i] >> bsh) & 0xFFu; }
-        if (kt + 1 < nk) { MX_LOAD((kt + 1) * MX_BK); MX_LOAD_SCALES(kt + 1); }
-        v8i af[4], wf[4];
+            for (int i = 0; i < 4; ++i) {
+                nxt_a[i] = *reinterpret_cast<const unsigned*>(a.sa + sa_off[i] + 4 * kt);
+                nxt_w[i] = *reinterpret_cast<const unsigned*>(a.sw + sw_off[i] + 4 * kt);
+            }
+            if (kt == 0) take_scales();
+        },
+        [&](int) { ra.store(smem); rb.store(sw); },
+        [&](int) {
+            v8i af[4], wf[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint4 lo = *reinterpret_cast<const uint4*>(sa_ + i * 16 * MX_ROWB), hi = *reinterpret_cast<const uint4*>(sa_ + i * 16 * MX_ROWB + 32);
-            af[i] = (v8i){(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
-            const uint4 wl = *reinterpret_cast<const uint4*>(sb_ + i * 16 * MX_ROWB), wh = *reinterpret_cast<const uint4*>(sb_ + i * 16 * MX_ROWB + 32);
-            wf[i] = (v8i){(int)wl.x, (int)wl.y, (int)wl.z, (int)wl.w, (int)wh.x, (int)wh.y, (int)wh.z, (int)wh.w};
-        }
+            for (int i = 0; i < 4; ++i) {
+                const uint4 lo = *reinterpret_cast<const uint4*>(sa_ + i * 16 * MX_ROWB), hi = *reinterpret_cast<const uint4*>(sa_ + i * 16 * MX_ROWB + 32);
+                af[i] = (v8i){(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
+                const uint4 wl = *reinterpret_cast<const uint4*>(sb_ + i * 16 * MX_ROWB), wh = *reinterpret_cast<const uint4*>(sb_ + i * 16 * MX_ROWB + 32);
+                wf[i] = (v8i){(int)wl.x, (int)wl.y, (int)wl.z, (int)wl.w, (int)wh.x, (int)wh.y, (int)wh.z, (int)wh.w};
+            }
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
+            for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int j = 0; j < 4; ++j)   // transposed product: the MFMA's rows = output columns (weight rows), columns = activation rows
-                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wf[j], af[i], acc[i][j], 0, 0, 0, (int)cur_w[j], 0, (int)cur_a[i]);
-        __syncthreads();
-        if (kt + 1 < nk) {
-            MX_STORE();
-            __syncthreads();
-        }
-    }
-#undef MX_LOAD
-#undef MX_STORE
-#undef MX_LOAD_SCALES
+                for (int j = 0; j < 4; ++j)   // transposed product: the MFMA's rows = output columns (weight rows), columns = activation rows
+                    acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wf[j], af[i], acc[i][j], 0, 0, 0, (int)cur_w[j], 0, (int)cur_a[i]);
+            take_scales();   // the prefetched k-tile's, if there is one
+        });
     gemm_tile_epilogue_t<false>(a, acc, smem, m0, n0);   // (no operand scales left to apply)
 }
 
