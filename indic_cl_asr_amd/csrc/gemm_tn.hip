@@ -12,6 +12,7 @@
 #include <hip/hip_bf16.h>
 
 #include "ia_common.h"
+#include "lds_transpose.h"
 #include "partials.h"
 
 namespace {
@@ -26,29 +27,7 @@ constexpr int TN_MS = 64;    // contracted rows per step
 constexpr int TN_ROWB = 256; // LDS bytes per tile row (128 bf16)
 constexpr int TN_TILE = TN_MS * TN_ROWB;
 
-// byte offset of 16-byte chunk ch (0..15) of row `row` in a [64][128 x bf16] tile: chunk index XOR-swizzled so that
-// both the row-wise store and the transposed 4-row block reads are conflict-free (cdna_hip_programming.md T10, image b)
-__device__ __forceinline__ int tn_off(int row, int ch) { return TN_ROWB * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
-
-// LDS byte addresses (address space 3) of the two 4-row blocks of one 16x16x32 operand fragment: 8 consecutive m =
-// rows r0..r0+7 for column col0 + (lane & 15).  Lane 4q+p of a 16-lane group addresses row q, columns 4p..4p+3 of its block.
-__device__ __forceinline__ void tn_frag_addr(unsigned tile_lds, int r0, int col0, int lane, unsigned* a0, unsigned* a1) {
-    const int l16 = lane & 15, q = l16 >> 2, p = l16 & 3;
-    const int ch = (col0 >> 3) + (p >> 1);
-    *a0 = tile_lds + tn_off(r0 + q, ch) + 8 * (p & 1);
-    *a1 = tile_lds + tn_off(r0 + 4 + q, ch) + 8 * (p & 1);
-}
-__device__ __forceinline__ bf4 tn_tr_read(unsigned addr) {
-    bf4 v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(addr));
-    return v;
-}
-__device__ __forceinline__ bf8 tn_join(bf4 lo, bf4 hi) {
-    bf8 o;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { o[j] = lo[j]; o[4 + j] = hi[j]; }
-    return o;
-}
+// (the [64][128 x bf16] tiles are staged with the swizzle of lds_transpose.h and read back through its transposing reads)
 
 // XCD-aware workgroup order shared by both kernels.  All output tiles of one split read the same rows of dY and X (an
 // [rps x (n + k)] slice, streamed 64 rows at a time in lock step); workgroup ids go round-robin over the 8 XCDs, so the ids
@@ -119,10 +98,10 @@ __device__ __forceinline__ void tn_tile_body(const __bf16* __restrict__ dY, int 
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 unsigned a0, a1;
-                tn_frag_addr(lY, ks * 32 + q4 * 8, wn * 64 + i * 16, lane, &a0, &a1);
-                alo[i] = tn_tr_read(a0); ahi[i] = tn_tr_read(a1);
-                tn_frag_addr(lX, ks * 32 + q4 * 8, wk * 64 + i * 16, lane, &a0, &a1);
-                blo[i] = tn_tr_read(a0); bhi[i] = tn_tr_read(a1);
+                trl_frag_addr<false>(lY, TN_ROWB, ks * 32 + q4 * 8, wn * 64 + i * 16, lane, &a0, &a1);
+                alo[i] = trl_read<bf4>(a0); ahi[i] = trl_read<bf4>(a1);
+                trl_frag_addr<false>(lX, TN_ROWB, ks * 32 + q4 * 8, wk * 64 + i * 16, lane, &a0, &a1);
+                blo[i] = trl_read<bf4>(a0); bhi[i] = trl_read<bf4>(a1);
             }
             asm volatile("s_waitcnt lgkmcnt(0)"
                          : "+v"(alo[0]), "+v"(alo[1]), "+v"(alo[2]), "+v"(alo[3]), "+v"(ahi[0]), "+v"(ahi[1]), "+v"(ahi[2]),
@@ -132,7 +111,7 @@ __device__ __forceinline__ void tn_tile_body(const __bf16* __restrict__ dY, int 
                          : "memory");
             bf8 af[4], bfr[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) { af[i] = tn_join(alo[i], ahi[i]); bfr[i] = tn_join(blo[i], bhi[i]); }
+            for (int i = 0; i < 4; ++i) { af[i] = trl_join(alo[i], ahi[i]); bfr[i] = trl_join(blo[i], bhi[i]); }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
 #pragma unroll
@@ -145,7 +124,7 @@ __device__ __forceinline__ void tn_tile_body(const __bf16* __restrict__ dY, int 
     // ---- interior tiles over whole 64-row steps (every projection of the encoder): the two operand tiles go global -> LDS
     // directly (global_load_lds_dwordx4: no staging registers, no ds_write, no branch per vector), two stages, ONE barrier per
     // step, the next step in flight under the current one's MFMAs.  One instruction fills 1 KB = 4 tile rows x 16 chunks with
-    // lane l at position l, so the XOR swizzle of tn_off is applied on the source side: lane l of block blk fetches, for row
+    // lane l at position l, so the XOR swizzle of trl_off is applied on the source side: lane l of block blk fetches, for row
     // 4 blk + (l >> 4), the logical chunk (l & 15) ^ (((l >> 4) << 2) | (blk & 3)).  Wave w issues blocks 4 w .. 4 w + 3 of both tiles.
     const bool dma_path = n0 + TN_BN <= n && k0 + TN_BK <= k && (m_end - m_beg) % TN_MS == 0 && m_end > m_beg;
     if (dma_path) {
@@ -200,8 +179,8 @@ __device__ __forceinline__ void tn_tile_body(const __bf16* __restrict__ dY, int 
     do {                                                                                                           \
         _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                            \
             const int idx_ = tid + 256 * i, row_ = idx_ >> 4, ch_ = idx_ & 15;                                     \
-            *reinterpret_cast<uint4*>(sY + tn_off(row_, ch_)) = ry[i];                                             \
-            *reinterpret_cast<uint4*>(sX + tn_off(row_, ch_)) = rx[i];                                             \
+            *reinterpret_cast<uint4*>(sY + trl_off<false>(TN_ROWB, row_, ch_)) = ry[i];                                             \
+            *reinterpret_cast<uint4*>(sX + trl_off<false>(TN_ROWB, row_, ch_)) = rx[i];                                             \
         }                                                                                                          \
     } while (0)
 

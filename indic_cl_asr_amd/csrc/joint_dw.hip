@@ -18,13 +18,16 @@
 // stay resident in LDS (27 KB at U+1 = 106): per step only the G tile (33 KB) and one or two 256-byte f rows are fetched,
 // instead of a full [64 x 128] f tile and g tile (another 32 KB of L2 traffic per step, 3.2 GB per launch).
 #include <cstdlib>
+#include <type_traits>
 
 #include "joint_common.h"
+#include "lds_transpose.h"
 #include "partials.h"
 
 namespace {
 
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+typedef unsigned u4v __attribute__((ext_vector_type(4)));
 
 constexpr int DW_THREADS = 512;       // 8 waves: 2 (vocabulary) x 4 (hidden), 144 x 32 outputs each, two waves per SIMD
 constexpr int DW_VP = 288;            // vocabulary rows per workgroup (LD <= 288): 2 waves x 9 row tiles
@@ -37,30 +40,9 @@ constexpr int DW_STAGE = DW_YTILE + DW_XTILE;   // 64 KB; two stages (double buf
 constexpr int DW_NY = 5;              // G chunks per thread per step: ceil(64 * 36 / 512)
 constexpr int DW_NX = 2;              // hidden chunks per thread per step: 64 * 16 / 512
 constexpr int DW_MAX_U1 = 128;        // prediction rows resident in LDS: 128 x 256 B = 32 KB behind the two stages
+constexpr int DW_TF = 8, DW_TU = 8;   // TILED: a step = 8 frames x 8 labels of one utterance
 
-// byte offset of 16-byte chunk ch of row `row`: the low 4 bits of the chunk index are XOR-swizzled (T10, image b) so that
-// row-wise stores and the transposed 4-row block reads are both conflict-free; rows are multiples of 256 B
-__device__ __forceinline__ int dw_off(int row, int ch, int rowb) {
-    return rowb * row + 16 * ((ch & ~15) | ((ch & 15) ^ (((row & 3) << 2) | ((row >> 2) & 3))));
-}
-__device__ __forceinline__ void dw_frag_addr(unsigned tile_lds, int rowb, int r0, int col0, int lane, unsigned* a0, unsigned* a1) {
-    const int l16 = lane & 15, q = l16 >> 2, p = l16 & 3;
-    const int ch = (col0 >> 3) + (p >> 1);
-    *a0 = tile_lds + dw_off(r0 + q, ch, rowb) + 8 * (p & 1);
-    *a1 = tile_lds + dw_off(r0 + 4 + q, ch, rowb) + 8 * (p & 1);
-}
-template <int OFF>
-__device__ __forceinline__ h4 dw_tr_read(unsigned addr) {
-    h4 v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-    return v;
-}
-__device__ __forceinline__ h8 dw_join(h4 lo, h4 hi) {
-    h8 o;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { o[j] = lo[j]; o[4 + j] = hi[j]; }
-    return o;
-}
+// (both tiles are staged with the XOR swizzle of lds_transpose.h and read back through its transposing reads)
 
 // q = x / d, r = x % d for x < 2^31 with a host-supplied m = ceil(2^32 / d) (0xFFFFFFFF for d == 1): one mulhi + fix-up
 __device__ __forceinline__ void dw_divmod(unsigned x, unsigned d, unsigned m, unsigned* q, unsigned* r) {
@@ -68,16 +50,6 @@ __device__ __forceinline__ void dw_divmod(unsigned x, unsigned d, unsigned m, un
     int rr = (int)(x - qq * d);
     const int lo = rr < 0 ? 1 : 0, hi = rr >= (int)d ? 1 : 0;   // branch-free fix-up
     *q = qq - lo + hi; *r = (unsigned)(rr + (lo - hi) * (int)d);
-}
-
-// live 64-cell steps of utterance b: up to its last live frame
-__device__ __forceinline__ int dw_live_spu(const int64_t* __restrict__ act_lens, int b, int T, int U1, int spu) {
-    if (!act_lens) return spu;
-    long long tb = act_lens[b];
-    tb = tb < 0 ? 0 : (tb > T ? T : tb);
-    int live = (int)((tb * U1 + DW_MS - 1) / DW_MS);
-    live = live < 1 ? 1 : live;
-    return live < spu ? live : spu;
 }
 
 struct DwArgs {
@@ -93,8 +65,16 @@ struct DwArgs {
     const int64_t* label_lens;           // TILED only: labels > label_lens[b] carry no gradient either
 };
 
-constexpr int DW_TF = 8, DW_TU = 8;      // TILED: a step = 8 frames x 8 labels of one utterance
-// TILED step grid of utterance b: live frame tiles x live label tiles (at least one step), its clamped frame count
+// live 64-cell steps of utterance b: up to its last live frame
+__device__ __forceinline__ int dw_live_spu(const int64_t* __restrict__ act_lens, int b, int T, int U1, int spu) {
+    if (!act_lens) return spu;
+    long long tb = act_lens[b];
+    tb = tb < 0 ? 0 : (tb > T ? T : tb);
+    int live = (int)((tb * U1 + DW_MS - 1) / DW_MS);
+    live = live < 1 ? 1 : live;
+    return live < spu ? live : spu;
+}
+
 // 64-bit load through the scalar unit (uniform address): inside the step loop a vector load of the lengths -- which is what
 // the compiler emits for them, uniform address or not -- is followed by s_waitcnt vmcnt(0) and drains every G load in flight
 __device__ __forceinline__ long long dw_sload64(const int64_t* p) {
@@ -102,6 +82,7 @@ __device__ __forceinline__ long long dw_sload64(const int64_t* p) {
     asm volatile("s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(p));
     return v;
 }
+// TILED step grid of utterance b: live frame tiles x live label tiles (at least one step), its label tiles, its clamped frame count
 template <bool UNIFORM>
 __device__ __forceinline__ void dw_tiles_of(const int64_t* act_lens, const int64_t* label_lens, int T, int U1, int b, int* n, int* nut,
                                             int* tb) {
@@ -115,7 +96,114 @@ __device__ __forceinline__ void dw_tiles_of(const int64_t* act_lens, const int64
     *n = ntt * *nut;
     *tb = (int)t;
 }
-#define dw_tiles(a_, b_, n_, nut_, tb_) dw_tiles_of<true>((a_).act_lens, (a_).label_lens, (a_).T, (a_).U1, (b_), (n_), (nut_), (tb_))
+// live steps of utterance b in the kernel's geometry; b may differ per lane (the prefix pass over the utterances)
+template <bool TILED>
+__device__ __forceinline__ int dw_live_steps(const DwArgs& a, int b) {
+    if constexpr (TILED) {
+        int n, nut, tb;
+        dw_tiles_of<false>(a.act_lens, a.label_lens, a.T, a.U1, b, &n, &nut, &tb);
+        return n;
+    } else {
+        return dw_live_spu(a.act_lens, b, a.T, a.U1, a.spu);
+    }
+}
+
+// Where a split stands: step s of the n live steps of utterance b, global step idx; all uniform.  The kernel keeps two: the step
+// being staged into LDS and, one or two steps ahead of it, the step being loaded (the step being multiplied is implicit).
+struct DwFlatPos {};
+struct DwTilePos { int tt, ut, nut, tb; };   // frame tile, label tile; label tiles and clamped frame count of the utterance
+template <bool TILED>
+struct DwCursor {
+    int b, s, idx, n;
+    std::conditional_t<TILED, DwTilePos, DwFlatPos> tile;
+
+    __device__ __forceinline__ void start(const DwArgs& a, int b_first, int s_first, int step_beg) {
+        b = __builtin_amdgcn_readfirstlane(b_first); s = __builtin_amdgcn_readfirstlane(s_first); idx = step_beg;
+        n = __builtin_amdgcn_readfirstlane(dw_live_steps<TILED>(a, b));
+        if constexpr (TILED) {
+            int n_, nut_, tb_;
+            dw_tiles_of<true>(a.act_lens, a.label_lens, a.T, a.U1, __builtin_amdgcn_readfirstlane(b), &n_, &nut_, &tb_);
+            tile.nut = __builtin_amdgcn_readfirstlane(nut_); tile.tb = __builtin_amdgcn_readfirstlane(tb_);
+            tile.tt = s / tile.nut; tile.ut = s - tile.tt * tile.nut;
+        }
+    }
+    // one step further, stopping at the split's last step (which is then staged once more at the end: harmless, and the loop
+    // body stays free of divergent branches)
+    __device__ __forceinline__ void advance(const DwArgs& a, int step_end) {
+        if (idx + 1 < step_end) {
+            ++idx;
+            if constexpr (TILED) {
+                if (++tile.ut == tile.nut) { tile.ut = 0; ++tile.tt; }
+            }
+            if (++s == n) {
+                s = 0; ++b;
+                if constexpr (TILED) {   // scalar loads: a vector load here drains vmcnt
+                    int n_, nut_, tb_;
+                    dw_tiles_of<true>(a.act_lens, a.label_lens, a.T, a.U1, __builtin_amdgcn_readfirstlane(b), &n_, &nut_, &tb_);
+                    n = __builtin_amdgcn_readfirstlane(n_); tile.nut = __builtin_amdgcn_readfirstlane(nut_);
+                    tile.tb = __builtin_amdgcn_readfirstlane(tb_); tile.tt = 0; tile.ut = 0;
+                } else {
+                    n = __builtin_amdgcn_readfirstlane(dw_live_steps<false>(a, b));
+                }
+            }
+        }
+    }
+};
+
+// What a thread holds of one step between its loads and its LDS stores.  y is an array of NATIVE vectors: the G chunks are only
+// ever copied whole, in from global memory and out to LDS, and for HIP's uint4 (a struct) both copies are memcpys, which give the
+// compiler no typed access to split the array by -- in the tiled kernels, which compile the member-wise masking out, uint4 y[] leaves
+// BOTH register sets in scratch memory (672 B per lane, no spill reported).  f and g may stay uint4: they are read through a union
+// as halves.  That the set is a struct, returned by value from a lambda, changes nothing.
+struct DwRegs {
+    u4v y[DW_NY];                   // G chunks idx = tid + 512 k of the step's 64 rows
+    uint4 f[DW_NX], g[DW_NX];       // the f row (and, when the g rows are streamed, the g row) of hidden rows xrow0, xrow0 + 32
+    unsigned u[DW_NX];              // their label index u; TILED: (cell in the utterance << 8) | u, bit 31 = row switched off
+};
+
+// 8 units of one regenerated hidden row: keep o relu(f + g), zero for a row that is switched off
+template <bool DROPOUT>
+__device__ __forceinline__ uint4 dw_hidden8(uint4 f, uint4 g, bool live, unsigned seed, unsigned cell, unsigned kg, unsigned thr) {
+    const h2 zero2 = {(_Float16)0, (_Float16)0};
+    union { uint4 u; h8 v; h2 p[4]; } x, y, z;
+    x.u = f; y.u = g;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) z.p[j] = __builtin_elementwise_max(x.p[j] + y.p[j], zero2);
+    if (DROPOUT) z.v = dropout_apply8(z.v, seed, cell, kg, thr);
+    z.u.x = live ? z.u.x : 0u; z.u.y = live ? z.u.y : 0u; z.u.z = live ? z.u.z : 0u; z.u.w = live ? z.u.w : 0u;
+    return z.u;
+}
+
+// One 32-cell k-step of the staged tiles into the wave's 144 x 32 outputs; a0 / a1 (G columns) and b0 / b1 (hidden columns) are
+// the fragment addresses of k-step 0, k-step 1 lies 32 rows further in the same swizzle phase: an immediate offset
+template <int KS>
+__device__ __forceinline__ void dw_kstep(f4 (&acc)[9][2], const unsigned (&a0)[9], const unsigned (&a1)[9], const unsigned (&b0)[2],
+                                         const unsigned (&b1)[2]) {
+    h4 blo[2], bhi[2], alo[9], ahi[9];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        blo[j] = trl_read<h4, KS * 32 * DW_XROW>(b0[j]); bhi[j] = trl_read<h4, KS * 32 * DW_XROW>(b1[j]);
+    }
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        alo[i] = trl_read<h4, KS * 32 * DW_YROW>(a0[i]); ahi[i] = trl_read<h4, KS * 32 * DW_YROW>(a1[i]);
+    }
+    // ONE wait that all fragment registers are tied to (the compiler does not know the asm reads LDS asynchronously)
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(alo[0]), "+v"(alo[1]), "+v"(alo[2]), "+v"(alo[3]), "+v"(alo[4]), "+v"(alo[5]), "+v"(alo[6]),
+                   "+v"(alo[7]), "+v"(alo[8]), "+v"(ahi[0]), "+v"(ahi[1]), "+v"(ahi[2]), "+v"(ahi[3]), "+v"(ahi[4]),
+                   "+v"(ahi[5]), "+v"(ahi[6]), "+v"(ahi[7]), "+v"(ahi[8]), "+v"(blo[0]), "+v"(blo[1]), "+v"(bhi[0]),
+                   "+v"(bhi[1])
+                 :
+                 : "memory");
+    const h8 bf0 = trl_join(blo[0], bhi[0]), bf1 = trl_join(blo[1], bhi[1]);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        const h8 af = trl_join(alo[i], ahi[i]);
+        acc[i][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf0, acc[i][0], 0, 0, 0);
+        acc[i][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf1, acc[i][1], 0, 0, 0);
+    }
+}
 
 // TILED (T >= 8 and U+1 >= 8): the 64 cells of a step are an 8-frame x 8-label tile instead of 64 consecutive cells, and an
 // utterance's steps cover its live frames x live labels only (the flat steps skip dead frames but not dead labels: another
@@ -144,17 +232,12 @@ __global__ __launch_bounds__(DW_THREADS, 1) void joint_dw_fused_kernel(DwArgs a)
     const int h0 = htile * DW_BH;
     const int T = a.T, U1 = a.U1, H = a.H, LD = a.LD, vpr = LD / 8;
     // Steps = 64 consecutive lattice cells of one utterance.  With the frame counts the steps of an utterance end behind its
-    // last live frame (G is zero beyond: a fifth of the lattice at lengths 0.6-1.0 x T), and the splits share the LIVE steps.
-    // live_spu(b) is uniform (scalar loads); the starting point of this split comes from a prefix pass through LDS.
-    auto live_steps = [&](int b_) -> int {
-        if (TILED) { int n_, nut_, tb_; dw_tiles_of<false>(a.act_lens, a.label_lens, T, U1, b_, &n_, &nut_, &tb_); return n_; }
-        return dw_live_spu(a.act_lens, b_, T, U1, a.spu);
-    };
-#define live_spu(b_) __builtin_amdgcn_readfirstlane(live_steps(b_))   /* uniform b only */
+    // last live frame (G is zero beyond: a fifth of the lattice at lengths 0.6-1.0 x T), and the splits share the LIVE steps:
+    // the starting point of this split comes from a prefix pass over the utterances' live steps through LDS.
     int nsteps = a.B * a.spu, step_beg, step_end, b_first = 0, s_first = 0;
     if ((a.act_lens || TILED) && a.B <= 4096) {
         int* s_spu = reinterpret_cast<int*>(smem);        // (the stages are free until the loop starts; re-zeroed below)
-        for (int i = tid; i < a.B; i += DW_THREADS) s_spu[i] = live_steps(i);
+        for (int i = tid; i < a.B; i += DW_THREADS) s_spu[i] = dw_live_steps<TILED>(a, i);
         __syncthreads();
         int total = 0;
         for (int i = 0; i < a.B; ++i) total += s_spu[i];
@@ -207,7 +290,7 @@ __global__ __launch_bounds__(DW_THREADS, 1) void joint_dw_fused_kernel(DwArgs a)
         unsigned yr, yc;
         dw_divmod(i, (unsigned)vpr, a.mV, &yr, &yc);
         // beyond the 64 rows: a private dump slot (logical chunks >= 36 of a row are never read)
-        yoff[k] = (i < (unsigned)(DW_MS * vpr)) ? dw_off((int)yr, (int)yc, DW_YROW) : dw_off(tid & 63, 40 + (tid >> 6), DW_YROW);
+        yoff[k] = (i < (unsigned)(DW_MS * vpr)) ? trl_off<true>(DW_YROW, (int)yr, (int)yc) : trl_off<true>(DW_YROW, tid & 63, 40 + (tid >> 6));
     }
     unsigned goff[TILED ? DW_NY : 1];   // TILED: byte offset of G chunk k from the tile's first row (run of 8 rows per frame)
     if (TILED) {
@@ -221,186 +304,150 @@ __global__ __launch_bounds__(DW_THREADS, 1) void joint_dw_fused_kernel(DwArgs a)
     }
     const int xrow0 = tid >> 4, xch = tid & 15;                    // rows xrow0 and xrow0 + 32
     int hcol = h0 + xch * 8; hcol = hcol <= H - 8 ? hcol : H - 8;  // columns >= H are never written out
-    const int xoff0 = dw_off(xrow0, xch, DW_XROW), xoff1 = dw_off(xrow0 + 32, xch, DW_XROW);
-    // two register sets: the loads of step n+2 and n+3 are in flight while step n is multiplied (a step is ~1.7 us, the
-    // loaded-HBM latency is of the same order: one step of distance left the staging phase waiting)
-    // (py as native vectors: HIP's uint4 struct is assigned by memcpy, which kept the whole array in scratch memory once
-    // the masking code -- the only member-wise access -- was compiled out of the tiled variant)
-    typedef unsigned u4v __attribute__((ext_vector_type(4)));
-    u4v py[2][DW_NY];
-    uint4 pf[2][DW_NX], pg[2][DW_NX];
-    unsigned pu[2][DW_NX];                                         // label index u of the hidden rows in flight
+    const int xoff0 = trl_off<true>(DW_XROW, xrow0, xch), xoff1 = trl_off<true>(DW_XROW, xrow0 + 32, xch);
     const unsigned nfull = (unsigned)(DW_MS * vpr);                // 16-byte chunks of a full G tile
-    const h2 zero2 = {(_Float16)0, (_Float16)0};
 
-    // step index -> (utterance b, step s inside it); b_, s_ are uniform
-#define DW_LOAD(R, b_, s_, tt_, ut_, tb_)                                                                       \
+    // tile step c -> register set r: 8 runs of 8 G rows at constant offsets from the (clamped) tile origin; the hidden rows'
+    // frame / label and whether the row belongs to this tile (a shifted tile shares rows with its neighbour) go into r.u
+    auto gather_tile = [&](const auto& c) {   // (generic: only the TILED kernels instantiate it)
+        DwRegs r;
+        const int t0n = c.tile.tt * DW_TF, u0n = c.tile.ut * DW_TU;
+        const int t0 = t0n < T - DW_TF ? t0n : T - DW_TF, u0 = u0n < U1 - DW_TU ? u0n : U1 - DW_TU;
+        const char* src = reinterpret_cast<const char*>(a.G + ((size_t)c.b * a.cpu + (size_t)t0 * U1 + u0) * LD);
+#pragma unroll
+        for (int k = 0; k < DW_NY; ++k) r.y[k] = *reinterpret_cast<const u4v*>(src + goff[k]);
+        const _Float16* fb = a.f + (size_t)c.b * T * H + hcol;
+#pragma unroll
+        for (int k = 0; k < DW_NX; ++k) {
+            const int row = xrow0 + 32 * k, t = t0 + (row >> 3), u = u0 + (row & 7);
+            r.f[k] = *reinterpret_cast<const uint4*>(fb + (size_t)t * H);
+            const bool in = t >= t0n && t < c.tile.tb && u >= u0n;
+            r.u[k] = ((unsigned)(t * U1 + u) << 8) | (unsigned)u | (in ? 0u : 0x80000000u);
+            if (!GRES) r.g[k] = *reinterpret_cast<const uint4*>(a.g + ((size_t)c.b * U1 + u) * H + hcol);
+        }
+        return r;
+    };
+    // flat step c_ -> register set r_: 64 consecutive cells from cell 64 s of the utterance (uniform base + 32-bit lane offsets);
+    // the utterance's last, partial step is clamped here and masked when it is stored.  (A macro like DW_STORE below: as a function
+    // that fills the set through a reference it costs the flat kernels up to 12 more spilled registers, and returning the set by value the
+    // compiler restructures its two branches: the flat steps measured 10 % slower, profiles/joint_dw_refactor.md.)
+#define DW_GATHER_FLAT(r_, c_)                                                                                 \
     do {                                                                                                       \
-        if (TILED) {                                                                                           \
-            const int t0n_ = (tt_) * DW_TF, u0n_ = (ut_) * DW_TU;                                               \
-            const int t0_ = t0n_ < T - DW_TF ? t0n_ : T - DW_TF, u0_ = u0n_ < U1 - DW_TU ? u0n_ : U1 - DW_TU;   \
-            const char* src_ = reinterpret_cast<const char*>(a.G + ((size_t)(b_) * a.cpu + (size_t)t0_ * U1 + u0_) * LD); \
-            _Pragma("unroll") for (int k = 0; k < DW_NY; ++k) py[R][k] = *reinterpret_cast<const u4v*>(src_ + goff[k]); \
-            const _Float16* fb_ = a.f + (size_t)(b_) * T * H + hcol;                                           \
-            _Pragma("unroll") for (int k = 0; k < DW_NX; ++k) {                                                \
-                const int r_ = xrow0 + 32 * k, t_ = t0_ + (r_ >> 3), u_ = u0_ + (r_ & 7);                      \
-                pf[R][k] = *reinterpret_cast<const uint4*>(fb_ + (size_t)t_ * H);                                 \
-                const bool in_ = t_ >= t0n_ && t_ < (tb_) && u_ >= u0n_;                                       \
-                pu[R][k] = ((unsigned)(t_ * U1 + u_) << 8) | (unsigned)u_ | (in_ ? 0u : 0x80000000u);             \
-                if (!GRES) pg[R][k] = *reinterpret_cast<const uint4*>(a.g + ((size_t)(b_) * U1 + u_) * H + hcol); \
-            }                                                                                                  \
-        } else {                                                                                               \
-        const unsigned ci0_ = (unsigned)(s_) * DW_MS;                       /* first cell of the step inside the utterance */ \
+        const unsigned ci0_ = (unsigned)(c_).s * DW_MS;                                                        \
         const unsigned rows_ = (unsigned)a.cpu - ci0_ < (unsigned)DW_MS ? (unsigned)a.cpu - ci0_ : (unsigned)DW_MS; \
         const unsigned nvalid_ = rows_ * (unsigned)vpr;                                                        \
-        const char* src_ = reinterpret_cast<const char*>(a.G + ((size_t)(b_) * a.cpu + ci0_) * LD);   /* uniform base + 32-bit lane offsets */ \
+        const char* src_ = reinterpret_cast<const char*>(a.G + ((size_t)(c_).b * a.cpu + ci0_) * LD);          \
         if (rows_ == (unsigned)DW_MS) {                                                                        \
             _Pragma("unroll") for (int k = 0; k < DW_NY; ++k)                                                  \
-                py[R][k] = *reinterpret_cast<const u4v*>(src_ + 16u * (tid + DW_THREADS * k < nfull ? tid + DW_THREADS * k : nfull - 1)); \
-        } else {   /* the utterance's last, partial step: clamped here, masked when it is stored */            \
+                (r_).y[k] = *reinterpret_cast<const u4v*>(src_ + 16u * (tid + DW_THREADS * k < nfull ? tid + DW_THREADS * k : nfull - 1)); \
+        } else {                                                                                               \
             _Pragma("unroll") for (int k = 0; k < DW_NY; ++k) {                                                \
                 const unsigned i_ = tid + DW_THREADS * k;                                                      \
-                py[R][k] = *reinterpret_cast<const u4v*>(src_ + 16u * (i_ < nvalid_ ? i_ : nvalid_ - 1));       \
+                (r_).y[k] = *reinterpret_cast<const u4v*>(src_ + 16u * (i_ < nvalid_ ? i_ : nvalid_ - 1));      \
             }                                                                                                  \
         }                                                                                                      \
-        const _Float16* fb_ = a.f + (size_t)(b_) * T * H + hcol;                                               \
+        const _Float16* fb_ = a.f + (size_t)(c_).b * T * H + hcol;                                             \
         _Pragma("unroll") for (int k = 0; k < DW_NX; ++k) {                                                    \
             unsigned ci_ = ci0_ + xrow0 + 32 * k;                                                              \
             ci_ = ci_ < (unsigned)a.cpu ? ci_ : (unsigned)a.cpu - 1;                                           \
             unsigned t_;                                                                                       \
-            dw_divmod(ci_, (unsigned)U1, a.mU1, &t_, &pu[R][k]);                                                  \
-            pf[R][k] = *reinterpret_cast<const uint4*>(fb_ + (size_t)t_ * H);                                     \
-            if (!GRES) pg[R][k] = *reinterpret_cast<const uint4*>(a.g + ((size_t)(b_) * U1 + pu[R][k]) * H + hcol); \
-        }                                                                                                      \
+            dw_divmod(ci_, (unsigned)U1, a.mU1, &t_, &(r_).u[k]);                                              \
+            (r_).f[k] = *reinterpret_cast<const uint4*>(fb_ + (size_t)t_ * H);                                 \
+            if (!GRES) (r_).g[k] = *reinterpret_cast<const uint4*>(a.g + ((size_t)(c_).b * U1 + (r_).u[k]) * H + hcol); \
         }                                                                                                      \
     } while (0)
-    // chunks beyond the 64 rows of a tile are stored unconditionally too (yoff = a never-read slot of the tile)
-#define DW_STORE(R, b_, s_, stage_)                                                              \
+#define DW_LOAD(r_, c_)                                                                                        \
+    do {                                                                                                       \
+        if constexpr (TILED) (r_) = gather_tile(c_);                                                           \
+        else DW_GATHER_FLAT(r_, c_);                                                                           \
+    } while (0)
+    // register set r_ (step c_) -> LDS stage: the G chunks as they are (chunks beyond the 64 rows of a tile unconditionally too:
+    // yoff = a never-read slot of the tile), the hidden rows regenerated from their f and g rows.
+    // DW_STORE and DW_STAGE_NEXT stay macros too: as a lambda or as a function either of them costs the GRES instantiations
+    // spilled registers (profiles/joint_dw_refactor.md has the table); everything they call is a function.
+#define DW_STORE(r_, c_, stage_)                                                                               \
     do {                                                                                                       \
         unsigned char* sY_ = smem + (stage_) * DW_STAGE;                                                       \
         unsigned char* sX_ = sY_ + DW_YTILE;                                                                   \
-        const unsigned ci0_ = (unsigned)(s_) * DW_MS;                                                          \
+        const unsigned ci0_ = TILED ? 0u : (unsigned)(c_).s * DW_MS;                                           \
         const unsigned rows_ = TILED ? (unsigned)DW_MS : ((unsigned)a.cpu - ci0_ < (unsigned)DW_MS ? (unsigned)a.cpu - ci0_ : (unsigned)DW_MS); \
         const unsigned nvalid_ = rows_ * (unsigned)vpr;                                                        \
         if (rows_ != (unsigned)DW_MS) {   /* (uniform) last, partial step of the utterance */                  \
             _Pragma("unroll") for (int k = 0; k < DW_NY; ++k) {                                                \
                 const bool ok_ = tid + DW_THREADS * k < nvalid_;                                               \
-                py[R][k].x = ok_ ? py[R][k].x : 0u; py[R][k].y = ok_ ? py[R][k].y : 0u; py[R][k].z = ok_ ? py[R][k].z : 0u; py[R][k].w = ok_ ? py[R][k].w : 0u; \
+                (r_).y[k].x = ok_ ? (r_).y[k].x : 0u; (r_).y[k].y = ok_ ? (r_).y[k].y : 0u;                    \
+                (r_).y[k].z = ok_ ? (r_).y[k].z : 0u; (r_).y[k].w = ok_ ? (r_).y[k].w : 0u;                    \
             }                                                                                                  \
         }                                                                                                      \
-        _Pragma("unroll") for (int k = 0; k < DW_NY; ++k) *reinterpret_cast<u4v*>(sY_ + yoff[k]) = py[R][k];    \
-        const unsigned cellb_ = (unsigned)(b_) * (unsigned)a.cpu + (TILED ? 0u : ci0_);                        \
+        _Pragma("unroll") for (int k = 0; k < DW_NY; ++k) *reinterpret_cast<u4v*>(sY_ + yoff[k]) = (r_).y[k];  \
+        const unsigned cellb_ = (unsigned)(c_).b * (unsigned)a.cpu + ci0_;                                     \
         _Pragma("unroll") for (int k = 0; k < DW_NX; ++k) {                                                    \
-            const unsigned r_ = xrow0 + 32 * k;                                                                \
-            const unsigned u_ = TILED ? (pu[R][k] & 0xFFu) : pu[R][k];                                         \
-            const unsigned cell_ = TILED ? cellb_ + ((pu[R][k] >> 8) & 0x7FFFFFu) : cellb_ + r_;               \
-            union { uint4 u; h8 v; h2 p[4]; } x_, y_, z_;                                                      \
-            x_.u = pf[R][k];                                                                                      \
-            if (GRES) y_.u = *reinterpret_cast<const uint4*>(gtile + u_ * DW_XROW + xch * 16);                 \
-            else y_.u = pg[R][k];                                                                              \
-            _Pragma("unroll") for (int j = 0; j < 4; ++j) z_.p[j] = __builtin_elementwise_max(x_.p[j] + y_.p[j], zero2); \
-            if (DROPOUT) z_.v = dropout_apply8(z_.v, a.seed, cell_, (unsigned)((h0 >> 3) + xch), a.thr);       \
-            const bool in_ = TILED ? !(pu[R][k] >> 31) : r_ < rows_;                                           \
-            z_.u.x = in_ ? z_.u.x : 0u; z_.u.y = in_ ? z_.u.y : 0u; z_.u.z = in_ ? z_.u.z : 0u; z_.u.w = in_ ? z_.u.w : 0u; \
-            *reinterpret_cast<uint4*>(sX_ + (k ? xoff1 : xoff0)) = z_.u;                                       \
+            const unsigned row_ = xrow0 + 32 * k;                                                              \
+            const unsigned u_ = TILED ? ((r_).u[k] & 0xFFu) : (r_).u[k];                                       \
+            const unsigned cell_ = TILED ? cellb_ + (((r_).u[k] >> 8) & 0x7FFFFFu) : cellb_ + row_;            \
+            const bool in_ = TILED ? !((r_).u[k] >> 31) : row_ < rows_;                                        \
+            uint4 grow_;                                                                                       \
+            if constexpr (GRES) grow_ = *reinterpret_cast<const uint4*>(gtile + u_ * DW_XROW + xch * 16);      \
+            else grow_ = (r_).g[k];                                                                            \
+            *reinterpret_cast<uint4*>(sX_ + (k ? xoff1 : xoff0)) =                                             \
+                dw_hidden8<DROPOUT>((r_).f[k], grow_, in_, a.seed, cell_, (unsigned)((h0 >> 3) + xch), a.thr); \
         }                                                                                                      \
     } while (0)
     // the utterance's prediction rows g[b, u, h0 : h0+128] -> LDS (row-major, 256 B per row); all threads, then a barrier
-#define DW_GTILE(b_)                                                                                           \
-    do {                                                                                                       \
-        if (!GRES) break;                                                                                      \
-        const _Float16* gb_ = a.g + (size_t)(b_) * U1 * H + hcol;                                              \
-        for (int i_ = tid; i_ < U1 * 16; i_ += DW_THREADS)   /* (i_ & 15) == xch for every i_ of this thread */ \
-            *reinterpret_cast<uint4*>(gtile + i_ * 16) = *reinterpret_cast<const uint4*>(gb_ + (size_t)(i_ >> 4) * H); \
-        __syncthreads();                                                                                       \
-    } while (0)
-    // advance (b, s) by one step, stopping at the split's last step (re-staged once more at the end: harmless, and the
-    // loop body stays free of divergent branches)
-#define DW_NEXT(b_, s_, idx_, n_, tt_, ut_, nut_, tb_)                                                          \
-    do {                                                                                                       \
-        if ((idx_) + 1 < step_end) {                                                                           \
-            ++(idx_);                                                                                          \
-            if (TILED) { if (++(ut_) == (nut_)) { (ut_) = 0; ++(tt_); } }                                      \
-            if (++(s_) == (n_)) {                                                                              \
-                (s_) = 0; ++(b_);                                                                              \
-                if (TILED) { int n2_, nu2_, tb2_; dw_tiles(a, __builtin_amdgcn_readfirstlane(b_), &n2_, &nu2_, &tb2_);   /* scalar loads: a vector load here drains vmcnt */ \
-                    (n_) = __builtin_amdgcn_readfirstlane(n2_); (nut_) = __builtin_amdgcn_readfirstlane(nu2_); \
-                    (tb_) = __builtin_amdgcn_readfirstlane(tb2_); (tt_) = 0; (ut_) = 0; }                       \
-                else (n_) = live_spu(b_);                                                                      \
-            }                                                                                                  \
-        }                                                                                                      \
-    } while (0)
+    auto fill_pred_rows = [&](int b) {
+        if constexpr (GRES) {
+            const _Float16* gb_ = a.g + (size_t)b * U1 * H + hcol;
+            for (int i = tid; i < U1 * 16; i += DW_THREADS)   // (i & 15) == xch for every i of this thread
+                *reinterpret_cast<uint4*>(gtile + i * 16) = *reinterpret_cast<const uint4*>(gb_ + (size_t)(i >> 4) * H);
+            __syncthreads();
+        }
+    };
 
-    // fragment addresses of k-step 0 in the current stage; k-step 1 = 32 rows further (same swizzle phase: an immediate
-    // offset), the other stage = address ^ 64 KB (the dynamic LDS block starts at a multiple of 128 KB: offset 0)
+    // fragment addresses of k-step 0 in the current stage; the other stage = address ^ 64 KB (the dynamic LDS block starts at a
+    // multiple of 128 KB: offset 0)
     unsigned bA0[2], bA1[2], aA0[9], aA1[9];
 #pragma unroll
-    for (int j = 0; j < 2; ++j) dw_frag_addr(lds0 + DW_YTILE, DW_XROW, q4 * 8, wh * 32 + j * 16, lane, &bA0[j], &bA1[j]);
+    for (int j = 0; j < 2; ++j) trl_frag_addr<true>(lds0 + DW_YTILE, DW_XROW, q4 * 8, wh * 32 + j * 16, lane, &bA0[j], &bA1[j]);
 #pragma unroll
-    for (int i = 0; i < 9; ++i) dw_frag_addr(lds0, DW_YROW, q4 * 8, wv * 144 + i * 16, lane, &aA0[i], &aA1[i]);
+    for (int i = 0; i < 9; ++i) trl_frag_addr<true>(lds0, DW_YROW, q4 * 8, wv * 144 + i * 16, lane, &aA0[i], &aA1[i]);
 
-    // (b, s) of the step being multiplied is implicit; sb/ss/si = the step being staged, lb/ls/li = the step being loaded
-    int sb = __builtin_amdgcn_readfirstlane(b_first), ss = __builtin_amdgcn_readfirstlane(s_first), si = step_beg;
-    int sn = live_spu(sb);            // live steps of the utterance being staged / loaded
-    int stt = 0, sut = 0, snut = 1, stb = T;   // TILED: frame tile, label tile, label tiles and frame count of that utterance
-    if (TILED) {
-        int n_, nut_, tb_;
-        dw_tiles(a, __builtin_amdgcn_readfirstlane(sb), &n_, &nut_, &tb_);
-        snut = __builtin_amdgcn_readfirstlane(nut_); stb = __builtin_amdgcn_readfirstlane(tb_);
-        stt = ss / snut; sut = ss - stt * snut;
-    }
-    int gb = sb;                      // utterance whose prediction rows are resident
+    // two register sets: the loads of step n+2 and n+3 are in flight while step n is multiplied (a step is ~1.7 us, the
+    // loaded-HBM latency is of the same order: one step of distance left the staging phase waiting)
+    DwRegs regs[2];
+    DwCursor<TILED> stg, ld;          // the step being staged, the step being loaded
+    stg.start(a, b_first, s_first, step_beg);
+    int gb = stg.b;                   // utterance whose prediction rows are resident
     __syncthreads();                  // zero fill done
-    DW_GTILE(gb);
-    DW_LOAD(0, sb, ss, stt, sut, stb);
-    DW_STORE(0, sb, ss, 0);
-    int lb = sb, ls = ss, li = si, ln = sn, ltt = stt, lut = sut, lnut = snut, ltb = stb;
+    fill_pred_rows(gb);
+    DW_LOAD(regs[0], stg);
+    DW_STORE(regs[0], stg, 0);
+    ld = stg;
     int cur = 0;
-#define DW_KSTEP(KS)                                                                                           \
-        {                                                                                                      \
-            h4 blo[2], bhi[2], alo[9], ahi[9];                                                                 \
-            _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                                    \
-                blo[j] = dw_tr_read<(KS) * 32 * DW_XROW>(bA0[j]); bhi[j] = dw_tr_read<(KS) * 32 * DW_XROW>(bA1[j]); \
-            }                                                                                                  \
-            _Pragma("unroll") for (int i = 0; i < 9; ++i) {                                                    \
-                alo[i] = dw_tr_read<(KS) * 32 * DW_YROW>(aA0[i]); ahi[i] = dw_tr_read<(KS) * 32 * DW_YROW>(aA1[i]); \
-            }                                                                                                  \
-            /* ONE wait that all fragment registers are tied to (the compiler does not know the asm reads LDS asynchronously) */ \
-            asm volatile("s_waitcnt lgkmcnt(0)"                                                                \
-                         : "+v"(alo[0]), "+v"(alo[1]), "+v"(alo[2]), "+v"(alo[3]), "+v"(alo[4]), "+v"(alo[5]), "+v"(alo[6]), \
-                           "+v"(alo[7]), "+v"(alo[8]), "+v"(ahi[0]), "+v"(ahi[1]), "+v"(ahi[2]), "+v"(ahi[3]), "+v"(ahi[4]), \
-                           "+v"(ahi[5]), "+v"(ahi[6]), "+v"(ahi[7]), "+v"(ahi[8]), "+v"(blo[0]), "+v"(blo[1]), "+v"(bhi[0]), \
-                           "+v"(bhi[1])                                                                        \
-                         :                                                                                     \
-                         : "memory");                                                                          \
-            const h8 b0 = dw_join(blo[0], bhi[0]), b1 = dw_join(blo[1], bhi[1]);                               \
-            _Pragma("unroll") for (int i = 0; i < 9; ++i) {                                                    \
-                const h8 af = dw_join(alo[i], ahi[i]);                                                         \
-                acc[i][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, b0, acc[i][0], 0, 0, 0);                \
-                acc[i][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, b1, acc[i][1], 0, 0, 0);                \
-            }                                                                                                  \
-        }
-    // one step: multiply the current stage, stage the next step (register set R) into the other LDS stage -- nobody reads
-    // it before the barrier -- and refill R with the step after the one already in flight in the other set
-#define DW_MMA DW_KSTEP(0) DW_KSTEP(1)
-    // stage the next step (register set R) into the other LDS stage -- nobody reads it before the barrier -- and refill R
-#define DW_STAGE_NEXT(R)                                                                                       \
-        DW_NEXT(sb, ss, si, sn, stt, sut, snut, stb);                                                          \
-        if (sb != gb) {   /* (uniform) next utterance: its prediction rows replace the resident ones (all readers of the */ \
-            gb = sb;      /* old rows finished before the previous step's barrier) */                          \
-            DW_GTILE(gb);                                                                                      \
+    auto multiply = [&] {
+        dw_kstep<0>(acc, aA0, aA1, bA0, bA1);
+        dw_kstep<1>(acc, aA0, aA1, bA0, bA1);
+    };
+    // stage the next step (register set r_) into the other LDS stage -- nobody reads it before the barrier -- and refill r_ with
+    // the step after the one already in flight in the other set
+#define DW_STAGE_NEXT(r_)                                                                                      \
+    do {                                                                                                       \
+        stg.advance(a, step_end);                                                                              \
+        if (stg.b != gb) {   /* (uniform) next utterance: its prediction rows replace the resident ones (all readers of */ \
+            gb = stg.b;      /* the old rows finished before the previous step's barrier) */                   \
+            fill_pred_rows(gb);                                                                                \
         }                                                                                                      \
-        DW_STORE(R, sb, ss, cur ^ 1);                                                                          \
-        DW_NEXT(lb, ls, li, ln, ltt, lut, lnut, ltb);                                                          \
-        DW_LOAD(R, lb, ls, ltt, lut, ltb);
-#define DW_BODY(FIRST, SECOND)                                                                                 \
-    {                                                                                                          \
-        FIRST SECOND                                                                                           \
-        __syncthreads();                                                                                       \
-        cur ^= 1;                                                                                              \
-        _Pragma("unroll") for (int j = 0; j < 2; ++j) { bA0[j] ^= DW_STAGE; bA1[j] ^= DW_STAGE; }              \
-        _Pragma("unroll") for (int i = 0; i < 9; ++i) { aA0[i] ^= DW_STAGE; aA1[i] ^= DW_STAGE; }              \
-    }
+        DW_STORE(r_, stg, cur ^ 1);                                                                            \
+        ld.advance(a, step_end);                                                                               \
+        DW_LOAD(r_, ld);                                                                                       \
+    } while (0)
+    auto flip = [&] {   // the step's one barrier; the stages swap
+        __syncthreads();
+        cur ^= 1;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) { bA0[j] ^= DW_STAGE; bA1[j] ^= DW_STAGE; }
+#pragma unroll
+        for (int i = 0; i < 9; ++i) { aA0[i] ^= DW_STAGE; aA1[i] ^= DW_STAGE; }
+    };
     // The two waves of a SIMD run the step's two phases in opposite order, so one wave's matrix instructions overlap the
     // other's vector / memory work instead of all eight contending for the same pipe at the same time (two separate
     // loops rather than a branch inside one: the register allocator treats them independently; every wave executes the
@@ -408,31 +455,34 @@ __global__ __launch_bounds__(DW_THREADS, 1) void joint_dw_fused_kernel(DwArgs a)
     // one register set is enough.  Waves 4-7 multiply first: the loads of the step they stage next were issued only one
     // multiply phase earlier, so they keep two sets in flight (steps n+2 and n+3 while step n is multiplied).
     if (__builtin_amdgcn_readfirstlane(wave >> 2) == 0) {
-        DW_NEXT(lb, ls, li, ln, ltt, lut, lnut, ltb);
-        DW_LOAD(0, lb, ls, ltt, lut, ltb);
+        ld.advance(a, step_end);
+        DW_LOAD(regs[0], ld);
         __syncthreads();
-        for (int step = step_beg; step < step_end; ++step) DW_BODY(DW_STAGE_NEXT(0), DW_MMA)
+        for (int step = step_beg; step < step_end; ++step) {
+            DW_STAGE_NEXT(regs[0]);
+            multiply();
+            flip();
+        }
     } else {
-        DW_NEXT(lb, ls, li, ln, ltt, lut, lnut, ltb);
-        DW_LOAD(1, lb, ls, ltt, lut, ltb);
-        DW_NEXT(lb, ls, li, ln, ltt, lut, lnut, ltb);
-        DW_LOAD(0, lb, ls, ltt, lut, ltb);
+        ld.advance(a, step_end);
+        DW_LOAD(regs[1], ld);
+        ld.advance(a, step_end);
+        DW_LOAD(regs[0], ld);
         __syncthreads();
         for (int step = step_beg; step < step_end; step += 2) {
-            DW_BODY(DW_MMA, DW_STAGE_NEXT(1))
+            multiply();
+            DW_STAGE_NEXT(regs[1]);
+            flip();
             if (step + 1 >= step_end) break;   // (uniform)
-            DW_BODY(DW_MMA, DW_STAGE_NEXT(0))
+            multiply();
+            DW_STAGE_NEXT(regs[0]);
+            flip();
         }
     }
-#undef DW_MMA
 #undef DW_STAGE_NEXT
-#undef DW_BODY
-#undef DW_KSTEP
-#undef DW_LOAD
 #undef DW_STORE
-#undef DW_GTILE
-#undef DW_NEXT
-#undef live_spu
+#undef DW_LOAD
+#undef DW_GATHER_FLAT
     // partial tile of this split: rows v < LD, columns h0 .. h0+127
     float* prow = a.part + (size_t)split * a.row_stride;
 #pragma unroll
@@ -461,6 +511,19 @@ inline int dw_splits(int64_t nsteps, int H) {
     return s < 1 ? 1 : s;
 }
 inline int64_t dw_nsteps(int B, int T, int U1) { return (int64_t)B * (((int64_t)T * U1 + DW_MS - 1) / DW_MS); }
+template <bool DROPOUT, bool GRES, bool TILED>
+int dw_launch_one(dim3 grid, int lds, hipStream_t st, const DwArgs& a) {
+    IA_SET_MAX_LDS_ONCE((joint_dw_fused_kernel<DROPOUT, GRES, TILED>), lds);
+    hipLaunchKernelGGL((joint_dw_fused_kernel<DROPOUT, GRES, TILED>), grid, dim3(DW_THREADS), lds, st, a);
+    return IA_OK;
+}
+inline int dw_launch(bool dropout, bool gres, bool tiled, dim3 grid, int lds, hipStream_t st, const DwArgs& a) {
+    static int (*const table[8])(dim3, int, hipStream_t, const DwArgs&) = {
+        dw_launch_one<false, false, false>, dw_launch_one<false, false, true>, dw_launch_one<false, true, false>,
+        dw_launch_one<false, true, true>,   dw_launch_one<true, false, false>, dw_launch_one<true, false, true>,
+        dw_launch_one<true, true, false>,   dw_launch_one<true, true, true>};
+    return table[4 * dropout + 2 * gres + tiled](grid, lds, st, a);
+}
 }  // namespace
 
 extern "C" int ia_joint_dw_fused_supported(int U1, int H, int LD) {
@@ -496,23 +559,15 @@ extern "C" int ia_joint_dw_fused_ex(const void* G, const void* f, const void* g,
     a.mU1 = magic((unsigned)U1); a.mV = magic((unsigned)(LD / 8)); a.mSpu = magic((unsigned)a.spu);
     hipStream_t st = (hipStream_t)stream;
     a.ntiles = (H + DW_BH - 1) / DW_BH; a.nsplit = Seff;
-    const dim3 grid(8 * ((Seff + 7) / 8) * a.ntiles), blk(DW_THREADS);
+    const dim3 grid(8 * ((Seff + 7) / 8) * a.ntiles);
     const int lds = 2 * DW_STAGE + DW_MAX_U1 * DW_XROW;
     const bool gres = U1 <= DW_MAX_U1;
     // tiled steps (live frames x live labels): the lengths must be there, a tile must fit the lattice, the packed
     // (cell, label) word of a hidden row holds 23 + 8 bits, the prefix pass over the utterances' step counts runs in LDS
     static const bool no_tiles = [] { const char* e = getenv("IA_DW_TILED"); return e && e[0] == '0'; }();
     const bool tiled = !no_tiles && act_lens && label_lens && T >= DW_TF && U1 >= DW_TU && U1 <= 256 && a.cpu < (1 << 23) && B <= 4096;
-#define IA_DW_LAUNCH(D_, G_, T_)                                                        \
-    do {                                                                                \
-        IA_SET_MAX_LDS_ONCE((joint_dw_fused_kernel<D_, G_, T_>), lds);                  \
-        hipLaunchKernelGGL((joint_dw_fused_kernel<D_, G_, T_>), grid, blk, lds, st, a); \
-    } while (0)
-#define IA_DW_LAUNCH2(D_, G_) do { if (tiled) IA_DW_LAUNCH(D_, G_, true); else IA_DW_LAUNCH(D_, G_, false); } while (0)
-    if (a.thr > 0) { if (gres) IA_DW_LAUNCH2(true, true); else IA_DW_LAUNCH2(true, false); }
-    else { if (gres) IA_DW_LAUNCH2(false, true); else IA_DW_LAUNCH2(false, false); }
-#undef IA_DW_LAUNCH2
-#undef IA_DW_LAUNCH
+    const int rc = dw_launch(a.thr > 0, gres, tiled, grid, lds, st, a);
+    if (rc != IA_OK) return rc;
     IA_RETURN_IF_LAUNCH_FAILED();
     ia_partials_finish_wide(scratch, Seff, (int64_t)a.row_stride, dW, st);
     IA_RETURN_IF_LAUNCH_FAILED();
