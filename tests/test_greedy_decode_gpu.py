@@ -166,18 +166,22 @@ def test_bf16_decode_mfma_head_and_clusters(B, T, Hp, Hj, V, blank_bias, ms):
     n_ref = sum(len(h) for h in ref)
     same = sum(int(a == b) for a, b in zip(one, ref))
     print("symbols", n_ref, "utterances identical", same, "of", B)
+    # every utterance is a member of the acceptable set of the fp64 replay (oracle/decode_ref.py): an fp32 near-tie needs no allowance
+    from oracle import decode_ref as R
+    acc = R.decode_reference(case, ms, "mfma")
+    R.check_conditions(acc, balanced=False)
+    assert all(R.member(h, r) for h, r in zip(one, acc)), (one, [sorted(r["accept"]) for r in acc])
     if blank_bias > 10:
         assert n_ref == 0 and one == ref
     elif blank_bias < -10:
-        assert one == ref or same >= B - 1
         assert all(len(h) == ms * int(l) for h, l in zip(one, case["lens"]))
     else:
         assert n_ref > 0
-        assert same >= B - max(1, B // 8), (one, ref)   # fp32 accumulation order differs: a near-tie may flip one path
     # the GEMV loop (fp32 activations into the head) decodes the same weights; it differs only by the bf16 rounding of the head's input
     gemv, _ = _bf16_decode_hip(case, 0, ms)
-    ref32 = _bf16_decode_torch(case, ms, act_bf16=False)
-    assert sum(int(a == b) for a, b in zip(gemv, ref32)) >= B - max(1, B // 8)
+    acc32 = R.decode_reference(case, ms, "gemv")
+    R.check_conditions(acc32, balanced=False)
+    assert all(R.member(h, r) for h, r in zip(gemv, acc32)), (gemv, [sorted(r["accept"]) for r in acc32])
     assert int(_lib.lib().ia_greedy_decode_cluster(32, 640, 640)) == 4 and int(_lib.lib().ia_greedy_decode_cluster(32, 640, 100)) == 0
 
 
