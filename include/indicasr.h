@@ -1039,6 +1039,27 @@ int ia_ctc_backward_logits(const float* logits, int ld, const float* lse, const 
                            const int64_t* target_lens, int B, int T, int V, int S, int blank, const float* nll_grad,
                            float grad_scale, void* grad_bf16, int ldg, void* workspace, size_t workspace_bytes, ia_stream_t stream);
 
+/* ---- CTC forced alignment (csrc/ctc_align.hip): the best path of each utterance through its extended label sequence
+ * (L = 2 S_b + 1 states: blank at even positions, target i at state 2i+1) and the backtrace, in one launch, one wave per
+ * utterance.  The semantics are NeMo forced aligner's viterbi_decoding (tools/nemo_forced_aligner/utils/viterbi_decoding.py:19-136)
+ * run on one utterance alone:  v_t(s) = max(v_{t-1}(s), v_{t-1}(s-1), v_{t-1}(s-2) if s is odd and label(s) != label(s-2)) + q_t(label(s)),
+ * fp32, the FIRST maximum wins (stay over s-1 over s-2; at the end state L-2 over L-1; L = 1 ends in state 0).
+ *   lp      [B,T,ld] f32: log-probs when lse is NULL, else raw logits with lse [B*T] their per-frame log-sum-exp
+ *           (ia_ctc_row_lse): q = logit - lse.  V valid columns, row stride ld >= V (the head's [M,264] logits go in unpadded).
+ *   targets [B,S] i64 padded, lens i64 (clamped to T and S); blank in [0,V).
+ *   path    [B,T] i32: state per frame, -1 for t >= input_lens[b].
+ *   spans   [B,S,2] i32: first and last frame of each target token, -1 beyond target_lens[b].
+ *   score   [B] f32: log-prob of the best path.
+ * An infeasible utterance (T_b < labels + adjacent repeats, or T_b <= 0) gets score = -inf, path = -1, spans = -1 and affects
+ * nothing else; an empty transcript aligns every frame to state 0.
+ *   workspace: ia_ctc_align_workspace_bytes(B,T,S) (the 2-bit backpointers, 128 bytes per frame), 256-byte aligned; 0 when
+ *   S > ia_ctc_align_max_targets() = 255, where ia_ctc_align returns IA_UNSUPPORTED. */
+int ia_ctc_align_max_targets(void);
+size_t ia_ctc_align_workspace_bytes(int B, int T, int S);
+int ia_ctc_align(const float* lp, int ld, const float* lse, const int64_t* targets, const int64_t* input_lens,
+                 const int64_t* target_lens, int B, int T, int V, int S, int blank, int32_t* path, int32_t* spans, float* score,
+                 void* workspace, size_t workspace_bytes, ia_stream_t stream);
+
 /* ---- Glue of the step's tail (csrc/tail_ops.hip): each replaces a handful of small ATen launches.
  * ia_select_rows_cast  rows [row0, row0+nrows) (+ extra_row if >= 0) of W [*, K] f32 (row stride ldw), times `scale`, as a 16-bit
  *                      operand out [rows_out, K] (bf16, or f16 when out_f16; rows beyond the selection zero); optionally the

@@ -325,9 +325,9 @@ class _CtcHeadHip(torch.autograd.Function):
     path spends 89 us in a 16-workgroup TN GEMM and 131 us in a bf16 column reduction for the bias)."""
 
     @staticmethod
-    def forward(ctx, x, w_sel, b_sel):
+    def padded(x, w_sel, b_sel):
+        """(logits [M, Vp] f32 with Vp = V rounded up to 8, the bf16 operands xb [M,d] and wp [Vp,d])."""
         from .ops import fast
-        shp = x.shape
         V, d = w_sel.shape
         Vp = (V + 7) // 8 * 8
         xb = x.reshape(-1, d).to(torch.bfloat16).contiguous()
@@ -337,6 +337,13 @@ class _CtcHeadHip(torch.autograd.Function):
         bp[:V] = b_sel.detach().float()
         out = torch.empty(xb.shape[0], Vp, dtype=torch.float32, device=x.device)
         fast.gemm(xb, wp, bp, out_f32=out, want_bf16=False)
+        return out, xb, wp
+
+    @staticmethod
+    def forward(ctx, x, w_sel, b_sel):
+        shp = x.shape
+        V = w_sel.shape[0]
+        out, xb, wp = _CtcHeadHip.padded(x, w_sel, b_sel)
         ctx.save_for_backward(xb, wp)
         ctx.meta = (shp, V, x.dtype, w_sel.dtype, b_sel.dtype)
         return out[:, :V].reshape(*shp[:-1], V)
@@ -416,6 +423,26 @@ class ConvASRDecoder(nn.Module):
         x = encoder_output.transpose(1, 2)   # [B,T,d]
         return tail.ctc_head_loss(x, conv.weight, conv.bias, targets, input_lengths, target_lengths, i * v, v, self._num_classes - 1,
                                   blank=v, zero_infinity=zero_infinity, keep=keep)
+
+    @torch.no_grad()
+    def language_logits(self, encoder_output, language_id):
+        """Raw logits [B,T,V] f32 of one language's rows (its tokens + the blank), what forward() feeds its log_softmax.  On the
+        HIP GEMM path the result is a view of the [B*T, 264] output narrowed to the V valid columns: the alignment kernel and
+        ia_ctc_row_lse read it in place by its row stride."""
+        _flush_pending()
+        w = self.decoder_layers[0].weight.squeeze(-1)
+        b = self.decoder_layers[0].bias
+        x = encoder_output.transpose(1, 2)  # [B,T,d]
+        rows = self._rows(language_id, x.device)
+        w_sel, b_sel = w.index_select(0, rows), b.index_select(0, rows)
+        if self.cfg.compute_dtype == "bf16" and x.is_cuda and x.shape[-1] % 8 == 0:
+            out = _CtcHeadHip.padded(x, w_sel, b_sel)[0]
+            out = out.view(x.shape[0], x.shape[1], out.shape[1])[..., :w_sel.shape[0]]
+        else:
+            out = F.linear(x.float(), w_sel.float(), b_sel.float())
+        if self.temperature != 1.0:
+            out = out / self.temperature
+        return out
 
     def forward(self, encoder_output, language_ids=None):
         _flush_pending()

@@ -195,3 +195,75 @@ class TranscriptionMixin:
         if self.cur_decoder != "rnnt" and logprobs:
             return logits_list
         return (hyps, list(hyps))
+
+    # -------------------------------------------------------------------------------------------------- align
+    @torch.no_grad()
+    def align(self, audio, transcripts=None, language_id: str = None, batch_size: int = 4, token_ids=None, *, _keep=None):
+        """Forced alignment of known transcripts, as NeMo's forced aligner does it for hybrid models (tools/nemo_forced_aligner:
+        switch to the CTC head, Viterbi over its log-probs): a list of align.UtteranceAlignment in input order.
+
+        `transcripts` (strings, tokenised by the attached data.MultilingualTokenizer in the loader) or `token_ids` (a list of
+        id lists local to the language: tensor audio, models without a tokenizer) -- exactly one of them.  Always the CTC
+        head, whatever `cur_decoder` says.  Per batch on the MI355X: forward, the language's head logits, ia_ctc_row_lse,
+        ia_ctc_align, one device-to-host copy of path, spans and score.  (`_keep`, a list: receives each batch's
+        (scores fed to the aligner, lse or None, frame lengths, targets, target lengths) -- for tests.)"""
+        from . import align as A
+        from . import cl
+        from .model import InternalTranscribeConfig, TranscribeConfig
+        if (transcripts is None) == (token_ids is None):
+            raise ValueError("align() needs exactly one of `transcripts` and `token_ids`")
+        if language_id is None:
+            raise ValueError("language_id is required by the multilingual heads (rnnt.py:1624-1640)")
+        if audio is None or (isinstance(audio, (list, tuple)) and len(audio) == 0):
+            raise ValueError("Input `audio` is empty")
+        n_audio = len(audio) if isinstance(audio, (list, tuple)) else 1
+        given = transcripts if transcripts is not None else token_ids
+        if len(given) != n_audio:
+            raise ValueError(f"{n_audio} audio inputs but {len(given)} {'transcripts' if transcripts is not None else 'token_ids'}")
+        cl.flush_pending_updates()
+        cfg = TranscribeConfig(batch_size=batch_size, language_id=language_id)
+        cfg._internal = InternalTranscribeConfig()
+        f = self.preprocessor.featurizer
+        cfg._internal.training_mode, cfg._internal.dither_value, cfg._internal.pad_to_value = self.training, f.dither, f.pad_to
+        cfg._internal.device = next(self.parameters()).device
+        dev = cfg._internal.device
+        f.dither, f.pad_to = 0.0, 0
+        self.eval()
+        frame_s = A.frame_seconds(self.cfg)
+        blank = self.cfg.vocab_per_lang            # the language's head: its tokens, then the blank
+        results, done = [], 0
+        try:
+            loader = self._transcribe_input_processing(audio, cfg, transcripts=transcripts, language_id=language_id)
+            for batch in loader:
+                sig, sig_len = batch[0], batch[1]
+                if not sig.is_cuda and dev.type == "cuda":
+                    sig, sig_len = sig.to(dev), sig_len.to(dev)
+                n = sig.shape[0]
+                if token_ids is not None:              # the loader keeps the input order: batch i holds inputs [done, done + n)
+                    ids = [[int(i) for i in t] for t in token_ids[done:done + n]]
+                    tg, tg_len = A.pad_token_ids(ids)
+                    tg, tg_len = tg.to(dev), tg_len.to(dev)
+                else:
+                    tg, tg_len = batch[2].to(dev), batch[3].to(dev)
+                    lens = lookup_host_lengths(batch[3]) or batch[3].tolist()
+                    rows = batch[2].cpu()
+                    ids = [rows[i, :int(m)].tolist() for i, m in enumerate(lens)]
+                done += n
+                encoded, encoded_len = self.forward(input_signal=sig, input_signal_length=sig_len)
+                if encoded.is_cuda:
+                    x = self.ctc_decoder.language_logits(encoded, language_id)
+                    lse = A.row_lse(x)
+                else:
+                    x, lse = self.ctc_decoder(encoder_output=encoded, language_ids=[language_id] * n), None
+                if encoded.is_cuda and tg.shape[1] <= A.max_targets():
+                    packed, path, spans, score = A._align_device(x, encoded_len, tg, tg_len, blank, lse)
+                    path, spans, score = A._carve(packed.cpu(), *path.shape, spans.shape[1])
+                else:   # the host routine (for device tensors beyond the kernel's limit: with ctc_forced_align's warning)
+                    path, spans, score = A.ctc_forced_align(x, encoded_len, tg, tg_len, blank, lse)
+                if _keep is not None:
+                    _keep.append((x, lse, encoded_len, tg, tg_len))
+                results += A.build_alignments(path, spans, score, ids, frame_s, self.tokenizer, language_id)
+        finally:
+            self.train(mode=cfg._internal.training_mode)
+            f.dither, f.pad_to = cfg._internal.dither_value, cfg._internal.pad_to_value
+        return results
