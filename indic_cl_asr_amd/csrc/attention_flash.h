@@ -1,5 +1,8 @@
-// Shared pieces of the key-tiled rel-pos attention kernels (attention_flash.hip forward, attention_flash_bwd.hip backward):
-// fragment types, the zero-padding head-row loader and the attention-dropout hash (the backward regenerates the forward's mask).
+// The one vocabulary of the key-tiled rel-pos attention kernels (attention_flash.hip forward, attention_flash_bwd.hip query-owner
+// and key-owner backward): fragment types, tile constants, the attention-dropout hash (the backward regenerates the forward's
+// mask), the zero-padding head-row loader, the swizzled LDS addresses and fragment reads, register staging of a tile (fetch /
+// commit), the K | V | P stage, the query fragments, the band block, the workgroup coordinates, the guarded head-row store and
+// the host's launch of a <DK64> pair.  tests/test_attention_flash_digests_gpu.py pins the bits of everything built from it.
 #pragma once
 #include <hip/hip_bf16.h>
 
@@ -11,6 +14,12 @@ namespace {
 typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
 typedef short s4v __attribute__((ext_vector_type(4)));
 typedef float f4 __attribute__((ext_vector_type(4)));
+
+constexpr int FA_THREADS = 256;
+constexpr int FA_ROWB = 128;               // bytes per LDS row (64 bf16, zero-padded beyond dk)
+constexpr int FA_T64 = 64 * FA_ROWB;       // a 64-row tile: 8 KB
+constexpr int FA_PBUF = 128 * FA_ROWB;     // 128 position rows: 16 KB
+constexpr int FA_SR_LD = 104;              // bf16 elements per forward band-strip row (208 B: conflict-free 8-byte reads)
 
 // attention-dropout randomness of these kernels: one word per (head, query, group of 4 keys); key j uses byte j & 3.  The
 // word comes from dropout_mask.h's full-rate construction (24-bit multiplies, shifts, xors): the 32-bit multiplies of a
@@ -32,6 +41,151 @@ __device__ __forceinline__ uint4 fa_load_slot(const __bf16* row, int slot, int d
         if (e0 + 4 < dk) { const uint2 a = *reinterpret_cast<const uint2*>(row + e0 + 4); v.z = a.x; v.w = a.y; }
         return v;
     }
+}
+
+// 16-byte slot `slot` of row `row` of an LDS tile: these kernels' own swizzle, slot ^ (row & 7)
+template <typename B>
+__device__ __forceinline__ B* fa_swz(B* tile, int row, int slot) { return tile + row * FA_ROWB + ((slot ^ (row & 7)) * 16); }
+
+// row-major MFMA fragment: elements 32 ks + 8 q4 .. + 7 of row `row`
+__device__ __forceinline__ bf8 fa_frag(const unsigned char* tile, int row, int ks, int q4) {
+    return *reinterpret_cast<const bf8*>(fa_swz(tile, row, ks * 4 + q4));
+}
+
+// transposed MFMA fragment by two ds_read_b64_tr_b16: 8-byte half `half` of slot `sl` of rows rowA (elements 0 .. 3) and rowB
+__device__ __forceinline__ bf8 fa_tr_pair(const unsigned char* tile, int rowA, int rowB, int sl, int half) {
+    typedef __attribute__((address_space(3))) s4v lds_s4v;
+    const s4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4v*)(fa_swz(tile, rowA, sl) + half * 8));
+    const s4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4v*)(fa_swz(tile, rowB, sl) + half * 8));
+    union { s4v s[2]; bf8 v; } f;
+    f.s[0] = lo; f.s[1] = hi;
+    return f.v;
+}
+
+// ---- register staging: thread tid holds slot idx & 7 of tile row idx >> 3, idx = tid + i * 256, i < N (N = rows / 32).  The
+// tile's row `row` is the global row base + clamp(row0 + row) * stride, clamped to <= hi and, with LOW, to >= 0.
+template <bool DK64, bool LOW, int N>
+__device__ __forceinline__ void fa_fetch_rows(uint4 (&r)[N], const __bf16* base, int stride, int row0, int hi, int dk, int tid) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const int idx = tid + i * FA_THREADS, row = idx >> 3, sl = idx & 7;
+        int g = row0 + row;
+        if constexpr (LOW) g = g < 0 ? 0 : (g > hi ? hi : g);
+        else g = g > hi ? hi : g;
+        r[i] = fa_load_slot<DK64>(base + (size_t)g * stride, sl, dk);
+    }
+}
+
+template <int N>
+__device__ __forceinline__ void fa_commit_rows(unsigned char* tile, const uint4 (&r)[N], int tid) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const int idx = tid + i * FA_THREADS, row = idx >> 3, sl = idx & 7;
+        *reinterpret_cast<uint4*>(fa_swz(tile, row, sl)) = r[i];
+    }
+}
+
+// The K | V | P stage of the forward and the query-owner (32 KB at `smem`): key tile t of one (utterance, head), rows clamped to
+// T - 1, and the 128 position rows T - 1 - I0 - 63 + 64 t .. + 127 that cover the bands of the four waves of query tile I0,
+// clamped to [0, 2T - 2].  fetch(t) brings tile t to registers (8 x 16 B per thread), commit() writes them to LDS.
+template <bool DK64>
+struct FaKvpStage {
+    uint4 rk[2], rv[2], rp[4];
+    const __bf16 *kbase, *vbase, *pbase;
+    unsigned char* smem;
+    int T, d, dk, I0, tid;
+    __device__ __forceinline__ FaKvpStage(const __bf16* qkv, const __bf16* pl, unsigned char* smem_, int b, int h, int T_, int d_,
+                                          int dk_, int I0_, int tid_)
+        : kbase(qkv + (size_t)b * T_ * (3 * d_) + d_ + h * dk_), vbase(kbase + d_), pbase(pl + h * dk_), smem(smem_), T(T_), d(d_),
+          dk(dk_), I0(I0_), tid(tid_) {}
+    __device__ __forceinline__ void fetch(int t) {
+        const int j0 = t * 64;
+        fa_fetch_rows<DK64, false>(rk, kbase, 3 * d, j0, T - 1, dk, tid);
+        fa_fetch_rows<DK64, false>(rv, vbase, 3 * d, j0, T - 1, dk, tid);
+        fa_fetch_rows<DK64, true>(rp, pbase, d, T - 1 - I0 - 63 + j0, 2 * T - 2, dk, tid);
+    }
+    __device__ __forceinline__ void commit() {
+        fa_commit_rows(smem, rk, tid);
+        fa_commit_rows(smem + FA_T64, rv, tid);
+        fa_commit_rows(smem + 2 * FA_T64, rp, tid);
+    }
+};
+
+// k-step ks of the B fragments (q+u)^T and (q+v)^T of the lane's query row `qrow` (head h's slice): lane (query c, q4) holds dk
+// elements 32 ks + 8 q4 .. + 7
+template <bool DK64>
+__device__ __forceinline__ void fa_query_frags(const __bf16* qrow, const float* bias_u, const float* bias_v, int h, int dk, int ks,
+                                               int q4, bf8& Qu, bf8& Qv) {
+    union { uint4 u; __bf16 e[8]; } q;
+    q.u = fa_load_slot<DK64>(qrow, ks * 4 + q4, dk);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int e = ks * 32 + q4 * 8 + j;
+        const float u = (e < dk) ? bias_u[h * dk + e] : 0.f, v = (e < dk) ? bias_v[h * dk + e] : 0.f;
+        Qu[j] = (__bf16)((float)q.e[j] + u);
+        Qv[j] = (__bf16)((float)q.e[j] + v);
+    }
+}
+
+// band R^T = P_band (q+v)^T [80 positions x 16 queries] of one wave, 5 x 2 MFMAs: rows = staged position rows pw0 + 16 rt + c,
+// columns = queries; then the skew through the wave's strip: strip[query c][rr + c + 1] = R^T[rr][c]  (rr = 16 rt + 4 q4 + r), so
+// that the band element of key tile column jl is at strip column jl + 16
+__device__ __forceinline__ void fa_band_to_strip(const unsigned char* sP, unsigned char* sR, int pw0, const bf8 (&Qv)[2], int c,
+                                                 int q4) {
+    f4 R[5];
+#pragma unroll
+    for (int rt = 0; rt < 5; ++rt) {
+        R[rt] = (f4){0.f, 0.f, 0.f, 0.f};
+        const int row = pw0 + rt * 16 + c;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+            R[rt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa_frag(sP, row, ks, q4), Qv[ks], R[rt], 0, 0, 0);
+    }
+#pragma unroll
+    for (int rt = 0; rt < 5; ++rt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            *reinterpret_cast<__bf16*>(sR + (c * FA_SR_LD + rt * 16 + q4 * 4 + r + c + 1) * 2) = (__bf16)R[rt][r];
+}
+
+// Workgroup coordinates of all three kernels: (utterance b, head h, 64-row tile) and the utterance's length clamped to [0, T].
+// XCD-aware order: the tiles of one (utterance, head) share K / V / position rows, so their workgroup ids are congruent mod 8.
+// Returned by value: filled through a reference with an early return it costs the query-owner 4 VGPRs and 120 instructions.
+struct FaWg { int bh, tile, h, b, len; };   // len < 0: no such (utterance, head)
+__device__ __forceinline__ FaWg fa_wg(int B, int T, int H, const int64_t* lens) {
+    const int nt = (T + 63) / 64;
+    const int xcd = blockIdx.x & 7, slot_id = blockIdx.x >> 3;
+    const int bh = xcd + 8 * (slot_id / nt);
+    FaWg w{bh, slot_id % nt, bh % H, bh / H, -1};
+    if (bh < B * H) {
+        const int len = (int)lens[w.b];
+        w.len = len < 0 ? 0 : (len > T ? T : len);
+    }
+    return w;
+}
+
+// elements 16 mt + 4 q4 .. + 3 of a head row as bf16, if they exist (dk is a multiple of 4)
+__device__ __forceinline__ void fa_store_head4(__bf16* row, int mt, int q4, int dk, f4 x, float scale = 1.f) {
+    if (mt * 16 + q4 * 4 < dk) {
+        union { uint2 u; __bf16 e[4]; } o;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o.e[r] = (__bf16)(x[r] * scale);
+        *reinterpret_cast<uint2*>(row + mt * 16 + q4 * 4) = o.u;
+    }
+}
+
+// host: raise the kernel's LDS limit once, launch it on FA_THREADS threads, IA_LAUNCH_FAILED if either fails
+template <typename Args, void (*KERNEL)(Args)>
+inline int fa_launch_one(int grid, int lds, hipStream_t st, const Args& a) {
+    IA_SET_MAX_LDS_ONCE(KERNEL, lds);
+    hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(FA_THREADS), lds, st, a);
+    IA_RETURN_IF_LAUNCH_FAILED();
+    return IA_OK;
+}
+// host: the <true> (dk = 64, whole 16-byte slots) or the <false> (zero-padding) instantiation of a kernel template
+template <typename Args, void (*FULL)(Args), void (*PADDED)(Args)>
+inline int fa_launch(bool full, int grid, int lds, hipStream_t st, const Args& a) {
+    return full ? fa_launch_one<Args, FULL>(grid, lds, st, a) : fa_launch_one<Args, PADDED>(grid, lds, st, a);
 }
 
 }  // namespace

@@ -22,22 +22,21 @@
 //       probabilities / score gradients used as B operands straight from the accumulators and the A operands read from
 //       the row-major query tiles with ds_read_b64_tr_b16.
 // LDS tiles: 128-byte rows (64 bf16, zero-padded beyond dk), 16-byte slots XOR-swizzled by row & 7, one stage + register
-// prefetch of the next tile (two workgroups per CU hide the two barriers per tile).
+// prefetch of the next tile (two workgroups per CU hide the two barriers per tile).  Tile constants, the swizzled addresses and
+// fragment reads, the register staging (the query-owner uses the forward's K | V | P stage as it is, the key-owner builds its
+// Qu | Qv | dO | P | lse, D stage from the same fetch / commit pair), the band block, the query fragments, the workgroup
+// coordinates and the head-row store are attention_flash.h's, shared with the forward; tests/test_attention_flash_digests_gpu.py
+// pins dqkv, dpl and the bias gradients bit for bit.
 #include "attention_flash.h"
 #include "partials.h"
 
 namespace {
 
-constexpr int FB_THREADS = 256;
-constexpr int FB_ROWB = 128;
-constexpr int FB_T64 = 64 * FB_ROWB;          // a 64-row tile: 8 KB
-constexpr int FB_PBUF = 128 * FB_ROWB;        // 128 position rows: 16 KB
-constexpr int FB_SR_LD = 104;                 // forward band strip (bf16 elements per row), as in attention_flash.hip
 constexpr int FB_SB_LD = 120;                 // dS band strip: columns [0,96) band rows of this tile, [96,112) carry
-constexpr int FB_Q_STRIP = 16 * (FB_SR_LD + FB_SB_LD) * 2;           // per wave: 7168 B
-constexpr int FB_Q_LDS = 2 * FB_T64 + FB_PBUF + 4 * FB_Q_STRIP;      // K | V | P | strips = 61 440 B
+constexpr int FB_Q_STRIP = 16 * (FA_SR_LD + FB_SB_LD) * 2;           // per wave: 7168 B
+constexpr int FB_Q_LDS = 2 * FA_T64 + FA_PBUF + 4 * FB_Q_STRIP;      // K | V | P | strips = 61 440 B
 constexpr int FB_S3_LD = 72;                  // key-major band strip: [16 keys][64 queries (+8 pad)]
-constexpr int FB_KV_STAGE = 3 * FB_T64 + FB_PBUF + 512;              // Qu | Qv | dO | P | lse[64] D[64]
+constexpr int FB_KV_STAGE = 3 * FA_T64 + FA_PBUF + 512;              // Qu | Qv | dO | P | lse[64] D[64]
 constexpr int FB_KV_LDS = FB_KV_STAGE + 4 * 16 * FB_S3_LD * 2;       // 50 688 B
 
 struct FbArgs {
@@ -53,31 +52,17 @@ __device__ __forceinline__ void fb_lds_fence() {   // order this wave's LDS acce
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-__device__ __forceinline__ bf8 fb_tr_pair(const unsigned char* tile, int rowA, int rowB, int sl, int half) {
-    const s4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (__attribute__((address_space(3))) s4v*)(tile + rowA * FB_ROWB + ((sl ^ (rowA & 7)) * 16) + half * 8));
-    const s4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (__attribute__((address_space(3))) s4v*)(tile + rowB * FB_ROWB + ((sl ^ (rowB & 7)) * 16) + half * 8));
-    union { s4v s[2]; bf8 v; } f;
-    f.s[0] = lo; f.s[1] = hi;
-    return f.v;
-}
-
 // ======================================================================================================== query-owner
 template <bool DK64>
-__global__ __launch_bounds__(FB_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArgs a) {
+__global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 15, q4 = lane >> 4;
     const int T = a.T, H = a.H, dk = a.dk, d = H * dk, B = a.B;
     const int nqt = (T + 63) / 64;
-    const int xcd = blockIdx.x & 7, slot_id = blockIdx.x >> 3;
-    const int bh = xcd + 8 * (slot_id / nqt);
-    if (bh >= B * H) return;
-    const int qt = slot_id % nqt;
-    const int h = bh % H, b = bh / H;
-    int len = (int)a.lens[b];
-    len = len < 0 ? 0 : (len > T ? T : len);
+    const FaWg wg = fa_wg(B, T, H, a.lens);
+    if (wg.len < 0) return;
+    const int bh = wg.bh, qt = wg.tile, h = wg.h, b = wg.b, len = wg.len;
     const int I0 = qt * 64, iw = I0 + wave * 16, iq = iw + c;
     const int iqc = iq < T ? iq : T - 1;
     const bool qvalid = iq < len;
@@ -92,19 +77,13 @@ __global__ __launch_bounds__(FB_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArg
         const __bf16* grow = a.dctx + ((size_t)b * T + iqc) * d + h * dk;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            union { uint4 u; __bf16 e[8]; bf8 v; } q, o, g;
-            q.u = fa_load_slot<DK64>(qrow, ks * 4 + q4, dk);
+            union { uint4 u; __bf16 e[8]; bf8 v; } o, g;
+            fa_query_frags<DK64>(qrow, a.bias_u, a.bias_v, h, dk, ks, q4, Qu[ks], Qv[ks]);
             o.u = fa_load_slot<DK64>(orow, ks * 4 + q4, dk);
             g.u = fa_load_slot<DK64>(grow, ks * 4 + q4, dk);
             dOa[ks] = g.v;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int e = ks * 32 + q4 * 8 + j;
-                const float bu = (e < dk) ? a.bias_u[h * dk + e] : 0.f, bv = (e < dk) ? a.bias_v[h * dk + e] : 0.f;
-                Qu[ks][j] = (__bf16)((float)q.e[j] + bu);
-                Qv[ks][j] = (__bf16)((float)q.e[j] + bv);
-                Drow += (float)g.e[j] * (float)o.e[j];
-            }
+            for (int j = 0; j < 8; ++j) Drow += (float)g.e[j] * (float)o.e[j];
             if (iq < T)   // head-major copy of (q+v): the X operand of dp = dBand^T (q+v)
                 *reinterpret_cast<bf8*>(a.QvHM + ((size_t)(h * B + b) * T + iq) * 64 + ks * 32 + q4 * 8) = Qv[ks];
         }
@@ -117,55 +96,22 @@ __global__ __launch_bounds__(FB_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArg
     __bf16* dqrow = a.dqkv + ((size_t)b * T + iqc) * (3 * d) + h * dk;
     if (I0 >= len) {   // workgroup-uniform: padded queries only -- zero gradient rows, zero bias partials
         if (iq < T)
-            for (int mt = 0; mt < 4; ++mt)
-                if (mt * 16 + q4 * 4 < dk) *reinterpret_cast<uint2*>(dqrow + mt * 16 + q4 * 4) = make_uint2(0, 0);
+            for (int mt = 0; mt < 4; ++mt) fa_store_head4(dqrow, mt, q4, dk, (f4){0.f, 0.f, 0.f, 0.f});
         if (tid < 2 * dk) part_row[(tid / dk) * d + h * dk + (tid % dk)] = 0.f;
         return;
     }
     const unsigned char* sK = smem;
-    const unsigned char* sV = smem + FB_T64;
-    const unsigned char* sP = smem + 2 * FB_T64;
-    unsigned char* sR = smem + 2 * FB_T64 + FB_PBUF + wave * FB_Q_STRIP;     // forward band strip [16][104] bf16
-    unsigned char* sB = sR + 16 * FB_SR_LD * 2;                               // dS band strip      [16][120] bf16
+    const unsigned char* sV = smem + FA_T64;
+    const unsigned char* sP = smem + 2 * FA_T64;
+    unsigned char* sR = smem + 2 * FA_T64 + FA_PBUF + wave * FB_Q_STRIP;     // forward band strip [16][104] bf16
+    unsigned char* sB = sR + 16 * FA_SR_LD * 2;                               // dS band strip      [16][120] bf16
     for (int i = lane; i < 16 * FB_SB_LD * 2 / 16; i += 64) reinterpret_cast<uint4*>(sB)[i] = make_uint4(0, 0, 0, 0);
 
-    uint4 rk[2], rv[2], rp[4];
-    const __bf16* kbase = a.qkv + (size_t)b * T * (3 * d) + d + h * dk;
-    const __bf16* vbase = kbase + d;
-    const __bf16* pbase = a.pl + h * dk;
-#define FBQ_FETCH(t_)                                                                                         \
-    do {                                                                                                      \
-        const int j0_ = (t_) * 64;                                                                            \
-        _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                                    \
-            const int idx_ = tid + i_ * FB_THREADS, row_ = idx_ >> 3, sl_ = idx_ & 7;                         \
-            int j_ = j0_ + row_; j_ = j_ < T ? j_ : T - 1;                                                    \
-            rk[i_] = fa_load_slot<DK64>(kbase + (size_t)j_ * (3 * d), sl_, dk);                               \
-            rv[i_] = fa_load_slot<DK64>(vbase + (size_t)j_ * (3 * d), sl_, dk);                               \
-        }                                                                                                     \
-        const int R0_ = T - 1 - I0 - 63 + j0_;                                                                \
-        _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                    \
-            const int idx_ = tid + i_ * FB_THREADS, row_ = idx_ >> 3, sl_ = idx_ & 7;                         \
-            int r_ = R0_ + row_; r_ = r_ < 0 ? 0 : (r_ > 2 * T - 2 ? 2 * T - 2 : r_);                         \
-            rp[i_] = fa_load_slot<DK64>(pbase + (size_t)r_ * d, sl_, dk);                                     \
-        }                                                                                                     \
-    } while (0)
-#define FBQ_COMMIT()                                                                                          \
-    do {                                                                                                      \
-        _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                                    \
-            const int idx_ = tid + i_ * FB_THREADS, row_ = idx_ >> 3, sl_ = idx_ & 7;                         \
-            const int off_ = row_ * FB_ROWB + ((sl_ ^ (row_ & 7)) * 16);                                      \
-            *reinterpret_cast<uint4*>(smem + off_) = rk[i_];                                                  \
-            *reinterpret_cast<uint4*>(smem + FB_T64 + off_) = rv[i_];                                         \
-        }                                                                                                     \
-        _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                    \
-            const int idx_ = tid + i_ * FB_THREADS, row_ = idx_ >> 3, sl_ = idx_ & 7;                         \
-            *reinterpret_cast<uint4*>(smem + 2 * FB_T64 + row_ * FB_ROWB + ((sl_ ^ (row_ & 7)) * 16)) = rp[i_]; \
-        }                                                                                                     \
-    } while (0)
+    FaKvpStage<DK64> stage(a.qkv, a.pl, smem, b, h, T, d, dk, I0, tid);
 
     const int nkt = (len + 63) / 64;
-    FBQ_FETCH(0);
-    FBQ_COMMIT();
+    stage.fetch(0);
+    stage.commit();
     __syncthreads();
 
     f4 dQu[4], dQv[4];
@@ -178,27 +124,10 @@ __global__ __launch_bounds__(FB_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArg
     const int pw0 = (3 - wave) * 16;   // first staged position row of this wave's band
 
     for (int t = 0; t < nkt; ++t) {
-        if (t + 1 < nkt) FBQ_FETCH(t + 1);
+        if (t + 1 < nkt) stage.fetch(t + 1);
         const int j0 = t * 64;
         // ---- R^T (band) -> forward strip
-        {
-            f4 R[5];
-#pragma unroll
-            for (int rt = 0; rt < 5; ++rt) {
-                R[rt] = (f4){0.f, 0.f, 0.f, 0.f};
-                const int row = pw0 + rt * 16 + c;
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-                    const bf8 pf = *reinterpret_cast<const bf8*>(sP + row * FB_ROWB + (((ks * 4 + q4) ^ (row & 7)) * 16));
-                    R[rt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, Qv[ks], R[rt], 0, 0, 0);
-                }
-            }
-#pragma unroll
-            for (int rt = 0; rt < 5; ++rt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    *reinterpret_cast<__bf16*>(sR + (c * FB_SR_LD + rt * 16 + q4 * 4 + r + c + 1) * 2) = (__bf16)R[rt][r];
-        }
+        fa_band_to_strip(sP, sR, pw0, Qv, c, q4);
         // ---- S^T = K (q+u)^T ,  dP^T = V dO^T
         f4 S[4], dP[4];
 #pragma unroll
@@ -208,11 +137,8 @@ __global__ __launch_bounds__(FB_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArg
             const int row = jt * 16 + c;
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                const int off = row * FB_ROWB + (((ks * 4 + q4) ^ (row & 7)) * 16);
-                const bf8 kf = *reinterpret_cast<const bf8*>(sK + off);
-                const bf8 vf = *reinterpret_cast<const bf8*>(sV + off);
-                S[jt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, Qu[ks], S[jt], 0, 0, 0);
-                dP[jt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, dOa[ks], dP[jt], 0, 0, 0);
+                S[jt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa_frag(sK, row, ks, q4), Qu[ks], S[jt], 0, 0, 0);
+                dP[jt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa_frag(sV, row, ks, q4), dOa[ks], dP[jt], 0, 0, 0);
             }
         }
         fb_lds_fence();
@@ -221,7 +147,7 @@ __global__ __launch_bounds__(FB_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArg
 #pragma unroll
         for (int jt = 0; jt < 4; ++jt) {
             union { uint2 u; __bf16 e[4]; } bd;
-            bd.u = *reinterpret_cast<const uint2*>(sR + (c * FB_SR_LD + jt * 16 + q4 * 4 + 16) * 2);
+            bd.u = *reinterpret_cast<const uint2*>(sR + (c * FA_SR_LD + jt * 16 + q4 * 4 + 16) * 2);
             unsigned rnd4 = 0;
             if (a.thr > 0) rnd4 = fa_keep_rand4(a.seed, bh, T, iq, (j0 + jt * 16 + q4 * 4) >> 2);
 #pragma unroll
@@ -244,7 +170,7 @@ __global__ __launch_bounds__(FB_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArg
             for (int mt = 0; mt < 4; ++mt) {
                 const int qq = c >> 2, p = c & 3;
                 const int rowA = kk * 32 + q4 * 4 + qq;
-                const bf8 kf = fb_tr_pair(sK, rowA, rowA + 16, mt * 2 + (p >> 1), p & 1);
+                const bf8 kf = fa_tr_pair(sK, rowA, rowA + 16, mt * 2 + (p >> 1), p & 1);
                 dQu[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, dSf[kk], dQu[mt], 0, 0, 0);
             }
         // ---- band strip of this tile: zero the 96 band columns, then strip[c][jl + 15 - c] = dS
@@ -268,7 +194,7 @@ __global__ __launch_bounds__(FB_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArg
                 const int qq = c >> 2, p = c & 3;
                 int rowA = pw0 + kk * 32 + q4 * 8 + qq, rowB = rowA + 4;
                 rowA = rowA < 127 ? rowA : 127; rowB = rowB < 127 ? rowB : 127;   // band rows >= 79 are zero in the strip
-                const bf8 pf = fb_tr_pair(sP, rowA, rowB, mt * 2 + (p >> 1), p & 1);
+                const bf8 pf = fa_tr_pair(sP, rowA, rowB, mt * 2 + (p >> 1), p & 1);
                 dQv[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, bfrag, dQv[mt], 0, 0, 0);
             }
         }
@@ -295,12 +221,10 @@ __global__ __launch_bounds__(FB_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArg
         }
         __syncthreads();
         if (t + 1 < nkt) {
-            FBQ_COMMIT();
+            stage.commit();
             __syncthreads();
         }
     }
-#undef FBQ_FETCH
-#undef FBQ_COMMIT
     // ---- last carry -> dBand columns 64 .. 79 behind the last processed tile
     fb_lds_fence();
     if ((lane & 3) == 0 && fvalid) {
@@ -311,14 +235,7 @@ __global__ __launch_bounds__(FB_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArg
     // ---- dq = d(q+u) + d(q+v): lane (query c, q4) holds e = 16 mt + 4 q4 + r
     if (iq < T) {
 #pragma unroll
-        for (int mt = 0; mt < 4; ++mt) {
-            if (mt * 16 + q4 * 4 < dk) {
-                union { uint2 u; __bf16 e[4]; } o;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o.e[r] = (__bf16)(dQu[mt][r] + dQv[mt][r]);
-                *reinterpret_cast<uint2*>(dqrow + mt * 16 + q4 * 4) = o.u;
-            }
-        }
+        for (int mt = 0; mt < 4; ++mt) fa_store_head4(dqrow, mt, q4, dk, dQu[mt] + dQv[mt]);
     }
     // ---- bias gradients: sums over the workgroup's 64 queries -> this workgroup's slice of its partial row
     float* red = reinterpret_cast<float*>(smem);   // [4 waves][2][64] (the K tile is no longer read: barrier above)
@@ -344,19 +261,14 @@ __global__ __launch_bounds__(FB_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArg
 
 // ========================================================================================================== key-owner
 template <bool DK64>
-__global__ __launch_bounds__(FB_THREADS, 2) void relpos_flash_bwd_kv_kernel(FbArgs a) {
+__global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_kv_kernel(FbArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 15, q4 = lane >> 4;
     const int T = a.T, H = a.H, dk = a.dk, d = H * dk, B = a.B;
-    const int nkt = (T + 63) / 64;
-    const int xcd = blockIdx.x & 7, slot_id = blockIdx.x >> 3;
-    const int bh = xcd + 8 * (slot_id / nkt);
-    if (bh >= B * H) return;
-    const int kt = slot_id % nkt;
-    const int h = bh % H, b = bh / H;
-    int len = (int)a.lens[b];
-    len = len < 0 ? 0 : (len > T ? T : len);
+    const FaWg wg = fa_wg(B, T, H, a.lens);
+    if (wg.len < 0) return;
+    const int bh = wg.bh, kt = wg.tile, h = wg.h, b = wg.b, len = wg.len;
     const int J0 = kt * 64, jw = J0 + wave * 16, j = jw + c;
     const int jc = j < T ? j : T - 1;
     const bool kvalid = j < len;
@@ -364,11 +276,10 @@ __global__ __launch_bounds__(FB_THREADS, 2) void relpos_flash_bwd_kv_kernel(FbAr
     __bf16* dvrow = dkrow + d;
     if (J0 >= len) {   // workgroup-uniform: padded keys only
         if (j < T)
-            for (int mt = 0; mt < 4; ++mt)
-                if (mt * 16 + q4 * 4 < dk) {
-                    *reinterpret_cast<uint2*>(dkrow + mt * 16 + q4 * 4) = make_uint2(0, 0);
-                    *reinterpret_cast<uint2*>(dvrow + mt * 16 + q4 * 4) = make_uint2(0, 0);
-                }
+            for (int mt = 0; mt < 4; ++mt) {
+                fa_store_head4(dkrow, mt, q4, dk, (f4){0.f, 0.f, 0.f, 0.f});
+                fa_store_head4(dvrow, mt, q4, dk, (f4){0.f, 0.f, 0.f, 0.f});
+            }
         return;
     }
     // ---- this lane's key: K and V rows as MFMA B fragments
@@ -384,10 +295,10 @@ __global__ __launch_bounds__(FB_THREADS, 2) void relpos_flash_bwd_kv_kernel(FbAr
         }
     }
     const unsigned char* sQu = smem;
-    const unsigned char* sQv = smem + FB_T64;
-    const unsigned char* sdO = smem + 2 * FB_T64;
-    const unsigned char* sP = smem + 3 * FB_T64;
-    const float* sL = reinterpret_cast<const float*>(smem + 3 * FB_T64 + FB_PBUF);   // lse[64] | D[64]
+    const unsigned char* sQv = smem + FA_T64;
+    const unsigned char* sdO = smem + 2 * FA_T64;
+    const unsigned char* sP = smem + 3 * FA_T64;
+    const float* sL = reinterpret_cast<const float*>(smem + 3 * FA_T64 + FA_PBUF);   // lse[64] | D[64]
     unsigned char* s3 = smem + FB_KV_STAGE + wave * (16 * FB_S3_LD * 2);
 
     // staging: thread -> slot sl = tid & 7 of rows (tid >> 3) and (tid >> 3) + 32; the biases of its 8 elements in registers
@@ -406,51 +317,39 @@ __global__ __launch_bounds__(FB_THREADS, 2) void relpos_flash_bwd_kv_kernel(FbAr
     const __bf16* qbase = a.qkv + (size_t)b * T * (3 * d) + h * dk;
     const __bf16* gbase = a.dctx + (size_t)b * T * d + h * dk;
     const __bf16* pbase = a.pl + h * dk;
-#define FBK_FETCH(t_)                                                                                         \
-    do {                                                                                                      \
-        const int i0_ = (t_) * 64;                                                                            \
-        _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                                    \
-            const int idx_ = tid + i_ * FB_THREADS, row_ = idx_ >> 3, sl_ = idx_ & 7;                         \
-            int q_ = i0_ + row_; q_ = q_ < T ? q_ : T - 1;                                                    \
-            rq[i_] = fa_load_slot<DK64>(qbase + (size_t)q_ * (3 * d), sl_, dk);                               \
-            rg[i_] = fa_load_slot<DK64>(gbase + (size_t)q_ * d, sl_, dk);                                     \
-        }                                                                                                     \
-        const int R0_ = T - 1 - i0_ - 63 + J0;                                                                \
-        _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                    \
-            const int idx_ = tid + i_ * FB_THREADS, row_ = idx_ >> 3, sl_ = idx_ & 7;                         \
-            int r_ = R0_ + row_; r_ = r_ < 0 ? 0 : (r_ > 2 * T - 2 ? 2 * T - 2 : r_);                         \
-            rp[i_] = fa_load_slot<DK64>(pbase + (size_t)r_ * d, sl_, dk);                                     \
-        }                                                                                                     \
-        if (tid < 128) {                                                                                      \
-            int q_ = i0_ + (tid & 63); q_ = q_ < T ? q_ : T - 1;                                              \
-            rl = (tid < 64 ? a.lse : a.D)[(size_t)bh * T + q_];                                               \
-        }                                                                                                     \
-    } while (0)
-#define FBK_COMMIT()                                                                                          \
-    do {                                                                                                      \
-        _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) {                                                    \
-            const int idx_ = tid + i_ * FB_THREADS, row_ = idx_ >> 3, sl_ = idx_ & 7;                         \
-            const int off_ = row_ * FB_ROWB + ((sl_ ^ (row_ & 7)) * 16);                                      \
-            union { uint4 u; __bf16 e[8]; } q_, u_, v_;                                                       \
-            q_.u = rq[i_];                                                                                    \
-            _Pragma("unroll") for (int e_ = 0; e_ < 8; ++e_) {                                                \
-                u_.e[e_] = (__bf16)((float)q_.e[e_] + bu[e_]);                                                \
-                v_.e[e_] = (__bf16)((float)q_.e[e_] + bv[e_]);                                                \
-            }                                                                                                 \
-            *reinterpret_cast<uint4*>(smem + off_) = u_.u;                                                    \
-            *reinterpret_cast<uint4*>(smem + FB_T64 + off_) = v_.u;                                           \
-            *reinterpret_cast<uint4*>(smem + 2 * FB_T64 + off_) = rg[i_];                                     \
-        }                                                                                                     \
-        _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                    \
-            const int idx_ = tid + i_ * FB_THREADS, row_ = idx_ >> 3, sl_ = idx_ & 7;                         \
-            *reinterpret_cast<uint4*>(smem + 3 * FB_T64 + row_ * FB_ROWB + ((sl_ ^ (row_ & 7)) * 16)) = rp[i_]; \
-        }                                                                                                     \
-        if (tid < 128) reinterpret_cast<float*>(smem + 3 * FB_T64 + FB_PBUF)[tid] = rl;                       \
-    } while (0)
+    const auto fetch = [&](int t) {
+        const int i0 = t * 64;
+        fa_fetch_rows<DK64, false>(rq, qbase, 3 * d, i0, T - 1, dk, tid);
+        fa_fetch_rows<DK64, false>(rg, gbase, d, i0, T - 1, dk, tid);
+        fa_fetch_rows<DK64, true>(rp, pbase, d, T - 1 - i0 - 63 + J0, 2 * T - 2, dk, tid);
+        if (tid < 128) {
+            int q = i0 + (tid & 63); q = q < T ? q : T - 1;
+            rl = (tid < 64 ? a.lse : a.D)[(size_t)bh * T + q];
+        }
+    };
+    const auto commit = [&]() {   // (q+u) and (q+v) are made here, from the fetched q rows and the thread's biases
+        uint4 ru[2], rw[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            union { uint4 u; __bf16 e[8]; } q, u, v;
+            q.u = rq[i];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                u.e[e] = (__bf16)((float)q.e[e] + bu[e]);
+                v.e[e] = (__bf16)((float)q.e[e] + bv[e]);
+            }
+            ru[i] = u.u; rw[i] = v.u;
+        }
+        fa_commit_rows(smem, ru, tid);
+        fa_commit_rows(smem + FA_T64, rw, tid);
+        fa_commit_rows(smem + 2 * FA_T64, rg, tid);
+        fa_commit_rows(smem + 3 * FA_T64, rp, tid);
+        if (tid < 128) reinterpret_cast<float*>(smem + 3 * FA_T64 + FA_PBUF)[tid] = rl;
+    };
 
     const int nqt = (len + 63) / 64;   // query tiles with at least one valid query
-    FBK_FETCH(0);
-    FBK_COMMIT();
+    fetch(0);
+    commit();
     __syncthreads();
 
     f4 dK[4], dV[4];
@@ -458,7 +357,7 @@ __global__ __launch_bounds__(FB_THREADS, 2) void relpos_flash_bwd_kv_kernel(FbAr
     for (int mt = 0; mt < 4; ++mt) { dK[mt] = (f4){0.f, 0.f, 0.f, 0.f}; dV[mt] = (f4){0.f, 0.f, 0.f, 0.f}; }
 
     for (int t = 0; t < nqt; ++t) {
-        if (t + 1 < nqt) FBK_FETCH(t + 1);
+        if (t + 1 < nqt) fetch(t + 1);
         const int I0 = t * 64;
         // ---- band: for the 16 queries of tile `it` the wave's keys need position rows n0 .. n0 + 31, n0 = 48 - 16 it + 16 w
         //      X_A[m][n] = (q+v)_{16 it + m} . p[n0 + n], X_B with n0 + 16;  bd[il = 16 it + m][key c] = c <= m ? X_A[m][15 - m + c]
@@ -471,9 +370,7 @@ __global__ __launch_bounds__(FB_THREADS, 2) void relpos_flash_bwd_kv_kernel(FbAr
             const int pa = n0 + c, pb = n0 + 16 + c;
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                const bf8 qf = *reinterpret_cast<const bf8*>(sQv + qrow * FB_ROWB + (((ks * 4 + q4) ^ (qrow & 7)) * 16));
-                const bf8 fa = *reinterpret_cast<const bf8*>(sP + pa * FB_ROWB + (((ks * 4 + q4) ^ (pa & 7)) * 16));
-                const bf8 fb = *reinterpret_cast<const bf8*>(sP + pb * FB_ROWB + (((ks * 4 + q4) ^ (pb & 7)) * 16));
+                const bf8 qf = fa_frag(sQv, qrow, ks, q4), fa = fa_frag(sP, pa, ks, q4), fb = fa_frag(sP, pb, ks, q4);
                 XA = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, fa, XA, 0, 0, 0);
                 XB = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, fb, XB, 0, 0, 0);
             }
@@ -494,11 +391,8 @@ __global__ __launch_bounds__(FB_THREADS, 2) void relpos_flash_bwd_kv_kernel(FbAr
             const int row = it * 16 + c;
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                const int off = row * FB_ROWB + (((ks * 4 + q4) ^ (row & 7)) * 16);
-                const bf8 qf = *reinterpret_cast<const bf8*>(sQu + off);
-                const bf8 gf = *reinterpret_cast<const bf8*>(sdO + off);
-                S[it] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, Kf[ks], S[it], 0, 0, 0);
-                dP[it] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(gf, Vf[ks], dP[it], 0, 0, 0);
+                S[it] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa_frag(sQu, row, ks, q4), Kf[ks], S[it], 0, 0, 0);
+                dP[it] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa_frag(sdO, row, ks, q4), Vf[ks], dP[it], 0, 0, 0);
             }
         }
         fb_lds_fence();
@@ -534,29 +428,22 @@ __global__ __launch_bounds__(FB_THREADS, 2) void relpos_flash_bwd_kv_kernel(FbAr
             for (int mt = 0; mt < 4; ++mt) {
                 const int qq = c >> 2, p = c & 3;
                 const int rowA = kk * 32 + q4 * 4 + qq;
-                const bf8 gf = fb_tr_pair(sdO, rowA, rowA + 16, mt * 2 + (p >> 1), p & 1);
-                const bf8 qf = fb_tr_pair(sQu, rowA, rowA + 16, mt * 2 + (p >> 1), p & 1);
+                const bf8 gf = fa_tr_pair(sdO, rowA, rowA + 16, mt * 2 + (p >> 1), p & 1);
+                const bf8 qf = fa_tr_pair(sQu, rowA, rowA + 16, mt * 2 + (p >> 1), p & 1);
                 dV[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(gf, Pdf[kk], dV[mt], 0, 0, 0);
                 dK[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, dSf[kk], dK[mt], 0, 0, 0);
             }
         __syncthreads();
         if (t + 1 < nqt) {
-            FBK_COMMIT();
+            commit();
             __syncthreads();
         }
     }
-#undef FBK_FETCH
-#undef FBK_COMMIT
     if (j < T) {
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
-            if (mt * 16 + q4 * 4 < dk) {
-                union { uint2 u; __bf16 e[4]; } ok, ov;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) { ok.e[r] = (__bf16)dK[mt][r]; ov.e[r] = (__bf16)dV[mt][r]; }
-                *reinterpret_cast<uint2*>(dkrow + mt * 16 + q4 * 4) = ok.u;
-                *reinterpret_cast<uint2*>(dvrow + mt * 16 + q4 * 4) = ov.u;
-            }
+            fa_store_head4(dkrow, mt, q4, dk, dK[mt]);
+            fa_store_head4(dvrow, mt, q4, dk, dV[mt]);
         }
     }
 }
@@ -650,22 +537,10 @@ extern "C" int ia_relpos_attention_flash_bwd(const void* qkv, const void* pos_pr
     const int nt = (T + 63) / 64;
     const int grid = 8 * ((B * H + 7) / 8) * nt;
     const bool full = (dk == 64);
-    if (full) {
-        IA_SET_MAX_LDS_ONCE((relpos_flash_bwd_q_kernel<true>), FB_Q_LDS);
-        hipLaunchKernelGGL((relpos_flash_bwd_q_kernel<true>), dim3(grid), dim3(FB_THREADS), FB_Q_LDS, st, a);
-    } else {
-        IA_SET_MAX_LDS_ONCE((relpos_flash_bwd_q_kernel<false>), FB_Q_LDS);
-        hipLaunchKernelGGL((relpos_flash_bwd_q_kernel<false>), dim3(grid), dim3(FB_THREADS), FB_Q_LDS, st, a);
-    }
-    IA_RETURN_IF_LAUNCH_FAILED();
-    if (full) {
-        IA_SET_MAX_LDS_ONCE((relpos_flash_bwd_kv_kernel<true>), FB_KV_LDS);
-        hipLaunchKernelGGL((relpos_flash_bwd_kv_kernel<true>), dim3(grid), dim3(FB_THREADS), FB_KV_LDS, st, a);
-    } else {
-        IA_SET_MAX_LDS_ONCE((relpos_flash_bwd_kv_kernel<false>), FB_KV_LDS);
-        hipLaunchKernelGGL((relpos_flash_bwd_kv_kernel<false>), dim3(grid), dim3(FB_THREADS), FB_KV_LDS, st, a);
-    }
-    IA_RETURN_IF_LAUNCH_FAILED();
+    int rc = fa_launch<FbArgs, relpos_flash_bwd_q_kernel<true>, relpos_flash_bwd_q_kernel<false>>(full, grid, FB_Q_LDS, st, a);
+    if (rc != IA_OK) return rc;
+    rc = fa_launch<FbArgs, relpos_flash_bwd_kv_kernel<true>, relpos_flash_bwd_kv_kernel<false>>(full, grid, FB_KV_LDS, st, a);
+    if (rc != IA_OK) return rc;
     ia_partials_finish(a.part, B * nt, 2 * H * dk, H * dk, dbias_u, dbias_v, st);
     IA_RETURN_IF_LAUNCH_FAILED();
     // position-projection gradient: per head dpos_h [Rs, 64] = dBand_h^T (q+v)_h over the B*T rows (split-K TN GEMM), then
