@@ -403,6 +403,17 @@ int ia_relpos_attention_flash(const void* qkv, const void* pos_proj, const float
 int ia_relpos_attention_flash_lse(const void* qkv, const void* pos_proj, const float* bias_u, const float* bias_v,
                                   const int64_t* lens, int B, int T, int H, int dk, float dropout_p, unsigned seed, void* ctx,
                                   float* lse, ia_stream_t stream);
+/* Local (windowed) forward of the same core (csrc/attention_local.hip): RelPositionMultiHeadAttentionLongformer.forward
+ * (A/parts/submodules/multi_head_attention.py:253-470) with LocalAttRelPositionalEncoding (:982-1026) for a symmetric window
+ * [window, window] and no global tokens -- query i attends the keys |i - j| <= window, j < lens[b].  A 64-query tile visits
+ * at most 1 + 2 ceil(window / 64) key tiles whatever T is.  Operands, layouts, lens semantics, alignment checks and the dropout
+ * hash are ia_relpos_attention_flash's, except pos_proj [>= 2 window + 1, H*dk] bf16, row r <-> relative position window - r
+ * (a window >= T-1 computes full attention: same bits as ia_relpos_attention_flash on the matching table).  window >= 1
+ * (IA_INVALID_VALUE otherwise), dk as the full kernel (IA_UNSUPPORTED otherwise).  Forward only: no lse, no backward. */
+int ia_relpos_attention_local_supported(int T, int dk, int window);
+int ia_relpos_attention_local(const void* qkv, const void* pos_proj, const float* bias_u, const float* bias_v,
+                              const int64_t* lens, int B, int T, int H, int dk, int window, float dropout_p, unsigned seed,
+                              void* ctx, ia_stream_t stream);
 /* Key-tiled backward of the same attention core (csrc/attention_flash_bwd.hip; autograd of multi_head_attention.py:197-250):
  * no [T,T] matrices in HBM.  In: the forward's qkv / pos_proj / biases / lens / ctx / lse, dctx [B*T, d] bf16 and the
  * forward's dropout p / seed.  Out: dqkv [B*T, 3d] bf16 (every row written), dpl [pl_rows, d] bf16 (rows >= 2T-1 zero),
@@ -457,7 +468,8 @@ int ia_lstm_backward(const float* dHout, const float* gates, const float* Cs, co
  * the length masking :458-462 and spec_augment_kernel A/parts/numba/spec_augment/spec_aug_numba.py:26-95.
  *   x, y [B,F,T] f32 (y may alias x); seq_len [B] i64; eps = 1e-5 added to the (unbiased) std.
  *   freq_starts/widths [B,n_freq_masks] i32, time_starts/widths [B,n_time_masks] i32 (device; counts may be 0):
- *   frequency spans mask whole rows, time spans only frames below seq_len[b].  Limit: T <= 4096. */
+ *   frequency spans mask whole rows, time spans only frames below seq_len[b].  T <= 4096: the row is held in registers; longer rows
+ *   (more than 41 s of audio) are read three times by a second kernel with the same statistics and fill rule. */
 /* Log-mel front end (FilterbankFeatures.forward A/parts/preprocessing/features.py:400-444) as five launches:
  *   ia_feat_frames   dither (counter-based N(0,1) keyed by (seed,b,sample)) + pre-emphasis (first sample kept, :414) +
  *                    centred, reflect-padded framing: frames [B*Tm, ldf] f32 (columns >= win zero); tap n of frame t is
@@ -555,7 +567,8 @@ int ia_ffn_fused_tail(float* x, int N, int d, int d_ff, const float* ln_g, const
 /* ------------------------------------------------------------------------------------------------
  * Native executor of the no-autograd Conformer prefix (frozen blocks / teacher / eval): one call enqueues the 14
  * kernels of each of `n_layers` blocks (ConformerLayer.forward, conformer_modules.py:141-214) on `stream`.
- * x [B*T, d] f32 residual stream, updated in place to the last block's norm_out; pos_emb [pos_rows >= 2T-1, d] bf16;
+ * x [B*T, d] f32 residual stream, updated in place to the last block's norm_out; pos_emb [pos_rows >= 2T-1, d] bf16
+ * (>= 2w+1 under local attention, ia_block_params.att_window = w);
  * block l uses dropout seeds seed_base + l*seed_stride + {1..7} (the sites of the Python path); training = 0 disables
  * dropout and uses the BatchNorm running statistics.  All pointers in ia_block_params are device pointers: bf16 weights
  * [out, in] (w_qkv = q|k|v rows concatenated, b_qkv likewise), f32 everything else.  Workspace from
@@ -575,6 +588,10 @@ typedef struct ia_block_params {
     const float* b_pw1_glu;  /* consecutive outputs are 64 value channels followed by THEIR 64 gate channels (rows 128t+j = value
                                 channel 64t+j, rows 128t+64+j = gate channel d+64t+j): the prefix executor then applies the GLU in
                                 the GEMM epilogue (act 4) and the depthwise conv reads the gated [N,d] bf16 tensor; NULL: off */
+    int att_window;          /* 0: full rel-pos attention (pos_rows >= 2T-1).  w > 0: local attention [w, w]
+                                (ia_relpos_attention_local; pos_emb / pl_cached hold 2w+1 rows, row r <-> position w - r, so
+                                pos_rows >= 2w+1).  All layers of a prefix call must agree (IA_INVALID_VALUE otherwise); the
+                                trainable-block executors take only 0 (IA_UNSUPPORTED otherwise) */
 } ia_block_params;
 size_t ia_conformer_prefix_ws_bytes(int B, int T, int d, int d_ff, int H, int ksz, int pos_rows);
 int ia_conformer_prefix_fwd(const ia_block_params* layers, int n_layers, float* x, const void* pos_emb, int pos_rows,

@@ -76,6 +76,8 @@ def config_from_nemo_yaml(cfg: dict, **overrides) -> ModelConfig:
     put("conv_kernel_size", enc, "conv_kernel_size", int); put("pos_emb_max_len", enc, "pos_emb_max_len", int)
     put("dropout", enc, "dropout", float); put("dropout_pre_encoder", enc, "dropout_pre_encoder", float)
     put("dropout_emb", enc, "dropout_emb", float); put("dropout_att", enc, "dropout_att", float)
+    put("self_attention_model", enc, "self_attention_model", str)
+    put("att_context_size", enc, "att_context_size", lambda v: [int(c) for c in v])
     put("pred_hidden", pred, "pred_hidden", int); put("pred_dropout", pred, "dropout", float)
     put("joint_hidden", jnt, "joint_hidden", int); put("joint_dropout", jnt, "dropout", float)
     put("fused_batch_size", cfg.get("joint", {}), "fused_batch_size", int)
@@ -108,7 +110,8 @@ def nemo_yaml_from_config(c: ModelConfig) -> dict:
                          "time_width": c.time_width},
         "encoder": {"feat_in": c.feat_in, "n_layers": c.n_layers, "d_model": c.d_model, "subsampling": "striding",
                     "subsampling_factor": 4, "subsampling_conv_channels": c.d_model, "ff_expansion_factor": c.ff_expansion_factor,
-                    "self_attention_model": "rel_pos", "n_heads": c.n_heads, "conv_kernel_size": c.conv_kernel_size,
+                    "self_attention_model": c.self_attention_model, "att_context_size": [int(v) for v in c.att_context_size],
+                    "n_heads": c.n_heads, "conv_kernel_size": c.conv_kernel_size,
                     "conv_norm_type": "batch_norm", "pos_emb_max_len": c.pos_emb_max_len, "dropout": c.dropout,
                     "dropout_pre_encoder": c.dropout_pre_encoder, "dropout_emb": c.dropout_emb, "dropout_att": c.dropout_att},
         "decoder": {"prednet": {"pred_hidden": c.pred_hidden, "pred_rnn_layers": 1, "dropout": c.pred_dropout}},

@@ -30,6 +30,10 @@ class ModelConfig:
     dropout_pre_encoder: float = 0.1
     dropout_emb: float = 0.0
     dropout_att: float = 0.1
+    # "rel_pos" (full attention) | "rel_pos_local_attn" (local attention, att_context_size = [w, w]); yaml :107-117,
+    # switched at run time by change_attention_model
+    self_attention_model: str = "rel_pos"
+    att_context_size: List[int] = field(default_factory=lambda: [-1, -1])
     # prediction / joint (yaml :130-158)
     pred_hidden: int = 640
     joint_hidden: int = 640

@@ -1,5 +1,5 @@
-// The one vocabulary of the key-tiled rel-pos attention kernels (attention_flash.hip forward, attention_flash_bwd.hip query-owner
-// and key-owner backward): fragment types, tile constants, the attention-dropout hash (the backward regenerates the forward's
+// The one vocabulary of the key-tiled rel-pos attention kernels (attention_flash.hip forward, attention_local.hip windowed
+// forward, attention_flash_bwd.hip query-owner and key-owner backward): fragment types, tile constants, the attention-dropout hash (the backward regenerates the forward's
 // mask), the zero-padding head-row loader, the swizzled LDS addresses and fragment reads, register staging of a tile (fetch /
 // commit), the K | V | P stage, the query fragments, the band block, the workgroup coordinates, the guarded head-row store and
 // the host's launch of a <DK64> pair.  tests/test_attention_flash_digests_gpu.py pins the bits of everything built from it.

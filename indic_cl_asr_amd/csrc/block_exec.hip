@@ -78,11 +78,15 @@ extern "C" int ia_conformer_prefix_fwd_seg(const ia_block_params* layers, int n_
     if (!layers || n_layers <= 0 || !x || !pos_emb || !lens || !workspace || B <= 0 || T <= 0) return IA_INVALID_VALUE;
     const ia_block_params& l0 = layers[0];
     const int d = l0.d, d_ff = l0.d_ff, H = l0.n_heads, dk = d / (H > 0 ? H : 1), ksz = l0.ksz;
-    if (pos_rows < 2 * T - 1) return IA_INVALID_VALUE;
+    const int window = l0.att_window;   // 0: full attention; w > 0: local attention [w, w] on a 2w+1-row position table
+    if (window < 0 || (long long)pos_rows < (window > 0 ? 2ll * window + 1 : 2ll * T - 1)) return IA_INVALID_VALUE;
+    for (int li = 0; li < n_layers; ++li)
+        if (layers[li].att_window != window) return IA_INVALID_VALUE;
     const PrefixWs w = prefix_ws(B, T, d, d_ff, ksz, pos_rows);
     if (workspace_bytes < w.total) return IA_WORKSPACE_TOO_SMALL;
     if (H <= 0) return IA_INVALID_VALUE;
     if (!ia_relpos_attention_flash_supported(T, dk)) return IA_UNSUPPORTED;   // before anything rewrites x in place
+    if (window > 0 && !ia_relpos_attention_local_supported(T, dk, window)) return IA_UNSUPPORTED;
     char* ws = (char*)workspace;
     void *y = ws + w.y, *h = ws + w.h, *qkv = ws + w.qkv, *pl = ws + w.pl, *ctx = ws + w.ctx, *c2 = ws + w.c2, *c3 = ws + w.c3;
     float *z = (float*)(ws + w.z), *sums = (float*)(ws + w.sums), *scr = (float*)(ws + w.scr);
@@ -139,7 +143,10 @@ extern "C" int ia_conformer_prefix_fwd_seg(const ia_block_params* layers, int n_
             IA_TRY(ia_gemm_bf16(pos_emb, d, L.w_pos, d, pos_rows, d, d, nullptr, 0, 0.f, 0, 1.f, nullptr, 0, nullptr, 0, pl, d, stream));
             plu = pl;
         }
-        IA_TRY(ia_relpos_attention_flash(qkv, plu, L.pos_u, L.pos_v, lens, B, T, H, dk, patt, seed + 7, ctx, stream));
+        if (window > 0)
+            IA_TRY(ia_relpos_attention_local(qkv, plu, L.pos_u, L.pos_v, lens, B, T, H, dk, window, patt, seed + 7, ctx, stream));
+        else
+            IA_TRY(ia_relpos_attention_flash(qkv, plu, L.pos_u, L.pos_v, lens, B, T, H, dk, patt, seed + 7, ctx, stream));
         // out-projection (+ residual) and the convolution module's LayerNorm: one launch at d_model = 256 (64 x 256 tiles own
         // whole rows), two otherwise
         static const bool ln_in_gemm = [] { const char* e = getenv("IA_LN_IN_GEMM"); return !(e && e[0] == '0'); }();

@@ -63,6 +63,41 @@ __global__ __launch_bounds__(FN_THREADS) void feat_normalize_kernel(
     }
 }
 
+// The same for rows that do not fit the registers (Tm > 4096: more than 41 s of audio, the recordings local attention is for):
+// the same two-pass statistics and fill rule with the row read three times (72 KB at 180 s: it stays in L2) instead of held.
+__global__ __launch_bounds__(FN_THREADS) void feat_normalize_long_kernel(
+    const float* __restrict__ x, const int64_t* __restrict__ seq_len, int F, int T, float eps,
+    const int* __restrict__ fs, const int* __restrict__ fw, int nf, const int* __restrict__ ts, const int* __restrict__ tw,
+    int ntm, float mask_value, float* __restrict__ y) {
+    __shared__ float sh[4];
+    const int row = blockIdx.x, b = row / F, f = row - b * F;
+    const int len = (int)seq_len[b];
+    const int nv = len < T ? len : T;   // frames that are both valid and there
+    const float* xr = x + (size_t)row * T;
+    float s = 0.f;
+    for (int t = threadIdx.x; t < nv; t += FN_THREADS) s += xr[t];
+    const float mean = block_sum256(s, sh) / (float)len;
+    float q = 0.f;
+    for (int t = threadIdx.x; t < nv; t += FN_THREADS) { const float d = xr[t] - mean; q += d * d; }
+    const float var = block_sum256(q, sh) / (float)(len - 1);
+    const float inv = 1.f / (sqrtf(var) + eps);
+    bool fmask = false;
+    for (int k = 0; k < nf; ++k) {
+        const int s0 = fs[b * nf + k];
+        fmask |= (f >= s0 && f < s0 + fw[b * nf + k]);
+    }
+    for (int t = threadIdx.x; t < T; t += FN_THREADS) {
+        float o = (t < len) ? (xr[t] - mean) * inv : 0.f;
+        bool m = fmask;
+        if (t < len)
+            for (int k = 0; k < ntm; ++k) {
+                const int s0 = ts[b * ntm + k];
+                m |= (t >= s0 && t < s0 + tw[b * ntm + k]);
+            }
+        y[(size_t)row * T + t] = m ? mask_value : o;
+    }
+}
+
 // ---- log-mel front end around the two exact-fp32 GEMMs (gemm_f32.hip) --------------------------------------------
 __device__ __forceinline__ unsigned fe_hash32(unsigned x) {
     x ^= x >> 16; x *= 0x85ebca6bu; x ^= x >> 13; x *= 0xc2b2ae35u; x ^= x >> 16;
@@ -184,10 +219,9 @@ extern "C" int ia_feat_normalize(const float* x, const int64_t* seq_len, int B, 
                                  const int* time_starts, const int* time_widths, int n_time_masks, float mask_value,
                                  float* y, ia_stream_t stream) {
     if (!x || !seq_len || !y || B <= 0 || F <= 0 || T <= 0) return IA_INVALID_VALUE;
-    if (T > FN_THREADS * FN_MAXV) return IA_UNSUPPORTED;
     if ((n_freq_masks > 0 && (!freq_starts || !freq_widths)) || (n_time_masks > 0 && (!time_starts || !time_widths)))
         return IA_INVALID_VALUE;
-    hipLaunchKernelGGL(feat_normalize_kernel, dim3(B * F), dim3(FN_THREADS), 0, (hipStream_t)stream, x, seq_len, F, T, eps,
+    hipLaunchKernelGGL(T > FN_THREADS * FN_MAXV ? feat_normalize_long_kernel : feat_normalize_kernel, dim3(B * F), dim3(FN_THREADS), 0, (hipStream_t)stream, x, seq_len, F, T, eps,
                        freq_starts, freq_widths, n_freq_masks, time_starts, time_widths, n_time_masks, mask_value, y);
     IA_RETURN_IF_LAUNCH_FAILED();
     return IA_OK;

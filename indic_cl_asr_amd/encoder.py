@@ -56,6 +56,10 @@ class RelPositionalEncoding(nn.Module):
         self.dropout = nn.Dropout(dropout_rate)
         self.dropout_emb = nn.Dropout(dropout_rate_emb) if dropout_rate_emb > 0 else None
         self.register_buffer("pe", self._table(max_len), persistent=False)
+        # local attention (LocalAttRelPositionalEncoding, multi_head_attention.py:982-1026): the 2w+1 rows of positions w .. -w,
+        # built for the window alone -- no dependence on max_len.  None under full attention.  Not persistent either.
+        self.local_window = None
+        self.register_buffer("pe_local", None, persistent=False)
 
     def _table(self, length):
         positions = torch.arange(length - 1, -length, -1, dtype=torch.float32).unsqueeze(1)
@@ -69,9 +73,21 @@ class RelPositionalEncoding(nn.Module):
         if self.pe.size(1) < 2 * length - 1:
             self.pe = self._table(length).to(device)
 
+    def set_local_window(self, window, device=None):
+        """window = w > 0: pos_emb_for returns the [1, 2w+1, d] table of a local window [w, w]; None: the full 2T-1 slice."""
+        self.local_window = window
+        self.pe_local = None if window is None else self._table(window + 1).to(device if device is not None else self.pe.device)
+
+    def table(self):
+        """The buffer pos_emb_for slices (the cache key of the encoder's bf16 images)."""
+        return self.pe if self.local_window is None else self.pe_local
+
     def pos_emb_for(self, T):
-        centre = self.pe.size(1) // 2 + 1
-        pos_emb = self.pe[:, centre - T: centre + T - 1]
+        if self.local_window is not None:
+            pos_emb = self.pe_local
+        else:
+            centre = self.pe.size(1) // 2 + 1
+            pos_emb = self.pe[:, centre - T: centre + T - 1]
         if self.dropout_emb is not None:
             pos_emb = self.dropout_emb(pos_emb)
         return pos_emb
@@ -94,6 +110,7 @@ class RelPositionMultiHeadAttention(nn.Module):
         self.pos_bias_u = nn.Parameter(torch.zeros(self.h, self.d_k))
         self.pos_bias_v = nn.Parameter(torch.zeros(self.h, self.d_k))
         self.dropout_rate = dropout_rate
+        self.att_window = None   # w: local attention [w, w] (RelPositionMultiHeadAttentionLongformer); same parameters either way
 
     def forward(self, x, lens, pos_emb):
         B, T, _ = x.shape
@@ -101,7 +118,8 @@ class RelPositionMultiHeadAttention(nn.Module):
         k = self.linear_k(x).view(B, T, self.h, self.d_k).transpose(1, 2)
         v = self.linear_v(x).view(B, T, self.h, self.d_k).transpose(1, 2)
         p = self.linear_pos(pos_emb.to(x.dtype)).view(-1, self.h, self.d_k).transpose(0, 1)  # [h,2T-1,dk]
-        ctx = ops.rel_pos_attention(q, k, v, p, self.pos_bias_u, self.pos_bias_v, lens, self.dropout_rate, self.training)
+        ctx = ops.rel_pos_attention(q, k, v, p, self.pos_bias_u, self.pos_bias_v, lens, self.dropout_rate, self.training,
+                                    window=self.att_window)
         return self.linear_out(ctx.transpose(1, 2).reshape(B, T, self.h * self.d_k))
 
 
@@ -197,14 +215,17 @@ class ConformerLayer(nn.Module):
         _, qkv = G(y, Wt(att.linear_q.weight, att.linear_k.weight, att.linear_v.weight),
                            fast.f32_cat(att.linear_q.bias, att.linear_k.bias, att.linear_v.bias))
         _, pl = fast.gemm(pos_emb, fast.bf16_shadow(att.linear_pos.weight))
-        if fast.attention_flash_supported(T, att.d_k):
+        if att.att_window is not None and fast.attention_local_supported(T, att.d_k, att.att_window):
+            ctx = fast.relpos_attention_local(qkv, pl, att.pos_bias_u, att.pos_bias_v, lens, B, T, att.h, att.d_k, att.att_window,
+                                              att.dropout_rate if tr else 0.0, seed + 7)
+        elif att.att_window is None and fast.attention_flash_supported(T, att.d_k):
             ctx = fast.relpos_attention_flash(qkv, pl, att.pos_bias_u, att.pos_bias_v, lens, B, T, att.h, att.d_k,
                                               att.dropout_rate if tr else 0.0, seed + 7)
         else:  # head sizes the key-tiled kernel does not take (above 64, or no multiple of 4): ATen composition
             qkv = qkv.view(B, T, 3, att.h, att.d_k)
             q, k, v = (qkv[:, :, i].transpose(1, 2) for i in range(3))
             ctx = ops.rel_pos_attention(q, k, v, pl.view(-1, att.h, att.d_k).transpose(0, 1), att.pos_bias_u,
-                                        att.pos_bias_v, lens, att.dropout_rate, tr)
+                                        att.pos_bias_v, lens, att.dropout_rate, tr, window=att.att_window)
             ctx = ctx.transpose(1, 2).reshape(B * T, d).contiguous()
         G(ctx, Wt(att.linear_out.weight), att.linear_out.bias, dropout_p=p, seed=seed + 3,
                   residual=x, out_f32=x, want_bf16=False)
@@ -258,6 +279,55 @@ class ConformerEncoder(nn.Module):
         self.use_fused_blocks = True   # trainable blocks as single autograd nodes on the HIP kernels
         self.fast_seed = 0             # per-step dropout seed for the fused path (set by the model)
         self._pos_cache = {}           # T -> bf16 images of the position table slice (plain dict: not a buffer, not copied state)
+        self.self_attention_model = "rel_pos"
+        self.att_context_size = [-1, -1]
+        if cfg.self_attention_model != "rel_pos" or list(cfg.att_context_size) != [-1, -1]:
+            self.change_attention_model(cfg.self_attention_model, list(cfg.att_context_size), update_config=False)
+
+    def change_attention_model(self, self_attention_model=None, att_context_size=None, update_config=True, device=None):
+        """conformer_encoder.py:938-1060: switch between full rel-pos attention ('rel_pos') and local attention with a window of
+        att_context_size = [w, w] frames ('rel_pos_local_attn': NeMo's long-audio switch).  None keeps a setting.  The reference
+        swaps the attention and position-encoding modules and reloads their state; the two attention models share every
+        parameter, so here the same modules change mode: state_dict keys and values are untouched, and 'rel_pos' gives back the
+        full-attention arithmetic bit for bit.
+
+        Not offered (NotImplementedError): 'abs_pos'; asymmetric windows (the reference adds the position term of an L != R
+        window to the wrong columns, multi_head_attention.py:355-360, and that is not reproduced); a limited context under
+        'rel_pos'.  One rule differs: 'rel_pos' without att_context_size means [-1, -1], not the local window left behind."""
+        if self_attention_model is None and att_context_size is None:
+            return
+        if self_attention_model is None:
+            self_attention_model = self.self_attention_model
+        if att_context_size:
+            att_context_size = [int(c) for c in att_context_size]
+        else:
+            att_context_size = [-1, -1] if self_attention_model == "rel_pos" else list(self.att_context_size)
+        if self_attention_model == "rel_pos_local_attn" and max(att_context_size) <= 0:
+            raise ValueError("When using local attention, context size must be set > 0")
+        if self_attention_model == "abs_pos":
+            raise NotImplementedError("self_attention_model 'abs_pos' is not implemented: this encoder's checkpoints are rel_pos")
+        if self_attention_model not in ("rel_pos", "rel_pos_local_attn"):
+            raise ValueError(f"Not valid self_attention_model: '{self_attention_model}'!")
+        if len(att_context_size) != 2:
+            raise ValueError(f"att_context_size must be [left, right], not {att_context_size}")
+        window = None
+        if self_attention_model == "rel_pos_local_attn":
+            left, right = att_context_size
+            if left != right:
+                raise NotImplementedError(
+                    f"asymmetric att_context_size {att_context_size}: the reference's local attention adds the position term of "
+                    "an L != R window to the wrong columns (multi_head_attention.py:355-360 index the table from its start, not "
+                    "from w - L); only symmetric windows [w, w] are offered")
+            window = left
+        elif att_context_size != [-1, -1]:
+            raise NotImplementedError(f"a limited context {att_context_size} under 'rel_pos' is not implemented: use "
+                                      "'rel_pos_local_attn' with a symmetric window")
+        self.pos_enc.set_local_window(window, device)
+        for layer in self.layers:
+            layer.self_attn.att_window = window
+        self.self_attention_model, self.att_context_size = self_attention_model, att_context_size
+        if update_config:
+            self.cfg.self_attention_model, self.cfg.att_context_size = self_attention_model, list(att_context_size)
 
     def _amp(self, x):
         if self.cfg.compute_dtype == "bf16" and x.is_cuda:
@@ -348,7 +418,7 @@ class ConformerEncoder(nn.Module):
         if self.pos_enc.dropout_emb is not None and self.training:
             from .ops import block
             return pos_emb.reshape(-1, d).to(torch.bfloat16).contiguous(), block.pad_pos_emb(pos_emb, d)
-        key = (pos_emb.shape[1], self.pos_enc.pe.data_ptr(), str(pos_emb.device))
+        key = (pos_emb.shape[1], self.pos_enc.table().data_ptr(), str(pos_emb.device))
         hit = self._pos_cache.get(key)
         if hit is None:
             from .ops import block
@@ -375,7 +445,8 @@ class ConformerEncoder(nn.Module):
         # the all-reduce of the BatchNorm sums in between (ops/fast.conformer_prefix).  fp8 projections: per-op path below.
         if fast.attention_flash_supported(T, l0.self_attn.d_k) and bn_ok and same_mode and not fp8:
             # native executor: one C call enqueues the 14 kernels of every block (csrc/block_exec.hip)
-            fast.conformer_prefix(list(self.layers[:n_fast]), xr, pe, length, B, T, base, 16, l0.training)
+            fast.conformer_prefix(list(self.layers[:n_fast]), xr, pe, length, B, T, base, 16, l0.training,
+                                  att_window=l0.self_attn.att_window or 0)
             return xr.view(B, T, d), n_fast
         y = None   # (the first module of a block applies its LayerNorm itself unless the previous block chained it)
         for l in range(n_fast):

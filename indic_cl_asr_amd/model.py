@@ -169,6 +169,20 @@ class EncDecHybridRNNTCTCModel(TranscriptionMixin, nn.Module):
                 mod.dropout_rate = 0.0
         return self
 
+    def change_attention_model(self, self_attention_model: str = None, att_context_size: List[int] = None,
+                               update_config: bool = True):
+        """ASRModuleMixin.change_attention_model (A/parts/mixins/mixins.py:501-544): 'rel_pos' (full attention) or
+        'rel_pos_local_attn' with att_context_size = [w, w] -- the reference's switch for long audio
+        (tools/nemo_forced_aligner/align.py:253).  Both None: nothing changes.  Rules and refusals:
+        ConformerEncoder.change_attention_model.  transcribe() and align() follow through the encoder's forward."""
+        if self_attention_model is None and att_context_size is None:
+            return
+        self.encoder.change_attention_model(self_attention_model, att_context_size, update_config,
+                                            next(self.encoder.parameters()).device)
+        if update_config:
+            self.cfg.self_attention_model = self.encoder.self_attention_model
+            self.cfg.att_context_size = list(self.encoder.att_context_size)
+
     # ------------------------------------------------------------------ forward (rnnt_models.py:606-655)
     def forward(self, input_signal=None, input_signal_length=None, processed_signal=None,
                 processed_signal_length=None, language_ids=None):

@@ -16,19 +16,34 @@ def _rel_shift_index(T, device):
     return (T - 1 - i + j)  # [T,T] indices into the 2T-1 axis
 
 
-def rel_pos_attention(q, k, v, p, bias_u, bias_v, lens, dropout_p=0.0, training=False, keep_mask=None):
-    """q,k,v: [B,h,T,dk]; p: [h,2T-1,dk]; bias_u/bias_v: [h,dk]; lens: [B] i64 -> context [B,h,T,dk]."""
+def rel_pos_attention(q, k, v, p, bias_u, bias_v, lens, dropout_p=0.0, training=False, keep_mask=None, window=None):
+    """q,k,v: [B,h,T,dk]; p: [h,2T-1,dk]; bias_u/bias_v: [h,dk]; lens: [B] i64 -> context [B,h,T,dk].
+
+    window = w > 0: local attention (RelPositionMultiHeadAttentionLongformer, multi_head_attention.py:253-470, symmetric window
+    [w, w], no global tokens): p is [h, >= 2w+1, dk] with row r <-> relative position w - r, scores[i,j] takes p[w-i+j] and only
+    the keys |i - j| <= w, j < len_b take part.  Differentiable like the full composition; window=None is unchanged."""
+    if window is not None and window <= 0:
+        raise ValueError("When using local attention, context size must be set > 0")
     B, h, T, dk = q.shape
     scale = 1.0 / math.sqrt(dk)
     qu = q + bias_u.view(1, h, 1, dk).to(q.dtype)
     qv = q + bias_v.view(1, h, 1, dk).to(q.dtype)
     ac = torch.matmul(qu, k.transpose(-2, -1))                       # [B,h,T,T]
-    bd_full = torch.matmul(qv, p.unsqueeze(0).transpose(-2, -1))     # [B,h,T,2T-1]
-    idx = _rel_shift_index(T, q.device)
-    bd = torch.gather(bd_full, 3, idx.view(1, 1, T, T).expand(B, h, T, T))
-    scores = (ac + bd).float() * scale
     valid = torch.arange(T, device=q.device)[None, :] < lens[:, None]            # [B,T]
     mask = ~(valid[:, :, None] & valid[:, None, :])                                # [B,T,T]
+    if window is None:
+        bd_full = torch.matmul(qv, p.unsqueeze(0).transpose(-2, -1))     # [B,h,T,2T-1]
+        idx = _rel_shift_index(T, q.device)
+    else:
+        if p.shape[1] < 2 * window + 1:
+            raise ValueError(f"rel_pos_attention: {p.shape[1]} position rows < 2 * {window} + 1")
+        bd_full = torch.matmul(qv, p[:, :2 * window + 1].unsqueeze(0).transpose(-2, -1))     # [B,h,T,2w+1]
+        rel = _rel_shift_index(T, q.device) - (T - 1)                    # j - i
+        idx = (window + rel).clamp(0, 2 * window)                        # (clamped entries lie outside the band)
+        mask = mask | (rel.abs() > window).unsqueeze(0)
+    bd = torch.gather(bd_full, 3, idx.view(1, 1, T, T).expand(B, h, T, T))
+    scores = ac + bd
+    scores = (scores if scores.dtype == torch.float64 else scores.float()) * scale   # (fp64 callers: the reference checks)
     scores = scores.masked_fill(mask.unsqueeze(1), -10000.0)
     attn = torch.softmax(scores, dim=-1).masked_fill(mask.unsqueeze(1), 0.0)
     if keep_mask is not None:      # explicit dropout mask (0 or 1/(1-p)) [B,h,T,T]: the HIP kernel's, for its backward

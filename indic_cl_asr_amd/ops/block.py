@@ -81,6 +81,8 @@ DIRECT_ACCUMULATE = True
 def block_supported(layer, x2d, T):
     d = x2d.shape[-1]
     bn = layer.conv.batch_norm
+    if getattr(layer.self_attn, "att_window", None) is not None:
+        return False   # local attention has no HIP backward: the trainable blocks go through the ATen composition
     return (x2d.is_cuda and d % 8 == 0 and d <= 1024 and fast.bn_module_ok(bn)
             and layer.conv.depthwise_conv.weight.shape[-1] <= 31 and fast.attention_flash_supported(T, layer.self_attn.d_k))
 

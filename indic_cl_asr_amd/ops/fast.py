@@ -448,6 +448,24 @@ def relpos_attention_flash(qkv_bf16, pos_proj_bf16, bias_u, bias_v, lens, B, T, 
     return (ctx, lse) if want_lse else ctx
 
 
+def attention_local_supported(T, dk, window):
+    return bool(_lib.lib().ia_relpos_attention_local_supported(int(T), int(dk), int(window)))
+
+
+def relpos_attention_local(qkv_bf16, pos_proj_bf16, bias_u, bias_v, lens, B, T, H, dk, window, dropout_p=0.0, seed=0):
+    """Local rel-pos attention forward (csrc/attention_local.hip): query i attends the keys |i - j| <= window, j < len.
+    qkv [B*T, 3*H*dk] bf16, pos_proj [>= 2*window+1, H*dk] bf16 (row r <-> relative position window - r) -> ctx [B*T, H*dk] bf16.
+    Forward only (no lse): training under local attention differentiates through ops.rel_pos_attention(window=...)."""
+    if pos_proj_bf16.shape[0] < 2 * int(window) + 1:
+        raise ValueError(f"relpos_attention_local: {pos_proj_bf16.shape[0]} position rows < 2 * {window} + 1")
+    ctx = torch.empty(B * T, H * dk, dtype=torch.bfloat16, device=qkv_bf16.device)
+    st = _lib.lib().ia_relpos_attention_local(_lib.ptr(qkv_bf16), _lib.ptr(pos_proj_bf16), _lib.ptr(bias_u), _lib.ptr(bias_v),
+                                              _lib.ptr(lens), B, T, H, dk, int(window), float(dropout_p), int(seed) & 0xFFFFFFFF,
+                                              _lib.ptr(ctx), _lib.stream_ptr())
+    _lib.check(st, "ia_relpos_attention_local")
+    return ctx
+
+
 def attention_flash_bwd_dims(T):
     import ctypes
     rs, p0 = ctypes.c_int(), ctypes.c_int()
@@ -731,13 +749,15 @@ def pos_proj_cached(layer, pos_emb_bf16, max_entries=8):
     return ent
 
 
-def conformer_prefix(layers, xr, pos_emb_bf16, lens, B, T, seed_base, seed_stride, training):
-    """Run `layers` (ConformerLayer list) over the fp32 residual stream xr [B*T, d] in place with ONE native call."""
+def conformer_prefix(layers, xr, pos_emb_bf16, lens, B, T, seed_base, seed_stride, training, att_window=0):
+    """Run `layers` (ConformerLayer list) over the fp32 residual stream xr [B*T, d] in place with ONE native call.
+    att_window = w > 0: local attention [w, w] (pos_emb_bf16 is the 2w+1-row table); 0: full attention."""
     L = _lib.lib()
     arr = (_lib.BlockParams * len(layers))(*[_block_params(l) for l in layers])
     for i, l in enumerate(layers):   # frozen position projections depend on T only: one GEMM per (layer, T), not per step
-        pl = pos_proj_cached(l, pos_emb_bf16)
+        pl = pos_proj_cached(l, pos_emb_bf16)   # (keyed by the row count; 2w+1 = some 2T-1 is the same centred table slice)
         arr[i].pl_cached = pl.data_ptr() if pl is not None else None
+        arr[i].att_window = int(att_window)
     p0 = arr[0]
     n = L.ia_conformer_prefix_ws_bytes(B, T, p0.d, p0.d_ff, p0.n_heads, p0.ksz, pos_emb_bf16.shape[0])
     key = (xr.device.index, torch.cuda.current_stream(xr.device).cuda_stream)

@@ -1,5 +1,8 @@
 """Key-tiled attention kernels at the bench shape (32 x 376 frames, 4 heads of 64): forward with / without dropout, backward.
-Developer tool."""
+--window W [W ...]: the forward of full attention against local attention [W, W] (csrc/attention_local.hip) at --shape
+(default 1 x T x 8 heads of 64 for T = 751, 3001, 15001: 30 s, 2 min and 10 min of audio), outputs preallocated and the C
+entry points called directly so that the window times launches, not allocations.  Developer tool."""
+import argparse
 import os
 import sys
 
@@ -22,14 +25,59 @@ def timeit(fn, n=50):
     return a.elapsed_time(b) / n * 1e3
 
 
+def _operands(B, T, H, dk, rows, g):
+    d = H * dk
+    qkv = (torch.randn(B * T, 3 * d, generator=g) * 0.8).bfloat16().cuda()
+    pl = (torch.randn(rows, d, generator=g) * 0.8).bfloat16().cuda()
+    bu = (torch.randn(H, dk, generator=g) * 0.3).cuda(); bv = (torch.randn(H, dk, generator=g) * 0.3).cuda()
+    return qkv, pl, bu, bv
+
+
+def bench_window(shapes, windows, n):
+    """Full against local forward.  The full kernel's table is built here for the T at hand (2T-1 rows): nothing depends on a
+    model's pos_emb_max_len.  The local table is the centre 2w+1 rows of the same one, so a window >= T-1 computes the same."""
+    from indic_cl_asr_amd import _lib
+    L, P = _lib.lib(), _lib.ptr
+    for B, T, H, dk in shapes:
+        g = torch.Generator().manual_seed(0)
+        qkv, pl, bu, bv = _operands(B, T, H, dk, 2 * T - 1, g)
+        lens = torch.full((B,), T, dtype=torch.int64).cuda()
+        ctx = torch.empty(B * T, H * dk, dtype=torch.bfloat16, device="cuda")
+        st = _lib.stream_ptr()
+
+        def full():
+            _lib.check(L.ia_relpos_attention_flash(P(qkv), P(pl), P(bu), P(bv), P(lens), B, T, H, dk, 0.0, 0, P(ctx), st), "full")
+
+        t_full = timeit(full, n)
+        nqt = (T + 63) // 64
+        print(f"B {B} T {T} H {H} dk {dk}: full {t_full:9.1f} us  ({B * H * nqt} workgroups x {nqt} key tiles)", flush=True)
+        for w in windows:
+            wc = min(w, T - 1)
+            plw = pl[T - 1 - wc: T + wc].contiguous()
+
+            def local():
+                _lib.check(L.ia_relpos_attention_local(P(qkv), P(plw), P(bu), P(bv), P(lens), B, T, H, dk, wc, 0.0, 0, P(ctx), st),
+                           "local")
+
+            t_loc = timeit(local, n)
+            print(f"    local [{w},{w}] {t_loc:9.1f} us   full / local = {t_full / t_loc:5.2f}   "
+                  f"(<= {1 + 2 * ((wc + 63) // 64)} key tiles per workgroup)", flush=True)
+
+
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--window", type=int, nargs="+", default=None, help="time full against local attention [W, W] (forward)")
+    ap.add_argument("--shape", type=int, nargs=4, action="append", metavar=("B", "T", "H", "DK"), default=None)
+    ap.add_argument("--iters", type=int, default=200)
+    args = ap.parse_args()
+    if args.window:
+        bench_window(args.shape or [(1, 751, 8, 64), (1, 3001, 8, 64), (1, 15001, 8, 64)], args.window, args.iters)
+        return
     from indic_cl_asr_amd.ops import fast
     B, T, H, dk = 32, 376, 4, 64
     d = H * dk
     g = torch.Generator().manual_seed(0)
-    qkv = (torch.randn(B * T, 3 * d, generator=g) * 0.8).bfloat16().cuda()
-    pl = (torch.randn(2 * T - 1, d, generator=g) * 0.8).bfloat16().cuda()
-    bu = (torch.randn(H, dk, generator=g) * 0.3).cuda(); bv = (torch.randn(H, dk, generator=g) * 0.3).cuda()
+    qkv, pl, bu, bv = _operands(B, T, H, dk, 2 * T - 1, g)
     lens = torch.round(T * (0.6 + 0.4 * torch.rand(B, generator=g))).long(); lens[0] = T
     lens = lens.cuda()
     dctx = torch.randn(B * T, d, device="cuda").bfloat16()
