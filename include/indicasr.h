@@ -409,11 +409,15 @@ int ia_relpos_attention_flash_lse(const void* qkv, const void* pos_proj, const f
  * at most 1 + 2 ceil(window / 64) key tiles whatever T is.  Operands, layouts, lens semantics, alignment checks and the dropout
  * hash are ia_relpos_attention_flash's, except pos_proj [>= 2 window + 1, H*dk] bf16, row r <-> relative position window - r
  * (a window >= T-1 computes full attention: same bits as ia_relpos_attention_flash on the matching table).  window >= 1
- * (IA_INVALID_VALUE otherwise), dk as the full kernel (IA_UNSUPPORTED otherwise).  Forward only: no lse, no backward. */
+ * (IA_INVALID_VALUE otherwise), dk as the full kernel (IA_UNSUPPORTED otherwise).  ia_relpos_attention_local_lse also returns
+ * lse [B*H, T] f32 as ia_relpos_attention_flash_lse defines it (NULL: skipped; ctx has the same bits either way). */
 int ia_relpos_attention_local_supported(int T, int dk, int window);
 int ia_relpos_attention_local(const void* qkv, const void* pos_proj, const float* bias_u, const float* bias_v,
                               const int64_t* lens, int B, int T, int H, int dk, int window, float dropout_p, unsigned seed,
                               void* ctx, ia_stream_t stream);
+int ia_relpos_attention_local_lse(const void* qkv, const void* pos_proj, const float* bias_u, const float* bias_v,
+                                  const int64_t* lens, int B, int T, int H, int dk, int window, float dropout_p, unsigned seed,
+                                  void* ctx, float* lse, ia_stream_t stream);
 /* Key-tiled backward of the same attention core (csrc/attention_flash_bwd.hip; autograd of multi_head_attention.py:197-250):
  * no [T,T] matrices in HBM.  In: the forward's qkv / pos_proj / biases / lens / ctx / lse, dctx [B*T, d] bf16 and the
  * forward's dropout p / seed.  Out: dqkv [B*T, 3d] bf16 (every row written), dpl [pl_rows, d] bf16 (rows >= 2T-1 zero),
@@ -426,6 +430,19 @@ int ia_relpos_attention_flash_bwd(const void* qkv, const void* pos_proj, const f
                                   const int64_t* lens, const void* ctx, const void* dctx, const float* lse, int B, int T, int H,
                                   int dk, float dropout_p, unsigned seed, void* dqkv, void* dpl, int pl_rows, float* dbias_u,
                                   float* dbias_v, void* dBand, void* QvHM, float* ws, ia_stream_t stream);
+/* Backward of ia_relpos_attention_local_lse (csrc/attention_local_bwd.hip): the same two kernels restricted to the band, each
+ * walking only the tiles the window reaches -- time and memory O(T window).  Arguments, outputs, return codes and alignment
+ * checks are ia_relpos_attention_flash_bwd's, plus `window` (>= 1) and with pos_proj / dpl [pl_rows >= 2 window + 1, d]: dpl rows
+ * 0 .. 2 window hold the gradient of the table rows a key can reach (with w' = min(window, T-1): rows window - w' .. window + w'),
+ * every other row is zero.  dBand [H, B*T, Rs] bf16 with ia_relpos_attention_local_bwd_dims' Rs = ceil8(pad0 + 2 w' + 1): no term
+ * in T.  QvHM [H, B*T, 64] bf16; ws: ia_relpos_attention_local_bwd_ws_elems f32 elements (0 for invalid arguments), linear in T.
+ * A window >= T-1 gives ia_relpos_attention_flash_bwd's dqkv / dbias bits.  No atomics: results reproduce bit for bit. */
+int ia_relpos_attention_local_bwd_dims(int T, int window, int* Rs, int* pad0);
+int64_t ia_relpos_attention_local_bwd_ws_elems(int B, int T, int H, int dk, int window);
+int ia_relpos_attention_local_bwd(const void* qkv, const void* pos_proj, const float* bias_u, const float* bias_v,
+                                  const int64_t* lens, const void* ctx, const void* dctx, const float* lse, int B, int T, int H,
+                                  int dk, int window, float dropout_p, unsigned seed, void* dqkv, void* dpl, int pl_rows,
+                                  float* dbias_u, float* dbias_v, void* dBand, void* QvHM, float* ws, ia_stream_t stream);
 /* Round-1 forward of the same core (csrc/attention.hip: all keys of a 16-query strip in registers), kept only as the
  * independent implementation the tests compare against; no product path calls it.  Operands as above, pos_proj [2T-1, H*dk];
  * vt_scratch: ia_attn_vt_elems(B,T,H) bf16 elements, caller-owned (holds V^T, filled by this call).  Its own dropout mask

@@ -87,6 +87,11 @@ SIGNATURES = {
     "ia_relpos_attention_flash_bwd_ws_elems": (_i64, [_i, _i, _i, _i]),
     "ia_relpos_attention_flash_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _c.c_uint, _vp, _vp, _i, _vp,
                                            _vp, _vp, _vp, _vp, _vp]),
+    "ia_relpos_attention_local_lse": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _c.c_uint, _vp, _vp, _vp]),
+    "ia_relpos_attention_local_bwd_dims": (_i, [_i, _i, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
+    "ia_relpos_attention_local_bwd_ws_elems": (_i64, [_i, _i, _i, _i, _i]),
+    "ia_relpos_attention_local_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _c.c_uint, _vp, _vp, _i, _vp,
+                                           _vp, _vp, _vp, _vp, _vp]),
     "ia_quantize_fp8_rows": (_i, [_vp, _i, _i, _i64, _i, _vp, _i, _vp, _vp]),
     "ia_gemm_fp8": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _i, _f, _c.c_uint, _f, _vp, _i, _vp, _i, _vp, _i, _vp]),
     "ia_gemm_tn_grouped_scratch_elems": (_i64, [_vp, _i]),

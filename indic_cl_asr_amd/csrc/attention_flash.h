@@ -1,8 +1,10 @@
 // The one vocabulary of the key-tiled rel-pos attention kernels (attention_flash.hip forward, attention_local.hip windowed
-// forward, attention_flash_bwd.hip query-owner and key-owner backward): fragment types, tile constants, the attention-dropout hash (the backward regenerates the forward's
-// mask), the zero-padding head-row loader, the swizzled LDS addresses and fragment reads, register staging of a tile (fetch /
-// commit), the K | V | P stage, the query fragments, the band block, the workgroup coordinates, the guarded head-row store and
-// the host's launch of a <DK64> pair.  tests/test_attention_flash_digests_gpu.py pins the bits of everything built from it.
+// forward, attention_flash_bwd.hip and attention_local_bwd.hip query-owner and key-owner backward): fragment types, tile
+// constants, the attention-dropout hash (the backward regenerates the forward's mask), the zero-padding head-row loader, the
+// swizzled LDS addresses and fragment reads, register staging of a tile (fetch / commit), the K | V | P stage (full and local),
+// the query fragments, the band block, the workgroup coordinates, the guarded head-row store, the backwards' strip geometry,
+// workspace layout and position-gradient step, and the host's launch of a <DK64> pair.
+// tests/test_attention_flash_digests_gpu.py pins the bits of everything the full-attention kernels build from it.
 #pragma once
 #include <hip/hip_bf16.h>
 
@@ -111,6 +113,31 @@ struct FaKvpStage {
     }
 };
 
+// FaKvpStage with a local window's position rows (attention_local.hip, attention_local_bwd.hip): key tile t, rows clamped to
+// T - 1, and the 128 position rows w - I0 - 63 + 64 t .. + 127 clamped to [0, 2w]
+template <bool DK64>
+struct FlKvpStage {
+    uint4 rk[2], rv[2], rp[4];
+    const __bf16 *kbase, *vbase, *pbase;
+    unsigned char* smem;
+    int T, d, dk, I0, w, tid;
+    __device__ __forceinline__ FlKvpStage(const __bf16* qkv, const __bf16* pl, unsigned char* smem_, int b, int h, int T_, int d_,
+                                          int dk_, int I0_, int w_, int tid_)
+        : kbase(qkv + (size_t)b * T_ * (3 * d_) + d_ + h * dk_), vbase(kbase + d_), pbase(pl + h * dk_), smem(smem_), T(T_), d(d_),
+          dk(dk_), I0(I0_), w(w_), tid(tid_) {}
+    __device__ __forceinline__ void fetch(int t) {
+        const int j0 = t * 64;
+        fa_fetch_rows<DK64, false>(rk, kbase, 3 * d, j0, T - 1, dk, tid);
+        fa_fetch_rows<DK64, false>(rv, vbase, 3 * d, j0, T - 1, dk, tid);
+        fa_fetch_rows<DK64, true>(rp, pbase, d, w - I0 - 63 + j0, 2 * w, dk, tid);
+    }
+    __device__ __forceinline__ void commit() {
+        fa_commit_rows(smem, rk, tid);
+        fa_commit_rows(smem + FA_T64, rv, tid);
+        fa_commit_rows(smem + 2 * FA_T64, rp, tid);
+    }
+};
+
 // k-step ks of the B fragments (q+u)^T and (q+v)^T of the lane's query row `qrow` (head h's slice): lane (query c, q4) holds dk
 // elements 32 ks + 8 q4 .. + 7
 template <bool DK64>
@@ -172,6 +199,84 @@ __device__ __forceinline__ void fa_store_head4(__bf16* row, int mt, int q4, int 
         for (int r = 0; r < 4; ++r) o.e[r] = (__bf16)(x[r] * scale);
         *reinterpret_cast<uint2*>(row + mt * 16 + q4 * 4) = o.u;
     }
+}
+
+// ---- shared by the two backwards (attention_flash_bwd.hip, attention_local_bwd.hip): strip geometry, the strip fence, the
+// workspace layout and the position-gradient step
+constexpr int FB_SB_LD = 120;                 // dS band strip: columns [0,96) band rows of this tile, [96,112) carry
+constexpr int FB_Q_STRIP = 16 * (FA_SR_LD + FB_SB_LD) * 2;           // per wave: 7168 B
+constexpr int FB_Q_LDS = 2 * FA_T64 + FA_PBUF + 4 * FB_Q_STRIP;      // K | V | P | strips = 61 440 B
+constexpr int FB_S3_LD = 72;                  // key-major band strip: [16 keys][64 queries (+8 pad)]
+constexpr int FB_KV_STAGE = 3 * FA_T64 + FA_PBUF + 512;              // Qu | Qv | dO | P | lse[64] D[64]
+constexpr int FB_KV_LDS = FB_KV_STAGE + 4 * 16 * FB_S3_LD * 2;       // 50 688 B
+
+__device__ __forceinline__ void fb_lds_fence() {   // order this wave's LDS accesses across differently typed views of a strip
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// dpl[r][h*dk + e] = bf16(dpos[h][pad0 + r][e]) for r < R, zero rows beyond (dpos rows are [Rs*64 | Rs] f32 blocks: the TN GEMM's
+// weight and bias gradient outputs, the latter unused)
+__global__ __launch_bounds__(256) void fb_dpos_pack_kernel(const float* __restrict__ dpos, int H, int Rs, int pad0, int R, int dk,
+                                                           int rows, __bf16* __restrict__ out) {
+    const int d = H * dk, q = dk / 4;
+    const int64_t total = (int64_t)rows * H * q;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int e4 = (int)(i % q);
+        const int h = (int)((i / q) % H);
+        const int r = (int)(i / ((int64_t)q * H));
+        union { uint2 u; __bf16 e[4]; } o;
+        o.u = make_uint2(0, 0);
+        if (r < R) {
+            const float4 v = *reinterpret_cast<const float4*>(dpos + (size_t)h * ((size_t)Rs * 64 + Rs) + (size_t)(pad0 + r) * 64 + e4 * 4);
+            o.e[0] = (__bf16)v.x; o.e[1] = (__bf16)v.y; o.e[2] = (__bf16)v.z; o.e[3] = (__bf16)v.w;
+        }
+        *reinterpret_cast<uint2*>(out + (size_t)r * d + h * dk + e4 * 4) = o.u;
+    }
+}
+
+// host: the backward's f32 workspace  part | D | dpos | tn  (element offsets) for a dBand row stride rs
+struct FbWs { int64_t part, D, dpos, tn, total; };
+inline FbWs fb_ws_layout(int B, int T, int H, int dk, int rs) {
+    FbWs w;
+    auto up = [](int64_t x) { return (x + 63) / 64 * 64; };
+    w.part = 0;
+    w.D = up((int64_t)B * ((T + 63) / 64) * 2 * H * dk);
+    w.dpos = w.D + up((int64_t)B * H * T);
+    w.tn = w.dpos + up((int64_t)H * ((int64_t)rs * 64 + rs));
+    {
+        ia_tn_problem pr[8];
+        const int nh = H < 8 ? H : 8;
+        for (int i = 0; i < nh; ++i) pr[i] = ia_tn_problem{nullptr, nullptr, nullptr, nullptr, rs, 64, B * T, rs, 64};
+        w.total = w.tn + up(ia_gemm_tn_grouped_scratch_elems(pr, nh));
+    }
+    return w;
+}
+
+// host: position-projection gradient: per head dpos_h [rs, 64] = dBand_h^T (q+v)_h over the B*T rows (split-K TN GEMM), then the
+// band columns pad0 .. pad0 + R - 1 go to rows 0 .. R - 1 of out [rows, d] bf16, zero rows behind them
+inline int fb_dpos_gemm_pack(const void* dBand, const void* QvHM, float* ws, const FbWs& w, int rs, int p0, int R, int B, int T, int H,
+                             int dk, void* out, int rows, ia_stream_t stream) {
+    float* dpos = ws + w.dpos;
+    for (int h0 = 0; h0 < H; h0 += 8) {   // the heads' TN GEMMs as grouped launches (one GEMM + one finishing pass per <= 8 heads)
+        ia_tn_problem pr[8];
+        const int nh = H - h0 < 8 ? H - h0 : 8;
+        for (int i = 0; i < nh; ++i) {
+            const int h = h0 + i;
+            float* o = dpos + (size_t)h * ((size_t)rs * 64 + rs);
+            pr[i] = ia_tn_problem{(const __bf16*)dBand + (size_t)h * B * T * rs, (const __bf16*)QvHM + (size_t)h * B * T * 64, o, nullptr,
+                                  rs, 64, B * T, rs, 64};
+        }
+        const int rc = ia_gemm_tn_bf16_grouped(pr, nh, ws + w.tn, stream);
+        if (rc != IA_OK) return rc;
+    }
+    const int64_t items = (int64_t)rows * H * (dk / 4);
+    const int64_t blocks = (items + 255) / 256;
+    hipLaunchKernelGGL(fb_dpos_pack_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)dpos, H, rs, p0, R, dk, rows, (__bf16*)out);
+    IA_RETURN_IF_LAUNCH_FAILED();
+    return IA_OK;
 }
 
 // host: raise the kernel's LDS limit once, launch it on FA_THREADS threads, IA_LAUNCH_FAILED if either fails

@@ -18,7 +18,8 @@
 //     running and new maximum are then both -inf, so the exponentials are taken against 0 instead (exp2(-inf) = 0, no NaN);
 //   - the mask-free score branch is per wave: the tile lies inside the window of each of the wave's 16 queries and below len.
 // The host reduces a window beyond T - 1 to T - 1 by advancing the table pointer (row r of the 2w+1 table is row
-// r - (w - w') of the 2w'+1 one), so the kernel's index arithmetic never sees a window larger than T.  No lse: no backward.
+// r - (w - w') of the 2w'+1 one), so the kernel's index arithmetic never sees a window larger than T.  The optional lse is the
+// full kernel's (natural-log log-sum-exp per query, 0 for padded queries): attention_local_bwd.hip recomputes P = exp(s - lse).
 #include "attention_flash.h"
 
 namespace {
@@ -31,31 +32,7 @@ constexpr int FL_LDS = FL_STAGE + 4 * FL_SR_BYTES;     // 46 080 B: three workgr
 struct FlArgs {
     const __bf16* qkv; const __bf16* pl; const float* bias_u; const float* bias_v; const int64_t* lens;
     __bf16* ctx; int B, T, H, dk, w; float scale; unsigned seed, thr; float keep_scale;
-};
-
-// FaKvpStage with the window's position rows: key tile t, rows clamped to T - 1, and the 128 position rows
-// w - I0 - 63 + 64 t .. + 127 clamped to [0, 2w]
-template <bool DK64>
-struct FlKvpStage {
-    uint4 rk[2], rv[2], rp[4];
-    const __bf16 *kbase, *vbase, *pbase;
-    unsigned char* smem;
-    int T, d, dk, I0, w, tid;
-    __device__ __forceinline__ FlKvpStage(const __bf16* qkv, const __bf16* pl, unsigned char* smem_, int b, int h, int T_, int d_,
-                                          int dk_, int I0_, int w_, int tid_)
-        : kbase(qkv + (size_t)b * T_ * (3 * d_) + d_ + h * dk_), vbase(kbase + d_), pbase(pl + h * dk_), smem(smem_), T(T_), d(d_),
-          dk(dk_), I0(I0_), w(w_), tid(tid_) {}
-    __device__ __forceinline__ void fetch(int t) {
-        const int j0 = t * 64;
-        fa_fetch_rows<DK64, false>(rk, kbase, 3 * d, j0, T - 1, dk, tid);
-        fa_fetch_rows<DK64, false>(rv, vbase, 3 * d, j0, T - 1, dk, tid);
-        fa_fetch_rows<DK64, true>(rp, pbase, d, w - I0 - 63 + j0, 2 * w, dk, tid);
-    }
-    __device__ __forceinline__ void commit() {
-        fa_commit_rows(smem, rk, tid);
-        fa_commit_rows(smem + FA_T64, rv, tid);
-        fa_commit_rows(smem + 2 * FA_T64, rp, tid);
-    }
+    float* lse;   // optional [B*H, T], as relpos_flash_fwd_kernel writes it
 };
 
 template <bool DK64>
@@ -72,8 +49,10 @@ __global__ __launch_bounds__(FA_THREADS, 3) void relpos_local_fwd_kernel(FlArgs 
     const int iq = iw + c;                               // this lane's query
     __bf16* orow = a.ctx + ((size_t)b * T + (iq < T ? iq : T - 1)) * d + h * dk;
     if (I0 >= len) {                                     // workgroup-uniform: only padded queries -> zero context
-        if (iq < T)
+        if (iq < T) {
             for (int mt = 0; mt < 4; ++mt) fa_store_head4(orow, mt, q4, dk, (f4){0.f, 0.f, 0.f, 0.f});
+            if (a.lse && q4 == 0) a.lse[(size_t)bh * T + iq] = 0.f;
+        }
         return;
     }
     unsigned char* sR = smem + FL_STAGE + wave * FL_SR_BYTES;
@@ -194,6 +173,7 @@ __global__ __launch_bounds__(FA_THREADS, 3) void relpos_local_fwd_kernel(FlArgs 
     l_run += __shfl_xor(l_run, 16, 64);
     l_run += __shfl_xor(l_run, 32, 64);
     if (iq < T) {
+        if (a.lse && q4 == 0) a.lse[(size_t)bh * T + iq] = (iq < len && l_run > 0.f) ? (m_run + __builtin_amdgcn_logf(l_run)) * 0.69314718055994531f : 0.f;
         const float inv = (iq < len && l_run > 0.f) ? a.keep_scale / l_run : 0.f;
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
@@ -213,6 +193,12 @@ extern "C" int ia_relpos_attention_local_supported(int T, int dk, int window) {
 extern "C" int ia_relpos_attention_local(const void* qkv, const void* pos_proj, const float* bias_u, const float* bias_v,
                                          const int64_t* lens, int B, int T, int H, int dk, int window, float dropout_p,
                                          unsigned seed, void* ctx, ia_stream_t stream) {
+    return ia_relpos_attention_local_lse(qkv, pos_proj, bias_u, bias_v, lens, B, T, H, dk, window, dropout_p, seed, ctx, nullptr, stream);
+}
+
+extern "C" int ia_relpos_attention_local_lse(const void* qkv, const void* pos_proj, const float* bias_u, const float* bias_v,
+                                             const int64_t* lens, int B, int T, int H, int dk, int window, float dropout_p,
+                                             unsigned seed, void* ctx, float* lse, ia_stream_t stream) {
     if (!qkv || !pos_proj || !bias_u || !bias_v || !lens || !ctx || B <= 0 || T <= 0 || H <= 0 || window <= 0) return IA_INVALID_VALUE;
     if (!ia_relpos_attention_local_supported(T, dk, window)) return IA_UNSUPPORTED;
     if (dropout_p < 0.f || dropout_p >= 1.f) return IA_INVALID_VALUE;
@@ -221,7 +207,7 @@ extern "C" int ia_relpos_attention_local(const void* qkv, const void* pos_proj, 
     const int w = window < T - 1 ? window : T - 1;
     FlArgs a;
     a.qkv = (const __bf16*)qkv; a.pl = (const __bf16*)pos_proj + (size_t)(window - w) * ((size_t)H * dk);
-    a.bias_u = bias_u; a.bias_v = bias_v; a.lens = lens;
+    a.bias_u = bias_u; a.bias_v = bias_v; a.lens = lens; a.lse = lse;
     a.ctx = (__bf16*)ctx; a.B = B; a.T = T; a.H = H; a.dk = dk; a.w = w; a.scale = 1.f / sqrtf((float)dk); a.seed = seed;
     const ia_dropout_t drop = ia_dropout_rule(dropout_p);
     a.thr = drop.thr; a.keep_scale = drop.keep_scale;

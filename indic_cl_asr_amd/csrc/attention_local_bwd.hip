@@ -1,51 +1,48 @@
-// Relative-position multi-head self-attention BACKWARD, key-tiled (gfx950): no [T,T] probability / score-gradient
-// matrices in HBM, any T, head dim any multiple of 4 up to 64.  Autograd of RelPositionMultiHeadAttention.forward
-// (A/parts/submodules/multi_head_attention.py:197-250) with the forward of attention_flash.hip (same dropout hash, the
-// forward's per-query log-sum-exp):
+// Local (windowed) relative-position multi-head self-attention BACKWARD (gfx950): the key-tiled pair of
+// attention_flash_bwd.hip restricted to the band |i - j| <= w, with the forward of attention_local.hip (same tile ranges, same
+// dropout hash, the forward's per-query log-sum-exp).  Work, memory and the dBand scratch are O(T w), not O(T^2).
 //
-//   s_ij = ((q_i+u).k_j + (q_i+v).p[T-1-i+j]) / sqrt(dk),  P = exp(s - lse_i) (j < len, i < len),  Pd = dropout(P)
+//   s_ij = ((q_i+u).k_j + (q_i+v).p[w-i+j]) / sqrt(dk),  admissible iff |i-j| <= w, j < len, i < len
+//   P = exp(s - lse_i) on admissible pairs, else 0 (by value: a clamped position row gives a finite score that means nothing)
 //   dP = keep o (dO V^T),  D_i = dO_i . O_i,  dS = P o (dP - D) / sqrt(dk)
-//   d(q+u) = dS K     d(q+v)_i = sum_j dS_ij p[T-1-i+j]     dK = dS^T (q+u)     dV = Pd^T dO
-//   dp[r] = sum_{b,i} dS_{i, r-(T-1)+i} (q_i+v)      dq = d(q+u) + d(q+v)     du = sum d(q+u)    dv = sum d(q+v)
+//   d(q+u) = dS K     d(q+v)_i = sum_j dS_ij p[w-i+j]     dK = dS^T (q+u)     dV = Pd^T dO
+//   dp[r] = sum_{b,i} dS_{i, i+r-w} (q_i+v), r in [0, 2w]     dq = d(q+u) + d(q+v)     du = sum d(q+u)    dv = sum d(q+v)
 //
-// Two kernels, each owning its outputs exclusively (no atomics, bit-reproducible):
-//   relpos_flash_bwd_q_kernel   workgroup = (utterance, head, 64 queries), 4 waves x 16 queries, walks the key tiles like
-//       the forward (transposed accumulators: lane = query).  Recomputes R^T, S^T, P; dP^T = V dO^T; dS.  dS is the B
-//       operand of d(q+u)^T += K^T dS^T as it lies in the accumulators, and goes through a wave-private band strip
-//       [query][band row] for d(q+v)^T += P_band^T dS_band^T (band row rr = j - j0 + 15 - il: the inverse of the forward's
-//       skew).  The same strip, tile by tile, is the band-skewed dS on the absolute relative-position axis
-//       dBand[h][b*T+i][pad0 + T-1-i+j] that the position-projection gradient dp = dBand^T (q+v) contracts as a plain
-//       TN GEMM (csrc/gemm_tn.hip) -- the one [T, 2T] matrix that still goes through HBM.
-//   relpos_flash_bwd_kv_kernel  workgroup = (utterance, head, 64 keys), 4 waves x 16 keys (lane = key), walks the query
-//       tiles.  S = (Q+u) K^T and the band (q+v) p^T in the key-major orientation (two 16x16 position tiles per 16
-//       queries, re-indexed through a wave-private strip), P, dP, then dV^T += dO^T Pd and dK^T += (Q+u)^T dS with the
-//       probabilities / score gradients used as B operands straight from the accumulators and the A operands read from
-//       the row-major query tiles with ds_read_b64_tr_b16.
-// LDS tiles: 128-byte rows (64 bf16, zero-padded beyond dk), 16-byte slots XOR-swizzled by row & 7, one stage + register
-// prefetch of the next tile (two workgroups per CU hide the two barriers per tile).  Tile constants, the swizzled addresses and
-// fragment reads, the register staging (the query-owner uses the forward's K | V | P stage as it is, the key-owner builds its
-// Qu | Qv | dO | P | lse, D stage from the same fetch / commit pair), the band block, the query fragments, the workgroup
-// coordinates and the head-row store are attention_flash.h's, shared with the forward; tests/test_attention_flash_digests_gpu.py
-// pins dqkv, dpl and the bias gradients bit for bit.
+// Two kernels, each owning its outputs exclusively (no atomics, bit-reproducible), in attention_flash.h's vocabulary; per tile
+// they are the full backward's kernels operation for operation, so a window >= T - 1 gives the full backward's dqkv / du / dv bits:
+//   relpos_local_bwd_q_kernel   workgroup = (utterance, head, 64 queries).  Walks the key tiles t_lo .. t_hi of the local forward
+//       (FlKvpStage: position rows w - I0 - 63 + 64 t .. + 127 clamped to [0, 2w]).  Writes dq, D, the head-major (q+v) copy, the
+//       bias partials and the band-skewed dS strip  dBand[h][b*T+i][pad0 + (w-i+j)].  Strip column s of (wave iw, tile j0) is
+//       the relative position w - iw - 15 + j0 + s on an UNCLAMPED axis: consecutive tiles continue each other's columns (64 per
+//       tile, the last 16 carried into the next tile's flush, as in the full kernel), so every dBand element of a query row has
+//       one writer.  Columns of that axis outside [0, 2w] belong to inadmissible pairs -- exact zeros -- and the flush drops the
+//       16-byte chunks that fall outside the row [0, Rs): Rs = ceil8(pad0 + 2w + 1) whatever T is, pad0 = -(w + 1) mod 8 keeps every
+//       chunk 16-byte aligned.  Nothing is written outside a row; what is not written is the memset's zero.
+//   relpos_local_bwd_kv_kernel  workgroup = (utterance, head, 64 keys).  Walks only the query tiles that hold a query of
+//       [J0 - w, J0 + 63 + w] and below len; position rows w - i0 - 63 + J0 .. + 127 clamped to [0, 2w].  Writes dK, dV (zero rows
+//       for keys >= len).
+// Position gradient: per head one TN GEMM dBand_h^T (q+v)_h over the B*T rows (fb_dpos_gemm_pack), Rs rows instead of the full
+// backward's ~2T; rows pad0 .. pad0 + 2w go to dpl.  The host reduces a window beyond T - 1 to w' = T - 1 as the forward does
+// (table pointer and dpl rows advanced by window - w').  LDS: the full backward's 61 440 B / 50 688 B, two workgroups per CU.
 #include "attention_flash.h"
 #include "partials.h"
 
 namespace {
 
-struct FbArgs {
+struct FlbArgs {
     const __bf16* qkv; const __bf16* pl; const float* bias_u; const float* bias_v; const int64_t* lens;
     const __bf16* ctx; const __bf16* dctx; const float* lse;
     __bf16* dqkv; __bf16* dBand; __bf16* QvHM; float* D; float* part;
-    int B, T, H, dk, Rs, pad0; float scale; unsigned seed, thr; float keep_scale;
+    int B, T, H, dk, w, Rs, pad0; float scale; unsigned seed, thr; float keep_scale;   // 0 <= w <= T - 1
 };
 
 // ======================================================================================================== query-owner
 template <bool DK64>
-__global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArgs a) {
+__global__ __launch_bounds__(FA_THREADS, 2) void relpos_local_bwd_q_kernel(FlbArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 15, q4 = lane >> 4;
-    const int T = a.T, H = a.H, dk = a.dk, d = H * dk, B = a.B;
+    const int T = a.T, H = a.H, dk = a.dk, d = H * dk, B = a.B, w = a.w;
     const int nqt = (T + 63) / 64;
     const FaWg wg = fa_wg(B, T, H, a.lens);
     if (wg.len < 0) return;
@@ -94,10 +91,15 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArg
     unsigned char* sB = sR + 16 * FA_SR_LD * 2;                               // dS band strip      [16][120] bf16
     for (int i = lane; i < 16 * FB_SB_LD * 2 / 16; i += 64) reinterpret_cast<uint4*>(sB)[i] = make_uint4(0, 0, 0, 0);
 
-    FaKvpStage<DK64> stage(a.qkv, a.pl, smem, b, h, T, d, dk, I0, tid);
+    FlKvpStage<DK64> stage(a.qkv, a.pl, smem, b, h, T, d, dk, I0, w, tid);
 
-    const int nkt = (len + 63) / 64;
-    stage.fetch(0);
+    // key tiles of this query tile, as the local forward walks them: those that hold a key of
+    // [max(I0 - w, 0), min(I0 + 63 + w, len - 1)] (I0 < len here: both ends non-negative, the first <= the second)
+    const int jlo = I0 - w > 0 ? I0 - w : 0;
+    const int jhi = I0 + 63 + w < len - 1 ? I0 + 63 + w : len - 1;
+    const int t_lo = jlo / 64, t_hi = jhi / 64;
+    const int kmin = iq - w, kmax = iq + w < len - 1 ? iq + w : len - 1;   // this query's admissible keys
+    stage.fetch(t_lo);
     stage.commit();
     __syncthreads();
 
@@ -110,8 +112,8 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArg
     const bool fvalid = iw + frow < T;
     const int pw0 = (3 - wave) * 16;   // first staged position row of this wave's band
 
-    for (int t = 0; t < nkt; ++t) {
-        if (t + 1 < nkt) stage.fetch(t + 1);
+    for (int t = t_lo; t <= t_hi; ++t) {
+        if (t < t_hi) stage.fetch(t + 1);
         const int j0 = t * 64;
         // ---- R^T (band) -> forward strip
         fa_band_to_strip(sP, sR, pw0, Qv, c, q4);
@@ -141,7 +143,8 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArg
             for (int r = 0; r < 4; ++r) {
                 const int j = j0 + jt * 16 + q4 * 4 + r;
                 const float s = (S[jt][r] + (float)bd.e[r]) * a.scale;
-                const float p = (qvalid && j < len) ? __expf(s - lse_i) : 0.f;
+                // outside the band or the length P is 0 by value, not by exp(-inf - lse)
+                const float p = (qvalid && j >= kmin && j <= kmax) ? __expf(s - lse_i) : 0.f;
                 float g = dP[jt][r];
                 if (a.thr > 0) g = (((rnd4 >> (8 * r)) & 0xFFu) >= a.thr) ? g * a.keep_scale : 0.f;
                 const float ds = p * (g - Drow) * a.scale;
@@ -180,7 +183,8 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArg
             for (int mt = 0; mt < 4; ++mt) {
                 const int qq = c >> 2, p = c & 3;
                 int rowA = pw0 + kk * 32 + q4 * 8 + qq, rowB = rowA + 4;
-                rowA = rowA < 127 ? rowA : 127; rowB = rowB < 127 ? rowB : 127;   // band rows >= 79 are zero in the strip
+                // band rows >= 79 are zero in the strip; so are the band rows of clamped position rows (keys outside the window)
+                rowA = rowA < 127 ? rowA : 127; rowB = rowB < 127 ? rowB : 127;
                 const bf8 pf = fa_tr_pair(sP, rowA, rowB, mt * 2 + (p >> 1), p & 1);
                 dQv[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, bfrag, dQv[mt], 0, 0, 0);
             }
@@ -200,14 +204,15 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArg
                 *reinterpret_cast<uint4*>(sB + (frow * FB_SB_LD + 104) * 2) = n1;
             }
             if (fvalid) {
-                // multiple of 8; negative only in a partial last wave (T - iw < 16), whose leading band columns are all zero
-                const int gcol = T - 16 - iw + j0 + a.pad0 + fch * 8;
-                if (gcol >= 0) *reinterpret_cast<uint4*>(brow + gcol) = v0;
-                if (gcol + 8 >= 0) *reinterpret_cast<uint4*>(brow + gcol + 8) = v1;
+                // gcol and Rs are multiples of 8: a 16-byte chunk lies inside the row [0, Rs) or outside it, and outside
+                // [pad0, pad0 + 2w] every value is a masked pair's zero
+                const int gcol = w - 15 - iw + j0 + a.pad0 + fch * 8;
+                if (gcol >= 0 && gcol + 8 <= a.Rs) *reinterpret_cast<uint4*>(brow + gcol) = v0;
+                if (gcol + 8 >= 0 && gcol + 16 <= a.Rs) *reinterpret_cast<uint4*>(brow + gcol + 8) = v1;
             }
         }
         __syncthreads();
-        if (t + 1 < nkt) {
+        if (t < t_hi) {
             stage.commit();
             __syncthreads();
         }
@@ -215,9 +220,11 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArg
     // ---- last carry -> dBand columns 64 .. 79 behind the last processed tile
     fb_lds_fence();
     if ((lane & 3) == 0 && fvalid) {
-        const int gcol = T - 16 - iw + (nkt - 1) * 64 + a.pad0 + 64;
-        *reinterpret_cast<uint4*>(brow + gcol) = *reinterpret_cast<const uint4*>(sB + (frow * FB_SB_LD + 96) * 2);
-        *reinterpret_cast<uint4*>(brow + gcol + 8) = *reinterpret_cast<const uint4*>(sB + (frow * FB_SB_LD + 104) * 2);
+        const int gcol = w - 15 - iw + t_hi * 64 + a.pad0 + 64;
+        if (gcol >= 0 && gcol + 8 <= a.Rs)
+            *reinterpret_cast<uint4*>(brow + gcol) = *reinterpret_cast<const uint4*>(sB + (frow * FB_SB_LD + 96) * 2);
+        if (gcol + 8 >= 0 && gcol + 16 <= a.Rs)
+            *reinterpret_cast<uint4*>(brow + gcol + 8) = *reinterpret_cast<const uint4*>(sB + (frow * FB_SB_LD + 104) * 2);
     }
     // ---- dq = d(q+u) + d(q+v): lane (query c, q4) holds e = 16 mt + 4 q4 + r
     if (iq < T) {
@@ -248,11 +255,11 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArg
 
 // ========================================================================================================== key-owner
 template <bool DK64>
-__global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_kv_kernel(FbArgs a) {
+__global__ __launch_bounds__(FA_THREADS, 2) void relpos_local_bwd_kv_kernel(FlbArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 15, q4 = lane >> 4;
-    const int T = a.T, H = a.H, dk = a.dk, d = H * dk, B = a.B;
+    const int T = a.T, H = a.H, dk = a.dk, d = H * dk, B = a.B, w = a.w;
     const FaWg wg = fa_wg(B, T, H, a.lens);
     if (wg.len < 0) return;
     const int bh = wg.bh, kt = wg.tile, h = wg.h, b = wg.b, len = wg.len;
@@ -304,11 +311,11 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_kv_kernel(FbAr
     const __bf16* qbase = a.qkv + (size_t)b * T * (3 * d) + h * dk;
     const __bf16* gbase = a.dctx + (size_t)b * T * d + h * dk;
     const __bf16* pbase = a.pl + h * dk;
-    const auto fetch = [&](int t) {
+    const auto fetch = [&](int t) {   // position rows w - i0 - 63 + J0 .. + 127 clamped to [0, 2w]
         const int i0 = t * 64;
         fa_fetch_rows<DK64, false>(rq, qbase, 3 * d, i0, T - 1, dk, tid);
         fa_fetch_rows<DK64, false>(rg, gbase, d, i0, T - 1, dk, tid);
-        fa_fetch_rows<DK64, true>(rp, pbase, d, T - 1 - i0 - 63 + J0, 2 * T - 2, dk, tid);
+        fa_fetch_rows<DK64, true>(rp, pbase, d, w - i0 - 63 + J0, 2 * w, dk, tid);
         if (tid < 128) {
             int q = i0 + (tid & 63); q = q < T ? q : T - 1;
             rl = (tid < 64 ? a.lse : a.D)[(size_t)bh * T + q];
@@ -334,8 +341,13 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_kv_kernel(FbAr
         if (tid < 128) reinterpret_cast<float*>(smem + 3 * FA_T64 + FA_PBUF)[tid] = rl;
     };
 
-    const int nqt = (len + 63) / 64;   // query tiles with at least one valid query
-    fetch(0);
+    // query tiles that hold a query of [max(J0 - w, 0), min(J0 + 63 + w, len - 1)] (J0 < len here: the first end <= the second)
+    const int ilo = J0 - w > 0 ? J0 - w : 0;
+    const int ihi = J0 + 63 + w < len - 1 ? J0 + 63 + w : len - 1;
+    const int t_lo = ilo / 64, t_hi = ihi / 64;
+    // this key's admissible queries [qmin, qmax]: |i - j| <= w, i < len; empty for a key >= len
+    const int qmin = kvalid ? j - w : T, qmax = j + w < len - 1 ? j + w : len - 1;
+    fetch(t_lo);
     commit();
     __syncthreads();
 
@@ -343,8 +355,8 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_kv_kernel(FbAr
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) { dK[mt] = (f4){0.f, 0.f, 0.f, 0.f}; dV[mt] = (f4){0.f, 0.f, 0.f, 0.f}; }
 
-    for (int t = 0; t < nqt; ++t) {
-        if (t + 1 < nqt) fetch(t + 1);
+    for (int t = t_lo; t <= t_hi; ++t) {
+        if (t < t_hi) fetch(t + 1);
         const int I0 = t * 64;
         // ---- band: for the 16 queries of tile `it` the wave's keys need position rows n0 .. n0 + 31, n0 = 48 - 16 it + 16 w
         //      X_A[m][n] = (q+v)_{16 it + m} . p[n0 + n], X_B with n0 + 16;  bd[il = 16 it + m][key c] = c <= m ? X_A[m][15 - m + c]
@@ -395,7 +407,7 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_kv_kernel(FbAr
             for (int r = 0; r < 4; ++r) {
                 const int i = I0 + it * 16 + q4 * 4 + r;
                 const float s = (S[it][r] + (float)bd.e[r]) * a.scale;
-                const float p = (kvalid && i < len) ? __expf(s - lsv[r]) : 0.f;
+                const float p = (i >= qmin && i <= qmax) ? __expf(s - lsv[r]) : 0.f;
                 float g = dP[it][r], pd = p;
                 if (a.thr > 0) {
                     const unsigned rnd = (fa_keep_rand4(a.seed, bh, T, i, j >> 2) >> (8 * (j & 3))) & 0xFFu;
@@ -421,7 +433,7 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_kv_kernel(FbAr
                 dK[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, dSf[kk], dK[mt], 0, 0, 0);
             }
         __syncthreads();
-        if (t + 1 < nqt) {
+        if (t < t_hi) {
             commit();
             __syncthreads();
         }
@@ -435,68 +447,66 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_kv_kernel(FbAr
     }
 }
 
+inline int flb_window(int T, int window) { return window < T - 1 ? window : T - 1; }   // a window beyond T - 1 admits no further key
+
 }  // namespace
 
-extern "C" int ia_relpos_attention_flash_bwd_dims(int T, int* Rs, int* pad0) {
-    if (T <= 0 || !Rs || !pad0) return IA_INVALID_VALUE;
-    const int p0 = (8 - ((T + 8 * 16 - 16) % 8)) % 8;          // (T - 16 + pad0) % 8 == 0: every wave's band starts on a 16-byte column
-    const int nkt = (T + 63) / 64;
+extern "C" int ia_relpos_attention_local_bwd_dims(int T, int window, int* Rs, int* pad0) {
+    if (T <= 0 || window <= 0 || !Rs || !pad0) return IA_INVALID_VALUE;
+    const int w = flb_window(T, window);
+    const int p0 = (8 - (w + 1) % 8) % 8;         // (w - 15 - iw + pad0) % 8 == 0: every flushed chunk starts on a 16-byte column
     *pad0 = p0;
-    *Rs = (T - 16 + p0 + 64 * nkt + 16 + 7) / 8 * 8;           // largest flushed column + 1 (first wave, last key tile + carry)
-    if (*Rs < p0 + 2 * T - 1) *Rs = (p0 + 2 * T - 1 + 7) / 8 * 8;
+    *Rs = (p0 + 2 * w + 1 + 7) / 8 * 8;           // relative positions 0 .. 2w behind pad0: no term in T
     return IA_OK;
 }
 
-namespace {
-inline FbWs fb_full_ws_layout(int B, int T, int H, int dk) {
+extern "C" int64_t ia_relpos_attention_local_bwd_ws_elems(int B, int T, int H, int dk, int window) {
     int rs, p0;
-    ia_relpos_attention_flash_bwd_dims(T, &rs, &p0);
-    return fb_ws_layout(B, T, H, dk, rs);
-}
-}  // namespace
-
-extern "C" int64_t ia_relpos_attention_flash_bwd_ws_elems(int B, int T, int H, int dk) {
-    if (B <= 0 || T <= 0 || H <= 0 || dk <= 0) return 0;
-    return fb_full_ws_layout(B, T, H, dk).total;
+    if (B <= 0 || H <= 0 || dk <= 0 || ia_relpos_attention_local_bwd_dims(T, window, &rs, &p0) != IA_OK) return 0;
+    return fb_ws_layout(B, T, H, dk, rs).total;
 }
 
-extern "C" int ia_relpos_attention_flash_bwd(const void* qkv, const void* pos_proj, const float* bias_u, const float* bias_v,
+extern "C" int ia_relpos_attention_local_bwd(const void* qkv, const void* pos_proj, const float* bias_u, const float* bias_v,
                                              const int64_t* lens, const void* ctx, const void* dctx, const float* lse, int B,
-                                             int T, int H, int dk, float dropout_p, unsigned seed, void* dqkv, void* dpl,
-                                             int pl_rows, float* dbias_u, float* dbias_v, void* dBand, void* QvHM, float* ws,
-                                             ia_stream_t stream) {
+                                             int T, int H, int dk, int window, float dropout_p, unsigned seed, void* dqkv,
+                                             void* dpl, int pl_rows, float* dbias_u, float* dbias_v, void* dBand, void* QvHM,
+                                             float* ws, ia_stream_t stream) {
     if (!qkv || !pos_proj || !bias_u || !bias_v || !lens || !ctx || !dctx || !lse || !dqkv || !dpl || !dBand || !QvHM || !ws ||
-        !dbias_u || !dbias_v || B <= 0 || T <= 0 || H <= 0 || pl_rows < 2 * T - 1)
+        !dbias_u || !dbias_v || B <= 0 || T <= 0 || H <= 0 || window <= 0 || (int64_t)pl_rows < 2 * (int64_t)window + 1)
         return IA_INVALID_VALUE;
-    if (!ia_relpos_attention_flash_supported(T, dk)) return IA_UNSUPPORTED;
+    if (!ia_relpos_attention_local_supported(T, dk, window)) return IA_UNSUPPORTED;
     if (dropout_p < 0.f || dropout_p >= 1.f) return IA_INVALID_VALUE;
     if (!ia_is_aligned(qkv, 16) || !ia_is_aligned(pos_proj, 16) || !ia_is_aligned(ctx, 8) || !ia_is_aligned(dctx, 8) ||
         !ia_is_aligned(dqkv, 8) || !ia_is_aligned(dBand, 16) || !ia_is_aligned(QvHM, 16) || !ia_is_aligned(ws, 16) ||
         !ia_is_aligned(dpl, 8))
         return IA_INVALID_VALUE;
-    const FbWs w = fb_full_ws_layout(B, T, H, dk);
-    FbArgs a;
-    a.qkv = (const __bf16*)qkv; a.pl = (const __bf16*)pos_proj; a.bias_u = bias_u; a.bias_v = bias_v; a.lens = lens;
-    a.ctx = (const __bf16*)ctx; a.dctx = (const __bf16*)dctx; a.lse = lse; a.dqkv = (__bf16*)dqkv; a.dBand = (__bf16*)dBand;
-    a.QvHM = (__bf16*)QvHM; a.D = ws + w.D; a.part = ws + w.part; a.B = B; a.T = T; a.H = H; a.dk = dk;
+    // as the forward: the band of w' = min(window, T - 1) on the table advanced by window - w' rows
+    const int w = flb_window(T, window), row0 = window - w;
+    const size_t d = (size_t)H * dk;
     int rs, p0;
-    ia_relpos_attention_flash_bwd_dims(T, &rs, &p0);
+    ia_relpos_attention_local_bwd_dims(T, window, &rs, &p0);
+    const FbWs lay = fb_ws_layout(B, T, H, dk, rs);
+    FlbArgs a;
+    a.qkv = (const __bf16*)qkv; a.pl = (const __bf16*)pos_proj + (size_t)row0 * d; a.bias_u = bias_u; a.bias_v = bias_v; a.lens = lens;
+    a.ctx = (const __bf16*)ctx; a.dctx = (const __bf16*)dctx; a.lse = lse; a.dqkv = (__bf16*)dqkv; a.dBand = (__bf16*)dBand;
+    a.QvHM = (__bf16*)QvHM; a.D = ws + lay.D; a.part = ws + lay.part; a.B = B; a.T = T; a.H = H; a.dk = dk; a.w = w;
     a.Rs = rs; a.pad0 = p0;
     a.scale = 1.f / sqrtf((float)dk); a.seed = seed;
     const ia_dropout_t drop = ia_dropout_rule(dropout_p);
     a.thr = drop.thr; a.keep_scale = drop.keep_scale;
     hipStream_t st = (hipStream_t)stream;
-    // band columns outside the processed key tiles (keys beyond the length, rows of padded queries) stay zero
+    // band columns no (wave, tile) flushes (keys beyond the length, rows of padded queries) stay zero
     if (hipMemsetAsync(dBand, 0, (size_t)H * B * T * rs * sizeof(__bf16), st) != hipSuccess) return IA_LAUNCH_FAILED;
     const int nt = (T + 63) / 64;
     const int grid = 8 * ((B * H + 7) / 8) * nt;
     const bool full = (dk == 64);
-    int rc = fa_launch<FbArgs, relpos_flash_bwd_q_kernel<true>, relpos_flash_bwd_q_kernel<false>>(full, grid, FB_Q_LDS, st, a);
+    int rc = fa_launch<FlbArgs, relpos_local_bwd_q_kernel<true>, relpos_local_bwd_q_kernel<false>>(full, grid, FB_Q_LDS, st, a);
     if (rc != IA_OK) return rc;
-    rc = fa_launch<FbArgs, relpos_flash_bwd_kv_kernel<true>, relpos_flash_bwd_kv_kernel<false>>(full, grid, FB_KV_LDS, st, a);
+    rc = fa_launch<FlbArgs, relpos_local_bwd_kv_kernel<true>, relpos_local_bwd_kv_kernel<false>>(full, grid, FB_KV_LDS, st, a);
     if (rc != IA_OK) return rc;
     ia_partials_finish(a.part, B * nt, 2 * H * dk, H * dk, dbias_u, dbias_v, st);
     IA_RETURN_IF_LAUNCH_FAILED();
-    // position-projection gradient: the band columns pad0 .. pad0 + 2T-2 of the heads' TN GEMMs go to dpl [pl_rows, d] bf16
-    return fb_dpos_gemm_pack(dBand, QvHM, ws, w, rs, p0, 2 * T - 1, B, T, H, dk, dpl, pl_rows, stream);
+    // position-projection gradient: band columns pad0 .. pad0 + 2w' -> dpl rows row0 .. row0 + 2w', every other row zero
+    if (row0 > 0 && hipMemsetAsync(dpl, 0, (size_t)row0 * d * sizeof(__bf16), st) != hipSuccess) return IA_LAUNCH_FAILED;
+    return fb_dpos_gemm_pack(dBand, QvHM, ws, lay, rs, p0, 2 * w + 1, B, T, H, dk, (__bf16*)dpl + (size_t)row0 * d, pl_rows - row0, stream);
 }

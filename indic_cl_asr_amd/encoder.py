@@ -389,7 +389,8 @@ class ConformerEncoder(nn.Module):
             # weights only, so the gradient all-reduce ran under it
             if cl._PENDING_OPTIMIZERS:
                 cl.flush_pending_updates()
-            # trainable suffix: one autograd node per block on the HIP kernels (ops/block.py), ATen composition otherwise
+            # trainable suffix: one autograd node per block on the HIP kernels (ops/block.py; under local attention pos_emb is the
+            # 2w+1-row table and the node takes the windowed attention pair), ATen composition otherwise
             blk_ok = False
             if (self.use_fast_path and self.use_fused_blocks and self.cfg.compute_dtype == "bf16" and x.is_cuda
                     and torch.is_grad_enabled() and lth < n_layers and self.training):

@@ -4,7 +4,8 @@ Forward = the fused no-autograd path of encoder.ConformerLayer.forward_fast (GEM
 GLU+depthwise conv+BatchNorm+SiLU, rel-pos attention) keeping the intermediates the backward needs; backward = manual
 chain rule: bf16 library GEMMs for the data gradients, batched split-K GEMMs for the weight gradients, and the
 kernels of csrc/encoder_bwd.hip for everything in between; the attention core is the key-tiled pair
-csrc/attention_flash.hip / attention_flash_bwd.hip (any T, no [T,T] matrices in HBM).
+csrc/attention_flash.hip / attention_flash_bwd.hip (any T, no [T,T] matrices in HBM) or, for a layer with a local window,
+csrc/attention_local.hip / attention_local_bwd.hip (O(T w)) in the per-op node.
 
 Semantics: ConformerLayer.forward, A/parts/submodules/conformer_modules.py:141-214 (bf16 projections, fp32 residual
 stream / norms / BatchNorm statistics), dropout masks are counter-based and regenerated in the backward.
@@ -81,10 +82,11 @@ DIRECT_ACCUMULATE = True
 def block_supported(layer, x2d, T):
     d = x2d.shape[-1]
     bn = layer.conv.batch_norm
-    if getattr(layer.self_attn, "att_window", None) is not None:
-        return False   # local attention has no HIP backward: the trainable blocks go through the ATen composition
+    w = getattr(layer.self_attn, "att_window", None)
+    att_ok = (fast.attention_flash_supported(T, layer.self_attn.d_k) if w is None
+              else fast.attention_local_supported(T, layer.self_attn.d_k, w))
     return (x2d.is_cuda and d % 8 == 0 and d <= 1024 and fast.bn_module_ok(bn)
-            and layer.conv.depthwise_conv.weight.shape[-1] <= 31 and fast.attention_flash_supported(T, layer.self_attn.d_k))
+            and layer.conv.depthwise_conv.weight.shape[-1] <= 31 and att_ok)
 
 
 class _ConformerBlockFn(torch.autograd.Function):
@@ -99,6 +101,7 @@ class _ConformerBlockFn(torch.autograd.Function):
         pff1 = float(ff1.dropout.p) if tr else 0.0
         pff2 = float(ff2.dropout.p) if tr else 0.0
         patt = float(att.dropout_rate) if tr else 0.0
+        window = getattr(att, "att_window", None)   # w: local attention [w, w], pe is the (padded) 2w+1-row table
         W = dict(w1=fast.bf16_shadow(ff1.linear1.weight), w2=fast.bf16_shadow(ff1.linear2.weight),
                  wqkv=fast.bf16_shadow(att.linear_q.weight, att.linear_k.weight, att.linear_v.weight),
                  wpos=fast.bf16_shadow(att.linear_pos.weight), wo=fast.bf16_shadow(att.linear_out.weight),
@@ -116,8 +119,12 @@ class _ConformerBlockFn(torch.autograd.Function):
         y2 = fast.layernorm(x1, layer.norm_self_att.weight, layer.norm_self_att.bias, layer.norm_self_att.eps)
         _, qkv = fast.gemm(y2, W["wqkv"], fast.f32_cat(att.linear_q.bias, att.linear_k.bias, att.linear_v.bias))
         _, pl = fast.gemm(pe, W["wpos"])
-        ctxv, lse = fast.relpos_attention_flash(qkv, pl, att.pos_bias_u, att.pos_bias_v, lens, B, T, att.h, att.d_k, patt, seed + 7,
-                                                want_lse=True)
+        if window is None:
+            ctxv, lse = fast.relpos_attention_flash(qkv, pl, att.pos_bias_u, att.pos_bias_v, lens, B, T, att.h, att.d_k, patt, seed + 7,
+                                                    want_lse=True)
+        else:
+            ctxv, lse = fast.relpos_attention_local(qkv, pl, att.pos_bias_u, att.pos_bias_v, lens, B, T, att.h, att.d_k, window, patt,
+                                                    seed + 7, want_lse=True)
         x2, _ = fast.gemm(ctxv, W["wo"], att.linear_out.bias, dropout_p=p, seed=seed + 3, residual=x1, out_f32=new(),
                           want_bf16=False)
         # convolution module
@@ -141,7 +148,7 @@ class _ConformerBlockFn(torch.autograd.Function):
             raise RuntimeError("trainable fused block expects train-mode BatchNorm (batch statistics)")
         ctx.S = dict(x0=x0, y1=y1, h1p=h1p, h1=h1, x1=x1, y2=y2, qkv=qkv, pl=pl, ctxv=ctxv, lse=lse, x2=x2, y3=y3, c2=c2, z=z, sums=sums,
                      c3=c3, x3=x3, y4=y4, h4p=h4p, h4=h4, x4=x4, W=W, pe=pe, lens=lens)
-        ctx.meta = (layer, B, T, seed, p, pff1, pff2, patt, [n for n, _ in layer.named_parameters()],
+        ctx.meta = (layer, B, T, seed, p, pff1, pff2, patt, window, [n for n, _ in layer.named_parameters()],
                     [q.requires_grad for q in params], params)
         return out
 
@@ -150,7 +157,7 @@ class _ConformerBlockFn(torch.autograd.Function):
         L = _lib.lib()
         S = ctx.S
         ctx.S = None
-        layer, B, T, seed, p, pff1, pff2, patt, names, req, params = ctx.meta
+        layer, B, T, seed, p, pff1, pff2, patt, window, names, req, params = ctx.meta
         W = S["W"]
         ff1, ff2, att, cv = layer.feed_forward1, layer.feed_forward2, layer.self_attn, layer.conv
         d = S["x0"].shape[1]
@@ -217,8 +224,12 @@ class _ConformerBlockFn(torch.autograd.Function):
         # self-attention
         dB = _branch_grad(dx2, 1.0, p, seed + 3)
         dctx, G["self_attn.linear_out.weight"], G["self_attn.linear_out.bias"] = _lin_bwd(dB, S["ctxv"], W["wo"])
-        dqkv, dpl, du, dv = fast.relpos_attention_flash_bwd(S["qkv"], S["pl"], att.pos_bias_u, att.pos_bias_v, S["lens"], S["ctxv"],
-                                                            dctx, S["lse"], B, T, att.h, att.d_k, patt, seed + 7)
+        if window is None:
+            dqkv, dpl, du, dv = fast.relpos_attention_flash_bwd(S["qkv"], S["pl"], att.pos_bias_u, att.pos_bias_v, S["lens"], S["ctxv"],
+                                                                dctx, S["lse"], B, T, att.h, att.d_k, patt, seed + 7)
+        else:
+            dqkv, dpl, du, dv = fast.relpos_attention_local_bwd(S["qkv"], S["pl"], att.pos_bias_u, att.pos_bias_v, S["lens"], S["ctxv"],
+                                                                dctx, S["lse"], B, T, att.h, att.d_k, window, patt, seed + 7)
         G["self_attn.pos_bias_u"], G["self_attn.pos_bias_v"] = du, dv
         dy, dWqkv, dbqkv = _lin_bwd(dqkv, S["y2"], W["wqkv"])
         for i, nm in enumerate(("q", "k", "v")):
@@ -262,8 +273,9 @@ def pad_pos_emb(pos_emb, d):
 
 def conformer_block(x2d, layer, lens, pe_bf16, B, T, seed):
     """x2d [B*T, d] f32 residual stream -> [B*T, d] f32 (autograd-connected to x2d and the block's parameters).
-    pe_bf16: pad_pos_emb(pos_emb) (>= 2T-1 rows)."""
-    if USE_NATIVE_BLOCKS and layer.training:
+    pe_bf16: pad_pos_emb(pos_emb) (>= 2T-1 rows; under a local window w the 2w+1-row table).  A layer with a window takes the
+    per-op node: the native executor does not know the window."""
+    if USE_NATIVE_BLOCKS and layer.training and getattr(layer.self_attn, "att_window", None) is None:
         att = layer.self_attn
         if _lib.lib().ia_conformer_block_supported(x2d.shape[-1], layer.feed_forward1.linear1.weight.shape[0], att.h,
                                                    layer.conv.depthwise_conv.weight.shape[-1], T):

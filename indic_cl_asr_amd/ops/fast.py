@@ -452,18 +452,50 @@ def attention_local_supported(T, dk, window):
     return bool(_lib.lib().ia_relpos_attention_local_supported(int(T), int(dk), int(window)))
 
 
-def relpos_attention_local(qkv_bf16, pos_proj_bf16, bias_u, bias_v, lens, B, T, H, dk, window, dropout_p=0.0, seed=0):
+def relpos_attention_local(qkv_bf16, pos_proj_bf16, bias_u, bias_v, lens, B, T, H, dk, window, dropout_p=0.0, seed=0, want_lse=False):
     """Local rel-pos attention forward (csrc/attention_local.hip): query i attends the keys |i - j| <= window, j < len.
     qkv [B*T, 3*H*dk] bf16, pos_proj [>= 2*window+1, H*dk] bf16 (row r <-> relative position window - r) -> ctx [B*T, H*dk] bf16.
-    Forward only (no lse): training under local attention differentiates through ops.rel_pos_attention(window=...)."""
+    want_lse: also the per-query log-sum-exp [B*H, T] f32 that relpos_attention_local_bwd needs -> (ctx, lse)."""
     if pos_proj_bf16.shape[0] < 2 * int(window) + 1:
         raise ValueError(f"relpos_attention_local: {pos_proj_bf16.shape[0]} position rows < 2 * {window} + 1")
     ctx = torch.empty(B * T, H * dk, dtype=torch.bfloat16, device=qkv_bf16.device)
-    st = _lib.lib().ia_relpos_attention_local(_lib.ptr(qkv_bf16), _lib.ptr(pos_proj_bf16), _lib.ptr(bias_u), _lib.ptr(bias_v),
-                                              _lib.ptr(lens), B, T, H, dk, int(window), float(dropout_p), int(seed) & 0xFFFFFFFF,
-                                              _lib.ptr(ctx), _lib.stream_ptr())
-    _lib.check(st, "ia_relpos_attention_local")
-    return ctx
+    lse = torch.empty(B * H, T, dtype=torch.float32, device=qkv_bf16.device) if want_lse else None
+    st = _lib.lib().ia_relpos_attention_local_lse(_lib.ptr(qkv_bf16), _lib.ptr(pos_proj_bf16), _lib.ptr(bias_u), _lib.ptr(bias_v),
+                                                  _lib.ptr(lens), B, T, H, dk, int(window), float(dropout_p),
+                                                  int(seed) & 0xFFFFFFFF, _lib.ptr(ctx), _lib.ptr(lse), _lib.stream_ptr())
+    _lib.check(st, "ia_relpos_attention_local_lse")
+    return (ctx, lse) if want_lse else ctx
+
+
+def attention_local_bwd_dims(T, window):
+    """(Rs, pad0) of the local backward's dBand [H, B*T, Rs]: Rs = ceil8(pad0 + 2 min(window, T-1) + 1), no term in T."""
+    import ctypes
+    rs, p0 = ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.lib().ia_relpos_attention_local_bwd_dims(int(T), int(window), ctypes.byref(rs), ctypes.byref(p0)), "dims")
+    return rs.value, p0.value
+
+
+def relpos_attention_local_bwd(qkv, pl, bias_u, bias_v, lens, ctx, dctx, lse, B, T, H, dk, window, dropout_p=0.0, seed=0, dub_out=None):
+    """Backward of relpos_attention_local (csrc/attention_local_bwd.hip): operands and results as relpos_attention_flash_bwd, pl
+    [>= 2*window+1, d]; dpl rows beyond 2*window are zero.  dBand, the workspace and the work are O(T * window)."""
+    L = _lib.lib()
+    dev = qkv.device
+    d = H * dk
+    bf = torch.bfloat16
+    Rs, pad0 = attention_local_bwd_dims(T, window)
+    dqkv = torch.empty(B * T, 3 * d, dtype=bf, device=dev)
+    dpl = torch.empty_like(pl)
+    dBand = torch.empty(H * B * T * Rs, dtype=bf, device=dev)
+    QvHM = torch.empty(H * B * T * 64, dtype=bf, device=dev)
+    ws = torch.empty(L.ia_relpos_attention_local_bwd_ws_elems(B, T, H, dk, int(window)), dtype=torch.float32, device=dev)
+    dub = dub_out if dub_out is not None else torch.empty(2, H, dk, dtype=torch.float32, device=dev)
+    dctx = dctx.contiguous()
+    st = L.ia_relpos_attention_local_bwd(_lib.ptr(qkv), _lib.ptr(pl), _lib.ptr(bias_u), _lib.ptr(bias_v), _lib.ptr(lens), _lib.ptr(ctx),
+                                         _lib.ptr(dctx), _lib.ptr(lse), B, T, H, dk, int(window), float(dropout_p),
+                                         int(seed) & 0xFFFFFFFF, _lib.ptr(dqkv), _lib.ptr(dpl), pl.shape[0], _lib.ptr(dub[0]),
+                                         _lib.ptr(dub[1]), _lib.ptr(dBand), _lib.ptr(QvHM), _lib.ptr(ws), _lib.stream_ptr())
+    _lib.check(st, "ia_relpos_attention_local_bwd")
+    return dqkv, dpl, dub[0], dub[1]
 
 
 def attention_flash_bwd_dims(T):
