@@ -385,7 +385,7 @@ int ia_glu_dwconv_fixed(const void* x2, const int64_t* lens, int B, int T, int d
                         float* z, long long* bn_sums_fixed, ia_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Rel-pos attention core, key-tile loop with online softmax (csrc/attention_flash.hip):
+ * Rel-pos attention core, key-tile loop with online softmax (csrc/attention_flash.hip: one kernel, full or local by its span):
  * RelPositionMultiHeadAttention.forward (A/parts/submodules/multi_head_attention.py:197-250, rel_shift :184-195, masking
  * :108-111) without materialising any [B,h,T,T] / [B,h,T,2T-1] tensor.  Any T (30 s audio: T' = 751), head dim any
  * multiple of 4 up to 64 (d = 144 / 4 heads = 36); ia_relpos_attention_flash_supported says so, IA_UNSUPPORTED otherwise.
@@ -403,7 +403,7 @@ int ia_relpos_attention_flash(const void* qkv, const void* pos_proj, const float
 int ia_relpos_attention_flash_lse(const void* qkv, const void* pos_proj, const float* bias_u, const float* bias_v,
                                   const int64_t* lens, int B, int T, int H, int dk, float dropout_p, unsigned seed, void* ctx,
                                   float* lse, ia_stream_t stream);
-/* Local (windowed) forward of the same core (csrc/attention_local.hip): RelPositionMultiHeadAttentionLongformer.forward
+/* Local (windowed) forward: the same kernel under its local span.  RelPositionMultiHeadAttentionLongformer.forward
  * (A/parts/submodules/multi_head_attention.py:253-470) with LocalAttRelPositionalEncoding (:982-1026) for a symmetric window
  * [window, window] and no global tokens -- query i attends the keys |i - j| <= window, j < lens[b].  A 64-query tile visits
  * at most 1 + 2 ceil(window / 64) key tiles whatever T is.  Operands, layouts, lens semantics, alignment checks and the dropout
@@ -430,7 +430,7 @@ int ia_relpos_attention_flash_bwd(const void* qkv, const void* pos_proj, const f
                                   const int64_t* lens, const void* ctx, const void* dctx, const float* lse, int B, int T, int H,
                                   int dk, float dropout_p, unsigned seed, void* dqkv, void* dpl, int pl_rows, float* dbias_u,
                                   float* dbias_v, void* dBand, void* QvHM, float* ws, ia_stream_t stream);
-/* Backward of ia_relpos_attention_local_lse (csrc/attention_local_bwd.hip): the same two kernels restricted to the band, each
+/* Backward of ia_relpos_attention_local_lse: the same two kernels under their local span, restricted to the band, each
  * walking only the tiles the window reaches -- time and memory O(T window).  Arguments, outputs, return codes and alignment
  * checks are ia_relpos_attention_flash_bwd's, plus `window` (>= 1) and with pos_proj / dpl [pl_rows >= 2 window + 1, d]: dpl rows
  * 0 .. 2 window hold the gradient of the table rows a key can reach (with w' = min(window, T-1): rows window - w' .. window + w'),

@@ -1,10 +1,12 @@
-// The one vocabulary of the key-tiled rel-pos attention kernels (attention_flash.hip forward, attention_local.hip windowed
-// forward, attention_flash_bwd.hip and attention_local_bwd.hip query-owner and key-owner backward): fragment types, tile
-// constants, the attention-dropout hash (the backward regenerates the forward's mask), the zero-padding head-row loader, the
-// swizzled LDS addresses and fragment reads, register staging of a tile (fetch / commit), the K | V | P stage (full and local),
-// the query fragments, the band block, the workgroup coordinates, the guarded head-row store, the backwards' strip geometry,
-// workspace layout and position-gradient step, and the host's launch of a <DK64> pair.
-// tests/test_attention_flash_digests_gpu.py pins the bits of everything the full-attention kernels build from it.
+// The key-tiled rel-pos attention kernels' one vocabulary.  There is one kernel template per role, written once as
+// template <bool DK64, class Span>: the forward (attention_flash.hip), the query-owner and the key-owner backward
+// (attention_flash_bwd.hip).  Full attention and local attention (|i - j| <= w) are the same kernels under two spans; the Span
+// section below lists everything in which they differ.  Here: fragment types, tile constants, the attention-dropout hash (the
+// backward regenerates the forward's mask), the zero-padding head-row loader, the swizzled LDS addresses and fragment reads,
+// register staging of a tile (fetch / commit), the spans, the K | V | P stage, the query fragments, the band block, the workgroup
+// coordinates, the guarded head-row store, the backwards' strip geometry, workspace layout and position-gradient step, and the
+// host's launch of a <DK64> pair.  tests/test_attention_flash_digests_gpu.py pins the bits of everything the kernels build from
+// it under the full span, tests/test_attention_local_digests_gpu.py under the local one.
 #pragma once
 #include <hip/hip_bf16.h>
 
@@ -87,49 +89,88 @@ __device__ __forceinline__ void fa_commit_rows(unsigned char* tile, const uint4 
     }
 }
 
+// ---- Span: which (query, key) pairs exist.  A small device-side value; FaFullSpan admits every key below the length,
+// FaLocalSpan the keys |i - j| <= w below the length (0 <= w <= T - 1: the host reduces a larger window).  It supplies what
+// differs between full and local attention, and nothing else:
+//   1. centre(): the position row of relative position 0, T - 1 (full) or w (local).  The stage's position rows are
+//      centre - I0 - 63 + j0 .. + 127 clamped to [0, 2 centre] (clamped rows give finite band values for pairs that the
+//      admissibility removes), the key-owner's centre - i0 - 63 + J0 .. + 127, and the dBand column of strip column 0 is
+//      centre - 15 - iw + j0 + pad0.
+//   2. tiles(X0, len): the 64-row tiles lo .. end - 1 of the OTHER axis that a query tile or key tile at X0 < len walks.  Full:
+//      every tile below len.  Local: those that hold a row of [max(X0 - w, 0), min(X0 + 63 + w, len - 1)] (both ends
+//      non-negative, the first <= X0 <= the second), 1 + 2 ceil(w / 64) tiles at the most whatever T is.  The one-stage prefetch
+//      follows them.  A plain aggregate read by its members, walked `t < end`, `t + 1 < end`: that is the form in which the full
+//      forward compiles to its earlier loop (walked `t <= last`, or through member functions, it is 1 % slower at T = 3001;
+//      profiles/attention_span_refactor.md).
+//   3. admit(own, valid, len): the rows of the other axis that pair with a lane's own row, built once per lane and asked once per
+//      element.  `valid` is own < len; the forward passes true (a padded query's context is zeroed at the store).  In the backward
+//      an inadmissible pair gives P = 0 by value, in the forward -inf before the row maximum.
+//   4. tile_unmasked(j0, iw, len): the forward's mask-free score branch.  Full: the key tile lies below len (workgroup-uniform).
+//      Local: it also lies inside the window of all 16 queries iw .. iw + 15 of the wave (per wave).
+//   5. Two compile-time facts, the points where the spans differ in output bits or in stores:
+//      kSparseTiles: a processed tile may hold no admissible key for a query (the tile left of the diagonal at a small w, a
+//        padded query).  Running and new maximum are then both -inf, so the forward takes its exponentials against 0 (exp2(-inf)
+//        = 0, no NaN) and zeroes a padded query's accumulator BY VALUE.  The full span uses the new maximum directly (finite: key
+//        j0 < len exists in every processed tile) and stores O * 0, which is -0.0 for a negative accumulator.
+//      kBoundedBand: the dBand row holds only [0, Rs), Rs = ceil8(pad0 + 2w + 1) whatever T is, and strip columns outside it
+//        (exact zeros of inadmissible pairs) are dropped chunk by chunk, the final carry included.  The full span's row holds
+//        every flushed column; only a partial last wave's leading chunks fall left of column 0.
+// Aggregates are returned by value: filled through a reference under control flow they cost the query-owner registers.
+struct FaTiles { int lo, end; };   // tiles lo .. end - 1
+
+struct FaFullSpan {
+    static constexpr bool kSparseTiles = false, kBoundedBand = false;
+    struct Adm {
+        bool ok; int len;
+        __device__ __forceinline__ bool operator()(int x) const { return ok && x < len; }
+    };
+    int T;
+    __device__ __forceinline__ FaFullSpan(int T_, int) : T(T_) {}
+    __device__ __forceinline__ int centre() const { return T - 1; }
+    __device__ __forceinline__ FaTiles tiles(int, int len) const { return FaTiles{0, (len + 63) / 64}; }
+    __device__ __forceinline__ Adm admit(int, bool valid, int len) const { return Adm{valid, len}; }
+    __device__ __forceinline__ bool tile_unmasked(int j0, int, int len) const { return j0 + 64 <= len; }
+};
+
+struct FaLocalSpan {
+    static constexpr bool kSparseTiles = true, kBoundedBand = true;
+    struct Adm {   // [lo, hi], empty (lo = len > hi) for an own row >= len
+        int lo, hi;
+        __device__ __forceinline__ bool operator()(int x) const { return x >= lo && x <= hi; }
+    };
+    int w;
+    __device__ __forceinline__ FaLocalSpan(int, int w_) : w(w_) {}
+    __device__ __forceinline__ int centre() const { return w; }
+    __device__ __forceinline__ FaTiles tiles(int X0, int len) const {
+        const int lo = X0 - w > 0 ? X0 - w : 0, hi = X0 + 63 + w < len - 1 ? X0 + 63 + w : len - 1;
+        return FaTiles{lo / 64, hi / 64 + 1};
+    }
+    __device__ __forceinline__ Adm admit(int own, bool valid, int len) const {
+        return Adm{valid ? own - w : len, own + w < len - 1 ? own + w : len - 1};
+    }
+    __device__ __forceinline__ bool tile_unmasked(int j0, int iw, int len) const {
+        return j0 + 64 <= len && j0 >= iw + 15 - w && j0 + 63 <= iw + w;
+    }
+};
+
 // The K | V | P stage of the forward and the query-owner (32 KB at `smem`): key tile t of one (utterance, head), rows clamped to
-// T - 1, and the 128 position rows T - 1 - I0 - 63 + 64 t .. + 127 that cover the bands of the four waves of query tile I0,
-// clamped to [0, 2T - 2].  fetch(t) brings tile t to registers (8 x 16 B per thread), commit() writes them to LDS.
+// T - 1, and the 128 position rows centre - I0 - 63 + 64 t .. + 127 that cover the bands of the four waves of query tile I0,
+// clamped to [0, 2 centre].  fetch(t) brings tile t to registers (8 x 16 B per thread), commit() writes them to LDS.
 template <bool DK64>
 struct FaKvpStage {
     uint4 rk[2], rv[2], rp[4];
     const __bf16 *kbase, *vbase, *pbase;
     unsigned char* smem;
-    int T, d, dk, I0, tid;
+    int T, d, dk, I0, centre, tid;
     __device__ __forceinline__ FaKvpStage(const __bf16* qkv, const __bf16* pl, unsigned char* smem_, int b, int h, int T_, int d_,
-                                          int dk_, int I0_, int tid_)
+                                          int dk_, int I0_, int centre_, int tid_)
         : kbase(qkv + (size_t)b * T_ * (3 * d_) + d_ + h * dk_), vbase(kbase + d_), pbase(pl + h * dk_), smem(smem_), T(T_), d(d_),
-          dk(dk_), I0(I0_), tid(tid_) {}
+          dk(dk_), I0(I0_), centre(centre_), tid(tid_) {}
     __device__ __forceinline__ void fetch(int t) {
         const int j0 = t * 64;
         fa_fetch_rows<DK64, false>(rk, kbase, 3 * d, j0, T - 1, dk, tid);
         fa_fetch_rows<DK64, false>(rv, vbase, 3 * d, j0, T - 1, dk, tid);
-        fa_fetch_rows<DK64, true>(rp, pbase, d, T - 1 - I0 - 63 + j0, 2 * T - 2, dk, tid);
-    }
-    __device__ __forceinline__ void commit() {
-        fa_commit_rows(smem, rk, tid);
-        fa_commit_rows(smem + FA_T64, rv, tid);
-        fa_commit_rows(smem + 2 * FA_T64, rp, tid);
-    }
-};
-
-// FaKvpStage with a local window's position rows (attention_local.hip, attention_local_bwd.hip): key tile t, rows clamped to
-// T - 1, and the 128 position rows w - I0 - 63 + 64 t .. + 127 clamped to [0, 2w]
-template <bool DK64>
-struct FlKvpStage {
-    uint4 rk[2], rv[2], rp[4];
-    const __bf16 *kbase, *vbase, *pbase;
-    unsigned char* smem;
-    int T, d, dk, I0, w, tid;
-    __device__ __forceinline__ FlKvpStage(const __bf16* qkv, const __bf16* pl, unsigned char* smem_, int b, int h, int T_, int d_,
-                                          int dk_, int I0_, int w_, int tid_)
-        : kbase(qkv + (size_t)b * T_ * (3 * d_) + d_ + h * dk_), vbase(kbase + d_), pbase(pl + h * dk_), smem(smem_), T(T_), d(d_),
-          dk(dk_), I0(I0_), w(w_), tid(tid_) {}
-    __device__ __forceinline__ void fetch(int t) {
-        const int j0 = t * 64;
-        fa_fetch_rows<DK64, false>(rk, kbase, 3 * d, j0, T - 1, dk, tid);
-        fa_fetch_rows<DK64, false>(rv, vbase, 3 * d, j0, T - 1, dk, tid);
-        fa_fetch_rows<DK64, true>(rp, pbase, d, w - I0 - 63 + j0, 2 * w, dk, tid);
+        fa_fetch_rows<DK64, true>(rp, pbase, d, centre - I0 - 63 + j0, 2 * centre, dk, tid);
     }
     __device__ __forceinline__ void commit() {
         fa_commit_rows(smem, rk, tid);
@@ -201,8 +242,8 @@ __device__ __forceinline__ void fa_store_head4(__bf16* row, int mt, int q4, int 
     }
 }
 
-// ---- shared by the two backwards (attention_flash_bwd.hip, attention_local_bwd.hip): strip geometry, the strip fence, the
-// workspace layout and the position-gradient step
+// ---- the backward's (attention_flash_bwd.hip): strip geometry, the strip fence, the workspace layout and the position-gradient
+// step
 constexpr int FB_SB_LD = 120;                 // dS band strip: columns [0,96) band rows of this tile, [96,112) carry
 constexpr int FB_Q_STRIP = 16 * (FA_SR_LD + FB_SB_LD) * 2;           // per wave: 7168 B
 constexpr int FB_Q_LDS = 2 * FA_T64 + FA_PBUF + 4 * FB_Q_STRIP;      // K | V | P | strips = 61 440 B

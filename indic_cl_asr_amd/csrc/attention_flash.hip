@@ -1,12 +1,20 @@
-// Relative-position multi-head self-attention forward, key-tile loop with online softmax (gfx950).
+// Relative-position multi-head self-attention forward, key-tile loop with online softmax (gfx950), full or local by its Span.
 //
-//   ctx[b,i,h,:] = sum_j softmax_j( ((q_i+u_h).k_j + (q_i+v_h).p_h[T-1-i+j]) / sqrt(dk) ) v_j ,   j < len_b
+//   ctx[b,i,h,:] = sum_j softmax_j( ((q_i+u_h).k_j + (q_i+v_h).p_h[centre-i+j]) / sqrt(dk) ) v_j ,   j < len_b  (and |i-j| <= w)
 //
-// RelPositionMultiHeadAttention.forward A/parts/submodules/multi_head_attention.py:197-250: rel_shift (:184-195) as index
-// arithmetic, the [B,T,T] mask replaced by lengths (keys >= len excluded = "-10000 then zero", :108-111; padded queries
-// give zero context), attention dropout on the probabilities.  The kernel walks 64-key tiles and keeps only the running
-// maximum, sum and output of a 16-query strip in registers, so T is unbounded (30 s audio: T' = 751); the head dim is any
-// multiple of 4 up to 64 (d = 144 / 4 heads = 36: tiles zero-padded to 64 in LDS).
+// Full span: RelPositionMultiHeadAttention.forward A/parts/submodules/multi_head_attention.py:197-250: rel_shift (:184-195) as
+// index arithmetic, centre = T - 1, the [B,T,T] mask replaced by lengths (keys >= len excluded = "-10000 then zero", :108-111;
+// padded queries give zero context), attention dropout on the probabilities.
+// Local span: RelPositionMultiHeadAttentionLongformer.forward (:253-470) with LocalAttRelPositionalEncoding (:982-1026) for a
+// symmetric window [w, w] and no global tokens: the sliding-chunk matmuls and their diagonal bookkeeping are the band
+// |i - j| <= w, the position table's row r holds relative position w - r (2w + 1 rows, centre = w).  Asymmetric windows are not
+// offered: the reference adds their position term to the wrong columns.  The host reduces a window beyond T - 1 to w' = T - 1
+// by advancing the table pointer (row r of the 2w+1 table is row r - (w - w') of the 2w'+1 one), so the kernel's index
+// arithmetic never sees a window larger than T; a window >= T - 1 gives the full span's values.
+//
+// The kernel walks 64-key tiles (the span's: all below len, or the 1 + 2 ceil(w / 64) at the most that meet the window) and
+// keeps only the running maximum, sum and output of a 16-query strip in registers, so T is unbounded (30 s audio: T' = 751);
+// the head dim is any multiple of 4 up to 64 (d = 144 / 4 heads = 36: tiles zero-padded to 64 in LDS).
 //
 // Workgroup = (utterance, head, 64 queries), 4 waves x 16 queries.  Per 64-key tile, staged once per workgroup in LDS
 // (K, V row-major [key][dk], 128 position rows covering the four waves' bands; 16-byte slots XOR-swizzled by row & 7):
@@ -18,10 +26,7 @@
 //   probabilities ARE the B operand of
 //   O^T += V^T P^T         [64 dv x 16 queries]             8 MFMAs   (A = V^T fragments by ds_read_b64_tr_b16 from the
 //   row-major V tile: no pre-transposed V copy, no probability round trip through LDS).
-// Key tiles at or beyond the utterance's length are skipped.
-//
-// The staging, the swizzled fragment reads, the band block, the query fragments, the workgroup coordinates and the head-row
-// store are attention_flash.h's, shared with the backward; tests/test_attention_flash_digests_gpu.py pins ctx and lse bit for bit.
+// The optional lse (natural-log log-sum-exp per query, 0 for padded queries) is what the backward recomputes P from.
 #include <type_traits>
 
 #include "attention_flash.h"
@@ -37,14 +42,16 @@ struct FaArgs {
     const __bf16* qkv; const __bf16* pl; const float* bias_u; const float* bias_v; const int64_t* lens;
     __bf16* ctx; int B, T, H, dk; float scale; unsigned seed, thr; float keep_scale;
     float* lse;   // optional [B*H, T]: log-sum-exp of each query's scaled scores (the backward recomputes P = exp(s - lse))
+    int w;        // the local span's window, 0 <= w <= T - 1.  Last: the full span does not read it and loads its arguments as before
 };
 
-template <bool DK64>
+template <bool DK64, class Span>
 __global__ __launch_bounds__(FA_THREADS, 3) void relpos_flash_fwd_kernel(FaArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 15, q4 = lane >> 4;
     const int T = a.T, H = a.H, dk = a.dk, d = H * dk;
+    const Span span(T, a.w);
     const FaWg wg = fa_wg(a.B, T, H, a.lens);
     if (wg.len < 0) return;
     const int bh = wg.bh, h = wg.h, b = wg.b, len = wg.len;
@@ -74,10 +81,10 @@ __global__ __launch_bounds__(FA_THREADS, 3) void relpos_flash_fwd_kernel(FaArgs 
     // then barrier, registers -> LDS, barrier.  One stage (45 KB with the strips) keeps three workgroups on a CU: the 768
     // workgroups of a 32 x 376-frame batch are all resident (two stages = 512 slots = a second, half-empty round: 41 us;
     // measured per-workgroup cost 5 us + 3.3 us per key tile), and three waves per SIMD hide each other's LDS round trips.
-    FaKvpStage<DK64> stage(a.qkv, a.pl, smem, b, h, T, d, dk, I0, tid);
+    FaKvpStage<DK64> stage(a.qkv, a.pl, smem, b, h, T, d, dk, I0, span.centre(), tid);
 
-    const int nkt = (len + FA_KT - 1) / FA_KT;   // key tiles with at least one valid key
-    stage.fetch(0);
+    const FaTiles ktiles = span.tiles(I0, len);   // the key tiles of this query tile
+    stage.fetch(ktiles.lo);
     stage.commit();
     __syncthreads();
 
@@ -87,11 +94,11 @@ __global__ __launch_bounds__(FA_THREADS, 3) void relpos_flash_fwd_kernel(FaArgs 
     float m_run = IA_NEG_INF, l_run = 0.f;      // running maximum of this lane's query, this lane's share of the sum
     const float scale2 = a.scale * 1.44269504088896341f;
 
-    for (int t = 0; t < nkt; ++t) {
+    for (int t = ktiles.lo; t < ktiles.end; ++t) {
         const unsigned char* sK = smem;
         const unsigned char* sV = sK + FA_T64;
         const unsigned char* sP = sK + 2 * FA_T64;
-        if (t + 1 < nkt) stage.fetch(t + 1);
+        if (t + 1 < ktiles.end) stage.fetch(t + 1);
         const int j0 = t * FA_KT;
         // ---- band R^T: rows = positions 16 (3 - wave + rt) + 4 q4 + r of the staged 128, columns = queries -> strip
         fa_band_to_strip(sP, sR, (3 - wave) * 16, Qv, c, q4);
@@ -107,9 +114,9 @@ __global__ __launch_bounds__(FA_THREADS, 3) void relpos_flash_fwd_kernel(FaArgs 
         }
         // ---- scores: lane (query c, q4), key j = j0 + 16 jt + 4 q4 + r; band element at strip column 16 jt + 4 q4 + r + 16
         // scores in base-2 units (scale * log2 e folded into one multiply, exp2 directly: no multiply per exponential); the
-        // length mask only exists in the tile that straddles the length (uniform branch)
+        // mask only exists in the tiles that straddle the length or the window's edge (uniform branch)
         float tmax = IA_NEG_INF;
-        if (j0 + FA_KT <= len) {
+        if (span.tile_unmasked(j0, iw, len)) {
 #pragma unroll
             for (int jt = 0; jt < 4; ++jt) {
                 union { uint2 u; __bf16 e[4]; } bd;
@@ -122,6 +129,7 @@ __global__ __launch_bounds__(FA_THREADS, 3) void relpos_flash_fwd_kernel(FaArgs 
                 }
             }
         } else {
+            const auto admitted = span.admit(iq, true, len);   // this query's keys
 #pragma unroll
             for (int jt = 0; jt < 4; ++jt) {
                 union { uint2 u; __bf16 e[4]; } bd;
@@ -129,7 +137,7 @@ __global__ __launch_bounds__(FA_THREADS, 3) void relpos_flash_fwd_kernel(FaArgs 
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int j = j0 + jt * 16 + q4 * 4 + r;
-                    const float s = (j < len) ? (S[jt][r] + (float)bd.e[r]) * scale2 : IA_NEG_INF;
+                    const float s = admitted(j) ? (S[jt][r] + (float)bd.e[r]) * scale2 : IA_NEG_INF;
                     S[jt][r] = s;
                     tmax = fmaxf(tmax, s);
                 }
@@ -137,8 +145,11 @@ __global__ __launch_bounds__(FA_THREADS, 3) void relpos_flash_fwd_kernel(FaArgs 
         }
         tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
         tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-        const float m_new = fmaxf(m_run, tmax);           // finite: key j0 < len exists in every processed tile
-        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);   // exp2(-inf) = 0 on the first tile
+        const float m_new = fmaxf(m_run, tmax);
+        // the exponentials' reference: the new maximum; 0 while a sparse span has shown this query no key (-inf - -inf = NaN)
+        float m_ref = m_new;
+        if constexpr (Span::kSparseTiles) m_ref = (m_new == IA_NEG_INF) ? 0.f : m_new;
+        const float alpha = __builtin_amdgcn_exp2f(m_run - m_ref);   // exp2(-inf) = 0 on the first tile
         m_run = m_new;
         float psum = 0.f;
         bf8 Pf[2];
@@ -148,7 +159,7 @@ __global__ __launch_bounds__(FA_THREADS, 3) void relpos_flash_fwd_kernel(FaArgs 
             if (a.thr > 0) rnd4 = fa_keep_rand4(a.seed, bh, T, iq, (j0 + jt * 16 + q4 * 4) >> 2);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                float p = __builtin_amdgcn_exp2f(S[jt][r] - m_new);   // exp2(-inf) = 0 for excluded keys
+                float p = __builtin_amdgcn_exp2f(S[jt][r] - m_ref);   // exp2(-inf) = 0 for excluded keys
                 psum += p;
                 // (the keep scale 1/(1-p) of the dropout is applied once, to the normalised output)
                 if (a.thr > 0) p = (((rnd4 >> (8 * r)) & 0xFFu) >= a.thr) ? p : 0.f;
@@ -173,7 +184,7 @@ __global__ __launch_bounds__(FA_THREADS, 3) void relpos_flash_fwd_kernel(FaArgs 
                 O[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, Pf[kk], O[mt], 0, 0, 0);
             }
         __syncthreads();                      // every wave is done with the stage
-        if (t + 1 < nkt) {
+        if (t + 1 < ktiles.end) {
             stage.commit();
             __syncthreads();
         }
@@ -186,8 +197,29 @@ __global__ __launch_bounds__(FA_THREADS, 3) void relpos_flash_fwd_kernel(FaArgs 
         if (a.lse && q4 == 0) a.lse[(size_t)bh * T + iq] = (iq < len && l_run > 0.f) ? (m_run + __builtin_amdgcn_logf(l_run)) * 0.69314718055994531f : 0.f;
         const float inv = (iq < len && l_run > 0.f) ? a.keep_scale / l_run : 0.f;
 #pragma unroll
-        for (int mt = 0; mt < 4; ++mt) fa_store_head4(orow, mt, q4, dk, O[mt], inv);
+        for (int mt = 0; mt < 4; ++mt) {
+            f4 o = O[mt];
+            // under a sparse span a padded query's accumulator is finite but arbitrary: zero by value, not by 0 * x
+            if constexpr (Span::kSparseTiles) o = (iq < len) ? O[mt] : (f4){0.f, 0.f, 0.f, 0.f};
+            fa_store_head4(orow, mt, q4, dk, o, inv);
+        }
     }
+}
+
+// host: the forward under one span, after the entry point's argument checks
+template <class Span>
+int fa_forward(const void* qkv, const __bf16* pl, const float* bias_u, const float* bias_v, const int64_t* lens, int B, int T, int H,
+               int dk, int w, float dropout_p, unsigned seed, void* ctx, float* lse, ia_stream_t stream) {
+    FaArgs a;
+    a.qkv = (const __bf16*)qkv; a.pl = pl; a.bias_u = bias_u; a.bias_v = bias_v; a.lens = lens;
+    a.lse = lse;
+    a.ctx = (__bf16*)ctx; a.B = B; a.T = T; a.H = H; a.dk = dk; a.w = w; a.scale = 1.f / sqrtf((float)dk); a.seed = seed;
+    const ia_dropout_t drop = ia_dropout_rule(dropout_p);
+    a.thr = drop.thr; a.keep_scale = drop.keep_scale;
+    const int nqt = (T + 63) / 64;
+    const int grid = 8 * ((B * H + 7) / 8) * nqt;
+    return fa_launch<FaArgs, relpos_flash_fwd_kernel<true, Span>, relpos_flash_fwd_kernel<false, Span>>(
+        dk == 64 && (H * dk) % 8 == 0, grid, FA_LDS, (hipStream_t)stream, a);
 }
 
 }  // namespace
@@ -207,15 +239,28 @@ extern "C" int ia_relpos_attention_flash_lse(const void* qkv, const void* pos_pr
     if (!ia_relpos_attention_flash_supported(T, dk)) return IA_UNSUPPORTED;
     if (dropout_p < 0.f || dropout_p >= 1.f) return IA_INVALID_VALUE;
     if (!ia_is_aligned(qkv, 16) || !ia_is_aligned(pos_proj, 16) || !ia_is_aligned(ctx, 8)) return IA_INVALID_VALUE;
-    FaArgs a;
-    a.qkv = (const __bf16*)qkv; a.pl = (const __bf16*)pos_proj; a.bias_u = bias_u; a.bias_v = bias_v; a.lens = lens;
-    a.lse = lse;
-    a.ctx = (__bf16*)ctx; a.B = B; a.T = T; a.H = H; a.dk = dk; a.scale = 1.f / sqrtf((float)dk); a.seed = seed;
-    const ia_dropout_t drop = ia_dropout_rule(dropout_p);
-    a.thr = drop.thr; a.keep_scale = drop.keep_scale;
-    const int nqt = (T + 63) / 64;
-    const int grid = 8 * ((B * H + 7) / 8) * nqt;
-    hipStream_t st = (hipStream_t)stream;
-    return fa_launch<FaArgs, relpos_flash_fwd_kernel<true>, relpos_flash_fwd_kernel<false>>(dk == 64 && (H * dk) % 8 == 0, grid, FA_LDS,
-                                                                                            st, a);
+    return fa_forward<FaFullSpan>(qkv, (const __bf16*)pos_proj, bias_u, bias_v, lens, B, T, H, dk, T - 1, dropout_p, seed, ctx, lse, stream);
+}
+
+extern "C" int ia_relpos_attention_local_supported(int T, int dk, int window) {
+    return (window >= 1 && ia_relpos_attention_flash_supported(T, dk)) ? 1 : 0;
+}
+
+extern "C" int ia_relpos_attention_local(const void* qkv, const void* pos_proj, const float* bias_u, const float* bias_v,
+                                         const int64_t* lens, int B, int T, int H, int dk, int window, float dropout_p,
+                                         unsigned seed, void* ctx, ia_stream_t stream) {
+    return ia_relpos_attention_local_lse(qkv, pos_proj, bias_u, bias_v, lens, B, T, H, dk, window, dropout_p, seed, ctx, nullptr, stream);
+}
+
+extern "C" int ia_relpos_attention_local_lse(const void* qkv, const void* pos_proj, const float* bias_u, const float* bias_v,
+                                             const int64_t* lens, int B, int T, int H, int dk, int window, float dropout_p,
+                                             unsigned seed, void* ctx, float* lse, ia_stream_t stream) {
+    if (!qkv || !pos_proj || !bias_u || !bias_v || !lens || !ctx || B <= 0 || T <= 0 || H <= 0 || window <= 0) return IA_INVALID_VALUE;
+    if (!ia_relpos_attention_local_supported(T, dk, window)) return IA_UNSUPPORTED;
+    if (dropout_p < 0.f || dropout_p >= 1.f) return IA_INVALID_VALUE;
+    if (!ia_is_aligned(qkv, 16) || !ia_is_aligned(pos_proj, 16) || !ia_is_aligned(ctx, 8)) return IA_INVALID_VALUE;
+    // a window beyond T - 1 admits no further key: the same band with w' = T - 1 and the table advanced by w - w' rows
+    const int w = window < T - 1 ? window : T - 1;
+    return fa_forward<FaLocalSpan>(qkv, (const __bf16*)pos_proj + (size_t)(window - w) * ((size_t)H * dk), bias_u, bias_v, lens, B, T, H,
+                                   dk, w, dropout_p, seed, ctx, lse, stream);
 }

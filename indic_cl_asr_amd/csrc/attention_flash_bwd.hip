@@ -1,32 +1,34 @@
-// Relative-position multi-head self-attention BACKWARD, key-tiled (gfx950): no [T,T] probability / score-gradient
-// matrices in HBM, any T, head dim any multiple of 4 up to 64.  Autograd of RelPositionMultiHeadAttention.forward
-// (A/parts/submodules/multi_head_attention.py:197-250) with the forward of attention_flash.hip (same dropout hash, the
-// forward's per-query log-sum-exp):
+// Relative-position multi-head self-attention BACKWARD, key-tiled (gfx950), full or local by its Span: no [T,T] probability /
+// score-gradient matrices in HBM, any T, head dim any multiple of 4 up to 64.  Autograd of RelPositionMultiHeadAttention.forward
+// (A/parts/submodules/multi_head_attention.py:197-250; local span: of the band |i - j| <= w of
+// RelPositionMultiHeadAttentionLongformer.forward) with the forward of attention_flash.hip (same span and tile ranges, same
+// dropout hash, the forward's per-query log-sum-exp).  c = the span's centre, T - 1 or w:
 //
-//   s_ij = ((q_i+u).k_j + (q_i+v).p[T-1-i+j]) / sqrt(dk),  P = exp(s - lse_i) (j < len, i < len),  Pd = dropout(P)
-//   dP = keep o (dO V^T),  D_i = dO_i . O_i,  dS = P o (dP - D) / sqrt(dk)
-//   d(q+u) = dS K     d(q+v)_i = sum_j dS_ij p[T-1-i+j]     dK = dS^T (q+u)     dV = Pd^T dO
-//   dp[r] = sum_{b,i} dS_{i, r-(T-1)+i} (q_i+v)      dq = d(q+u) + d(q+v)     du = sum d(q+u)    dv = sum d(q+v)
+//   s_ij = ((q_i+u).k_j + (q_i+v).p[c-i+j]) / sqrt(dk),  admissible iff j < len, i < len (and |i-j| <= w)
+//   P = exp(s - lse_i) on admissible pairs, else 0 (by value: a clamped position row gives a finite score that means nothing)
+//   Pd = dropout(P),  dP = keep o (dO V^T),  D_i = dO_i . O_i,  dS = P o (dP - D) / sqrt(dk)
+//   d(q+u) = dS K     d(q+v)_i = sum_j dS_ij p[c-i+j]     dK = dS^T (q+u)     dV = Pd^T dO
+//   dp[r] = sum_{b,i} dS_{i, r-c+i} (q_i+v)      dq = d(q+u) + d(q+v)     du = sum d(q+u)    dv = sum d(q+v)
 //
 // Two kernels, each owning its outputs exclusively (no atomics, bit-reproducible):
 //   relpos_flash_bwd_q_kernel   workgroup = (utterance, head, 64 queries), 4 waves x 16 queries, walks the key tiles like
 //       the forward (transposed accumulators: lane = query).  Recomputes R^T, S^T, P; dP^T = V dO^T; dS.  dS is the B
 //       operand of d(q+u)^T += K^T dS^T as it lies in the accumulators, and goes through a wave-private band strip
 //       [query][band row] for d(q+v)^T += P_band^T dS_band^T (band row rr = j - j0 + 15 - il: the inverse of the forward's
-//       skew).  The same strip, tile by tile, is the band-skewed dS on the absolute relative-position axis
-//       dBand[h][b*T+i][pad0 + T-1-i+j] that the position-projection gradient dp = dBand^T (q+v) contracts as a plain
-//       TN GEMM (csrc/gemm_tn.hip) -- the one [T, 2T] matrix that still goes through HBM.
+//       skew).  The same strip, tile by tile, is the band-skewed dS on the relative-position axis
+//       dBand[h][b*T+i][pad0 + c-i+j] that the position-projection gradient dp = dBand^T (q+v) contracts as a plain TN GEMM
+//       (csrc/gemm_tn.hip) -- the one matrix that still goes through HBM, [T, ~2T] under the full span and [T, ~2w] under the
+//       local one.  Strip column s of (wave iw, tile j0) is relative position c - iw - 15 + j0 + s on an UNCLAMPED axis:
+//       consecutive tiles continue each other's columns (64 per tile, the last 16 carried into the next tile's flush), so every
+//       dBand element of a query row has one writer; what no (wave, tile) writes is the memset's zero.
 //   relpos_flash_bwd_kv_kernel  workgroup = (utterance, head, 64 keys), 4 waves x 16 keys (lane = key), walks the query
 //       tiles.  S = (Q+u) K^T and the band (q+v) p^T in the key-major orientation (two 16x16 position tiles per 16
 //       queries, re-indexed through a wave-private strip), P, dP, then dV^T += dO^T Pd and dK^T += (Q+u)^T dS with the
 //       probabilities / score gradients used as B operands straight from the accumulators and the A operands read from
 //       the row-major query tiles with ds_read_b64_tr_b16.
 // LDS tiles: 128-byte rows (64 bf16, zero-padded beyond dk), 16-byte slots XOR-swizzled by row & 7, one stage + register
-// prefetch of the next tile (two workgroups per CU hide the two barriers per tile).  Tile constants, the swizzled addresses and
-// fragment reads, the register staging (the query-owner uses the forward's K | V | P stage as it is, the key-owner builds its
-// Qu | Qv | dO | P | lse, D stage from the same fetch / commit pair), the band block, the query fragments, the workgroup
-// coordinates and the head-row store are attention_flash.h's, shared with the forward; tests/test_attention_flash_digests_gpu.py
-// pins dqkv, dpl and the bias gradients bit for bit.
+// prefetch of the next tile (two workgroups per CU hide the two barriers per tile).  The query-owner uses the forward's
+// K | V | P stage as it is, the key-owner builds its Qu | Qv | dO | P | lse, D stage from the same fetch / commit pair.
 #include "attention_flash.h"
 #include "partials.h"
 
@@ -36,16 +38,24 @@ struct FbArgs {
     const __bf16* qkv; const __bf16* pl; const float* bias_u; const float* bias_v; const int64_t* lens;
     const __bf16* ctx; const __bf16* dctx; const float* lse;
     __bf16* dqkv; __bf16* dBand; __bf16* QvHM; float* D; float* part;
-    int B, T, H, dk, Rs, pad0; float scale; unsigned seed, thr; float keep_scale;
+    int B, T, H, dk, w, Rs, pad0; float scale; unsigned seed, thr; float keep_scale;   // w: the local span's, 0 <= w <= T - 1
 };
 
+// a 16-byte chunk at dBand column gcol is written: inside [0, rs) of a bounded band, right of column 0 of an unbounded one
+template <class Span>
+__device__ __forceinline__ bool fb_chunk_in_row(int gcol, int rs) {
+    if constexpr (Span::kBoundedBand) return gcol >= 0 && gcol + 8 <= rs;
+    else return gcol >= 0;
+}
+
 // ======================================================================================================== query-owner
-template <bool DK64>
+template <bool DK64, class Span>
 __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 15, q4 = lane >> 4;
     const int T = a.T, H = a.H, dk = a.dk, d = H * dk, B = a.B;
+    const Span span(T, a.w);
     const int nqt = (T + 63) / 64;
     const FaWg wg = fa_wg(B, T, H, a.lens);
     if (wg.len < 0) return;
@@ -94,10 +104,11 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArg
     unsigned char* sB = sR + 16 * FA_SR_LD * 2;                               // dS band strip      [16][120] bf16
     for (int i = lane; i < 16 * FB_SB_LD * 2 / 16; i += 64) reinterpret_cast<uint4*>(sB)[i] = make_uint4(0, 0, 0, 0);
 
-    FaKvpStage<DK64> stage(a.qkv, a.pl, smem, b, h, T, d, dk, I0, tid);
+    FaKvpStage<DK64> stage(a.qkv, a.pl, smem, b, h, T, d, dk, I0, span.centre(), tid);
 
-    const int nkt = (len + 63) / 64;
-    stage.fetch(0);
+    const FaTiles ktiles = span.tiles(I0, len);                  // the key tiles of this query tile, as the forward walks them
+    const auto admitted = span.admit(iq, qvalid, len);       // this query's keys
+    stage.fetch(ktiles.lo);
     stage.commit();
     __syncthreads();
 
@@ -110,8 +121,8 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArg
     const bool fvalid = iw + frow < T;
     const int pw0 = (3 - wave) * 16;   // first staged position row of this wave's band
 
-    for (int t = 0; t < nkt; ++t) {
-        if (t + 1 < nkt) stage.fetch(t + 1);
+    for (int t = ktiles.lo; t < ktiles.end; ++t) {
+        if (t + 1 < ktiles.end) stage.fetch(t + 1);
         const int j0 = t * 64;
         // ---- R^T (band) -> forward strip
         fa_band_to_strip(sP, sR, pw0, Qv, c, q4);
@@ -141,7 +152,7 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArg
             for (int r = 0; r < 4; ++r) {
                 const int j = j0 + jt * 16 + q4 * 4 + r;
                 const float s = (S[jt][r] + (float)bd.e[r]) * a.scale;
-                const float p = (qvalid && j < len) ? __expf(s - lse_i) : 0.f;
+                const float p = admitted(j) ? __expf(s - lse_i) : 0.f;
                 float g = dP[jt][r];
                 if (a.thr > 0) g = (((rnd4 >> (8 * r)) & 0xFFu) >= a.thr) ? g * a.keep_scale : 0.f;
                 const float ds = p * (g - Drow) * a.scale;
@@ -180,7 +191,8 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArg
             for (int mt = 0; mt < 4; ++mt) {
                 const int qq = c >> 2, p = c & 3;
                 int rowA = pw0 + kk * 32 + q4 * 8 + qq, rowB = rowA + 4;
-                rowA = rowA < 127 ? rowA : 127; rowB = rowB < 127 ? rowB : 127;   // band rows >= 79 are zero in the strip
+                // band rows >= 79 are zero in the strip; so are the band rows of clamped position rows (inadmissible pairs)
+                rowA = rowA < 127 ? rowA : 127; rowB = rowB < 127 ? rowB : 127;
                 const bf8 pf = fa_tr_pair(sP, rowA, rowB, mt * 2 + (p >> 1), p & 1);
                 dQv[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, bfrag, dQv[mt], 0, 0, 0);
             }
@@ -199,15 +211,17 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArg
                 *reinterpret_cast<uint4*>(sB + (frow * FB_SB_LD + 96) * 2) = n0;
                 *reinterpret_cast<uint4*>(sB + (frow * FB_SB_LD + 104) * 2) = n1;
             }
+            // gcol (and a bounded band's Rs) are multiples of 8: a 16-byte chunk lies inside the dBand row or outside it, and
+            // outside it every value is an inadmissible pair's zero.  Unbounded band: gcol is negative only in a partial last
+            // wave (T - iw < 16), whose leading band columns are all zero
             if (fvalid) {
-                // multiple of 8; negative only in a partial last wave (T - iw < 16), whose leading band columns are all zero
-                const int gcol = T - 16 - iw + j0 + a.pad0 + fch * 8;
-                if (gcol >= 0) *reinterpret_cast<uint4*>(brow + gcol) = v0;
-                if (gcol + 8 >= 0) *reinterpret_cast<uint4*>(brow + gcol + 8) = v1;
+                const int gcol = span.centre() - 15 - iw + j0 + a.pad0 + fch * 8;
+                if (fb_chunk_in_row<Span>(gcol, a.Rs)) *reinterpret_cast<uint4*>(brow + gcol) = v0;
+                if (fb_chunk_in_row<Span>(gcol + 8, a.Rs)) *reinterpret_cast<uint4*>(brow + gcol + 8) = v1;
             }
         }
         __syncthreads();
-        if (t + 1 < nkt) {
+        if (t + 1 < ktiles.end) {
             stage.commit();
             __syncthreads();
         }
@@ -215,9 +229,11 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArg
     // ---- last carry -> dBand columns 64 .. 79 behind the last processed tile
     fb_lds_fence();
     if ((lane & 3) == 0 && fvalid) {
-        const int gcol = T - 16 - iw + (nkt - 1) * 64 + a.pad0 + 64;
-        *reinterpret_cast<uint4*>(brow + gcol) = *reinterpret_cast<const uint4*>(sB + (frow * FB_SB_LD + 96) * 2);
-        *reinterpret_cast<uint4*>(brow + gcol + 8) = *reinterpret_cast<const uint4*>(sB + (frow * FB_SB_LD + 104) * 2);
+        const int gcol = span.centre() - 15 - iw + (ktiles.end - 1) * 64 + a.pad0 + 64;
+        const uint4 c0 = *reinterpret_cast<const uint4*>(sB + (frow * FB_SB_LD + 96) * 2);
+        const uint4 c1 = *reinterpret_cast<const uint4*>(sB + (frow * FB_SB_LD + 104) * 2);
+        if (!Span::kBoundedBand || fb_chunk_in_row<Span>(gcol, a.Rs)) *reinterpret_cast<uint4*>(brow + gcol) = c0;
+        if (!Span::kBoundedBand || fb_chunk_in_row<Span>(gcol + 8, a.Rs)) *reinterpret_cast<uint4*>(brow + gcol + 8) = c1;
     }
     // ---- dq = d(q+u) + d(q+v): lane (query c, q4) holds e = 16 mt + 4 q4 + r
     if (iq < T) {
@@ -247,12 +263,13 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArg
 }
 
 // ========================================================================================================== key-owner
-template <bool DK64>
+template <bool DK64, class Span>
 __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_kv_kernel(FbArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 15, q4 = lane >> 4;
     const int T = a.T, H = a.H, dk = a.dk, d = H * dk, B = a.B;
+    const Span span(T, a.w);
     const FaWg wg = fa_wg(B, T, H, a.lens);
     if (wg.len < 0) return;
     const int bh = wg.bh, kt = wg.tile, h = wg.h, b = wg.b, len = wg.len;
@@ -304,11 +321,12 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_kv_kernel(FbAr
     const __bf16* qbase = a.qkv + (size_t)b * T * (3 * d) + h * dk;
     const __bf16* gbase = a.dctx + (size_t)b * T * d + h * dk;
     const __bf16* pbase = a.pl + h * dk;
-    const auto fetch = [&](int t) {
+    const int centre = span.centre();
+    const auto fetch = [&](int t) {   // position rows centre - i0 - 63 + J0 .. + 127 clamped to [0, 2 centre]
         const int i0 = t * 64;
         fa_fetch_rows<DK64, false>(rq, qbase, 3 * d, i0, T - 1, dk, tid);
         fa_fetch_rows<DK64, false>(rg, gbase, d, i0, T - 1, dk, tid);
-        fa_fetch_rows<DK64, true>(rp, pbase, d, T - 1 - i0 - 63 + J0, 2 * T - 2, dk, tid);
+        fa_fetch_rows<DK64, true>(rp, pbase, d, centre - i0 - 63 + J0, 2 * centre, dk, tid);
         if (tid < 128) {
             int q = i0 + (tid & 63); q = q < T ? q : T - 1;
             rl = (tid < 64 ? a.lse : a.D)[(size_t)bh * T + q];
@@ -334,8 +352,9 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_kv_kernel(FbAr
         if (tid < 128) reinterpret_cast<float*>(smem + 3 * FA_T64 + FA_PBUF)[tid] = rl;
     };
 
-    const int nqt = (len + 63) / 64;   // query tiles with at least one valid query
-    fetch(0);
+    const FaTiles qtiles = span.tiles(J0, len);                 // the query tiles of this key tile
+    const auto admitted = span.admit(j, kvalid, len);       // this key's queries
+    fetch(qtiles.lo);
     commit();
     __syncthreads();
 
@@ -343,8 +362,8 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_kv_kernel(FbAr
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) { dK[mt] = (f4){0.f, 0.f, 0.f, 0.f}; dV[mt] = (f4){0.f, 0.f, 0.f, 0.f}; }
 
-    for (int t = 0; t < nqt; ++t) {
-        if (t + 1 < nqt) fetch(t + 1);
+    for (int t = qtiles.lo; t < qtiles.end; ++t) {
+        if (t + 1 < qtiles.end) fetch(t + 1);
         const int I0 = t * 64;
         // ---- band: for the 16 queries of tile `it` the wave's keys need position rows n0 .. n0 + 31, n0 = 48 - 16 it + 16 w
         //      X_A[m][n] = (q+v)_{16 it + m} . p[n0 + n], X_B with n0 + 16;  bd[il = 16 it + m][key c] = c <= m ? X_A[m][15 - m + c]
@@ -395,7 +414,9 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_kv_kernel(FbAr
             for (int r = 0; r < 4; ++r) {
                 const int i = I0 + it * 16 + q4 * 4 + r;
                 const float s = (S[it][r] + (float)bd.e[r]) * a.scale;
-                const float p = (kvalid && i < len) ? __expf(s - lsv[r]) : 0.f;
+                // the exponential unconditionally, then the select: behind a branch this kernel spills 4 to 12 B per lane more
+                const float e = __expf(s - lsv[r]);
+                const float p = admitted(i) ? e : 0.f;
                 float g = dP[it][r], pd = p;
                 if (a.thr > 0) {
                     const unsigned rnd = (fa_keep_rand4(a.seed, bh, T, i, j >> 2) >> (8 * (j & 3))) & 0xFFu;
@@ -421,7 +442,7 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_kv_kernel(FbAr
                 dK[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, dSf[kk], dK[mt], 0, 0, 0);
             }
         __syncthreads();
-        if (t + 1 < nqt) {
+        if (t + 1 < qtiles.end) {
             commit();
             __syncthreads();
         }
@@ -435,6 +456,41 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_kv_kernel(FbAr
     }
 }
 
+// host: the backward under one span, after the entry point's argument checks: both kernels, the bias-partials pass and the
+// position gradient.  dBand [H, B*T, rs] holds relative positions 0 .. 2w behind p0 columns; they go to rows 0 .. 2w of
+// dpl [pl_rows, d], zero rows behind them.
+template <class Span>
+int fb_backward(const void* qkv, const __bf16* pl, const float* bias_u, const float* bias_v, const int64_t* lens, const void* ctx,
+                const void* dctx, const float* lse, int B, int T, int H, int dk, int w, int rs, int p0, float dropout_p, unsigned seed,
+                void* dqkv, __bf16* dpl, int pl_rows, float* dbias_u, float* dbias_v, void* dBand, void* QvHM, float* ws,
+                ia_stream_t stream) {
+    const FbWs lay = fb_ws_layout(B, T, H, dk, rs);
+    FbArgs a;
+    a.qkv = (const __bf16*)qkv; a.pl = pl; a.bias_u = bias_u; a.bias_v = bias_v; a.lens = lens;
+    a.ctx = (const __bf16*)ctx; a.dctx = (const __bf16*)dctx; a.lse = lse; a.dqkv = (__bf16*)dqkv; a.dBand = (__bf16*)dBand;
+    a.QvHM = (__bf16*)QvHM; a.D = ws + lay.D; a.part = ws + lay.part; a.B = B; a.T = T; a.H = H; a.dk = dk; a.w = w;
+    a.Rs = rs; a.pad0 = p0;
+    a.scale = 1.f / sqrtf((float)dk); a.seed = seed;
+    const ia_dropout_t drop = ia_dropout_rule(dropout_p);
+    a.thr = drop.thr; a.keep_scale = drop.keep_scale;
+    hipStream_t st = (hipStream_t)stream;
+    // band columns no (wave, tile) flushes (keys beyond the length or the window, rows of padded queries) stay zero
+    if (hipMemsetAsync(dBand, 0, (size_t)H * B * T * rs * sizeof(__bf16), st) != hipSuccess) return IA_LAUNCH_FAILED;
+    const int nt = (T + 63) / 64;
+    const int grid = 8 * ((B * H + 7) / 8) * nt;
+    const bool full = (dk == 64);
+    int rc = fa_launch<FbArgs, relpos_flash_bwd_q_kernel<true, Span>, relpos_flash_bwd_q_kernel<false, Span>>(full, grid, FB_Q_LDS, st, a);
+    if (rc != IA_OK) return rc;
+    rc = fa_launch<FbArgs, relpos_flash_bwd_kv_kernel<true, Span>, relpos_flash_bwd_kv_kernel<false, Span>>(full, grid, FB_KV_LDS, st, a);
+    if (rc != IA_OK) return rc;
+    ia_partials_finish(a.part, B * nt, 2 * H * dk, H * dk, dbias_u, dbias_v, st);
+    IA_RETURN_IF_LAUNCH_FAILED();
+    // position-projection gradient: the band columns p0 .. p0 + 2w of the heads' TN GEMMs
+    return fb_dpos_gemm_pack(dBand, QvHM, ws, lay, rs, p0, 2 * w + 1, B, T, H, dk, dpl, pl_rows, stream);
+}
+
+inline int fb_window(int T, int window) { return window < T - 1 ? window : T - 1; }   // a window beyond T - 1 admits no further key
+
 }  // namespace
 
 extern "C" int ia_relpos_attention_flash_bwd_dims(int T, int* Rs, int* pad0) {
@@ -447,17 +503,11 @@ extern "C" int ia_relpos_attention_flash_bwd_dims(int T, int* Rs, int* pad0) {
     return IA_OK;
 }
 
-namespace {
-inline FbWs fb_full_ws_layout(int B, int T, int H, int dk) {
-    int rs, p0;
-    ia_relpos_attention_flash_bwd_dims(T, &rs, &p0);
-    return fb_ws_layout(B, T, H, dk, rs);
-}
-}  // namespace
-
 extern "C" int64_t ia_relpos_attention_flash_bwd_ws_elems(int B, int T, int H, int dk) {
+    int rs, p0;
     if (B <= 0 || T <= 0 || H <= 0 || dk <= 0) return 0;
-    return fb_full_ws_layout(B, T, H, dk).total;
+    ia_relpos_attention_flash_bwd_dims(T, &rs, &p0);
+    return fb_ws_layout(B, T, H, dk, rs).total;
 }
 
 extern "C" int ia_relpos_attention_flash_bwd(const void* qkv, const void* pos_proj, const float* bias_u, const float* bias_v,
@@ -474,29 +524,49 @@ extern "C" int ia_relpos_attention_flash_bwd(const void* qkv, const void* pos_pr
         !ia_is_aligned(dqkv, 8) || !ia_is_aligned(dBand, 16) || !ia_is_aligned(QvHM, 16) || !ia_is_aligned(ws, 16) ||
         !ia_is_aligned(dpl, 8))
         return IA_INVALID_VALUE;
-    const FbWs w = fb_full_ws_layout(B, T, H, dk);
-    FbArgs a;
-    a.qkv = (const __bf16*)qkv; a.pl = (const __bf16*)pos_proj; a.bias_u = bias_u; a.bias_v = bias_v; a.lens = lens;
-    a.ctx = (const __bf16*)ctx; a.dctx = (const __bf16*)dctx; a.lse = lse; a.dqkv = (__bf16*)dqkv; a.dBand = (__bf16*)dBand;
-    a.QvHM = (__bf16*)QvHM; a.D = ws + w.D; a.part = ws + w.part; a.B = B; a.T = T; a.H = H; a.dk = dk;
     int rs, p0;
     ia_relpos_attention_flash_bwd_dims(T, &rs, &p0);
-    a.Rs = rs; a.pad0 = p0;
-    a.scale = 1.f / sqrtf((float)dk); a.seed = seed;
-    const ia_dropout_t drop = ia_dropout_rule(dropout_p);
-    a.thr = drop.thr; a.keep_scale = drop.keep_scale;
-    hipStream_t st = (hipStream_t)stream;
-    // band columns outside the processed key tiles (keys beyond the length, rows of padded queries) stay zero
-    if (hipMemsetAsync(dBand, 0, (size_t)H * B * T * rs * sizeof(__bf16), st) != hipSuccess) return IA_LAUNCH_FAILED;
-    const int nt = (T + 63) / 64;
-    const int grid = 8 * ((B * H + 7) / 8) * nt;
-    const bool full = (dk == 64);
-    int rc = fa_launch<FbArgs, relpos_flash_bwd_q_kernel<true>, relpos_flash_bwd_q_kernel<false>>(full, grid, FB_Q_LDS, st, a);
-    if (rc != IA_OK) return rc;
-    rc = fa_launch<FbArgs, relpos_flash_bwd_kv_kernel<true>, relpos_flash_bwd_kv_kernel<false>>(full, grid, FB_KV_LDS, st, a);
-    if (rc != IA_OK) return rc;
-    ia_partials_finish(a.part, B * nt, 2 * H * dk, H * dk, dbias_u, dbias_v, st);
-    IA_RETURN_IF_LAUNCH_FAILED();
-    // position-projection gradient: the band columns pad0 .. pad0 + 2T-2 of the heads' TN GEMMs go to dpl [pl_rows, d] bf16
-    return fb_dpos_gemm_pack(dBand, QvHM, ws, w, rs, p0, 2 * T - 1, B, T, H, dk, dpl, pl_rows, stream);
+    return fb_backward<FaFullSpan>(qkv, (const __bf16*)pos_proj, bias_u, bias_v, lens, ctx, dctx, lse, B, T, H, dk, T - 1, rs, p0, dropout_p,
+                                   seed, dqkv, (__bf16*)dpl, pl_rows, dbias_u, dbias_v, dBand, QvHM, ws, stream);
+}
+
+extern "C" int ia_relpos_attention_local_bwd_dims(int T, int window, int* Rs, int* pad0) {
+    if (T <= 0 || window <= 0 || !Rs || !pad0) return IA_INVALID_VALUE;
+    const int w = fb_window(T, window);
+    const int p0 = (8 - (w + 1) % 8) % 8;         // (w - 15 - iw + pad0) % 8 == 0: every flushed chunk starts on a 16-byte column
+    *pad0 = p0;
+    *Rs = (p0 + 2 * w + 1 + 7) / 8 * 8;           // relative positions 0 .. 2w behind pad0: no term in T
+    return IA_OK;
+}
+
+extern "C" int64_t ia_relpos_attention_local_bwd_ws_elems(int B, int T, int H, int dk, int window) {
+    int rs, p0;
+    if (B <= 0 || H <= 0 || dk <= 0 || ia_relpos_attention_local_bwd_dims(T, window, &rs, &p0) != IA_OK) return 0;
+    return fb_ws_layout(B, T, H, dk, rs).total;
+}
+
+extern "C" int ia_relpos_attention_local_bwd(const void* qkv, const void* pos_proj, const float* bias_u, const float* bias_v,
+                                             const int64_t* lens, const void* ctx, const void* dctx, const float* lse, int B,
+                                             int T, int H, int dk, int window, float dropout_p, unsigned seed, void* dqkv,
+                                             void* dpl, int pl_rows, float* dbias_u, float* dbias_v, void* dBand, void* QvHM,
+                                             float* ws, ia_stream_t stream) {
+    if (!qkv || !pos_proj || !bias_u || !bias_v || !lens || !ctx || !dctx || !lse || !dqkv || !dpl || !dBand || !QvHM || !ws ||
+        !dbias_u || !dbias_v || B <= 0 || T <= 0 || H <= 0 || window <= 0 || (int64_t)pl_rows < 2 * (int64_t)window + 1)
+        return IA_INVALID_VALUE;
+    if (!ia_relpos_attention_local_supported(T, dk, window)) return IA_UNSUPPORTED;
+    if (dropout_p < 0.f || dropout_p >= 1.f) return IA_INVALID_VALUE;
+    if (!ia_is_aligned(qkv, 16) || !ia_is_aligned(pos_proj, 16) || !ia_is_aligned(ctx, 8) || !ia_is_aligned(dctx, 8) ||
+        !ia_is_aligned(dqkv, 8) || !ia_is_aligned(dBand, 16) || !ia_is_aligned(QvHM, 16) || !ia_is_aligned(ws, 16) ||
+        !ia_is_aligned(dpl, 8))
+        return IA_INVALID_VALUE;
+    // as the forward: the band of w' = min(window, T - 1) on the table advanced by window - w' rows; so are dpl's rows, and the
+    // rows in front of them are zero
+    const int w = fb_window(T, window), row0 = window - w;
+    const size_t d = (size_t)H * dk;
+    int rs, p0;
+    ia_relpos_attention_local_bwd_dims(T, window, &rs, &p0);
+    if (row0 > 0 && hipMemsetAsync(dpl, 0, (size_t)row0 * d * sizeof(__bf16), (hipStream_t)stream) != hipSuccess) return IA_LAUNCH_FAILED;
+    return fb_backward<FaLocalSpan>(qkv, (const __bf16*)pos_proj + (size_t)row0 * d, bias_u, bias_v, lens, ctx, dctx, lse, B, T, H, dk, w, rs,
+                                    p0, dropout_p, seed, dqkv, (__bf16*)dpl + (size_t)row0 * d, pl_rows - row0, dbias_u, dbias_v, dBand,
+                                    QvHM, ws, stream);
 }

@@ -5,7 +5,7 @@ GLU+depthwise conv+BatchNorm+SiLU, rel-pos attention) keeping the intermediates 
 chain rule: bf16 library GEMMs for the data gradients, batched split-K GEMMs for the weight gradients, and the
 kernels of csrc/encoder_bwd.hip for everything in between; the attention core is the key-tiled pair
 csrc/attention_flash.hip / attention_flash_bwd.hip (any T, no [T,T] matrices in HBM) or, for a layer with a local window,
-csrc/attention_local.hip / attention_local_bwd.hip (O(T w)) in the per-op node.
+csrc/attention_flash.hip / attention_flash_bwd.hip under their local span (O(T w)) in the per-op node.
 
 Semantics: ConformerLayer.forward, A/parts/submodules/conformer_modules.py:141-214 (bf16 projections, fp32 residual
 stream / norms / BatchNorm statistics), dropout masks are counter-based and regenerated in the backward.

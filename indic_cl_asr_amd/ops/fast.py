@@ -435,99 +435,95 @@ def attention_flash_supported(T, dk):
     return bool(_lib.lib().ia_relpos_attention_flash_supported(int(T), int(dk)))
 
 
-def relpos_attention_flash(qkv_bf16, pos_proj_bf16, bias_u, bias_v, lens, B, T, H, dk, dropout_p=0.0, seed=0, want_lse=False):
-    """qkv [B*T, 3*H*dk] bf16, pos_proj [>= 2T-1, H*dk] bf16 -> ctx [B*T, H*dk] bf16: key-tile loop with online softmax
-    (csrc/attention_flash.hip), any T, head dim <= 64.  want_lse: also the per-query log-sum-exp [B*H, T] f32 that
-    relpos_attention_flash_bwd needs -> (ctx, lse)."""
-    ctx = torch.empty(B * T, H * dk, dtype=torch.bfloat16, device=qkv_bf16.device)
-    lse = torch.empty(B * H, T, dtype=torch.float32, device=qkv_bf16.device) if want_lse else None
-    st = _lib.lib().ia_relpos_attention_flash_lse(_lib.ptr(qkv_bf16), _lib.ptr(pos_proj_bf16), _lib.ptr(bias_u), _lib.ptr(bias_v),
-                                                  _lib.ptr(lens), B, T, H, dk, float(dropout_p), int(seed) & 0xFFFFFFFF,
-                                                  _lib.ptr(ctx), _lib.ptr(lse), _lib.stream_ptr())
-    _lib.check(st, "ia_relpos_attention_flash_lse")
-    return (ctx, lse) if want_lse else ctx
-
-
 def attention_local_supported(T, dk, window):
     return bool(_lib.lib().ia_relpos_attention_local_supported(int(T), int(dk), int(window)))
 
 
+def _span(window):
+    """(entry-point infix, extra C arguments) of the key-tiled attention under the full (window None) or the local span."""
+    return ("flash", ()) if window is None else ("local", (int(window),))
+
+
+def _attention_fwd(window, qkv_bf16, pos_proj_bf16, bias_u, bias_v, lens, B, T, H, dk, dropout_p, seed, want_lse):
+    kind, win = _span(window)
+    ctx = torch.empty(B * T, H * dk, dtype=torch.bfloat16, device=qkv_bf16.device)
+    lse = torch.empty(B * H, T, dtype=torch.float32, device=qkv_bf16.device) if want_lse else None
+    name = f"ia_relpos_attention_{kind}_lse"
+    st = getattr(_lib.lib(), name)(_lib.ptr(qkv_bf16), _lib.ptr(pos_proj_bf16), _lib.ptr(bias_u), _lib.ptr(bias_v), _lib.ptr(lens),
+                                   B, T, H, dk, *win, float(dropout_p), int(seed) & 0xFFFFFFFF, _lib.ptr(ctx), _lib.ptr(lse),
+                                   _lib.stream_ptr())
+    _lib.check(st, name)
+    return (ctx, lse) if want_lse else ctx
+
+
+def relpos_attention_flash(qkv_bf16, pos_proj_bf16, bias_u, bias_v, lens, B, T, H, dk, dropout_p=0.0, seed=0, want_lse=False):
+    """qkv [B*T, 3*H*dk] bf16, pos_proj [>= 2T-1, H*dk] bf16 -> ctx [B*T, H*dk] bf16: key-tile loop with online softmax
+    (csrc/attention_flash.hip under the full span), any T, head dim <= 64.  want_lse: also the per-query log-sum-exp [B*H, T] f32
+    that relpos_attention_flash_bwd needs -> (ctx, lse)."""
+    return _attention_fwd(None, qkv_bf16, pos_proj_bf16, bias_u, bias_v, lens, B, T, H, dk, dropout_p, seed, want_lse)
+
+
 def relpos_attention_local(qkv_bf16, pos_proj_bf16, bias_u, bias_v, lens, B, T, H, dk, window, dropout_p=0.0, seed=0, want_lse=False):
-    """Local rel-pos attention forward (csrc/attention_local.hip): query i attends the keys |i - j| <= window, j < len.
+    """Local rel-pos attention forward (the same kernel under the local span): query i attends the keys |i - j| <= window, j < len.
     qkv [B*T, 3*H*dk] bf16, pos_proj [>= 2*window+1, H*dk] bf16 (row r <-> relative position window - r) -> ctx [B*T, H*dk] bf16.
     want_lse: also the per-query log-sum-exp [B*H, T] f32 that relpos_attention_local_bwd needs -> (ctx, lse)."""
     if pos_proj_bf16.shape[0] < 2 * int(window) + 1:
         raise ValueError(f"relpos_attention_local: {pos_proj_bf16.shape[0]} position rows < 2 * {window} + 1")
-    ctx = torch.empty(B * T, H * dk, dtype=torch.bfloat16, device=qkv_bf16.device)
-    lse = torch.empty(B * H, T, dtype=torch.float32, device=qkv_bf16.device) if want_lse else None
-    st = _lib.lib().ia_relpos_attention_local_lse(_lib.ptr(qkv_bf16), _lib.ptr(pos_proj_bf16), _lib.ptr(bias_u), _lib.ptr(bias_v),
-                                                  _lib.ptr(lens), B, T, H, dk, int(window), float(dropout_p),
-                                                  int(seed) & 0xFFFFFFFF, _lib.ptr(ctx), _lib.ptr(lse), _lib.stream_ptr())
-    _lib.check(st, "ia_relpos_attention_local_lse")
-    return (ctx, lse) if want_lse else ctx
+    return _attention_fwd(window, qkv_bf16, pos_proj_bf16, bias_u, bias_v, lens, B, T, H, dk, dropout_p, seed, want_lse)
+
+
+def _attention_bwd_dims(window, T):
+    kind, win = _span(window)
+    rs, p0 = ctypes.c_int(), ctypes.c_int()
+    _lib.check(getattr(_lib.lib(), f"ia_relpos_attention_{kind}_bwd_dims")(int(T), *win, ctypes.byref(rs), ctypes.byref(p0)), "dims")
+    return rs.value, p0.value
+
+
+def attention_flash_bwd_dims(T):
+    return _attention_bwd_dims(None, T)
 
 
 def attention_local_bwd_dims(T, window):
     """(Rs, pad0) of the local backward's dBand [H, B*T, Rs]: Rs = ceil8(pad0 + 2 min(window, T-1) + 1), no term in T."""
-    import ctypes
-    rs, p0 = ctypes.c_int(), ctypes.c_int()
-    _lib.check(_lib.lib().ia_relpos_attention_local_bwd_dims(int(T), int(window), ctypes.byref(rs), ctypes.byref(p0)), "dims")
-    return rs.value, p0.value
+    return _attention_bwd_dims(window, T)
 
 
-def relpos_attention_local_bwd(qkv, pl, bias_u, bias_v, lens, ctx, dctx, lse, B, T, H, dk, window, dropout_p=0.0, seed=0, dub_out=None):
-    """Backward of relpos_attention_local (csrc/attention_local_bwd.hip): operands and results as relpos_attention_flash_bwd, pl
-    [>= 2*window+1, d]; dpl rows beyond 2*window are zero.  dBand, the workspace and the work are O(T * window)."""
+def _attention_bwd(window, qkv, pl, bias_u, bias_v, lens, ctx, dctx, lse, B, T, H, dk, dropout_p, seed, dub_out):
+    kind, win = _span(window)
     L = _lib.lib()
     dev = qkv.device
     d = H * dk
     bf = torch.bfloat16
-    Rs, pad0 = attention_local_bwd_dims(T, window)
+    Rs, pad0 = _attention_bwd_dims(window, T)
     dqkv = torch.empty(B * T, 3 * d, dtype=bf, device=dev)
     dpl = torch.empty_like(pl)
     dBand = torch.empty(H * B * T * Rs, dtype=bf, device=dev)
     QvHM = torch.empty(H * B * T * 64, dtype=bf, device=dev)
-    ws = torch.empty(L.ia_relpos_attention_local_bwd_ws_elems(B, T, H, dk, int(window)), dtype=torch.float32, device=dev)
+    ws = torch.empty(getattr(L, f"ia_relpos_attention_{kind}_bwd_ws_elems")(B, T, H, dk, *win), dtype=torch.float32, device=dev)
     dub = dub_out if dub_out is not None else torch.empty(2, H, dk, dtype=torch.float32, device=dev)
     dctx = dctx.contiguous()
-    st = L.ia_relpos_attention_local_bwd(_lib.ptr(qkv), _lib.ptr(pl), _lib.ptr(bias_u), _lib.ptr(bias_v), _lib.ptr(lens), _lib.ptr(ctx),
-                                         _lib.ptr(dctx), _lib.ptr(lse), B, T, H, dk, int(window), float(dropout_p),
-                                         int(seed) & 0xFFFFFFFF, _lib.ptr(dqkv), _lib.ptr(dpl), pl.shape[0], _lib.ptr(dub[0]),
-                                         _lib.ptr(dub[1]), _lib.ptr(dBand), _lib.ptr(QvHM), _lib.ptr(ws), _lib.stream_ptr())
-    _lib.check(st, "ia_relpos_attention_local_bwd")
+    name = f"ia_relpos_attention_{kind}_bwd"
+    st = getattr(L, name)(_lib.ptr(qkv), _lib.ptr(pl), _lib.ptr(bias_u), _lib.ptr(bias_v), _lib.ptr(lens), _lib.ptr(ctx), _lib.ptr(dctx),
+                          _lib.ptr(lse), B, T, H, dk, *win, float(dropout_p), int(seed) & 0xFFFFFFFF, _lib.ptr(dqkv), _lib.ptr(dpl),
+                          pl.shape[0], _lib.ptr(dub[0]), _lib.ptr(dub[1]), _lib.ptr(dBand), _lib.ptr(QvHM), _lib.ptr(ws),
+                          _lib.stream_ptr())
+    _lib.check(st, name)
     return dqkv, dpl, dub[0], dub[1]
-
-
-def attention_flash_bwd_dims(T):
-    import ctypes
-    rs, p0 = ctypes.c_int(), ctypes.c_int()
-    _lib.check(_lib.lib().ia_relpos_attention_flash_bwd_dims(int(T), ctypes.byref(rs), ctypes.byref(p0)), "dims")
-    return rs.value, p0.value
 
 
 def relpos_attention_flash_bwd(qkv, pl, bias_u, bias_v, lens, ctx, dctx, lse, B, T, H, dk, dropout_p=0.0, seed=0, dub_out=None):
-    """Backward of relpos_attention_flash (csrc/attention_flash_bwd.hip): qkv [B*T,3d], pl [>=2T-1,d], ctx / dctx [B*T,d] bf16,
-    lse [B*H,T] f32 -> (dqkv [B*T,3d] bf16, dpl [pl rows, d] bf16, dbias_u [H,dk] f32, dbias_v [H,dk] f32).  Two key-tiled
-    kernels (query-owner: dq, bias gradients, band-skewed dS; key-owner: dK, dV) + one TN GEMM per head for dpl, all issued
-    by one C call."""
-    L = _lib.lib()
-    dev = qkv.device
-    d = H * dk
-    bf = torch.bfloat16
-    Rs, pad0 = attention_flash_bwd_dims(T)
-    dqkv = torch.empty(B * T, 3 * d, dtype=bf, device=dev)
-    dpl = torch.empty_like(pl)
-    dBand = torch.empty(H * B * T * Rs, dtype=bf, device=dev)
-    QvHM = torch.empty(H * B * T * 64, dtype=bf, device=dev)
-    ws = torch.empty(L.ia_relpos_attention_flash_bwd_ws_elems(B, T, H, dk), dtype=torch.float32, device=dev)
-    dub = dub_out if dub_out is not None else torch.empty(2, H, dk, dtype=torch.float32, device=dev)
-    dctx = dctx.contiguous()
-    st = L.ia_relpos_attention_flash_bwd(_lib.ptr(qkv), _lib.ptr(pl), _lib.ptr(bias_u), _lib.ptr(bias_v), _lib.ptr(lens), _lib.ptr(ctx),
-                                         _lib.ptr(dctx), _lib.ptr(lse), B, T, H, dk, float(dropout_p), int(seed) & 0xFFFFFFFF,
-                                         _lib.ptr(dqkv), _lib.ptr(dpl), pl.shape[0], _lib.ptr(dub[0]), _lib.ptr(dub[1]),
-                                         _lib.ptr(dBand), _lib.ptr(QvHM), _lib.ptr(ws), _lib.stream_ptr())
-    _lib.check(st, "ia_relpos_attention_flash_bwd")
-    return dqkv, dpl, dub[0], dub[1]
+    """Backward of relpos_attention_flash (csrc/attention_flash_bwd.hip under the full span): qkv [B*T,3d], pl [>=2T-1,d], ctx / dctx
+    [B*T,d] bf16, lse [B*H,T] f32 -> (dqkv [B*T,3d] bf16, dpl [pl rows, d] bf16, dbias_u [H,dk] f32, dbias_v [H,dk] f32).  Two
+    key-tiled kernels (query-owner: dq, bias gradients, band-skewed dS; key-owner: dK, dV) + one TN GEMM per head for dpl, all
+    issued by one C call."""
+    return _attention_bwd(None, qkv, pl, bias_u, bias_v, lens, ctx, dctx, lse, B, T, H, dk, dropout_p, seed, dub_out)
+
+
+def relpos_attention_local_bwd(qkv, pl, bias_u, bias_v, lens, ctx, dctx, lse, B, T, H, dk, window, dropout_p=0.0, seed=0, dub_out=None):
+    """Backward of relpos_attention_local (the same two kernels under the local span): operands and results as
+    relpos_attention_flash_bwd, pl [>= 2*window+1, d]; dpl rows beyond 2*window are zero.  dBand, the workspace and the work are
+    O(T * window)."""
+    return _attention_bwd(window, qkv, pl, bias_u, bias_v, lens, ctx, dctx, lse, B, T, H, dk, dropout_p, seed, dub_out)
 
 
 def relpos_attention(qkv_bf16, pos_proj_bf16, bias_u, bias_v, lens, B, T, H, dk, dropout_p=0.0, seed=0):

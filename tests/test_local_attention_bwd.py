@@ -1,6 +1,6 @@
 """Local rel-pos attention backward on the host: the oracle and the entry points' argument checks.
 
-The GPU tests (tests/test_local_attention_bwd_gpu.py) hold csrc/attention_local_bwd.hip to fp64 autograd of the band-masked
+The GPU tests (tests/test_local_attention_bwd_gpu.py) hold csrc/attention_flash_bwd.hip under its local span to fp64 autograd of the band-masked
 composition ops.rel_pos_attention(window=w).  Here that composition's own gradients are held to the reference's
 (RelPositionMultiHeadAttentionLongformer in fp64, tests/golden/make_local_attention_grad_golden.py) to 1e-10 relative: two fp64
 evaluations of the same function in different summation orders.  The C entry points answer every bad argument before a launch.

@@ -1,4 +1,4 @@
-"""csrc/attention_local_bwd.hip (local rel-pos attention backward: the key-tiled pair restricted to the band |i - j| <= w)
+"""csrc/attention_flash_bwd.hip under its local span (local rel-pos attention backward: the key-tiled pair on the band |i - j| <= w)
 against fp64 autograd of the band-masked composition on the kernel's bf16 inputs, against the full backward where the window
 covers everything, and up through the trainable-block node and model.training_step.
 

@@ -1,4 +1,4 @@
-"""csrc/attention_local.hip (local rel-pos attention forward: the key-tile loop restricted to the band |i - j| <= w) against an
+"""csrc/attention_flash.hip under its local span (local rel-pos attention forward: the key-tile loop on the band |i - j| <= w) against an
 fp64 restatement of the reference's RelPositionMultiHeadAttentionLongformer on the kernel's bf16 inputs, against the full
 kernel where the window covers everything, and through the encoder (native prefix executor, per-op chain, transcribe, align).
 

@@ -1,6 +1,6 @@
 """Key-tiled attention kernels at the bench shape (32 x 376 frames, 4 heads of 64): forward with / without dropout, backward.
---window W [W ...]: forward and backward of full attention against local attention [W, W] (csrc/attention_local.hip,
-attention_local_bwd.hip) at --shape (default 1 x T x 8 heads of 64 for T = 751, 3001, 15001: 30 s, 2 min and 10 min of audio),
+--window W [W ...]: forward and backward of full attention against local attention [W, W] (the kernels of csrc/attention_flash.hip and
+attention_flash_bwd.hip under their local span) at --shape (default 1 x T x 8 heads of 64 for T = 751, 3001, 15001: 30 s, 2 min and 10 min of audio),
 outputs and scratch preallocated and the C entry points called directly so that the window times launches, not allocations.
 The full backward is skipped at a shape only if its dBand does not fit in free device memory.  Developer tool."""
 import argparse
