@@ -140,8 +140,7 @@ __global__ __launch_bounds__(FF_THREADS, 2) void ffn_fused_kernel(FfnArgs a) {
         for (int i = 0; i < 4; ++i) {
             const unsigned xm = (unsigned)(i & 1) * 64u + (unsigned)(i >> 1) * 2u * xm1;
             const unsigned vo = (off ^ xm) + (unsigned)i * stride;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(base + vo),
-                                             (__attribute__((address_space(3))) void*)(dst + i * 1024), 16, 0, 0);
+            ia_lds_dma16(base + vo, dst + i * 1024);
         }
     };
     // rendezvous in front of slot sq: this wave's share of slot sq has landed (later slots stay in flight) and everybody is
@@ -470,9 +469,7 @@ __global__ __launch_bounds__(FF_THREADS, 2) void ffn_fused_kernel(FfnArgs a) {
             unsigned char* dst = sRing + (sl & 3) * SLOT + wv * 4096;
             const unsigned char* base = Wt + (size_t)sl * (64 * D * 2);
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(base + toff[i]),
-                                                 (__attribute__((address_space(3))) void*)(dst + i * 1024), 16, 0, 0);
+            for (int i = 0; i < 4; ++i) ia_lds_dma16(base + toff[i], dst + i * 1024);
         };
         // the projection's bias goes where b1 was (plain loads inside the loop would drain the request queue: vmcnt(0))
         for (int i = tid; i < a.nt; i += FF_THREADS) sB1[i] = a.bt ? a.bt[i] : 0.f;

@@ -112,10 +112,10 @@ __global__ __launch_bounds__(G_THREADS, 2) void gemm_bf16_nt_dma_kernel(GemmArgs
     int m0, n0;
     if (!gemm_xcd_tile<BM, BN>(a.M, a.N, m0, n0)) return;
 
-    // 8-row blocks by LDS-DMA (gemm_glds_lane): wave w issues A blocks 2 w, 2 w + 1 and B blocks 4 w .. 4 w + 3.  Rows past M / N:
+    // 8-row blocks by LDS-DMA (ia_lds_dma_lane): wave w issues A blocks 2 w, 2 w + 1 and B blocks 4 w .. 4 w + 3.  Rows past M / N:
     // clamped.
     int lrow;
-    const unsigned lsw = gemm_glds_lane(lane, lrow);
+    const unsigned lsw = ia_lds_dma_lane(lane, lrow);
     unsigned aoff[2], boff[4];
     unsigned avalid[2] = {0u, 0u};   // CONV: bits 0-2 = tap rows dt in bounds, bits 3-5 = tap columns df in bounds (0 for rows past M)
 #pragma unroll
@@ -168,10 +168,10 @@ __global__ __launch_bounds__(G_THREADS, 2) void gemm_bf16_nt_dma_kernel(GemmArgs
             // first row / column: signed 32-bit, the image is < 2 GB)
             const unsigned char* src = CONV ? ak + (long long)(int)aoff[i] : ak + aoff[i];
             if constexpr (CONV) src = ((avalid[i] & tapbits) == tapbits) ? src : zpage;
-            gemm_glds16(src, dA + i * 1024);
+            ia_lds_dma16(src, dA + i * 1024);
         }
 #pragma unroll
-        for (int i = 0; i < 4; ++i) gemm_glds16(wk + boff[i], dB + i * 1024);
+        for (int i = 0; i < 4; ++i) ia_lds_dma16(wk + boff[i], dB + i * 1024);
     };
 
     f4 acc[BM / 32][BN / 32];

@@ -45,10 +45,10 @@ __global__ __launch_bounds__(GEMM_THREADS, 1) void gemm_big_kernel(GemmArgs a) {
     int m0, n0;
     if (!gemm_xcd_tile<GB_T, GB_T>(a.M, a.N, m0, n0)) return;
 
-    // ---- stage loader: 8-row blocks by LDS-DMA (gemm_glds_lane).  Wave w issues blocks 8 w .. 8 w + 7 of both operand tiles
+    // ---- stage loader: 8-row blocks by LDS-DMA (ia_lds_dma_lane).  Wave w issues blocks 8 w .. 8 w + 7 of both operand tiles
     // (rows 64 w .. 64 w + 63).  Rows of A beyond M are fetched from row M - 1 (finite values, never stored).
     int lrow;
-    const unsigned lsw = gemm_glds_lane(lane, lrow);
+    const unsigned lsw = ia_lds_dma_lane(lane, lrow);
     unsigned aoff[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -65,9 +65,9 @@ __global__ __launch_bounds__(GEMM_THREADS, 1) void gemm_big_kernel(GemmArgs a) {
         unsigned char* dA = smem + buf * GB_STAGE + wave * 8192;
         unsigned char* dW = dA + GB_TILE;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) gemm_glds16(ak + aoff[i], dA + i * 1024);
+        for (int i = 0; i < 8; ++i) ia_lds_dma16(ak + aoff[i], dA + i * 1024);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) gemm_glds16(wk + woff + (unsigned)(i * 8 * a.ldw * 2), dW + i * 1024);
+        for (int i = 0; i < 8; ++i) ia_lds_dma16(wk + woff + (unsigned)(i * 8 * a.ldw * 2), dW + i * 1024);
     };
 
     // ---- fragment addresses: lane (row l31 of a 32-row tile, k half hh) reads the 16 bytes of logical chunk 2 ks + hh,

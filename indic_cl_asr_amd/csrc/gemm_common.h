@@ -220,18 +220,7 @@ __device__ __forceinline__ void gemm_mfma_bf16_ktile(const unsigned char* sa, co
     }
 }
 
-// ---- LDS-DMA staging (gemm_bf16_nt_dma_kernel, gemm_big_kernel).  One instruction moves 1 KB = 8 rows x 8 chunks of 16 bytes
-// into unpadded 128-byte LDS rows, lane l's 16 bytes to dst + 16 l (dst is wave-uniform).  The conflict-free placement (chunk c
-// of row r at position c ^ (r & 7)) is produced on the SOURCE side: lane l fetches row l >> 3 of the block, logical chunk
-// (l & 7) ^ (l >> 3), whose byte offset inside the row is returned.
-__device__ __forceinline__ unsigned gemm_glds_lane(int lane, int& row) {
-    row = lane >> 3;
-    return (unsigned)(((lane & 7) ^ row) * 16);
-}
-__device__ __forceinline__ void gemm_glds16(const unsigned char* src, unsigned char* dst) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)dst,
-                                     16, 0, 0);
-}
+// (LDS-DMA staging of gemm_bf16_nt_dma_kernel and gemm_big_kernel: ia_lds_dma_lane / ia_lds_dma16 in ia_common.h)
 
 // sum over the 32 lanes of a half wave (as csrc/ffn_fused.hip): every lane of the half wave gets the total
 __device__ __forceinline__ float gemm_half_wave_sum(float v) {

@@ -144,13 +144,9 @@ __device__ __forceinline__ void tn_tile_body(const __bf16* __restrict__ dY, int 
             const unsigned char* px = gx + (size_t)st * TN_MS * ldx * 2;
             unsigned char* dy_ = smem + buf * 2 * TN_TILE + wv * 4096;
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(py + oy[i]),
-                                                 (__attribute__((address_space(3))) void*)(dy_ + i * 1024), 16, 0, 0);
+            for (int i = 0; i < 4; ++i) ia_lds_dma16(py + oy[i], dy_ + i * 1024);
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(px + ox[i]),
-                                                 (__attribute__((address_space(3))) void*)(dy_ + TN_TILE + i * 1024), 16, 0, 0);
+            for (int i = 0; i < 4; ++i) ia_lds_dma16(px + ox[i], dy_ + TN_TILE + i * 1024);
         };
         const int nst = (m_end - m_beg) / TN_MS;
         issue(0, 0);

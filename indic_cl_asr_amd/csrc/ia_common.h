@@ -40,6 +40,21 @@ static inline ia_dropout_t ia_dropout_rule(float p) {
 static inline size_t ia_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline int ia_is_aligned(const void* p, size_t a) { return ((uintptr_t)p % a) == 0; }
 
+// ---- LDS-DMA (global_load_lds_dwordx4): one instruction moves 64 x 16 bytes global -> LDS with no staging registers and no
+// ds_write, lane l's 16 bytes to dst + 16 l (dst is wave-uniform), from a per-lane source address.  A swizzled LDS layout is
+// therefore produced on the SOURCE side.  For unpadded 128-byte rows (1 KB = 8 rows x 8 chunks, chunk c of row r at position
+// c ^ (r & 7)) ia_lds_dma_lane gives lane l its row l >> 3 of the block and the byte offset inside that row of the logical chunk
+// (l & 7) ^ (l >> 3).  ia_lds_dma_wait: every LDS-DMA load of THIS wave has landed (vmcnt(0)); a barrier makes that everybody's.
+__device__ __forceinline__ unsigned ia_lds_dma_lane(int lane, int& row) {
+    row = lane >> 3;
+    return (unsigned)(((lane & 7) ^ row) * 16);
+}
+__device__ __forceinline__ void ia_lds_dma16(const unsigned char* src, unsigned char* dst) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)dst,
+                                     16, 0, 0);
+}
+__device__ __forceinline__ void ia_lds_dma_wait() { __builtin_amdgcn_s_waitcnt(0x0F70); }
+
 // 64-lane butterfly reductions (every lane ends with the result).
 __device__ __forceinline__ float ia_wave_max(float v) {
 #pragma unroll

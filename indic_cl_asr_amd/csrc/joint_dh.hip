@@ -43,7 +43,8 @@ constexpr int DH_TT = 16;                // frames per workgroup (= the partial-
 //                  others' MFMAs; all ten read the same A fragments from LDS.  0.74 ms (A/B in one process: 0.977 -> 0.742).
 //   (NT 2 with 12 waves -- 384 units per workgroup, three waves on EVERY SIMD, four idle waves in the second workgroup of H = 640 --
 //    measured the same 0.74 ms: the 3 / 3 / 2 / 2 imbalance is not what limits the 10-wave form.)
-// IA_DH_WAVES=4 selects the first (A/B switch); results are bit-identical (same products, same summation order per unit).
+// IA_DH_WAVES=4 selects the first (A/B switch); results are bit-identical (same products, same summation order per unit):
+// tests/test_joint_fwd_dh_digests_gpu.py records both and holds them equal.
 
 struct DhArgs {
     const _Float16* G; const _Float16* Wt; const _Float16* f; const _Float16* g;
@@ -62,6 +63,72 @@ struct DhArgs {
 // one full-latency wait, five MFMAs, repeat) and shuffles ~100 values per pass through v_accvgpr moves.
 __device__ __forceinline__ void dh_mfma(f4& acc, const h8& a_frag, const h8& b_frag) {
     asm("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a_frag), "a"(b_frag));
+}
+
+// Every accumulator of a pass as a read-write operand of one inline-asm statement (an operand list has no function form: these are
+// the file's only two macros, written out for the 5 and the 2 column tiles of the two decompositions)
+#define DH_TIE_ACC5                                                                                                 \
+    "+v"(acc[0][0]), "+v"(acc[0][1]), "+v"(acc[0][2]), "+v"(acc[0][3]), "+v"(acc[0][4]), "+v"(acc[1][0]), "+v"(acc[1][1]),  \
+        "+v"(acc[1][2]), "+v"(acc[1][3]), "+v"(acc[1][4]), "+v"(acc[2][0]), "+v"(acc[2][1]), "+v"(acc[2][2]), "+v"(acc[2][3]), \
+        "+v"(acc[2][4]), "+v"(acc[3][0]), "+v"(acc[3][1]), "+v"(acc[3][2]), "+v"(acc[3][3]), "+v"(acc[3][4])
+#define DH_TIE_ACC2                                                                                                 \
+    "+v"(acc[0][0]), "+v"(acc[0][1]), "+v"(acc[1][0]), "+v"(acc[1][1]), "+v"(acc[2][0]), "+v"(acc[2][1]), "+v"(acc[3][0]), "+v"(acc[3][1])
+
+// acc = (the pass's 64 G rows) x (this wave's 16 NT units of W^T) over the DH_KS k-steps.  sAl = the lane's A-fragment address in
+// the pass's LDS buffer (row c of the first frame, k chunk q); Bf = the resident fragments.  skip (diag & 1): no fragment reads, no
+// MFMAs.  The MFMAs are inline asm, so the compiler's hazard recogniser does not see them: both s_nop waits are tied to every
+// accumulator and therefore sit after the VALU zero-fill / after the last MFMA and before any use.
+template <int NT>
+__device__ __forceinline__ void dh_multiply(f4 (&acc)[4][NT], const unsigned char* sAl, const h8 (&Bf)[NT][DH_KS], bool skip) {
+    static_assert(NT == 5 || NT == 2, "the accumulator tie lists are written out for 5 and 2 column tiles");
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = (f4){0.f, 0.f, 0.f, 0.f};
+    if constexpr (NT == 5) { asm volatile("s_nop 4" : DH_TIE_ACC5); } else { asm volatile("s_nop 4" : DH_TIE_ACC2); }
+    // one wave per SIMD: the A fragments of k-step ks+1 are requested before the 4 NT MFMAs of k-step ks are issued
+    if (!skip) {
+        h8 Af[2][4];
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) Af[0][mt] = *reinterpret_cast<const h8*>(sAl + mt * 16 * DH_AROW);
+#pragma unroll
+        for (int ks = 0; ks < DH_KS; ++ks) {
+            if (ks + 1 < DH_KS) {
+#pragma unroll
+                for (int mt = 0; mt < 4; ++mt)
+                    Af[(ks + 1) & 1][mt] = *reinterpret_cast<const h8*>(sAl + mt * 16 * DH_AROW + (ks + 1) * 64);
+            }
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                for (int mt = 0; mt < 4; ++mt)
+                    dh_mfma(acc[mt][nt], Af[ks & 1][mt], Bf[nt][ks]);
+        }
+    }
+    if constexpr (NT == 5) { asm volatile("s_nop 15\n\ts_nop 15" : DH_TIE_ACC5); } else { asm volatile("s_nop 15\n\ts_nop 15" : DH_TIE_ACC2); }
+}
+
+// G loader: the 64 G rows of a pass (frames t_first .. + 3, labels u_first .. + 15 of utterance b) go global -> LDS directly, into
+// the tile image at `dst` (LDS-DMA: the data lands while the previous pass is multiplied).  One instruction fills 1 KB = 64
+// consecutive 16-byte slots of the image (rows of 37 slots = 592 B): lane l of block k owns slot 64k + l = (row, column chunk);
+// lanes on the 3-4 padding slots of a row stay idle (those slots keep their initial zeros).  Rows outside the tensor (t >= T or
+// u >= U1) are fetched from a clamped address -- finite values -- and switched off through the keep table.  This wave's share:
+// blocks wave, wave + WAVES, ...  (diag & 4: no loads.)
+// (As a [&] lambda of the kernel over (label tile, pass, buffer): 4-wave form +6 %, 10-wave form +3 % -- profiles/joint_fwd_dh_refactor.md.)
+template <int WAVES>
+__device__ __forceinline__ void dh_load_g_rows(unsigned char* dst, const _Float16* G, int b, int T, int U1, int LD, int t_first, int u_first,
+                                               int wave, int lane, int diag) {
+    constexpr int SLOTS = DH_AROW / 16, NBLK = (DH_ROWS * SLOTS + 63) / 64;
+    const int vpr = LD / 8;
+    for (int blk = wave; blk < NBLK; blk += WAVES) {
+        const int P = blk * 64 + lane;
+        const int row = P / SLOTS, col = P - row * SLOTS;
+        int t = t_first + (row >> 4); t = t < T ? t : T - 1;
+        int u = u_first + (row & 15); u = u < U1 ? u : U1 - 1;
+        const _Float16* src = G + (((size_t)b * T + t) * U1 + u) * LD + col * 8;
+        if (row < DH_ROWS && col < vpr && !(diag & 4))
+            ia_lds_dma16(reinterpret_cast<const unsigned char*>(src), dst + blk * 1024);
+    }
 }
 
 template <bool DROPOUT, int DH_NT, int DH_WAVES>
@@ -116,36 +183,62 @@ __global__ __launch_bounds__(DH_WAVES * 64, (DH_WAVES + 3) / 4) void joint_dh_fu
     for (int i = tid; i < DH_TT * DH_NB; i += DH_THREADS) sdf[i] = 0.f;
     __syncthreads();
 
-    // ---- loader: the pass's 64 G rows go global -> LDS directly (global_load_lds_dwordx4: no staging registers, no
-    // ds_write; the data lands while the previous pass is multiplied).  One instruction fills 1 KB = 64 consecutive 16-byte
-    // slots of the tile image (rows of 37 slots = 592 B): lane l of block k owns slot 64k + l = (row, column chunk); lanes
-    // on the 3-4 padding slots of a row stay idle (those slots keep their initial zeros).  Rows outside the tensor
-    // (t >= T or u >= U1) are fetched from a clamped address -- finite values -- and switched off through the keep table.
-    constexpr int DH_SLOTS = DH_AROW / 16;                         // 37
-    constexpr int DH_NBLK = (DH_ROWS * DH_SLOTS + 63) / 64;        // 37 blocks
-    const int vpr = LD / 8;
-#define DH_ASYNC(ut_, pt_, buf_)                                                                                   \
-    do {                                                                                                           \
-        for (int blk_ = wave; blk_ < DH_NBLK; blk_ += DH_WAVES) {                                                  \
-            const int P_ = blk_ * 64 + lane;                                                                       \
-            const int row_ = P_ / DH_SLOTS, col_ = P_ - row_ * DH_SLOTS;                                           \
-            int t_ = t0 + (pt_) * 4 + (row_ >> 4); t_ = t_ < T ? t_ : T - 1;                                       \
-            int u_ = (ut_) * 16 + (row_ & 15); u_ = u_ < U1 ? u_ : U1 - 1;                                         \
-            const _Float16* src_ = a.G + (((size_t)b * T + t_) * U1 + u_) * LD + col_ * 8;                         \
-            if (row_ < DH_ROWS && col_ < vpr && !(a.diag & 4))                                                     \
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src_,              \
-                                                 (__attribute__((address_space(3))) void*)(sA + (buf_) * (DH_ROWS * DH_AROW) + blk_ * 1024), 16, 0, 0); \
-        }                                                                                                          \
-    } while (0)
-#define DH_WAIT() __builtin_amdgcn_s_waitcnt(0x0F70)   /* vmcnt(0) */
-
-    const int npass = nut * npt;  // label tile outer, 4-frame pass inner
-    DH_ASYNC(0, 0, 0);
-    DH_WAIT();
-    __syncthreads();
+    // ---- the moving parts of a pass (frames tp .. tp + 3, labels u0 .. u0 + 15), next to dh_load_g_rows and dh_multiply
     unsigned char* smw = smask + wave * 1024;
-    float dgacc[4][DH_NT];
-    _Float16 gh[4][DH_NT];
+    float dgacc[4][DH_NT];     // d g of the label tile's rows u0 + 4 q + r, summed over the chunk's frames
+    _Float16 gh[4][DH_NT];     // g of the same rows, this lane's units n0 + 16 nt + c
+    // g rows of label tile u0 (clamped at U1) and a fresh d g accumulator
+    auto begin_label_tile = [&](int u0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            int u = u0 + q * 4 + r; u = u < U1 ? u : U1 - 1;
+            const _Float16* gp = a.g + ((size_t)b * U1 + u) * H + n0 + c;
+#pragma unroll
+            for (int nt = 0; nt < DH_NT; ++nt) { gh[r][nt] = gp[nt * 16]; dgacc[r][nt] = 0.f; }
+        }
+    };
+    // f rows of the pass's four frames (clamped at T)
+    auto load_f_rows = [&](int tp, _Float16 (&fh)[4][DH_NT]) {
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) {
+            int t = tp + mt; t = t < T ? t : T - 1;
+            const _Float16* fp = a.f + ((size_t)b * T + t) * H + n0 + c;
+#pragma unroll
+            for (int nt = 0; nt < DH_NT; ++nt) fh[mt][nt] = fp[nt * 16];
+        }
+    };
+    // keep bits of the pass's 64 cells x this wave's 2 NT unit groups: table[row][c>>3][nt] (8-byte groups); rows outside the
+    // tensor (their G rows were fetched from a clamped address) get all-zero bits
+    auto fill_keep_table = [&](int tp, int u0) {
+#pragma unroll
+        for (int i = 0; i < 2 * DH_NT; ++i) {  // 64 rows x 2 NT groups = 128 NT entries: exactly 2 NT per lane
+            const int e = lane + 64 * i, row = e / (2 * DH_NT), j = e - row * (2 * DH_NT);
+            const int nt = j >> 1, cp = j & 1;
+            const int tr = tp + (row >> 4), ur = u0 + (row & 15);
+            const unsigned cell = (unsigned)((((size_t)b * T + tr) * U1) + ur);
+            unsigned bits = 0xFFu;
+            if (DROPOUT) bits = dropout_keep8(a.seed, cell, (unsigned)((n0 >> 3) + j), a.thr);
+            smw[row * 16 + cp * 8 + nt] = (unsigned char)((tr < T && ur < U1) ? bits : 0u);
+        }
+    };
+    // label tile done for this 16-frame chunk: its partial d g rows (plain stores)
+    auto store_dg_partial = [&](int u0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int u = u0 + q * 4 + r;
+            if (u < U1) {
+                float* pp = a.part + ((((size_t)b * ntt + tt) * U1) + u) * H + n0 + c;
+#pragma unroll
+                for (int nt = 0; nt < DH_NT; ++nt) pp[nt * 16] = dgacc[r][nt];
+            }
+        }
+    };
+
+    // ---- the passes: label tile outer, 4-frame pass inner; one barrier per pass
+    const int npass = nut * npt;
+    dh_load_g_rows<DH_WAVES>(sA, a.G, b, T, U1, LD, t0, 0, wave, lane, a.diag);
+    ia_lds_dma_wait();
+    __syncthreads();
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -153,81 +246,20 @@ __global__ __launch_bounds__(DH_WAVES * 64, (DH_WAVES + 3) / 4) void joint_dh_fu
     for (int ps = 0; ps < npass; ++ps) {
         const int ut = ps / npt, pt = ps - ut * npt;
         const int u0 = ut * 16, tp = t0 + pt * 4;
-        if (ps + 1 < npass)   // the other buffer (its readers passed the previous barrier): lands under this pass
-            DH_ASYNC((ps + 1) / npt, (ps + 1) - ((ps + 1) / npt) * npt, (ps + 1) & 1);
+        if (ps + 1 < npass) {   // the other buffer (its readers passed the previous barrier): lands under this pass
+            const int utn = (ps + 1) / npt, ptn = (ps + 1) - utn * npt;
+            dh_load_g_rows<DH_WAVES>(sA + ((ps + 1) & 1) * (DH_ROWS * DH_AROW), a.G, b, T, U1, LD, t0 + ptn * 4, utn * 16, wave, lane, a.diag);
+        }
         if (wave_on) {
-            if (pt == 0 && !(a.diag & 16)) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    int u = u0 + q * 4 + r; u = u < U1 ? u : U1 - 1;
-                    const _Float16* gp = a.g + ((size_t)b * U1 + u) * H + n0 + c;
-#pragma unroll
-                    for (int nt = 0; nt < DH_NT; ++nt) { gh[r][nt] = gp[nt * 16]; dgacc[r][nt] = 0.f; }
-                }
-            }
+            if (pt == 0 && !(a.diag & 16)) begin_label_tile(u0);
             _Float16 fh[4][DH_NT] = {};
-            if (!(a.diag & 16))
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) {
-                int t = tp + mt; t = t < T ? t : T - 1;
-                const _Float16* fp = a.f + ((size_t)b * T + t) * H + n0 + c;
-#pragma unroll
-                for (int nt = 0; nt < DH_NT; ++nt) fh[mt][nt] = fp[nt * 16];
-            }
-            if (!(a.diag & 8)) {
-                // keep bits of the pass's 64 cells x this wave's 10 unit groups: table[row][c>>3][nt] (8-byte groups); rows
-                // outside the tensor (their G rows were fetched from a clamped address) get all-zero bits
-#pragma unroll
-                for (int i = 0; i < 2 * DH_NT; ++i) {  // 64 rows x 10 groups = 640 entries: exactly 10 per lane
-                    const int e = lane + 64 * i, row = e / (2 * DH_NT), j = e - row * (2 * DH_NT);
-                    const int nt = j >> 1, cp = j & 1;
-                    const int tr = tp + (row >> 4), ur = u0 + (row & 15);
-                    const unsigned cell = (unsigned)((((size_t)b * T + tr) * U1) + ur);
-                    unsigned bits = 0xFFu;
-                    if (DROPOUT) bits = dropout_keep8(a.seed, cell, (unsigned)((n0 >> 3) + j), a.thr);
-                    smw[row * 16 + cp * 8 + nt] = (unsigned char)((tr < T && ur < U1) ? bits : 0u);
-                }
-            }
-            // ---- MFMA: 64 rows x 80 units x K
-            f4 acc[4][DH_NT];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < DH_NT; ++nt) acc[mt][nt] = (f4){0.f, 0.f, 0.f, 0.f};
-            const unsigned char* sAl = sA + (ps & 1) * (DH_ROWS * DH_AROW) + c * DH_AROW + q * 16;
-#define DH_TIE_ACC5                                                                                                 \
-    "+v"(acc[0][0]), "+v"(acc[0][1]), "+v"(acc[0][2]), "+v"(acc[0][3]), "+v"(acc[0][4]), "+v"(acc[1][0]), "+v"(acc[1][1]),  \
-        "+v"(acc[1][2]), "+v"(acc[1][3]), "+v"(acc[1][4]), "+v"(acc[2][0]), "+v"(acc[2][1]), "+v"(acc[2][2]), "+v"(acc[2][3]), \
-        "+v"(acc[2][4]), "+v"(acc[3][0]), "+v"(acc[3][1]), "+v"(acc[3][2]), "+v"(acc[3][3]), "+v"(acc[3][4])
-#define DH_TIE_ACC2                                                                                                 \
-    "+v"(acc[0][0]), "+v"(acc[0][1]), "+v"(acc[1][0]), "+v"(acc[1][1]), "+v"(acc[2][0]), "+v"(acc[2][1]), "+v"(acc[3][0]), "+v"(acc[3][1])
-            static_assert(DH_NT == 5 || DH_NT == 2, "the accumulator tie lists are written out for 5 and 2 column tiles");
-            // The MFMAs below are inline asm: the compiler's hazard recogniser does not see them.  Both waits are tied to every
-            // accumulator, so they sit after the VALU zero-fill / after the last MFMA and before any use.
-            if constexpr (DH_NT == 5) { asm volatile("s_nop 4" : DH_TIE_ACC5); } else { asm volatile("s_nop 4" : DH_TIE_ACC2); }
-            // one wave per SIMD: the A fragments of k-step ks+1 are requested before the 20 MFMAs of k-step ks are issued
-            if (!(a.diag & 1)) {
-            h8 Af[2][4];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt) Af[0][mt] = *reinterpret_cast<const h8*>(sAl + mt * 16 * DH_AROW);
-#pragma unroll
-            for (int ks = 0; ks < DH_KS; ++ks) {
-                if (ks + 1 < DH_KS) {
-#pragma unroll
-                    for (int mt = 0; mt < 4; ++mt)
-                        Af[(ks + 1) & 1][mt] = *reinterpret_cast<const h8*>(sAl + mt * 16 * DH_AROW + (ks + 1) * 64);
-                }
-#pragma unroll
-                for (int nt = 0; nt < DH_NT; ++nt)
-#pragma unroll
-                    for (int mt = 0; mt < 4; ++mt)
-                        dh_mfma(acc[mt][nt], Af[ks & 1][mt], Bf[nt][ks]);
-            }
-            }   // (diag & 1)
-            if constexpr (DH_NT == 5) { asm volatile("s_nop 15\n\ts_nop 15" : DH_TIE_ACC5); } else { asm volatile("s_nop 15\n\ts_nop 15" : DH_TIE_ACC2); }
-#undef DH_TIE_ACC5
-#undef DH_TIE_ACC2
-            // ---- epilogue on the accumulator layout: row = mt*16 + q*4 + r -> (t = tp+mt, u = u0+4q+r), col = nt*16+c
+            if (!(a.diag & 16)) load_f_rows(tp, fh);
+            if (!(a.diag & 8)) fill_keep_table(tp, u0);
+            f4 acc[4][DH_NT];   // 64 rows x 16 NT units
+            dh_multiply<DH_NT>(acc, sA + (ps & 1) * (DH_ROWS * DH_AROW) + c * DH_AROW + q * 16, Bf, a.diag & 1);
+            // ---- masked epilogue on the accumulator layout: row = mt*16 + q*4 + r -> (t = tp+mt, u = u0+4q+r), col = nt*16+c.  The kept
+            // values go into dgacc (over frames) and, summed over the pass's 16 labels, into the wave's d f rows in LDS.
+            // (Written out here: as a [&] lambda over (acc, fh, pt) the 4-wave form ran +8 % -- profiles/joint_fwd_dh_refactor.md.)
             if (!(a.diag & 2)) {
             __builtin_amdgcn_s_waitcnt(0xC07F);  // mask table written (wave-private, in-order LDS)
             float ssum[4][DH_NT];
@@ -275,24 +307,12 @@ __global__ __launch_bounds__(DH_WAVES * 64, (DH_WAVES + 3) / 4) void joint_dh_fu
 #pragma unroll
                     for (int nt = 0; nt < DH_NT; ++nt) dfrow[mt * DH_NB + nt * 16] = old[mt][nt] + ssum[mt][nt];
             }
-            if (pt == npt - 1) {  // label tile done for this 16-frame chunk: its partial d g rows (plain stores)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int u = u0 + q * 4 + r;
-                    if (u < U1) {
-                        float* pp = a.part + ((((size_t)b * ntt + tt) * U1) + u) * H + n0 + c;
-#pragma unroll
-                        for (int nt = 0; nt < DH_NT; ++nt) pp[nt * 16] = dgacc[r][nt];
-                    }
-                }
-            }
+            if (pt == npt - 1) store_dg_partial(u0);
             } else if (acc[0][0][0] == 1.2345e-30f) sdf[0] = 1.f;   // (diag & 2: timing only; keeps the accumulators alive)
         }
-        DH_WAIT();
+        ia_lds_dma_wait();
         __syncthreads();
     }
-#undef DH_ASYNC
-#undef DH_WAIT
     // ---- d f rows of this chunk (every label tile summed)
     if (wave_on) {
         for (int i = lane; i < DH_TT * DH_NW; i += 64) {
@@ -354,6 +374,29 @@ __global__ __launch_bounds__(256) void joint_dh_dg_finish_kernel(const float* __
         }
     }
 }
+// One instantiation's launch: the decomposition fixes the hidden units per workgroup, hence the hidden halves, the grid and the
+// LDS size (two G buffers, the d f accumulator, one keep table per wave).
+template <bool DROPOUT, int NT, int WAVES>
+int dh_launch(DhArgs a, hipStream_t st) {
+    constexpr int nb = 16 * NT * WAVES;
+    constexpr size_t lds = 2 * (size_t)DH_ROWS * DH_AROW + (size_t)DH_TT * nb * sizeof(float) + (size_t)WAVES * 1024;
+    a.nh = (a.H + nb - 1) / nb;
+    const int ntt = (a.T + DH_TT - 1) / DH_TT;
+    IA_SET_MAX_LDS_ONCE((joint_dh_fused_kernel<DROPOUT, NT, WAVES>), (int)lds);
+    hipLaunchKernelGGL((joint_dh_fused_kernel<DROPOUT, NT, WAVES>), dim3((unsigned)(a.B * ntt * a.nh)), dim3(WAVES * 64), lds, st, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        if (getenv("IA_DEBUG")) {
+            hipFuncAttributes fa;
+            const hipError_t e2 = hipFuncGetAttributes(&fa, (const void*)joint_dh_fused_kernel<DROPOUT, NT, WAVES>);
+            fprintf(stderr, "ia_joint_dh_fused: launch failed: %s (waves %d, lds %zu; attr rc %d maxThreadsPerBlock %d numRegs %d "
+                            "maxDynShared %d sharedSizeBytes %zu localSizeBytes %zu)\n", hipGetErrorString(e), WAVES, lds, (int)e2,
+                    fa.maxThreadsPerBlock, fa.numRegs, fa.maxDynamicSharedSizeBytes, fa.sharedSizeBytes, fa.localSizeBytes);
+        }
+        return IA_LAUNCH_FAILED;
+    }
+    return IA_OK;
+}
 }  // namespace
 
 extern "C" int ia_joint_dh_fused_supported(int U1, int H, int LD) {
@@ -391,54 +434,15 @@ extern "C" int ia_joint_dh_fused_ex(const void* G, const void* Wt, const void* f
     a.act_lens = act_lens; a.label_lens = label_lens; a.df = df; a.dfb = (__bf16*)df_bf16; a.part = (float*)scratch;
     { const char* e = getenv("IA_DH_DIAG"); a.diag = e ? atoi(e) : 0; }
     a.B = B; a.T = T; a.U1 = U1; a.H = H; a.LD = LD;
-    a.nh = 0;   // (set with the decomposition below)
+    a.nh = 0;   // (set by dh_launch with the decomposition)
     a.inv_kappa = inv_kappa; a.seed = seed;
     a.thr = ia_dropout_rule(dropout_p).thr;
     const char* wv_env = getenv("IA_DH_WAVES");
-    int waves = (H % 32 == 0) ? 10 : 4;
-    if (wv_env && atoi(wv_env) == 4) waves = 4;
-    const bool ten = waves == 10;
-    const int nb = waves == 4 ? 320 : 32 * waves;
-    a.nh = (H + nb - 1) / nb;
-    const size_t lds = 2 * (size_t)DH_ROWS * DH_AROW + (size_t)DH_TT * nb * sizeof(float) + (size_t)waves * 1024;
-    const int ntt = (T + DH_TT - 1) / DH_TT;
-    const dim3 grid((unsigned)(B * ntt * a.nh)), blk(waves * 64);
+    const bool ten = H % 32 == 0 && !(wv_env && atoi(wv_env) == 4);
     hipStream_t st = (hipStream_t)stream;
-#define DH_LAUNCH(DROP_, NT_, WV_)                                                                  \
-    do {                                                                                            \
-        static int granted_ = -1;                                                                   \
-        if ((int)lds > granted_) {                                                                  \
-            const hipError_t ea_ = hipFuncSetAttribute((const void*)joint_dh_fused_kernel<DROP_, NT_, WV_>,                     \
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                   \
-            if (ea_ != hipSuccess) {                                                                \
-                if (getenv("IA_DEBUG")) fprintf(stderr, "ia_joint_dh_fused: hipFuncSetAttribute(%d waves, %zu B): %s\n", WV_, lds, hipGetErrorString(ea_)); \
-                (void)hipGetLastError();                                                            \
-                return IA_LAUNCH_FAILED;                                                            \
-            }                                                                                       \
-            granted_ = (int)lds;                                                                    \
-        }                                                                                           \
-        hipLaunchKernelGGL((joint_dh_fused_kernel<DROP_, NT_, WV_>), grid, blk, lds, st, a);         \
-    } while (0)
-    if (ten) {
-        if (a.thr > 0) DH_LAUNCH(true, 2, 10); else DH_LAUNCH(false, 2, 10);
-    } else {
-        if (a.thr > 0) DH_LAUNCH(true, 5, 4); else DH_LAUNCH(false, 5, 4);
-    }
-#undef DH_LAUNCH
-    {
-        const hipError_t e_ = hipGetLastError();
-        if (e_ != hipSuccess) {
-            if (getenv("IA_DEBUG")) {
-                hipFuncAttributes fa;
-                const hipError_t e2 = ten ? hipFuncGetAttributes(&fa, (const void*)joint_dh_fused_kernel<true, 2, 10>)
-                                          : hipFuncGetAttributes(&fa, (const void*)joint_dh_fused_kernel<true, 5, 4>);
-                fprintf(stderr, "ia_joint_dh_fused: launch failed: %s (waves %d, lds %zu; attr rc %d maxThreadsPerBlock %d numRegs %d "
-                                "maxDynShared %d sharedSizeBytes %zu localSizeBytes %zu)\n", hipGetErrorString(e_), waves, lds, (int)e2,
-                        fa.maxThreadsPerBlock, fa.numRegs, fa.maxDynamicSharedSizeBytes, fa.sharedSizeBytes, fa.localSizeBytes);
-            }
-            return IA_LAUNCH_FAILED;
-        }
-    }
+    const int rc = ten ? (a.thr > 0 ? dh_launch<true, 2, 10>(a, st) : dh_launch<false, 2, 10>(a, st))
+                       : (a.thr > 0 ? dh_launch<true, 5, 4>(a, st) : dh_launch<false, 5, 4>(a, st));
+    if (rc != IA_OK) return rc;
     const int64_t n4 = (int64_t)B * U1 * H / 4;
     const int fgrid = (int)((n4 + 255) / 256 < 8192 ? (n4 + 255) / 256 : 8192);
     hipLaunchKernelGGL(joint_dh_dg_finish_kernel, dim3(fgrid < 1 ? 1 : fgrid), dim3(256), 0, st, (const float*)scratch, dg,

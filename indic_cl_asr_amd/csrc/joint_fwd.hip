@@ -42,6 +42,73 @@ struct JointFwdArgs {
     unsigned seed, thr;
 };
 
+constexpr int JF_LDT = JVP * 2 + 16;   // bytes per row of a wave's transpose scratch (16 rows; it reuses the W buffers)
+
+// W chunk kc (JVP rows x 64 k, 128 B per row) straight from global memory into the LDS buffer `dst` (LDS-DMA: the data lands
+// while the MFMAs run).  Unpadded 128-byte rows, conflict-free by the source-side swizzle of ia_lds_dma_lane: wsrc_lane is the
+// lane's byte offset inside a block's 8 rows of W.  This wave's share: blocks wave, wave + NWAVES, ... of the chunk's JVP / 8.
+template <int NWAVES>
+__device__ __forceinline__ void jf_load_w_chunk(unsigned char* dst, const _Float16* W, int H, int kc, unsigned wsrc_lane, int wave) {
+    for (int blk = wave; blk < JVP / 8; blk += NWAVES)
+        ia_lds_dma16(reinterpret_cast<const unsigned char*>(W + (size_t)(8 * blk) * H + kc * JKC) + wsrc_lane, dst + blk * 1024);
+}
+
+// Hidden operands (Acur / Anext of the k-loop) of k-step `kstep` (32 hidden units) for the wave's JS frames: relu(f + g) with the
+// dropout mask, built in registers.  f_rows / g_row
+// point at this lane's 8 values of k-step 0 in the wave's first frame row / the lane's label row (LDS rows of frow bytes); lane
+// group q holds hidden units kstep * 32 + q * 8 .. + 7 of lattice cell cell_base + s * U1.
+template <bool DROPOUT, int JS>
+__device__ __forceinline__ void jf_build_a(h8 (&dst)[JS], const unsigned char* f_rows, const unsigned char* g_row, int frow, int kstep,
+                                           int q, unsigned seed, unsigned cell_base, int U1, unsigned thr) {
+    const h2 zero2 = {(_Float16)0, (_Float16)0};
+    const h8 gf = *reinterpret_cast<const h8*>(g_row + kstep * 64);
+#pragma unroll
+    for (int s = 0; s < JS; ++s) {
+        const h8 ff = *reinterpret_cast<const h8*>(f_rows + s * frow + kstep * 64);
+        union { h8 v; h2 p[4]; } x, y, z;
+        x.v = gf; y.v = ff;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) z.p[j] = __builtin_elementwise_max(x.p[j] + y.p[j], zero2);
+        dst[s] = z.v;
+        if (DROPOUT) dst[s] = dropout_apply8(dst[s], seed, cell_base + (unsigned)(s * U1), (unsigned)(kstep * 4 + q), thr);
+    }
+}
+
+// Epilogue of one subtile (one frame), up to the LDS image; the row stores and the per-row scalars follow in the kernel.  Lane (c, q) holds columns 16 n + 4 q + r of row c: round them to f16 in
+// pairs (v_cvt_pk_f16_f32, nearest even; the denominator is computed from the ROUNDED logits), reduce the rounded row over the
+// lane's columns and the four q groups (m = maximum, sum = sum of exp(x - m)), and write the row's image to the wave's transpose
+// scratch, one 8-byte word per column tile (row_q = the row's address + this q group's 8 bytes).
+__device__ __forceinline__ void jf_round_reduce_stage(const f4 (&acc)[JNT], unsigned char* row_q, float& m, float& sum) {
+    h2 pk[JNT][2];
+    h2 mx = {(_Float16)-65504.f, (_Float16)-65504.f};
+#pragma unroll
+    for (int n = 0; n < JNT; ++n) {
+        pk[n][0] = (h2){(_Float16)acc[n][0], (_Float16)acc[n][1]};
+        pk[n][1] = (h2){(_Float16)acc[n][2], (_Float16)acc[n][3]};
+        mx = __builtin_elementwise_max(mx, __builtin_elementwise_max(pk[n][0], pk[n][1]));
+    }
+    m = fmaxf((float)mx[0], (float)mx[1]);
+    m = fmaxf(m, __shfl_xor(m, 16));   // the four q groups of row c
+    m = fmaxf(m, __shfl_xor(m, 32));
+    const float ml = -m * 1.44269504088896341f;
+    sum = 0.f;
+#pragma unroll
+    for (int n = 0; n < JNT; ++n)
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            sum += __builtin_amdgcn_exp2f(__builtin_fmaf((float)pk[n][e][0], 1.44269504088896341f, ml));
+            sum += __builtin_amdgcn_exp2f(__builtin_fmaf((float)pk[n][e][1], 1.44269504088896341f, ml));
+        }
+    sum += __shfl_xor(sum, 16);
+    sum += __shfl_xor(sum, 32);
+#pragma unroll
+    for (int n = 0; n < JNT; ++n) {
+        union { h2 p[2]; uint2 u; } w2;
+        w2.p[0] = pk[n][0]; w2.p[1] = pk[n][1];
+        *reinterpret_cast<uint2*>(row_q + 32 * n) = w2.u;
+    }
+}
+
 // Template parameters: JS = frames (row sub-tiles) per wave, NWAVES = waves per workgroup (JS x NWAVES frames per workgroup).
 //   <3, 4>  one wave per SIMD, 204 accumulator registers (the round-2 form);
 //   <2, 8>  two waves per SIMD: while one wave runs its operand construction / epilogue, the SIMD's other wave issues MFMAs.
@@ -84,24 +151,12 @@ __global__ __launch_bounds__(NWAVES * 64, (NWAVES + 3) / 4) void joint_fwd_kerne
             }
         }
     }
-    // ---- W chunk staging: JVP rows x 64 k (128 B per row) straight from global memory into LDS (global_load_lds_dwordx4:
-    // no staging registers, no ds_write, the data lands while the MFMAs run).  One instruction fills 1 KB of consecutive LDS
-    // = 8 rows x 8 chunks of 16 B with lane l at position l, so the layout is rows of 128 B WITHOUT padding and the
-    // conflict-free placement is done on the source side: physical chunk p of row r holds the row's chunk p ^ (r & 7).
-    // 34 such blocks per chunk: wave w fills blocks w, w + 4, ...
+    // ---- W chunk staging (jf_load_w_chunk): 34 blocks of 8 rows per chunk, wave w fills blocks w, w + NWAVES, ...
     constexpr int WROW = JKC * 2;                        // 128 B
     constexpr int WBUF = JVP * WROW;                     // 34 816 B per buffer
-    constexpr int WBLK = JVP / 8;                        // 34 blocks of 8 rows
-    const unsigned wsrc_lane = (unsigned)((lane >> 3) * H * 2 + 16 * ((lane & 7) ^ (lane >> 3)));   // byte offset inside a block's 8 rows
-#define J_W_ASYNC(kc_, buf_)                                                                             \
-    do {                                                                                                 \
-        for (int blk_ = wave; blk_ < WBLK; blk_ += NWAVES) {                                             \
-            const unsigned char* src_ = reinterpret_cast<const unsigned char*>(a.W + (size_t)(8 * blk_) * H + (kc_) * JKC) + wsrc_lane; \
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src_,        \
-                                             (__attribute__((address_space(3))) void*)(sW + (buf_) * WBUF + blk_ * 1024), 16, 0, 0); \
-        }                                                                                                \
-    } while (0)
-#define J_W_WAIT() __builtin_amdgcn_s_waitcnt(0x0F70)   /* vmcnt(0): this wave's LDS-DMA loads have landed */
+    int wsrc_row;
+    const unsigned wsrc_chunk = ia_lds_dma_lane(lane, wsrc_row);
+    const unsigned wsrc_lane = (unsigned)(wsrc_row * H * 2) + wsrc_chunk;   // this lane's byte offset inside a block's 8 rows
 
     // accumulators start from the bias (lane (c, q) owns columns 16n + 4q + r).  Columns >= V: W rows are zero and the
     // "bias" -65504 makes the stored padding logit the most negative f16 -- it never wins the row maximum, its exp is exactly
@@ -117,36 +172,24 @@ __global__ __launch_bounds__(NWAVES * 64, (NWAVES + 3) / 4) void joint_fwd_kerne
     }
 
     const int nkc = H / JKC;
-    J_W_ASYNC(0, 0);
-    J_W_WAIT();
+    jf_load_w_chunk<NWAVES>(sW, a.W, H, 0, wsrc_lane, wave);
+    ia_lds_dma_wait();
     __syncthreads();
     const int tw = t0 + wave * JS;  // first t of this wave
     const unsigned cell_base = (unsigned)(((size_t)b * a.T + tw) * a.U1 + u0 + c);  // + s*U1 per subtile
-    const h2 zero2 = {(_Float16)0, (_Float16)0};
-    // A operands of k-step `kstep` (32 hidden units): relu(f + g) with the dropout mask, JS subtiles
-#define J_BUILD_A(dst_, kstep_)                                                                              \
-    do {                                                                                                     \
-        const int kbyte_ = ((kstep_) * 32 + q * 8) * 2;  /* byte offset of this lane's 8 k values in an f/g row */ \
-        const h8 gf_ = *reinterpret_cast<const h8*>(sG + c * frow + kbyte_);                                 \
-        _Pragma("unroll") for (int s = 0; s < JS; ++s) {                                                     \
-            const h8 ff_ = *reinterpret_cast<const h8*>(sF + (wave * JS + s) * frow + kbyte_);               \
-            union { h8 v; h2 p[4]; } x_, y_, z_;                                                             \
-            x_.v = gf_; y_.v = ff_;                                                                          \
-            _Pragma("unroll") for (int j = 0; j < 4; ++j) z_.p[j] = __builtin_elementwise_max(x_.p[j] + y_.p[j], zero2); \
-            dst_[s] = z_.v;                                                                                  \
-            if (DROPOUT) dst_[s] = dropout_apply8(dst_[s], a.seed, cell_base + (unsigned)(s * a.U1), (unsigned)((kstep_) * 4 + q), a.thr); \
-        }                                                                                                    \
-    } while (0)
+    const unsigned char* g_row = sG + c * frow + q * 16;                  // this lane's 8 k values of k-step 0: label row c ...
+    const unsigned char* f_rows = sF + wave * JS * frow + q * 16;         // ... and the wave's first frame row
+    auto build_a = [&](h8 (&dst)[JS], int kstep) { jf_build_a<DROPOUT, JS>(dst, f_rows, g_row, frow, kstep, q, a.seed, cell_base, a.U1, a.thr); };
     // One wave per SIMD: nothing else hides LDS latency, so every k-step first requests ALL 17 W fragments, builds the NEXT
     // k-step's hidden operands while they arrive (VALU under the LDS latency), then issues its 51 MFMAs.
     // Operand order: the W fragment is the MFMA's A operand and the hidden fragment its B operand, i.e. the accumulators
     // hold the TRANSPOSED tile -- lane (c, q) owns logits[u = u0 + c][v = 16n + 4q + r], four CONSECUTIVE vocabulary
     // columns of one lattice cell: the epilogue packs / reduces / stores them as pairs and 8-byte words.
     h8 Acur[JS], Anext[JS];
-    J_BUILD_A(Acur, 0);
+    build_a(Acur, 0);
     const int nks = H / 32;
     for (int kc = 0; kc < nkc; ++kc) {
-        if (kc + 1 < nkc) J_W_ASYNC(kc + 1, (kc + 1) & 1);   // the other buffer: its readers passed the previous barrier
+        if (kc + 1 < nkc) jf_load_w_chunk<NWAVES>(sW + ((kc + 1) & 1) * WBUF, a.W, H, kc + 1, wsrc_lane, wave);   // the other buffer: its readers passed the previous barrier
         const unsigned char* wb = sW + (kc & 1) * WBUF;
 #pragma unroll
         for (int ks = 0; ks < JKC / 32; ++ks) {
@@ -154,7 +197,7 @@ __global__ __launch_bounds__(NWAVES * 64, (NWAVES + 3) / 4) void joint_fwd_kerne
 #pragma unroll
             for (int n = 0; n < JNT; ++n) Bf[n] = *reinterpret_cast<const h8*>(wb + (n * 16 + c) * WROW + 16 * ((ks * 4 + q) ^ (c & 7)));
             const int knext = kc * (JKC / 32) + ks + 1;
-            J_BUILD_A(Anext, knext < nks ? knext : 0);
+            build_a(Anext, knext < nks ? knext : 0);
 #pragma unroll
             for (int n = 0; n < JNT; ++n)
 #pragma unroll
@@ -162,49 +205,20 @@ __global__ __launch_bounds__(NWAVES * 64, (NWAVES + 3) / 4) void joint_fwd_kerne
 #pragma unroll
             for (int s = 0; s < JS; ++s) Acur[s] = Anext[s];
         }
-        J_W_WAIT();
+        ia_lds_dma_wait();
         __syncthreads();               // chunk kc+1 is in LDS for everyone; everyone is done reading buffer kc & 1
     }
-#undef J_BUILD_A
 
     // ---- epilogue: per subtile s (one t): lane (c, q) holds row u = u0 + c, columns v = 16n + 4q + r
-    // transpose scratch: per wave 16 rows x LDT bytes, LDT = JVP*2 + 16
-    constexpr int LDT = JVP * 2 + 16;
+    // transpose scratch: per wave 16 rows x LDT bytes
+    constexpr int LDT = JF_LDT;
     unsigned char* sT = sW + wave * (16 * LDT);
     const int64_t* lab = a.labels + (int64_t)b * (a.U1 - 1);
 #pragma unroll
     for (int s = 0; s < JS; ++s) {
         const int t = tw + s;
-        // round to f16 in pairs (the denominator is computed from the ROUNDED logits), packed row maximum
-        h2 pk[JNT][2];
-        h2 mx = {(_Float16)-65504.f, (_Float16)-65504.f};
-#pragma unroll
-        for (int n = 0; n < JNT; ++n) {
-            pk[n][0] = (h2){(_Float16)acc[s][n][0], (_Float16)acc[s][n][1]};   // v_cvt_pk_f16_f32, round to nearest even
-            pk[n][1] = (h2){(_Float16)acc[s][n][2], (_Float16)acc[s][n][3]};
-            mx = __builtin_elementwise_max(mx, __builtin_elementwise_max(pk[n][0], pk[n][1]));
-        }
-        float m = fmaxf((float)mx[0], (float)mx[1]);
-        m = fmaxf(m, __shfl_xor(m, 16));   // the four q groups of row c
-        m = fmaxf(m, __shfl_xor(m, 32));
-        const float ml = -m * 1.44269504088896341f;
-        float sum = 0.f;
-#pragma unroll
-        for (int n = 0; n < JNT; ++n)
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                sum += __builtin_amdgcn_exp2f(__builtin_fmaf((float)pk[n][e][0], 1.44269504088896341f, ml));
-                sum += __builtin_amdgcn_exp2f(__builtin_fmaf((float)pk[n][e][1], 1.44269504088896341f, ml));
-            }
-        sum += __shfl_xor(sum, 16);
-        sum += __shfl_xor(sum, 32);
-        // accumulator layout -> LDS rows [u_local = c][v]: one 8-byte word per column tile
-#pragma unroll
-        for (int n = 0; n < JNT; ++n) {
-            union { h2 p[2]; uint2 u; } w2;
-            w2.p[0] = pk[n][0]; w2.p[1] = pk[n][1];
-            *reinterpret_cast<uint2*>(sT + c * LDT + (16 * n + 4 * q) * 2) = w2.u;
-        }
+        float m, sum;   // of row u0 + c: maximum and sum of exp(x - m) of the rounded logits
+        jf_round_reduce_stage(acc[s], sT + c * LDT + 8 * q, m, sum);
         __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's LDS writes landed (scratch is wave-private)
         if (t < Tx) {
             // coalesced row stores: 16 rows x (LD*2/16) vectors
@@ -236,6 +250,21 @@ __global__ __launch_bounds__(NWAVES * 64, (NWAVES + 3) / 4) void joint_fwd_kerne
         }
         __builtin_amdgcn_s_waitcnt(0xC07F);
     }
+}
+
+// One instantiation's launch: the decomposition fixes frames per workgroup, grid and LDS size (f / g tiles + the W double buffer,
+// which the epilogue reuses as the transpose scratch).
+template <bool DROPOUT, int JS, int NWAVES>
+int jf_launch(const JointFwdArgs& a, hipStream_t st) {
+    constexpr int JT = JS * NWAVES;
+    constexpr size_t wbytes = 2 * (size_t)JVP * JKC * 2, tbytes = (size_t)NWAVES * 16 * JF_LDT;
+    const size_t lds = (size_t)(JT + JU) * (a.H * 2 + 16) + (wbytes > tbytes ? wbytes : tbytes);
+    if (lds > 160 * 1024) return IA_UNSUPPORTED;
+    const int nut = (a.U1 + JU - 1) / JU, ntt = (a.T + JT - 1) / JT;
+    IA_SET_MAX_LDS_ONCE((joint_fwd_kernel<DROPOUT, JS, NWAVES>), (int)lds);
+    hipLaunchKernelGGL((joint_fwd_kernel<DROPOUT, JS, NWAVES>), dim3((unsigned)((int64_t)a.B * ntt * nut)), dim3(NWAVES * 64), lds, st, a);
+    IA_RETURN_IF_LAUNCH_FAILED();
+    return IA_OK;
 }
 
 }  // namespace
@@ -277,28 +306,9 @@ extern "C" int ia_joint_fwd_box(const void* f, const void* g, const void* W, con
     a.B = B; a.T = T; a.U1 = U1; a.H = H; a.V = V; a.LD = LD; a.blank = blank; a.rows = w.rows; a.U1s = w.U1s;
     a.seed = seed;
     a.thr = ia_dropout_rule(dropout_p).thr;
-    const int frow = H * 2 + 16;
     const char* wv_env = getenv("IA_JFWD_WAVES");       // A/B switch: 4 = one wave per SIMD x 3 frames, 8 = two waves per SIMD x 2 frames
-    const int waves = (wv_env && atoi(wv_env) == 4) ? 4 : 8;
-    const int js = waves == 4 ? 3 : 2, jt = js * waves;
-    constexpr int LDT_H = JVP * 2 + 16;
-    const size_t wbytes = 2 * (size_t)JVP * JKC * 2, tbytes = (size_t)waves * 16 * LDT_H;   // W double buffer, reused as the transpose scratch
-    const size_t lds = (size_t)(jt + JU) * frow + (wbytes > tbytes ? wbytes : tbytes);
-    if (lds > 160 * 1024) return IA_UNSUPPORTED;
-    const int nut = (U1 + JU - 1) / JU, ntt = (T + jt - 1) / jt;
-    const dim3 grid((unsigned)((int64_t)B * ntt * nut)), blk(waves * 64);
+    const bool four = wv_env && atoi(wv_env) == 4;
     hipStream_t st = (hipStream_t)stream;
-#define JF_LAUNCH(DROP_, JS_, WV_)                                                          \
-    do {                                                                                    \
-        IA_SET_MAX_LDS_ONCE((joint_fwd_kernel<DROP_, JS_, WV_>), (int)lds);                  \
-        hipLaunchKernelGGL((joint_fwd_kernel<DROP_, JS_, WV_>), grid, blk, lds, st, a);      \
-    } while (0)
-    if (waves == 4) {
-        if (a.thr > 0) JF_LAUNCH(true, 3, 4); else JF_LAUNCH(false, 3, 4);
-    } else {
-        if (a.thr > 0) JF_LAUNCH(true, 2, 8); else JF_LAUNCH(false, 2, 8);
-    }
-#undef JF_LAUNCH
-    IA_RETURN_IF_LAUNCH_FAILED();
-    return IA_OK;
+    if (four) return a.thr > 0 ? jf_launch<true, 3, 4>(a, st) : jf_launch<false, 3, 4>(a, st);
+    return a.thr > 0 ? jf_launch<true, 2, 8>(a, st) : jf_launch<false, 2, 8>(a, st);
 }
