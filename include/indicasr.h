@@ -443,6 +443,41 @@ int ia_relpos_attention_local_bwd(const void* qkv, const void* pos_proj, const f
                                   const int64_t* lens, const void* ctx, const void* dctx, const float* lse, int B, int T, int H,
                                   int dk, int window, float dropout_p, unsigned seed, void* dqkv, void* dpl, int pl_rows,
                                   float* dbias_u, float* dbias_v, void* dBand, void* QvHM, float* ws, ia_stream_t stream);
+/* Limited-context rel-pos attention: the same kernel under its context span (csrc/attention_flash.h FaContextSpan), the
+ * reference encoder's att_context_size = [left, right] with att_context_style 'regular' (style 0) or 'chunked_limited' (style 1)
+ * under self_attention_model 'rel_pos' (A/modules/conformer_encoder.py:686-740, a [T,T] mask there).  Query i and key j, both
+ * below len_b, pair when
+ *   regular:                    i - j <= left and j - i <= right;
+ *   chunked, right >= 0:        0 <= i / C - j / C <= left / C, C = right + 1;
+ *   chunked, right == -1:       i - j <= left;
+ * a side of -1 is unlimited.  Operands, layouts (pos_proj [>= 2T-1, H*dk], row r <-> relative position T-1-r), lens semantics,
+ * alignment checks, return codes and the dropout hash are ia_relpos_attention_flash's; padded query rows are zero.  A 64-row
+ * tile visits only the tiles its interval reaches: O(T (left + right)) work when both sides are limited.  IA_INVALID_VALUE for
+ * an unknown style, left < -1, right < -1, or chunked with left >= 0, right >= 0 and left % (right + 1) != 0; dk as the full
+ * kernel (IA_UNSUPPORTED otherwise); refused before any device work.  A context that admits every pair ([-1,-1], regular with
+ * both sides >= T-1, chunked with right + 1 >= T) runs the full kernel: ia_relpos_attention_flash's bits.
+ * ia_relpos_attention_context_lse also returns lse [B*H, T] f32 as ia_relpos_attention_flash_lse defines it (NULL: skipped). */
+int ia_relpos_attention_context_supported(int T, int dk, int style, int left, int right);
+int ia_relpos_attention_context(const void* qkv, const void* pos_proj, const float* bias_u, const float* bias_v,
+                                const int64_t* lens, int B, int T, int H, int dk, int style, int left, int right,
+                                float dropout_p, unsigned seed, void* ctx, ia_stream_t stream);
+int ia_relpos_attention_context_lse(const void* qkv, const void* pos_proj, const float* bias_u, const float* bias_v,
+                                    const int64_t* lens, int B, int T, int H, int dk, int style, int left, int right,
+                                    float dropout_p, unsigned seed, void* ctx, float* lse, ia_stream_t stream);
+/* Backward of ia_relpos_attention_context_lse: the same two kernels under the context span, each walking only the tiles its
+ * interval reaches.  Arguments, outputs, return codes and alignment checks are ia_relpos_attention_flash_bwd's, plus (style,
+ * left, right) with the forward's rules.  dBand keeps the FULL layout: Rs / pad0 and the workspace size are
+ * ia_relpos_attention_flash_bwd_dims' / _ws_elems' (the _context_ functions return them after checking the context; 0 elements
+ * for an invalid one), so memory is O(T^2) per head although time is not -- a bounded band for this span is not built.  dpl
+ * rows of relative positions no admissible pair reaches are zero.  A context that admits every pair gives
+ * ia_relpos_attention_flash_bwd's bits.  No atomics: results reproduce bit for bit. */
+int ia_relpos_attention_context_bwd_dims(int T, int style, int left, int right, int* Rs, int* pad0);
+int64_t ia_relpos_attention_context_bwd_ws_elems(int B, int T, int H, int dk, int style, int left, int right);
+int ia_relpos_attention_context_bwd(const void* qkv, const void* pos_proj, const float* bias_u, const float* bias_v,
+                                    const int64_t* lens, const void* ctx, const void* dctx, const float* lse, int B, int T, int H,
+                                    int dk, int style, int left, int right, float dropout_p, unsigned seed, void* dqkv, void* dpl,
+                                    int pl_rows, float* dbias_u, float* dbias_v, void* dBand, void* QvHM, float* ws,
+                                    ia_stream_t stream);
 /* Round-1 forward of the same core (csrc/attention.hip: all keys of a 16-query strip in registers), kept only as the
  * independent implementation the tests compare against; no product path calls it.  Operands as above, pos_proj [2T-1, H*dk];
  * vt_scratch: ia_attn_vt_elems(B,T,H) bf16 elements, caller-owned (holds V^T, filled by this call).  Its own dropout mask
@@ -609,6 +644,11 @@ typedef struct ia_block_params {
                                 (ia_relpos_attention_local; pos_emb / pl_cached hold 2w+1 rows, row r <-> position w - r, so
                                 pos_rows >= 2w+1).  All layers of a prefix call must agree (IA_INVALID_VALUE otherwise); the
                                 trainable-block executors take only 0 (IA_UNSUPPORTED otherwise) */
+    int att_style;           /* 0: no limited context (att_left / att_right unread).  1: regular, 2: chunked_limited -- the style
+                                of ia_relpos_attention_context plus one, so that all-zero fields are full attention -- with */
+    int att_left, att_right; /* the context [left, right] (-1: unlimited): the prefix executor calls ia_relpos_attention_context,
+                                pos_rows >= 2T-1 as under full attention.  All layers of a prefix call must agree, and att_style
+                                != 0 with att_window > 0 is IA_INVALID_VALUE; the trainable-block executors take only 0 */
 } ia_block_params;
 size_t ia_conformer_prefix_ws_bytes(int B, int T, int d, int d_ff, int H, int ksz, int pos_rows);
 int ia_conformer_prefix_fwd(const ia_block_params* layers, int n_layers, float* x, const void* pos_emb, int pos_rows,

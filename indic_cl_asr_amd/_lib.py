@@ -28,7 +28,8 @@ class BlockParams(_c.Structure):
         "pos_u", "pos_v", "dw_w", "dw_b", "bn_g", "bn_b", "bn_rm", "bn_rv", "bn_nbt")]
         + [(n, _c.c_float) for n in ("ln_eps", "bn_eps", "bn_momentum", "p_drop", "p_ff", "p_att", "fc_factor")]
         + [(n, _c.c_int) for n in ("d", "d_ff", "n_heads", "ksz")]
-        + [("pl_cached", _c.c_void_p), ("w_pw1_glu", _c.c_void_p), ("b_pw1_glu", _c.c_void_p), ("att_window", _c.c_int)])
+        + [("pl_cached", _c.c_void_p), ("w_pw1_glu", _c.c_void_p), ("b_pw1_glu", _c.c_void_p), ("att_window", _c.c_int),
+           ("att_style", _c.c_int), ("att_left", _c.c_int), ("att_right", _c.c_int)])
 
 
 class BlockSaved(_c.Structure):
@@ -92,6 +93,11 @@ SIGNATURES = {
     "ia_relpos_attention_local_bwd_ws_elems": (_i64, [_i, _i, _i, _i, _i]),
     "ia_relpos_attention_local_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _c.c_uint, _vp, _vp, _i, _vp,
                                            _vp, _vp, _vp, _vp, _vp]),
+    "ia_relpos_attention_context_lse": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _c.c_uint, _vp, _vp, _vp]),
+    "ia_relpos_attention_context_bwd_dims": (_i, [_i, _i, _i, _i, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
+    "ia_relpos_attention_context_bwd_ws_elems": (_i64, [_i, _i, _i, _i, _i, _i, _i]),
+    "ia_relpos_attention_context_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _c.c_uint, _vp, _vp,
+                                             _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ia_quantize_fp8_rows": (_i, [_vp, _i, _i, _i64, _i, _vp, _i, _vp, _vp]),
     "ia_gemm_fp8": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _i, _f, _c.c_uint, _f, _vp, _i, _vp, _i, _vp, _i, _vp]),
     "ia_gemm_tn_grouped_scratch_elems": (_i64, [_vp, _i]),
@@ -152,6 +158,8 @@ SIGNATURES = {
     "ia_relpos_attention_flash_supported": (_i, [_i, _i]),
     "ia_relpos_attention_flash": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _c.c_uint, _vp, _vp]),
     "ia_relpos_attention_local_supported": (_i, [_i, _i, _i]),
+    "ia_relpos_attention_context_supported": (_i, [_i, _i, _i, _i, _i]),
+    "ia_relpos_attention_context": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _c.c_uint, _vp, _vp]),
     "ia_relpos_attention_local": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _c.c_uint, _vp, _vp]),
     "ia_lstm_scratch_bytes": (_sz, [_i, _i]),
     "ia_lstm_lds_bytes": (_i, [_i, _i]),

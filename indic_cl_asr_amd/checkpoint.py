@@ -77,7 +77,10 @@ def config_from_nemo_yaml(cfg: dict, **overrides) -> ModelConfig:
     put("dropout", enc, "dropout", float); put("dropout_pre_encoder", enc, "dropout_pre_encoder", float)
     put("dropout_emb", enc, "dropout_emb", float); put("dropout_att", enc, "dropout_att", float)
     put("self_attention_model", enc, "self_attention_model", str)
-    put("att_context_size", enc, "att_context_size", lambda v: [int(c) for c in v])
+    put("att_context_size", enc, "att_context_size",
+        lambda v: [[int(c) for c in cs] if isinstance(cs, (list, tuple)) else int(cs) for cs in v])
+    put("att_context_style", enc, "att_context_style", str)
+    put("att_context_probs", enc, "att_context_probs", lambda v: [float(p) for p in v])
     put("pred_hidden", pred, "pred_hidden", int); put("pred_dropout", pred, "dropout", float)
     put("joint_hidden", jnt, "joint_hidden", int); put("joint_dropout", jnt, "dropout", float)
     put("fused_batch_size", cfg.get("joint", {}), "fused_batch_size", int)
@@ -101,7 +104,7 @@ def model_from_nemo(path, strict=False, **overrides):
 
 
 def nemo_yaml_from_config(c: ModelConfig) -> dict:
-    return {
+    y = {
         "sample_rate": c.sample_rate,
         "preprocessor": {"sample_rate": c.sample_rate, "window_size": c.n_window_size / c.sample_rate,
                          "window_stride": c.n_window_stride / c.sample_rate, "features": c.feat_in, "n_fft": c.n_fft,
@@ -110,7 +113,7 @@ def nemo_yaml_from_config(c: ModelConfig) -> dict:
                          "time_width": c.time_width},
         "encoder": {"feat_in": c.feat_in, "n_layers": c.n_layers, "d_model": c.d_model, "subsampling": "striding",
                     "subsampling_factor": 4, "subsampling_conv_channels": c.d_model, "ff_expansion_factor": c.ff_expansion_factor,
-                    "self_attention_model": c.self_attention_model, "att_context_size": [int(v) for v in c.att_context_size],
+                    "self_attention_model": c.self_attention_model, "att_context_size": [[int(x) for x in v] if isinstance(v, (list, tuple)) else int(v) for v in c.att_context_size],
                     "n_heads": c.n_heads, "conv_kernel_size": c.conv_kernel_size,
                     "conv_norm_type": "batch_norm", "pos_emb_max_len": c.pos_emb_max_len, "dropout": c.dropout,
                     "dropout_pre_encoder": c.dropout_pre_encoder, "dropout_emb": c.dropout_emb, "dropout_att": c.dropout_att},
@@ -119,6 +122,11 @@ def nemo_yaml_from_config(c: ModelConfig) -> dict:
                   "jointnet": {"joint_hidden": c.joint_hidden, "activation": "relu", "dropout": c.joint_dropout}},
         "aux_ctc": {"ctc_loss_weight": c.ctc_loss_weight},
     }
+    if c.att_context_style is not None:   # (absent keys are the reference's defaults: a default model's yaml stays as it was)
+        y["encoder"]["att_context_style"] = c.att_context_style
+    if c.att_context_probs is not None:
+        y["encoder"]["att_context_probs"] = [float(p) for p in c.att_context_probs]
+    return y
 
 
 def write_nemo(model, path):

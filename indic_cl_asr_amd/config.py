@@ -34,6 +34,10 @@ class ModelConfig:
     # switched at run time by change_attention_model
     self_attention_model: str = "rel_pos"
     att_context_size: List[int] = field(default_factory=lambda: [-1, -1])
+    # a limited context under "rel_pos" (yaml :107-117): None (a limited context is refused) | "regular" | "chunked_limited";
+    # att_context_size is then [L, R] or, for multi-look-ahead training, a list of such pairs drawn with att_context_probs
+    att_context_style: Optional[str] = None
+    att_context_probs: Optional[List[float]] = None
     # prediction / joint (yaml :130-158)
     pred_hidden: int = 640
     joint_hidden: int = 640

@@ -1,7 +1,8 @@
 // The key-tiled rel-pos attention kernels' one vocabulary.  There is one kernel template per role, written once as
 // template <bool DK64, class Span>: the forward (attention_flash.hip), the query-owner and the key-owner backward
-// (attention_flash_bwd.hip).  Full attention and local attention (|i - j| <= w) are the same kernels under two spans; the Span
-// section below lists everything in which they differ.  Here: fragment types, tile constants, the attention-dropout hash (the
+// (attention_flash_bwd.hip).  Full attention, local attention (|i - j| <= w) and a limited context under full rel-pos attention
+// (regular [L, R] or chunked_limited) are the same kernels under three spans; the Span section below lists everything in which
+// they differ.  Here: fragment types, tile constants, the attention-dropout hash (the
 // backward regenerates the forward's mask), the zero-padding head-row loader, the swizzled LDS addresses and fragment reads,
 // register staging of a tile (fetch / commit), the spans, the K | V | P stage, the query fragments, the band block, the workgroup
 // coordinates, the guarded head-row store, the backwards' strip geometry, workspace layout and position-gradient step, and the
@@ -90,19 +91,22 @@ __device__ __forceinline__ void fa_commit_rows(unsigned char* tile, const uint4 
 }
 
 // ---- Span: which (query, key) pairs exist.  A small device-side value; FaFullSpan admits every key below the length,
-// FaLocalSpan the keys |i - j| <= w below the length (0 <= w <= T - 1: the host reduces a larger window).  It supplies what
-// differs between full and local attention, and nothing else:
-//   1. centre(): the position row of relative position 0, T - 1 (full) or w (local).  The stage's position rows are
+// FaLocalSpan the keys |i - j| <= w below the length (0 <= w <= T - 1: the host reduces a larger window), FaContextSpan one
+// interval of keys per query on the full span's position table (below).  Every span is built from (T, FaSpanArgs) and reads of
+// the three integers what it needs.  It supplies what differs between the attention models, and nothing else.  The owner of a
+// walk is named by a tag, FaQueryOwner (forward, query-owner backward: a query tile walks key tiles, a query admits keys) or
+// FaKeyOwner (key-owner backward: a key tile walks query tiles, a key admits queries); the two symmetric spans ignore it.
+//   1. centre(): the position row of relative position 0, T - 1 (full, context) or w (local).  The stage's position rows are
 //      centre - I0 - 63 + j0 .. + 127 clamped to [0, 2 centre] (clamped rows give finite band values for pairs that the
 //      admissibility removes), the key-owner's centre - i0 - 63 + J0 .. + 127, and the dBand column of strip column 0 is
 //      centre - 15 - iw + j0 + pad0.
-//   2. tiles(X0, len): the 64-row tiles lo .. end - 1 of the OTHER axis that a query tile or key tile at X0 < len walks.  Full:
+//   2. tiles(owner, X0, len): the 64-row tiles lo .. end - 1 of the OTHER axis that a query tile or key tile at X0 < len walks.  Full:
 //      every tile below len.  Local: those that hold a row of [max(X0 - w, 0), min(X0 + 63 + w, len - 1)] (both ends
 //      non-negative, the first <= X0 <= the second), 1 + 2 ceil(w / 64) tiles at the most whatever T is.  The one-stage prefetch
 //      follows them.  A plain aggregate read by its members, walked `t < end`, `t + 1 < end`: that is the form in which the full
 //      forward compiles to its earlier loop (walked `t <= last`, or through member functions, it is 1 % slower at T = 3001;
 //      profiles/attention_span_refactor.md).
-//   3. admit(own, valid, len): the rows of the other axis that pair with a lane's own row, built once per lane and asked once per
+//   3. admit(owner, own, valid, len): the rows of the other axis that pair with a lane's own row, built once per lane and asked once per
 //      element.  `valid` is own < len; the forward passes true (a padded query's context is zeroed at the store).  In the backward
 //      an inadmissible pair gives P = 0 by value, in the forward -inf before the row maximum.
 //   4. tile_unmasked(j0, iw, len): the forward's mask-free score branch.  Full: the key tile lies below len (workgroup-uniform).
@@ -117,6 +121,9 @@ __device__ __forceinline__ void fa_commit_rows(unsigned char* tile, const uint4 
 //        every flushed column; only a partial last wave's leading chunks fall left of column 0.
 // Aggregates are returned by value: filled through a reference under control flow they cost the query-owner registers.
 struct FaTiles { int lo, end; };   // tiles lo .. end - 1
+struct FaSpanArgs { int w, w2, chunk; };   // local: w.  context: regular (L, R, 0) or chunked (n, -, C).  full: unread
+struct FaQueryOwner {};
+struct FaKeyOwner {};
 
 struct FaFullSpan {
     static constexpr bool kSparseTiles = false, kBoundedBand = false;
@@ -125,10 +132,12 @@ struct FaFullSpan {
         __device__ __forceinline__ bool operator()(int x) const { return ok && x < len; }
     };
     int T;
-    __device__ __forceinline__ FaFullSpan(int T_, int) : T(T_) {}
+    __device__ __forceinline__ FaFullSpan(int T_, const FaSpanArgs&) : T(T_) {}
     __device__ __forceinline__ int centre() const { return T - 1; }
-    __device__ __forceinline__ FaTiles tiles(int, int len) const { return FaTiles{0, (len + 63) / 64}; }
-    __device__ __forceinline__ Adm admit(int, bool valid, int len) const { return Adm{valid, len}; }
+    template <class Owner>
+    __device__ __forceinline__ FaTiles tiles(Owner, int, int len) const { return FaTiles{0, (len + 63) / 64}; }
+    template <class Owner>
+    __device__ __forceinline__ Adm admit(Owner, int, bool valid, int len) const { return Adm{valid, len}; }
     __device__ __forceinline__ bool tile_unmasked(int j0, int, int len) const { return j0 + 64 <= len; }
 };
 
@@ -139,17 +148,67 @@ struct FaLocalSpan {
         __device__ __forceinline__ bool operator()(int x) const { return x >= lo && x <= hi; }
     };
     int w;
-    __device__ __forceinline__ FaLocalSpan(int, int w_) : w(w_) {}
+    __device__ __forceinline__ FaLocalSpan(int, const FaSpanArgs& s) : w(s.w) {}
     __device__ __forceinline__ int centre() const { return w; }
-    __device__ __forceinline__ FaTiles tiles(int X0, int len) const {
+    template <class Owner>
+    __device__ __forceinline__ FaTiles tiles(Owner, int X0, int len) const {
         const int lo = X0 - w > 0 ? X0 - w : 0, hi = X0 + 63 + w < len - 1 ? X0 + 63 + w : len - 1;
         return FaTiles{lo / 64, hi / 64 + 1};
     }
-    __device__ __forceinline__ Adm admit(int own, bool valid, int len) const {
+    template <class Owner>
+    __device__ __forceinline__ Adm admit(Owner, int own, bool valid, int len) const {
         return Adm{valid ? own - w : len, own + w < len - 1 ? own + w : len - 1};
     }
     __device__ __forceinline__ bool tile_unmasked(int j0, int iw, int len) const {
         return j0 + 64 <= len && j0 >= iw + 15 - w && j0 + 63 <= iw + w;
+    }
+};
+
+// A limited context under full rel-pos attention: the reference encoder's att_context_size = [L, R] with att_context_style
+// 'regular' or 'chunked_limited' (A/modules/conformer_encoder.py:686-740, a [T, T] mask there).  The keys of a query are ONE
+// interval and so are the queries of a key; the position table is the full span's (2T - 1 rows, centre T - 1):
+//   regular [L, R]            keys of i: [i - L, i + R]                        queries of j: [j - R, j + L]
+//   chunked, C = R + 1,       keys of i: [(i/C - n) C, (i/C + 1) C - 1]        queries of j: [(j/C) C, (j/C + n + 1) C - 1]
+//     n = L / C
+// The host reduces every form to these two with bounded integers: an unlimited side of a regular context is T, chunked
+// [L, -1] is regular [L, T], C is at most T and n at most (T - 1) / C (so n C <= T - 1: no overflow for T < 2^29).  chunk == 0
+// selects the regular form, (w, w2) = (L, R); chunk = C > 0 the chunked one, w = n.
+//   tiles(owner, X0, len): the tiles that hold a row of [lo(X0), hi(min(X0 + 63, len - 1))] clamped to [0, len - 1], lo / hi the
+//     owner's interval ends (both monotone in the row; lo(x) <= x <= hi(x), so the range is never empty).  Only these are
+//     visited: O(T (L + R)) work when both sides are limited.
+//   tile_unmasked: the key tile lies below len, at or right of the first key of query iw + 15 and at or left of the last key of
+//     query iw: inside the interval of all 16 queries of the wave, by monotonicity, under either style.
+//   kSparseTiles: a visited tile can hold no key for a query (everything right of the diagonal under [L, 0], a chunk edge
+//     inside a tile), so the all-masked guard and the by-value zero apply as under the local span.
+//   kBoundedBand = false: the backward keeps the FULL span's dBand layout (ia_relpos_attention_flash_bwd_dims' Rs and pad0,
+//     every flushed column written, the memset's zeros elsewhere) and the position gradient contracts all 2T - 1 rows.  A
+//     bounded band for this span is not built.
+struct FaContextSpan {
+    static constexpr bool kSparseTiles = true, kBoundedBand = false;
+    struct Adm {   // [lo, hi], empty (lo = len > hi) for an own row >= len
+        int lo, hi;
+        __device__ __forceinline__ bool operator()(int x) const { return x >= lo && x <= hi; }
+    };
+    int T, a, b, C;
+    __device__ __forceinline__ FaContextSpan(int T_, const FaSpanArgs& s) : T(T_), a(s.w), b(s.w2), C(s.chunk) {}
+    __device__ __forceinline__ int centre() const { return T - 1; }
+    // first and last row of the other axis that pair with row x of the owner's (not clamped to the utterance)
+    __device__ __forceinline__ int lo(FaQueryOwner, int x) const { return C > 0 ? (x / C - a) * C : x - a; }
+    __device__ __forceinline__ int hi(FaQueryOwner, int x) const { return C > 0 ? (x / C + 1) * C - 1 : x + b; }
+    __device__ __forceinline__ int lo(FaKeyOwner, int x) const { return C > 0 ? (x / C) * C : x - b; }
+    __device__ __forceinline__ int hi(FaKeyOwner, int x) const { return C > 0 ? (x / C + a + 1) * C - 1 : x + a; }
+    template <class Owner>
+    __device__ __forceinline__ FaTiles tiles(Owner o, int X0, int len) const {
+        const int l = lo(o, X0), h = hi(o, X0 + 63 < len - 1 ? X0 + 63 : len - 1);
+        return FaTiles{(l > 0 ? l : 0) / 64, (h < len - 1 ? h : len - 1) / 64 + 1};
+    }
+    template <class Owner>
+    __device__ __forceinline__ Adm admit(Owner o, int own, bool valid, int len) const {
+        const int l = lo(o, own), h = hi(o, own);
+        return Adm{valid ? l : len, h < len - 1 ? h : len - 1};
+    }
+    __device__ __forceinline__ bool tile_unmasked(int j0, int iw, int len) const {
+        return j0 + 64 <= len && j0 >= lo(FaQueryOwner{}, iw + 15) && j0 + 63 <= hi(FaQueryOwner{}, iw);
     }
 };
 
@@ -318,6 +377,26 @@ inline int fb_dpos_gemm_pack(const void* dBand, const void* QvHM, float* ws, con
                        (const float*)dpos, H, rs, p0, R, dk, rows, (__bf16*)out);
     IA_RETURN_IF_LAUNCH_FAILED();
     return IA_OK;
+}
+
+// host: (style, left, right) of the limited-context entry points (style 0 regular, 1 chunked_limited; a side of -1 is unlimited)
+// -> the context span's bounded integers.  FA_CTX_FULL: the context admits every pair (the caller runs the full span);
+// FA_CTX_INVALID: unknown style, a side below -1, or chunked with left >= 0, right >= 0 and left % (right + 1) != 0.
+enum { FA_CTX_INVALID = -1, FA_CTX_SPAN = 0, FA_CTX_FULL = 1 };
+inline int fa_context_args(int T, int style, int left, int right, FaSpanArgs* sp) {
+    if (T <= 0 || (style != 0 && style != 1) || left < -1 || right < -1) return FA_CTX_INVALID;
+    if (style == 1 && right >= 0) {
+        if (left >= 0 && left % (right + 1) != 0) return FA_CTX_INVALID;
+        if (right + 1 >= T) return FA_CTX_FULL;   // one chunk holds every frame
+        const int C = right + 1, nmax = (T - 1) / C;
+        *sp = FaSpanArgs{(left < 0 || left / C > nmax) ? nmax : left / C, 0, C};
+        return FA_CTX_SPAN;
+    }
+    // regular, and chunked [L, -1] (i - j <= L alone); i - j and j - i never exceed T - 1
+    const int L = (left < 0 || left > T - 1) ? T - 1 : left, R = (right < 0 || right > T - 1) ? T - 1 : right;
+    if (L == T - 1 && R == T - 1) return FA_CTX_FULL;
+    *sp = FaSpanArgs{L, R, 0};
+    return FA_CTX_SPAN;
 }
 
 // host: raise the kernel's LDS limit once, launch it on FA_THREADS threads, IA_LAUNCH_FAILED if either fails

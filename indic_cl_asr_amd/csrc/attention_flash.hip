@@ -1,4 +1,5 @@
-// Relative-position multi-head self-attention forward, key-tile loop with online softmax (gfx950), full or local by its Span.
+// Relative-position multi-head self-attention forward, key-tile loop with online softmax (gfx950), full, local or limited-context
+// by its Span.
 //
 //   ctx[b,i,h,:] = sum_j softmax_j( ((q_i+u_h).k_j + (q_i+v_h).p_h[centre-i+j]) / sqrt(dk) ) v_j ,   j < len_b  (and |i-j| <= w)
 //
@@ -11,8 +12,13 @@
 // offered: the reference adds their position term to the wrong columns.  The host reduces a window beyond T - 1 to w' = T - 1
 // by advancing the table pointer (row r of the 2w+1 table is row r - (w - w') of the 2w'+1 one), so the kernel's index
 // arithmetic never sees a window larger than T; a window >= T - 1 gives the full span's values.
+// Context span: the full span's formula and table under the attention mask of ConformerEncoder._create_masks
+// (A/modules/conformer_encoder.py:686-740) for att_context_style 'regular' / 'chunked_limited': one interval of keys per query
+// (attention_flash.h, FaContextSpan); the host reduces (style, left, right) to bounded integers and runs the full span when the
+// context admits every pair.
 //
-// The kernel walks 64-key tiles (the span's: all below len, or the 1 + 2 ceil(w / 64) at the most that meet the window) and
+// The kernel walks 64-key tiles (the span's: all below len, the 1 + 2 ceil(w / 64) at the most that meet the window, or those
+// that meet the context's interval) and
 // keeps only the running maximum, sum and output of a 16-query strip in registers, so T is unbounded (30 s audio: T' = 751);
 // the head dim is any multiple of 4 up to 64 (d = 144 / 4 heads = 36: tiles zero-padded to 64 in LDS).
 //
@@ -42,7 +48,7 @@ struct FaArgs {
     const __bf16* qkv; const __bf16* pl; const float* bias_u; const float* bias_v; const int64_t* lens;
     __bf16* ctx; int B, T, H, dk; float scale; unsigned seed, thr; float keep_scale;
     float* lse;   // optional [B*H, T]: log-sum-exp of each query's scaled scores (the backward recomputes P = exp(s - lse))
-    int w;        // the local span's window, 0 <= w <= T - 1.  Last: the full span does not read it and loads its arguments as before
+    FaSpanArgs sp;   // the span's integers (local: w, 0 <= w <= T - 1).  Last: the full span does not read them
 };
 
 template <bool DK64, class Span>
@@ -51,7 +57,7 @@ __global__ __launch_bounds__(FA_THREADS, 3) void relpos_flash_fwd_kernel(FaArgs 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 15, q4 = lane >> 4;
     const int T = a.T, H = a.H, dk = a.dk, d = H * dk;
-    const Span span(T, a.w);
+    const Span span(T, a.sp);
     const FaWg wg = fa_wg(a.B, T, H, a.lens);
     if (wg.len < 0) return;
     const int bh = wg.bh, h = wg.h, b = wg.b, len = wg.len;
@@ -83,7 +89,7 @@ __global__ __launch_bounds__(FA_THREADS, 3) void relpos_flash_fwd_kernel(FaArgs 
     // measured per-workgroup cost 5 us + 3.3 us per key tile), and three waves per SIMD hide each other's LDS round trips.
     FaKvpStage<DK64> stage(a.qkv, a.pl, smem, b, h, T, d, dk, I0, span.centre(), tid);
 
-    const FaTiles ktiles = span.tiles(I0, len);   // the key tiles of this query tile
+    const FaTiles ktiles = span.tiles(FaQueryOwner{}, I0, len);   // the key tiles of this query tile
     stage.fetch(ktiles.lo);
     stage.commit();
     __syncthreads();
@@ -129,7 +135,7 @@ __global__ __launch_bounds__(FA_THREADS, 3) void relpos_flash_fwd_kernel(FaArgs 
                 }
             }
         } else {
-            const auto admitted = span.admit(iq, true, len);   // this query's keys
+            const auto admitted = span.admit(FaQueryOwner{}, iq, true, len);   // this query's keys
 #pragma unroll
             for (int jt = 0; jt < 4; ++jt) {
                 union { uint2 u; __bf16 e[4]; } bd;
@@ -209,11 +215,11 @@ __global__ __launch_bounds__(FA_THREADS, 3) void relpos_flash_fwd_kernel(FaArgs 
 // host: the forward under one span, after the entry point's argument checks
 template <class Span>
 int fa_forward(const void* qkv, const __bf16* pl, const float* bias_u, const float* bias_v, const int64_t* lens, int B, int T, int H,
-               int dk, int w, float dropout_p, unsigned seed, void* ctx, float* lse, ia_stream_t stream) {
+               int dk, FaSpanArgs sp, float dropout_p, unsigned seed, void* ctx, float* lse, ia_stream_t stream) {
     FaArgs a;
     a.qkv = (const __bf16*)qkv; a.pl = pl; a.bias_u = bias_u; a.bias_v = bias_v; a.lens = lens;
     a.lse = lse;
-    a.ctx = (__bf16*)ctx; a.B = B; a.T = T; a.H = H; a.dk = dk; a.w = w; a.scale = 1.f / sqrtf((float)dk); a.seed = seed;
+    a.ctx = (__bf16*)ctx; a.B = B; a.T = T; a.H = H; a.dk = dk; a.sp = sp; a.scale = 1.f / sqrtf((float)dk); a.seed = seed;
     const ia_dropout_t drop = ia_dropout_rule(dropout_p);
     a.thr = drop.thr; a.keep_scale = drop.keep_scale;
     const int nqt = (T + 63) / 64;
@@ -239,7 +245,7 @@ extern "C" int ia_relpos_attention_flash_lse(const void* qkv, const void* pos_pr
     if (!ia_relpos_attention_flash_supported(T, dk)) return IA_UNSUPPORTED;
     if (dropout_p < 0.f || dropout_p >= 1.f) return IA_INVALID_VALUE;
     if (!ia_is_aligned(qkv, 16) || !ia_is_aligned(pos_proj, 16) || !ia_is_aligned(ctx, 8)) return IA_INVALID_VALUE;
-    return fa_forward<FaFullSpan>(qkv, (const __bf16*)pos_proj, bias_u, bias_v, lens, B, T, H, dk, T - 1, dropout_p, seed, ctx, lse, stream);
+    return fa_forward<FaFullSpan>(qkv, (const __bf16*)pos_proj, bias_u, bias_v, lens, B, T, H, dk, FaSpanArgs{T - 1, 0, 0}, dropout_p, seed, ctx, lse, stream);
 }
 
 extern "C" int ia_relpos_attention_local_supported(int T, int dk, int window) {
@@ -262,5 +268,34 @@ extern "C" int ia_relpos_attention_local_lse(const void* qkv, const void* pos_pr
     // a window beyond T - 1 admits no further key: the same band with w' = T - 1 and the table advanced by w - w' rows
     const int w = window < T - 1 ? window : T - 1;
     return fa_forward<FaLocalSpan>(qkv, (const __bf16*)pos_proj + (size_t)(window - w) * ((size_t)H * dk), bias_u, bias_v, lens, B, T, H,
-                                   dk, w, dropout_p, seed, ctx, lse, stream);
+                                   dk, FaSpanArgs{w, 0, 0}, dropout_p, seed, ctx, lse, stream);
+}
+
+// ---- limited context: (style, left, right) -> the context span's bounded integers (attention_flash.h), or "admits every pair"
+extern "C" int ia_relpos_attention_context_supported(int T, int dk, int style, int left, int right) {
+    FaSpanArgs sp;
+    return (fa_context_args(T, style, left, right, &sp) != FA_CTX_INVALID && ia_relpos_attention_flash_supported(T, dk)) ? 1 : 0;
+}
+
+extern "C" int ia_relpos_attention_context(const void* qkv, const void* pos_proj, const float* bias_u, const float* bias_v,
+                                           const int64_t* lens, int B, int T, int H, int dk, int style, int left, int right,
+                                           float dropout_p, unsigned seed, void* ctx, ia_stream_t stream) {
+    return ia_relpos_attention_context_lse(qkv, pos_proj, bias_u, bias_v, lens, B, T, H, dk, style, left, right, dropout_p, seed, ctx,
+                                           nullptr, stream);
+}
+
+extern "C" int ia_relpos_attention_context_lse(const void* qkv, const void* pos_proj, const float* bias_u, const float* bias_v,
+                                               const int64_t* lens, int B, int T, int H, int dk, int style, int left, int right,
+                                               float dropout_p, unsigned seed, void* ctx, float* lse, ia_stream_t stream) {
+    if (!qkv || !pos_proj || !bias_u || !bias_v || !lens || !ctx || B <= 0 || T <= 0 || H <= 0) return IA_INVALID_VALUE;
+    FaSpanArgs sp;
+    const int kind = fa_context_args(T, style, left, right, &sp);
+    if (kind == FA_CTX_INVALID) return IA_INVALID_VALUE;
+    if (!ia_relpos_attention_flash_supported(T, dk)) return IA_UNSUPPORTED;
+    if (dropout_p < 0.f || dropout_p >= 1.f) return IA_INVALID_VALUE;
+    if (!ia_is_aligned(qkv, 16) || !ia_is_aligned(pos_proj, 16) || !ia_is_aligned(ctx, 8)) return IA_INVALID_VALUE;
+    if (kind == FA_CTX_FULL)   // every pair admitted: the full span's kernel and bits
+        return fa_forward<FaFullSpan>(qkv, (const __bf16*)pos_proj, bias_u, bias_v, lens, B, T, H, dk, FaSpanArgs{T - 1, 0, 0}, dropout_p, seed,
+                                      ctx, lse, stream);
+    return fa_forward<FaContextSpan>(qkv, (const __bf16*)pos_proj, bias_u, bias_v, lens, B, T, H, dk, sp, dropout_p, seed, ctx, lse, stream);
 }

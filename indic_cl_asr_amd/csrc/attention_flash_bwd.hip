@@ -1,4 +1,5 @@
-// Relative-position multi-head self-attention BACKWARD, key-tiled (gfx950), full or local by its Span: no [T,T] probability /
+// Relative-position multi-head self-attention BACKWARD, key-tiled (gfx950), full, local or limited-context by its Span (the
+// context span: the full span's centre, table and dBand layout, the pairs and tiles of FaContextSpan): no [T,T] probability /
 // score-gradient matrices in HBM, any T, head dim any multiple of 4 up to 64.  Autograd of RelPositionMultiHeadAttention.forward
 // (A/parts/submodules/multi_head_attention.py:197-250; local span: of the band |i - j| <= w of
 // RelPositionMultiHeadAttentionLongformer.forward) with the forward of attention_flash.hip (same span and tile ranges, same
@@ -39,6 +40,7 @@ struct FbArgs {
     const __bf16* ctx; const __bf16* dctx; const float* lse;
     __bf16* dqkv; __bf16* dBand; __bf16* QvHM; float* D; float* part;
     int B, T, H, dk, w, Rs, pad0; float scale; unsigned seed, thr; float keep_scale;   // w: the local span's, 0 <= w <= T - 1
+    int w2, chunk;   // with w the context span's integers (FaSpanArgs).  Last: the other spans do not read them
 };
 
 // a 16-byte chunk at dBand column gcol is written: inside [0, rs) of a bounded band, right of column 0 of an unbounded one
@@ -55,7 +57,7 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArg
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 15, q4 = lane >> 4;
     const int T = a.T, H = a.H, dk = a.dk, d = H * dk, B = a.B;
-    const Span span(T, a.w);
+    const Span span(T, FaSpanArgs{a.w, a.w2, a.chunk});
     const int nqt = (T + 63) / 64;
     const FaWg wg = fa_wg(B, T, H, a.lens);
     if (wg.len < 0) return;
@@ -106,8 +108,8 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_q_kernel(FbArg
 
     FaKvpStage<DK64> stage(a.qkv, a.pl, smem, b, h, T, d, dk, I0, span.centre(), tid);
 
-    const FaTiles ktiles = span.tiles(I0, len);                  // the key tiles of this query tile, as the forward walks them
-    const auto admitted = span.admit(iq, qvalid, len);       // this query's keys
+    const FaTiles ktiles = span.tiles(FaQueryOwner{}, I0, len);                  // the key tiles of this query tile, as the forward walks them
+    const auto admitted = span.admit(FaQueryOwner{}, iq, qvalid, len);       // this query's keys
     stage.fetch(ktiles.lo);
     stage.commit();
     __syncthreads();
@@ -269,7 +271,7 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_kv_kernel(FbAr
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 15, q4 = lane >> 4;
     const int T = a.T, H = a.H, dk = a.dk, d = H * dk, B = a.B;
-    const Span span(T, a.w);
+    const Span span(T, FaSpanArgs{a.w, a.w2, a.chunk});
     const FaWg wg = fa_wg(B, T, H, a.lens);
     if (wg.len < 0) return;
     const int bh = wg.bh, kt = wg.tile, h = wg.h, b = wg.b, len = wg.len;
@@ -352,8 +354,8 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_kv_kernel(FbAr
         if (tid < 128) reinterpret_cast<float*>(smem + 3 * FA_T64 + FA_PBUF)[tid] = rl;
     };
 
-    const FaTiles qtiles = span.tiles(J0, len);                 // the query tiles of this key tile
-    const auto admitted = span.admit(j, kvalid, len);       // this key's queries
+    const FaTiles qtiles = span.tiles(FaKeyOwner{}, J0, len);                 // the query tiles of this key tile
+    const auto admitted = span.admit(FaKeyOwner{}, j, kvalid, len);       // this key's queries
     fetch(qtiles.lo);
     commit();
     __syncthreads();
@@ -457,18 +459,19 @@ __global__ __launch_bounds__(FA_THREADS, 2) void relpos_flash_bwd_kv_kernel(FbAr
 }
 
 // host: the backward under one span, after the entry point's argument checks: both kernels, the bias-partials pass and the
-// position gradient.  dBand [H, B*T, rs] holds relative positions 0 .. 2w behind p0 columns; they go to rows 0 .. 2w of
-// dpl [pl_rows, d], zero rows behind them.
+// position gradient.  dBand [H, B*T, rs] holds relative positions 0 .. 2c (c = the span's centre: sp.w under the full and local
+// spans, T - 1 under the context span) behind p0 columns; they go to rows 0 .. 2c of dpl [pl_rows, d], zero rows behind them.
 template <class Span>
 int fb_backward(const void* qkv, const __bf16* pl, const float* bias_u, const float* bias_v, const int64_t* lens, const void* ctx,
-                const void* dctx, const float* lse, int B, int T, int H, int dk, int w, int rs, int p0, float dropout_p, unsigned seed,
+                const void* dctx, const float* lse, int B, int T, int H, int dk, FaSpanArgs sp, int centre, int rs, int p0, float dropout_p, unsigned seed,
                 void* dqkv, __bf16* dpl, int pl_rows, float* dbias_u, float* dbias_v, void* dBand, void* QvHM, float* ws,
                 ia_stream_t stream) {
     const FbWs lay = fb_ws_layout(B, T, H, dk, rs);
     FbArgs a;
     a.qkv = (const __bf16*)qkv; a.pl = pl; a.bias_u = bias_u; a.bias_v = bias_v; a.lens = lens;
     a.ctx = (const __bf16*)ctx; a.dctx = (const __bf16*)dctx; a.lse = lse; a.dqkv = (__bf16*)dqkv; a.dBand = (__bf16*)dBand;
-    a.QvHM = (__bf16*)QvHM; a.D = ws + lay.D; a.part = ws + lay.part; a.B = B; a.T = T; a.H = H; a.dk = dk; a.w = w;
+    a.QvHM = (__bf16*)QvHM; a.D = ws + lay.D; a.part = ws + lay.part; a.B = B; a.T = T; a.H = H; a.dk = dk; a.w = sp.w;
+    a.w2 = sp.w2; a.chunk = sp.chunk;
     a.Rs = rs; a.pad0 = p0;
     a.scale = 1.f / sqrtf((float)dk); a.seed = seed;
     const ia_dropout_t drop = ia_dropout_rule(dropout_p);
@@ -485,8 +488,8 @@ int fb_backward(const void* qkv, const __bf16* pl, const float* bias_u, const fl
     if (rc != IA_OK) return rc;
     ia_partials_finish(a.part, B * nt, 2 * H * dk, H * dk, dbias_u, dbias_v, st);
     IA_RETURN_IF_LAUNCH_FAILED();
-    // position-projection gradient: the band columns p0 .. p0 + 2w of the heads' TN GEMMs
-    return fb_dpos_gemm_pack(dBand, QvHM, ws, lay, rs, p0, 2 * w + 1, B, T, H, dk, dpl, pl_rows, stream);
+    // position-projection gradient: the band columns p0 .. p0 + 2 centre of the heads' TN GEMMs
+    return fb_dpos_gemm_pack(dBand, QvHM, ws, lay, rs, p0, 2 * centre + 1, B, T, H, dk, dpl, pl_rows, stream);
 }
 
 inline int fb_window(int T, int window) { return window < T - 1 ? window : T - 1; }   // a window beyond T - 1 admits no further key
@@ -526,8 +529,8 @@ extern "C" int ia_relpos_attention_flash_bwd(const void* qkv, const void* pos_pr
         return IA_INVALID_VALUE;
     int rs, p0;
     ia_relpos_attention_flash_bwd_dims(T, &rs, &p0);
-    return fb_backward<FaFullSpan>(qkv, (const __bf16*)pos_proj, bias_u, bias_v, lens, ctx, dctx, lse, B, T, H, dk, T - 1, rs, p0, dropout_p,
-                                   seed, dqkv, (__bf16*)dpl, pl_rows, dbias_u, dbias_v, dBand, QvHM, ws, stream);
+    return fb_backward<FaFullSpan>(qkv, (const __bf16*)pos_proj, bias_u, bias_v, lens, ctx, dctx, lse, B, T, H, dk, FaSpanArgs{T - 1, 0, 0}, T - 1, rs,
+                                   p0, dropout_p, seed, dqkv, (__bf16*)dpl, pl_rows, dbias_u, dbias_v, dBand, QvHM, ws, stream);
 }
 
 extern "C" int ia_relpos_attention_local_bwd_dims(int T, int window, int* Rs, int* pad0) {
@@ -566,7 +569,46 @@ extern "C" int ia_relpos_attention_local_bwd(const void* qkv, const void* pos_pr
     int rs, p0;
     ia_relpos_attention_local_bwd_dims(T, window, &rs, &p0);
     if (row0 > 0 && hipMemsetAsync(dpl, 0, (size_t)row0 * d * sizeof(__bf16), (hipStream_t)stream) != hipSuccess) return IA_LAUNCH_FAILED;
-    return fb_backward<FaLocalSpan>(qkv, (const __bf16*)pos_proj + (size_t)row0 * d, bias_u, bias_v, lens, ctx, dctx, lse, B, T, H, dk, w, rs,
-                                    p0, dropout_p, seed, dqkv, (__bf16*)dpl + (size_t)row0 * d, pl_rows - row0, dbias_u, dbias_v, dBand,
+    return fb_backward<FaLocalSpan>(qkv, (const __bf16*)pos_proj + (size_t)row0 * d, bias_u, bias_v, lens, ctx, dctx, lse, B, T, H, dk,
+                                    FaSpanArgs{w, 0, 0}, w, rs, p0, dropout_p, seed, dqkv, (__bf16*)dpl + (size_t)row0 * d, pl_rows - row0, dbias_u, dbias_v, dBand,
                                     QvHM, ws, stream);
+}
+
+// ---- limited context: the full span's dBand layout and workspace (kBoundedBand = false), the context span's pairs
+extern "C" int ia_relpos_attention_context_bwd_dims(int T, int style, int left, int right, int* Rs, int* pad0) {
+    FaSpanArgs sp;
+    if (!Rs || !pad0 || fa_context_args(T, style, left, right, &sp) == FA_CTX_INVALID) return IA_INVALID_VALUE;
+    return ia_relpos_attention_flash_bwd_dims(T, Rs, pad0);
+}
+
+extern "C" int64_t ia_relpos_attention_context_bwd_ws_elems(int B, int T, int H, int dk, int style, int left, int right) {
+    FaSpanArgs sp;
+    if (fa_context_args(T, style, left, right, &sp) == FA_CTX_INVALID) return 0;
+    return ia_relpos_attention_flash_bwd_ws_elems(B, T, H, dk);
+}
+
+extern "C" int ia_relpos_attention_context_bwd(const void* qkv, const void* pos_proj, const float* bias_u, const float* bias_v,
+                                               const int64_t* lens, const void* ctx, const void* dctx, const float* lse, int B,
+                                               int T, int H, int dk, int style, int left, int right, float dropout_p,
+                                               unsigned seed, void* dqkv, void* dpl, int pl_rows, float* dbias_u, float* dbias_v,
+                                               void* dBand, void* QvHM, float* ws, ia_stream_t stream) {
+    if (!qkv || !pos_proj || !bias_u || !bias_v || !lens || !ctx || !dctx || !lse || !dqkv || !dpl || !dBand || !QvHM || !ws ||
+        !dbias_u || !dbias_v || B <= 0 || T <= 0 || H <= 0 || pl_rows < 2 * T - 1)
+        return IA_INVALID_VALUE;
+    FaSpanArgs sp;
+    const int kind = fa_context_args(T, style, left, right, &sp);
+    if (kind == FA_CTX_INVALID) return IA_INVALID_VALUE;
+    if (!ia_relpos_attention_flash_supported(T, dk)) return IA_UNSUPPORTED;
+    if (dropout_p < 0.f || dropout_p >= 1.f) return IA_INVALID_VALUE;
+    if (!ia_is_aligned(qkv, 16) || !ia_is_aligned(pos_proj, 16) || !ia_is_aligned(ctx, 8) || !ia_is_aligned(dctx, 8) ||
+        !ia_is_aligned(dqkv, 8) || !ia_is_aligned(dBand, 16) || !ia_is_aligned(QvHM, 16) || !ia_is_aligned(ws, 16) ||
+        !ia_is_aligned(dpl, 8))
+        return IA_INVALID_VALUE;
+    int rs, p0;
+    ia_relpos_attention_flash_bwd_dims(T, &rs, &p0);
+    if (kind == FA_CTX_FULL)   // every pair admitted: the full span's kernels and bits
+        return fb_backward<FaFullSpan>(qkv, (const __bf16*)pos_proj, bias_u, bias_v, lens, ctx, dctx, lse, B, T, H, dk, FaSpanArgs{T - 1, 0, 0},
+                                       T - 1, rs, p0, dropout_p, seed, dqkv, (__bf16*)dpl, pl_rows, dbias_u, dbias_v, dBand, QvHM, ws, stream);
+    return fb_backward<FaContextSpan>(qkv, (const __bf16*)pos_proj, bias_u, bias_v, lens, ctx, dctx, lse, B, T, H, dk, sp, T - 1, rs, p0,
+                                      dropout_p, seed, dqkv, (__bf16*)dpl, pl_rows, dbias_u, dbias_v, dBand, QvHM, ws, stream);
 }

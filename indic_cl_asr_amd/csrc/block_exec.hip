@@ -80,13 +80,19 @@ extern "C" int ia_conformer_prefix_fwd_seg(const ia_block_params* layers, int n_
     const int d = l0.d, d_ff = l0.d_ff, H = l0.n_heads, dk = d / (H > 0 ? H : 1), ksz = l0.ksz;
     const int window = l0.att_window;   // 0: full attention; w > 0: local attention [w, w] on a 2w+1-row position table
     if (window < 0 || (long long)pos_rows < (window > 0 ? 2ll * window + 1 : 2ll * T - 1)) return IA_INVALID_VALUE;
-    for (int li = 0; li < n_layers; ++li)
-        if (layers[li].att_window != window) return IA_INVALID_VALUE;
+    // att_style 1 / 2: a limited context [att_left, att_right] (regular / chunked_limited) on the full 2T-1-row table
+    const int cstyle = l0.att_style, cleft = l0.att_left, cright = l0.att_right;
+    if (cstyle < 0 || cstyle > 2 || (cstyle != 0 && window > 0)) return IA_INVALID_VALUE;
+    for (int li = 0; li < n_layers; ++li) {
+        if (layers[li].att_window != window || layers[li].att_style != cstyle) return IA_INVALID_VALUE;
+        if (cstyle != 0 && (layers[li].att_left != cleft || layers[li].att_right != cright)) return IA_INVALID_VALUE;
+    }
     const PrefixWs w = prefix_ws(B, T, d, d_ff, ksz, pos_rows);
     if (workspace_bytes < w.total) return IA_WORKSPACE_TOO_SMALL;
     if (H <= 0) return IA_INVALID_VALUE;
     if (!ia_relpos_attention_flash_supported(T, dk)) return IA_UNSUPPORTED;   // before anything rewrites x in place
     if (window > 0 && !ia_relpos_attention_local_supported(T, dk, window)) return IA_UNSUPPORTED;
+    if (cstyle != 0 && !ia_relpos_attention_context_supported(T, dk, cstyle - 1, cleft, cright)) return IA_INVALID_VALUE;
     char* ws = (char*)workspace;
     void *y = ws + w.y, *h = ws + w.h, *qkv = ws + w.qkv, *pl = ws + w.pl, *ctx = ws + w.ctx, *c2 = ws + w.c2, *c3 = ws + w.c3;
     float *z = (float*)(ws + w.z), *sums = (float*)(ws + w.sums), *scr = (float*)(ws + w.scr);
@@ -145,6 +151,9 @@ extern "C" int ia_conformer_prefix_fwd_seg(const ia_block_params* layers, int n_
         }
         if (window > 0)
             IA_TRY(ia_relpos_attention_local(qkv, plu, L.pos_u, L.pos_v, lens, B, T, H, dk, window, patt, seed + 7, ctx, stream));
+        else if (cstyle != 0)
+            IA_TRY(ia_relpos_attention_context(qkv, plu, L.pos_u, L.pos_v, lens, B, T, H, dk, cstyle - 1, cleft, cright, patt, seed + 7, ctx,
+                                               stream));
         else
             IA_TRY(ia_relpos_attention_flash(qkv, plu, L.pos_u, L.pos_v, lens, B, T, H, dk, patt, seed + 7, ctx, stream));
         // out-projection (+ residual) and the convolution module's LayerNorm: one launch at d_model = 256 (64 x 256 tiles own

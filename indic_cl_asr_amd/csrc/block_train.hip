@@ -294,7 +294,7 @@ extern "C" int ia_conformer_block_fwd_phase(const ia_block_params* Lp, const flo
     const ia_block_params& L = *Lp;
     const ia_block_saved& S = *Sp;
     const int d = L.d, d_ff = L.d_ff, H = L.n_heads, dk = d / (H > 0 ? H : 1), ksz = L.ksz, N = B * T;
-    if (!ia_conformer_block_supported(d, d_ff, H, ksz, T) || pos_rows < 2 * T - 1 || L.att_window != 0) return IA_UNSUPPORTED;
+    if (!ia_conformer_block_supported(d, d_ff, H, ksz, T) || pos_rows < 2 * T - 1 || L.att_window != 0 || L.att_style != 0) return IA_UNSUPPORTED;
     const float p = L.p_drop, pff = L.p_ff, patt = L.p_att;
     if (phase != 2) {
     // 1/2 feed-forward (pre-activation kept for the backward)

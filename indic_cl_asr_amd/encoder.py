@@ -6,6 +6,7 @@ Differences in HOW (not WHAT): no [B,T',T'] mask tensor and no all_reduce(MAX)+.
 dense projections run in cfg.compute_dtype on the matrix cores, norms/softmax/BN in fp32.
 """
 import math
+import random
 from contextlib import nullcontext
 
 import torch
@@ -111,6 +112,7 @@ class RelPositionMultiHeadAttention(nn.Module):
         self.pos_bias_v = nn.Parameter(torch.zeros(self.h, self.d_k))
         self.dropout_rate = dropout_rate
         self.att_window = None   # w: local attention [w, w] (RelPositionMultiHeadAttentionLongformer); same parameters either way
+        self.att_context = None  # (style, L, R): a limited context under full rel-pos attention (the reference's attention mask)
 
     def forward(self, x, lens, pos_emb):
         B, T, _ = x.shape
@@ -119,7 +121,7 @@ class RelPositionMultiHeadAttention(nn.Module):
         v = self.linear_v(x).view(B, T, self.h, self.d_k).transpose(1, 2)
         p = self.linear_pos(pos_emb.to(x.dtype)).view(-1, self.h, self.d_k).transpose(0, 1)  # [h,2T-1,dk]
         ctx = ops.rel_pos_attention(q, k, v, p, self.pos_bias_u, self.pos_bias_v, lens, self.dropout_rate, self.training,
-                                    window=self.att_window)
+                                    window=self.att_window, context=self.att_context)
         return self.linear_out(ctx.transpose(1, 2).reshape(B, T, self.h * self.d_k))
 
 
@@ -215,17 +217,20 @@ class ConformerLayer(nn.Module):
         _, qkv = G(y, Wt(att.linear_q.weight, att.linear_k.weight, att.linear_v.weight),
                            fast.f32_cat(att.linear_q.bias, att.linear_k.bias, att.linear_v.bias))
         _, pl = fast.gemm(pos_emb, fast.bf16_shadow(att.linear_pos.weight))
-        if att.att_window is not None and fast.attention_local_supported(T, att.d_k, att.att_window):
+        if att.att_context is not None and fast.attention_context_supported(T, att.d_k, att.att_context):
+            ctx = fast.relpos_attention_context(qkv, pl, att.pos_bias_u, att.pos_bias_v, lens, B, T, att.h, att.d_k, att.att_context,
+                                                att.dropout_rate if tr else 0.0, seed + 7)
+        elif att.att_context is None and att.att_window is not None and fast.attention_local_supported(T, att.d_k, att.att_window):
             ctx = fast.relpos_attention_local(qkv, pl, att.pos_bias_u, att.pos_bias_v, lens, B, T, att.h, att.d_k, att.att_window,
                                               att.dropout_rate if tr else 0.0, seed + 7)
-        elif att.att_window is None and fast.attention_flash_supported(T, att.d_k):
+        elif att.att_context is None and att.att_window is None and fast.attention_flash_supported(T, att.d_k):
             ctx = fast.relpos_attention_flash(qkv, pl, att.pos_bias_u, att.pos_bias_v, lens, B, T, att.h, att.d_k,
                                               att.dropout_rate if tr else 0.0, seed + 7)
         else:  # head sizes the key-tiled kernel does not take (above 64, or no multiple of 4): ATen composition
             qkv = qkv.view(B, T, 3, att.h, att.d_k)
             q, k, v = (qkv[:, :, i].transpose(1, 2) for i in range(3))
             ctx = ops.rel_pos_attention(q, k, v, pl.view(-1, att.h, att.d_k).transpose(0, 1), att.pos_bias_u,
-                                        att.pos_bias_v, lens, att.dropout_rate, tr, window=att.att_window)
+                                        att.pos_bias_v, lens, att.dropout_rate, tr, window=att.att_window, context=att.att_context)
             ctx = ctx.transpose(1, 2).reshape(B * T, d).contiguous()
         G(ctx, Wt(att.linear_out.weight), att.linear_out.bias, dropout_p=p, seed=seed + 3,
                   residual=x, out_f32=x, want_bf16=False)
@@ -281,10 +286,66 @@ class ConformerEncoder(nn.Module):
         self._pos_cache = {}           # T -> bf16 images of the position table slice (plain dict: not a buffer, not copied state)
         self.self_attention_model = "rel_pos"
         self.att_context_size = [-1, -1]
+        self.att_context_size_all = [[-1, -1]]   # multi-look-ahead: every context a training forward may draw; [0] is the default
+        self.att_context_probs = [1.0]
+        self.att_context_style = getattr(cfg, "att_context_style", None)   # None | "regular" | "chunked_limited"
+        if self.att_context_style not in (None, "regular", "chunked_limited"):
+            raise ValueError(f"Invalid att_context_style: {self.att_context_style}")
         if cfg.self_attention_model != "rel_pos" or list(cfg.att_context_size) != [-1, -1]:
-            self.change_attention_model(cfg.self_attention_model, list(cfg.att_context_size), update_config=False)
+            self.change_attention_model(cfg.self_attention_model, list(cfg.att_context_size), update_config=False,
+                                        att_context_probs=getattr(cfg, "att_context_probs", None))
 
-    def change_attention_model(self, self_attention_model=None, att_context_size=None, update_config=True, device=None):
+    @staticmethod
+    def _calc_context_sizes(att_context_size, att_context_probs, att_context_style):
+        """conformer_encoder.py:749-778: (list of [L, R] pairs, probabilities) with the reference's checks."""
+        sizes = list(att_context_size)
+        if isinstance(sizes[0], int):
+            sizes = [sizes]
+        sizes = [[int(c) for c in cs] for cs in sizes]
+        for i, cs in enumerate(sizes):
+            if len(cs) != 2:
+                raise ValueError(f"att_context_size must be [left, right], not {cs}")
+            if att_context_style == "chunked_limited":
+                if cs[1] >= 0 and cs[0] > 0 and cs[0] % (cs[1] + 1) > 0:
+                    raise ValueError(f"att_context_size[{i}][0] % (att_context_size[{i}][1] + 1) should be zero!")
+                # (a sole [-1, -1] is full attention under either style -- the way back from a chunked model -- not a chunk rule)
+                if cs[1] < 0 and len(sizes) <= 1 and cs[0] >= 0:
+                    raise ValueError(f"Right context (att_context_size[{i}][1]) can not be unlimited for chunked_limited style!")
+        if att_context_probs:
+            if len(att_context_probs) != len(sizes):
+                raise ValueError("The size of the att_context_probs should be the same as att_context_size.")
+            probs = [float(p) for p in att_context_probs]
+            if abs(sum(probs) - 1.0) > 1e-9:   # (the reference compares with == 1, which 0.4 + 0.3 + 0.2 + 0.1 fails in binary)
+                raise ValueError("The sum of numbers in att_context_probs should be equal to one to be a distribution.")
+        else:
+            probs = [1.0 / len(sizes)] * len(sizes)
+        return sizes, probs
+
+    def _layer_context(self, att_context_size):
+        """What a layer's attention is told for a context [L, R] under 'rel_pos': None (every pair) or (style, L, R)."""
+        left, right = att_context_size
+        if self.self_attention_model != "rel_pos" or (left < 0 and right < 0):
+            return None
+        return (self.att_context_style, int(left), int(right))
+
+    def _set_layer_context(self, att_context_size):
+        c = self._layer_context(att_context_size)
+        for layer in self.layers:
+            layer.self_attn.att_context = c
+
+    def set_default_att_context_size(self, att_context_size):
+        """conformer_encoder.py:796-803: the context that evaluation, transcribe() and align() use (training draws from
+        att_context_size_all).  A context outside the list is refused with the text the reference only warns with: nothing
+        has validated it."""
+        att_context_size = [int(c) for c in att_context_size]
+        if att_context_size not in self.att_context_size_all:
+            raise ValueError(f"att_context_size={att_context_size} is not among the list of the supported look-aheads: "
+                             f"{self.att_context_size_all}")
+        self.att_context_size = att_context_size
+        self._set_layer_context(att_context_size)
+
+    def change_attention_model(self, self_attention_model=None, att_context_size=None, update_config=True, device=None, *,
+                               att_context_style=None, att_context_probs=None):
         """conformer_encoder.py:938-1060: switch between full rel-pos attention ('rel_pos') and local attention with a window of
         att_context_size = [w, w] frames ('rel_pos_local_attn': NeMo's long-audio switch).  None keeps a setting.  The reference
         swaps the attention and position-encoding modules and reloads their state; the two attention models share every
@@ -293,13 +354,48 @@ class ConformerEncoder(nn.Module):
 
         Not offered (NotImplementedError): 'abs_pos'; asymmetric windows (the reference adds the position term of an L != R
         window to the wrong columns, multi_head_attention.py:355-360, and that is not reproduced); a limited context under
-        'rel_pos'.  One rule differs: 'rel_pos' without att_context_size means [-1, -1], not the local window left behind."""
-        if self_attention_model is None and att_context_size is None:
+        'rel_pos' while att_context_style is unset.  One rule differs: 'rel_pos' without att_context_size means [-1, -1], not the
+        local window left behind.
+
+        A limited context under 'rel_pos' (conformer_encoder.py:686-740, the reference's attention mask): with att_context_style
+        'regular' (i - j <= L, j - i <= R) or 'chunked_limited' (chunks of R + 1 frames, L // (R + 1) chunks to the left),
+        att_context_size = [L, R] runs the attention kernels under their context span on the ordinary position table; -1 is an
+        unlimited side.  The style is the keyword if given (it then becomes the encoder's), else the encoder's attribute
+        (ModelConfig.att_context_style).  The keyword alone re-validates the contexts in force under the new style and keeps
+        them; with 'rel_pos_local_attn', which reads no style, it is a ValueError.  A sole [-1, -1] is full attention under
+        either style, so change_attention_model('rel_pos') is the way back from any of them.  A second rule differs: the
+        reference's style defaults to 'regular'; here an UNSET style (the default config) keeps refusing a limited context under
+        'rel_pos', and a config that says att_context_style: regular, as NeMo's yaml does, behaves as NeMo.
+        Validation is the reference's (:749-778).  att_context_size may be a list of [L, R] pairs (multi-look-ahead) with att_context_probs (uniform by default): a training forward draws one with
+        random.choices, the frozen prefix and the trainable blocks of that forward use the same draw; evaluation uses the default,
+        the first pair, which set_default_att_context_size changes.  The cache-aware streaming step and causal convolutions are
+        not part of this: a chunk-limited model is trained and evaluated offline here."""
+        if self_attention_model is None and att_context_size is None and att_context_style is None:
             return
+        if att_context_style is not None and att_context_style not in ("regular", "chunked_limited"):
+            raise ValueError(f"Invalid att_context_style: {att_context_style}")
+        keep_default = None
         if self_attention_model is None:
             self_attention_model = self.self_attention_model
+            if att_context_size is None and self_attention_model == "rel_pos":
+                # the style alone: the contexts in force are kept and validated again under the new style
+                att_context_size, keep_default = [list(cs) for cs in self.att_context_size_all], list(self.att_context_size)
+                att_context_probs = att_context_probs or list(self.att_context_probs)
+                if len(att_context_size) == 1:
+                    att_context_size, att_context_probs = att_context_size[0], None
+        if att_context_style is not None and self_attention_model == "rel_pos_local_attn":
+            raise ValueError("att_context_style belongs to 'rel_pos': local attention ('rel_pos_local_attn') has no context style")
+        style = att_context_style if att_context_style is not None else self.att_context_style
+        sizes_all, probs = None, None
         if att_context_size:
-            att_context_size = [int(c) for c in att_context_size]
+            att_context_size = list(att_context_size)
+            if not isinstance(att_context_size[0], int):   # a list of contexts: multi-look-ahead, 'rel_pos' only
+                if self_attention_model != "rel_pos":
+                    raise ValueError("a list of att_context_size pairs (multi-look-ahead) needs self_attention_model 'rel_pos'")
+                sizes_all, probs = self._calc_context_sizes(att_context_size, att_context_probs, style)
+                att_context_size = sizes_all[0]
+            else:
+                att_context_size = [int(c) for c in att_context_size]
         else:
             att_context_size = [-1, -1] if self_attention_model == "rel_pos" else list(self.att_context_size)
         if self_attention_model == "rel_pos_local_attn" and max(att_context_size) <= 0:
@@ -319,15 +415,28 @@ class ConformerEncoder(nn.Module):
                     "an L != R window to the wrong columns (multi_head_attention.py:355-360 index the table from its start, not "
                     "from w - L); only symmetric windows [w, w] are offered")
             window = left
-        elif att_context_size != [-1, -1]:
-            raise NotImplementedError(f"a limited context {att_context_size} under 'rel_pos' is not implemented: use "
-                                      "'rel_pos_local_attn' with a symmetric window")
+        else:
+            if sizes_all is None:
+                sizes_all, probs = self._calc_context_sizes(att_context_size, att_context_probs, style)
+            if style is None and any(cs != [-1, -1] for cs in sizes_all):
+                raise NotImplementedError(f"a limited context {att_context_size} under 'rel_pos' is not implemented while "
+                                          "att_context_style is unset: set att_context_style to 'regular' or 'chunked_limited', "
+                                          "or use 'rel_pos_local_attn' with a symmetric window")
+        if sizes_all is None:
+            sizes_all, probs = [list(att_context_size)], [1.0]
         self.pos_enc.set_local_window(window, device)
         for layer in self.layers:
             layer.self_attn.att_window = window
         self.self_attention_model, self.att_context_size = self_attention_model, att_context_size
+        self.att_context_size_all, self.att_context_probs, self.att_context_style = sizes_all, probs, style
+        self._set_layer_context(att_context_size)
+        if keep_default is not None and keep_default != att_context_size:
+            self.set_default_att_context_size(keep_default)
         if update_config:
-            self.cfg.self_attention_model, self.cfg.att_context_size = self_attention_model, list(att_context_size)
+            self.cfg.self_attention_model = self_attention_model
+            self.cfg.att_context_size = [list(cs) for cs in sizes_all] if len(sizes_all) > 1 else list(att_context_size)
+            self.cfg.att_context_style = style
+            self.cfg.att_context_probs = list(probs) if len(sizes_all) > 1 else None
 
     def _amp(self, x):
         if self.cfg.compute_dtype == "bf16" and x.is_cuda:
@@ -339,6 +448,13 @@ class ConformerEncoder(nn.Module):
         `subsampled_len`: optional precomputed [B] i64 device tensor of the output lengths (the caller knew the lengths on
         the host: saves the half-dozen tiny integer kernels of the frame-count rule)."""
         from . import cl
+        # multi-look-ahead (conformer_encoder.py:522-527): a training forward draws its context, every layer of it -- frozen
+        # prefix and trainable blocks -- uses that draw; evaluation uses the default
+        if len(self.att_context_size_all) > 1:
+            if self.training:
+                self._set_layer_context(random.choices(self.att_context_size_all, weights=self.att_context_probs)[0])
+            else:
+                self._set_layer_context(self.att_context_size)
         if cl._PENDING_OPTIMIZERS and any(p.requires_grad for p in self.pre_encode.parameters()):
             cl.flush_pending_updates()   # deferred data-parallel update: the subsampling weights are about to be read
         with self._amp(audio_signal):
@@ -447,7 +563,7 @@ class ConformerEncoder(nn.Module):
         if fast.attention_flash_supported(T, l0.self_attn.d_k) and bn_ok and same_mode and not fp8:
             # native executor: one C call enqueues the 14 kernels of every block (csrc/block_exec.hip)
             fast.conformer_prefix(list(self.layers[:n_fast]), xr, pe, length, B, T, base, 16, l0.training,
-                                  att_window=l0.self_attn.att_window or 0)
+                                  att_window=l0.self_attn.att_window or 0, att_context=l0.self_attn.att_context)
             return xr.view(B, T, d), n_fast
         y = None   # (the first module of a block applies its LayerNorm itself unless the previous block chained it)
         for l in range(n_fast):

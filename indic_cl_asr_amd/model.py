@@ -170,18 +170,29 @@ class EncDecHybridRNNTCTCModel(TranscriptionMixin, nn.Module):
         return self
 
     def change_attention_model(self, self_attention_model: str = None, att_context_size: List[int] = None,
-                               update_config: bool = True):
+                               update_config: bool = True, *, att_context_style: str = None, att_context_probs=None):
         """ASRModuleMixin.change_attention_model (A/parts/mixins/mixins.py:501-544): 'rel_pos' (full attention) or
         'rel_pos_local_attn' with att_context_size = [w, w] -- the reference's switch for long audio
-        (tools/nemo_forced_aligner/align.py:253).  Both None: nothing changes.  Rules and refusals:
+        (tools/nemo_forced_aligner/align.py:253), or 'rel_pos' with a limited context att_context_size = [L, R] (or a list of
+        such pairs: multi-look-ahead) under att_context_style 'regular' / 'chunked_limited'.  All three None: nothing changes.  Rules
+        and refusals:
         ConformerEncoder.change_attention_model.  transcribe() and align() follow through the encoder's forward."""
-        if self_attention_model is None and att_context_size is None:
+        if self_attention_model is None and att_context_size is None and att_context_style is None:
             return
         self.encoder.change_attention_model(self_attention_model, att_context_size, update_config,
-                                            next(self.encoder.parameters()).device)
+                                            next(self.encoder.parameters()).device, att_context_style=att_context_style,
+                                            att_context_probs=att_context_probs)
         if update_config:
-            self.cfg.self_attention_model = self.encoder.self_attention_model
-            self.cfg.att_context_size = list(self.encoder.att_context_size)
+            enc = self.encoder
+            multi = len(enc.att_context_size_all) > 1
+            self.cfg.self_attention_model = enc.self_attention_model
+            self.cfg.att_context_size = [list(cs) for cs in enc.att_context_size_all] if multi else list(enc.att_context_size)
+            self.cfg.att_context_style = enc.att_context_style
+            self.cfg.att_context_probs = list(enc.att_context_probs) if multi else None
+
+    def set_default_att_context_size(self, att_context_size):
+        """The context that evaluation, transcribe() and align() use under multi-look-ahead (ConformerEncoder's)."""
+        self.encoder.set_default_att_context_size(att_context_size)
 
     # ------------------------------------------------------------------ forward (rnnt_models.py:606-655)
     def forward(self, input_signal=None, input_signal_length=None, processed_signal=None,

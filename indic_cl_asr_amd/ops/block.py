@@ -83,8 +83,12 @@ def block_supported(layer, x2d, T):
     d = x2d.shape[-1]
     bn = layer.conv.batch_norm
     w = getattr(layer.self_attn, "att_window", None)
-    att_ok = (fast.attention_flash_supported(T, layer.self_attn.d_k) if w is None
-              else fast.attention_local_supported(T, layer.self_attn.d_k, w))
+    c = getattr(layer.self_attn, "att_context", None)   # (style, L, R): a limited context; excludes a window
+    if c is not None:
+        att_ok = w is None and fast.attention_context_supported(T, layer.self_attn.d_k, c)
+    else:
+        att_ok = (fast.attention_flash_supported(T, layer.self_attn.d_k) if w is None
+                  else fast.attention_local_supported(T, layer.self_attn.d_k, w))
     return (x2d.is_cuda and d % 8 == 0 and d <= 1024 and fast.bn_module_ok(bn)
             and layer.conv.depthwise_conv.weight.shape[-1] <= 31 and att_ok)
 
@@ -102,6 +106,7 @@ class _ConformerBlockFn(torch.autograd.Function):
         pff2 = float(ff2.dropout.p) if tr else 0.0
         patt = float(att.dropout_rate) if tr else 0.0
         window = getattr(att, "att_window", None)   # w: local attention [w, w], pe is the (padded) 2w+1-row table
+        context = getattr(att, "att_context", None)  # (style, L, R): a limited context on the full table (this forward's draw)
         W = dict(w1=fast.bf16_shadow(ff1.linear1.weight), w2=fast.bf16_shadow(ff1.linear2.weight),
                  wqkv=fast.bf16_shadow(att.linear_q.weight, att.linear_k.weight, att.linear_v.weight),
                  wpos=fast.bf16_shadow(att.linear_pos.weight), wo=fast.bf16_shadow(att.linear_out.weight),
@@ -119,7 +124,10 @@ class _ConformerBlockFn(torch.autograd.Function):
         y2 = fast.layernorm(x1, layer.norm_self_att.weight, layer.norm_self_att.bias, layer.norm_self_att.eps)
         _, qkv = fast.gemm(y2, W["wqkv"], fast.f32_cat(att.linear_q.bias, att.linear_k.bias, att.linear_v.bias))
         _, pl = fast.gemm(pe, W["wpos"])
-        if window is None:
+        if context is not None:
+            ctxv, lse = fast.relpos_attention_context(qkv, pl, att.pos_bias_u, att.pos_bias_v, lens, B, T, att.h, att.d_k, context, patt,
+                                                      seed + 7, want_lse=True)
+        elif window is None:
             ctxv, lse = fast.relpos_attention_flash(qkv, pl, att.pos_bias_u, att.pos_bias_v, lens, B, T, att.h, att.d_k, patt, seed + 7,
                                                     want_lse=True)
         else:
@@ -148,7 +156,7 @@ class _ConformerBlockFn(torch.autograd.Function):
             raise RuntimeError("trainable fused block expects train-mode BatchNorm (batch statistics)")
         ctx.S = dict(x0=x0, y1=y1, h1p=h1p, h1=h1, x1=x1, y2=y2, qkv=qkv, pl=pl, ctxv=ctxv, lse=lse, x2=x2, y3=y3, c2=c2, z=z, sums=sums,
                      c3=c3, x3=x3, y4=y4, h4p=h4p, h4=h4, x4=x4, W=W, pe=pe, lens=lens)
-        ctx.meta = (layer, B, T, seed, p, pff1, pff2, patt, window, [n for n, _ in layer.named_parameters()],
+        ctx.meta = (layer, B, T, seed, p, pff1, pff2, patt, (window, context), [n for n, _ in layer.named_parameters()],
                     [q.requires_grad for q in params], params)
         return out
 
@@ -157,7 +165,7 @@ class _ConformerBlockFn(torch.autograd.Function):
         L = _lib.lib()
         S = ctx.S
         ctx.S = None
-        layer, B, T, seed, p, pff1, pff2, patt, window, names, req, params = ctx.meta
+        layer, B, T, seed, p, pff1, pff2, patt, (window, context), names, req, params = ctx.meta
         W = S["W"]
         ff1, ff2, att, cv = layer.feed_forward1, layer.feed_forward2, layer.self_attn, layer.conv
         d = S["x0"].shape[1]
@@ -224,7 +232,10 @@ class _ConformerBlockFn(torch.autograd.Function):
         # self-attention
         dB = _branch_grad(dx2, 1.0, p, seed + 3)
         dctx, G["self_attn.linear_out.weight"], G["self_attn.linear_out.bias"] = _lin_bwd(dB, S["ctxv"], W["wo"])
-        if window is None:
+        if context is not None:
+            dqkv, dpl, du, dv = fast.relpos_attention_context_bwd(S["qkv"], S["pl"], att.pos_bias_u, att.pos_bias_v, S["lens"], S["ctxv"],
+                                                                  dctx, S["lse"], B, T, att.h, att.d_k, context, patt, seed + 7)
+        elif window is None:
             dqkv, dpl, du, dv = fast.relpos_attention_flash_bwd(S["qkv"], S["pl"], att.pos_bias_u, att.pos_bias_v, S["lens"], S["ctxv"],
                                                                 dctx, S["lse"], B, T, att.h, att.d_k, patt, seed + 7)
         else:
@@ -273,9 +284,10 @@ def pad_pos_emb(pos_emb, d):
 
 def conformer_block(x2d, layer, lens, pe_bf16, B, T, seed):
     """x2d [B*T, d] f32 residual stream -> [B*T, d] f32 (autograd-connected to x2d and the block's parameters).
-    pe_bf16: pad_pos_emb(pos_emb) (>= 2T-1 rows; under a local window w the 2w+1-row table).  A layer with a window takes the
-    per-op node: the native executor does not know the window."""
-    if USE_NATIVE_BLOCKS and layer.training and getattr(layer.self_attn, "att_window", None) is None:
+    pe_bf16: pad_pos_emb(pos_emb) (>= 2T-1 rows; under a local window w the 2w+1-row table).  A layer with a window or a limited context
+    takes the per-op node: the native executor knows neither."""
+    if (USE_NATIVE_BLOCKS and layer.training and getattr(layer.self_attn, "att_window", None) is None
+            and getattr(layer.self_attn, "att_context", None) is None):
         att = layer.self_attn
         if _lib.lib().ia_conformer_block_supported(x2d.shape[-1], layer.feed_forward1.linear1.weight.shape[0], att.h,
                                                    layer.conv.depthwise_conv.weight.shape[-1], T):

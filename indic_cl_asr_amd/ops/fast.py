@@ -439,9 +439,31 @@ def attention_local_supported(T, dk, window):
     return bool(_lib.lib().ia_relpos_attention_local_supported(int(T), int(dk), int(window)))
 
 
+CONTEXT_STYLES = {"regular": 0, "chunked_limited": 1}   # att_context_style -> the C entry points' style
+
+
+def context_args(context):
+    """(style, L, R) with the style by name ('regular', 'chunked_limited') or by the C number -> the C entry points' three ints."""
+    style, left, right = context
+    if isinstance(style, str):
+        if style not in CONTEXT_STYLES:
+            raise ValueError(f"Invalid att_context_style: {style}")
+        style = CONTEXT_STYLES[style]
+    return int(style), int(left), int(right)
+
+
+def attention_context_supported(T, dk, context):
+    return bool(_lib.lib().ia_relpos_attention_context_supported(int(T), int(dk), *context_args(context)))
+
+
 def _span(window):
-    """(entry-point infix, extra C arguments) of the key-tiled attention under the full (window None) or the local span."""
-    return ("flash", ()) if window is None else ("local", (int(window),))
+    """(entry-point infix, extra C arguments) of the key-tiled attention under the full span (window None), the local span (an
+    int: the window) or the context span (a tuple: (style, L, R))."""
+    if window is None:
+        return "flash", ()
+    if isinstance(window, (tuple, list)):
+        return "context", context_args(window)
+    return "local", (int(window),)
 
 
 def _attention_fwd(window, qkv_bf16, pos_proj_bf16, bias_u, bias_v, lens, B, T, H, dk, dropout_p, seed, want_lse):
@@ -472,6 +494,16 @@ def relpos_attention_local(qkv_bf16, pos_proj_bf16, bias_u, bias_v, lens, B, T, 
     return _attention_fwd(window, qkv_bf16, pos_proj_bf16, bias_u, bias_v, lens, B, T, H, dk, dropout_p, seed, want_lse)
 
 
+def relpos_attention_context(qkv_bf16, pos_proj_bf16, bias_u, bias_v, lens, B, T, H, dk, context, dropout_p=0.0, seed=0,
+                             want_lse=False):
+    """Limited-context rel-pos attention forward (the same kernel under the context span): context = (style, L, R), style
+    'regular' (i - j <= L and j - i <= R) or 'chunked_limited' (0 <= i // C - j // C <= L // C, C = R + 1; R = -1: i - j <= L), a
+    side of -1 unlimited.  Operands and result as relpos_attention_flash: pos_proj [>= 2T-1, H*dk] bf16."""
+    if pos_proj_bf16.shape[0] < 2 * int(T) - 1:
+        raise ValueError(f"relpos_attention_context: {pos_proj_bf16.shape[0]} position rows < 2 * {T} - 1")
+    return _attention_fwd(tuple(context), qkv_bf16, pos_proj_bf16, bias_u, bias_v, lens, B, T, H, dk, dropout_p, seed, want_lse)
+
+
 def _attention_bwd_dims(window, T):
     kind, win = _span(window)
     rs, p0 = ctypes.c_int(), ctypes.c_int()
@@ -486,6 +518,11 @@ def attention_flash_bwd_dims(T):
 def attention_local_bwd_dims(T, window):
     """(Rs, pad0) of the local backward's dBand [H, B*T, Rs]: Rs = ceil8(pad0 + 2 min(window, T-1) + 1), no term in T."""
     return _attention_bwd_dims(window, T)
+
+
+def attention_context_bwd_dims(T, context):
+    """(Rs, pad0) of the context backward's dBand [H, B*T, Rs]: the full layout, attention_flash_bwd_dims(T)."""
+    return _attention_bwd_dims(tuple(context), T)
 
 
 def _attention_bwd(window, qkv, pl, bias_u, bias_v, lens, ctx, dctx, lse, B, T, H, dk, dropout_p, seed, dub_out):
@@ -524,6 +561,12 @@ def relpos_attention_local_bwd(qkv, pl, bias_u, bias_v, lens, ctx, dctx, lse, B,
     relpos_attention_flash_bwd, pl [>= 2*window+1, d]; dpl rows beyond 2*window are zero.  dBand, the workspace and the work are
     O(T * window)."""
     return _attention_bwd(window, qkv, pl, bias_u, bias_v, lens, ctx, dctx, lse, B, T, H, dk, dropout_p, seed, dub_out)
+
+
+def relpos_attention_context_bwd(qkv, pl, bias_u, bias_v, lens, ctx, dctx, lse, B, T, H, dk, context, dropout_p=0.0, seed=0, dub_out=None):
+    """Backward of relpos_attention_context (the same two kernels under the context span): operands and results as
+    relpos_attention_flash_bwd, dBand in the full layout; dpl rows of relative positions no admissible pair reaches are zero."""
+    return _attention_bwd(tuple(context), qkv, pl, bias_u, bias_v, lens, ctx, dctx, lse, B, T, H, dk, dropout_p, seed, dub_out)
 
 
 def relpos_attention(qkv_bf16, pos_proj_bf16, bias_u, bias_v, lens, B, T, H, dk, dropout_p=0.0, seed=0):
@@ -777,15 +820,20 @@ def pos_proj_cached(layer, pos_emb_bf16, max_entries=8):
     return ent
 
 
-def conformer_prefix(layers, xr, pos_emb_bf16, lens, B, T, seed_base, seed_stride, training, att_window=0):
+def conformer_prefix(layers, xr, pos_emb_bf16, lens, B, T, seed_base, seed_stride, training, att_window=0, att_context=None):
     """Run `layers` (ConformerLayer list) over the fp32 residual stream xr [B*T, d] in place with ONE native call.
-    att_window = w > 0: local attention [w, w] (pos_emb_bf16 is the 2w+1-row table); 0: full attention."""
+    att_window = w > 0: local attention [w, w] (pos_emb_bf16 is the 2w+1-row table); 0: full attention.
+    att_context = (style, L, R): a limited context on the full 2T-1-row table (ia_block_params.att_style is the C style + 1)."""
     L = _lib.lib()
+    cstyle, cleft, cright = (0, 0, 0) if att_context is None else context_args(att_context)
+    if att_context is not None:
+        cstyle += 1
     arr = (_lib.BlockParams * len(layers))(*[_block_params(l) for l in layers])
     for i, l in enumerate(layers):   # frozen position projections depend on T only: one GEMM per (layer, T), not per step
         pl = pos_proj_cached(l, pos_emb_bf16)   # (keyed by the row count; 2w+1 = some 2T-1 is the same centred table slice)
         arr[i].pl_cached = pl.data_ptr() if pl is not None else None
         arr[i].att_window = int(att_window)
+        arr[i].att_style, arr[i].att_left, arr[i].att_right = cstyle, cleft, cright
     p0 = arr[0]
     n = L.ia_conformer_prefix_ws_bytes(B, T, p0.d, p0.d_ff, p0.n_heads, p0.ksz, pos_emb_bf16.shape[0])
     key = (xr.device.index, torch.cuda.current_stream(xr.device).cuda_stream)
