@@ -1099,6 +1099,56 @@ int ia_pack_prune(float* theta, float* exp_avg, float* exp_avg_sq, uint8_t* owne
                   void* workspace, size_t workspace_bytes, ia_stream_t stream);
 int ia_pack_apply(float* theta, const float* base, const uint8_t* owner, const int32_t* chunk_table, int nchunks,
                   const int32_t* seg_kind, int nseg, int lo, int hi, void* shadow_bf16, ia_stream_t stream);
+/* Model merging (csrc/merge.hip): one copy of the model is fine-tuned per language from the same `base`, and the weight deltas
+ * ("task vectors", tau_k = theta_k - base) are combined afterwards.  vectors: fp32 [max_tasks, stride] on the device, row k the
+ * task vector of task k laid out as theta (GEM's convention for `refs`: stride a multiple of 4 and at least the flat length, +0 in
+ * the alignment gaps); rows 0 .. ntasks-1 are merged, in that order, 1 <= ntasks <= IA_MERGE_MAX_TASKS.  Every product, sum and
+ * quotient named below is rounded to fp32 on its own, never contracted, in task order: one torch op per rounding reproduces theta
+ * bit for bit.  All three stream HBM with 16-byte accesses in a chunk's body and scalar ones in its tail, touch no alignment gap,
+ * synchronise nothing with the host and allocate nothing; integer atomics only, where counts are reduced, so no result depends
+ * on scheduling.  shadow_bf16 (may be NULL): shadow = bf16(theta) for every element of every tensor.
+ * ia_merge_linear   task arithmetic (Ilharco et al. 2023); weight averaging is coef_k = 1 / K with scale = 1.  One pass, 4 K + 10 B
+ *                   per element (K rows and base read, theta and its bf16 image written):
+ *                     s = coef_0 * tau_0;  s = s + coef_k * tau_k for k = 1 .. K-1;  theta = base + scale * s.
+ *                   coef: a HOST array of ntasks floats, read during the call and passed to the kernel by value.
+ * ia_merge_trim     TIES (Yadav et al. 2023), trimming.  seg_of_scope: int32[tensors] on the device, the scope segment each tensor
+ *                   of the chunk table belongs to, in 0 .. nscope-1 (a value outside is clamped into the range): the identity for
+ *                   a selection per tensor, all zeros with nscope = 1 for one selection over the whole task vector.  For every
+ *                   (task k, scope segment s) on its own: n = the elements of row k in the tensors of s (alignment gaps are never
+ *                   counted), r = floor((double)trim * n) computed on the device from the float `trim`.  r == 0: the cutoff is
+ *                   0 and everything stays.  Otherwise the cutoff c is the r-th smallest (1-based) |tau|, and an element stays
+ *                   iff |tau| >= c: ties at the cutoff all stay, as kthvalue followed by abs() >= kth has it.  The order is
+ *                   that of the 31-bit pattern of |tau|: exact for finite values, and what it says for infinities and NaNs
+ *                   (above every finite value) is the definition.  cutoffs: uint32[ntasks, nscope] on the device, the pattern
+ *                   of c.  The exact radix select of ia_pack_prune (digits of 8, 8, 8 and 7 bits): per digit one streaming pass
+ *                   over the K rows, 16 K B per element in all.  workspace: ia_merge_trim_workspace_bytes(ntasks, nscope),
+ *                   caller-owned.
+ * ia_merge_ties     TIES, sign election and disjoint mean.  One pass, 4 K + 10 B per element.  Per element, with t_k = tau_k where
+ *                   it stays and +0.0f where it does not:
+ *                     mass  = t_0;  mass = mass + t_k for k = 1 .. K-1
+ *                     gamma = +1 when mass > 0, -1 when mass < 0, none otherwise (a zero or NaN mass)
+ *                     sel   = { k : t_k > 0 } for gamma = +1, { k : t_k < 0 } for gamma = -1, empty otherwise
+ *                     m     = (the t_k of sel added in task order, from +0.0f) / (float)|sel| in IEEE division; +0.0f for an empty sel
+ *                     theta = base + scale * m
+ *                   seg_counts: int32[3 * nseg] on the device, zeroed here; per tensor {elements with an entry t_k != 0 (a NaN
+ *                   included), elements with entries of both signs, elements whose mass is zero (those without any entry
+ *                   included: the elements whose entries cancelled are [2] - (numel - [0]))}.
+ *                   DIVERGENCE from the authors' code: where the surviving entries cancel to a mass of exactly zero no sign is
+ *                   elected and the element takes the base value; theirs gives such elements the majority sign of the whole
+ *                   model, which would cost a second full pass for a case of measure zero.
+ * IA_INVALID_VALUE before any device work: a NULL required pointer, counts <= 0, ntasks outside 1..IA_MERGE_MAX_TASKS, a stride
+ * that is not a positive multiple of 4, trim outside [0, 1) (NaN included), a non-finite scale, misaligned buffers (16 bytes for
+ * theta, base, vectors, the chunk table and the trim workspace, 8 for the shadow, 4 for seg_of_scope, cutoffs and seg_counts). */
+#define IA_MERGE_MAX_TASKS 32
+int ia_merge_linear(float* theta, const float* base, const float* vectors, int64_t stride, int ntasks, const float* coef,
+                    float scale, const int32_t* chunk_table, int nchunks, void* shadow_bf16, ia_stream_t stream);
+size_t ia_merge_trim_workspace_bytes(int ntasks, int nscope);
+int ia_merge_trim(const float* vectors, int64_t stride, int ntasks, const int32_t* chunk_table, int nchunks,
+                  const int32_t* seg_of_scope, int nscope, float trim, uint32_t* cutoffs, void* workspace,
+                  size_t workspace_bytes, ia_stream_t stream);
+int ia_merge_ties(float* theta, const float* base, const float* vectors, int64_t stride, int ntasks, const uint32_t* cutoffs,
+                  const int32_t* seg_of_scope, int nscope, float scale, const int32_t* chunk_table, int nchunks, int nseg,
+                  void* shadow_bf16, int32_t* seg_counts, ia_stream_t stream);
 
 /* ---- CTC head + loss on RAW logits (ConvASRDecoder.forward + CTCLoss.forward, A/modules/conv_asr.py:459-490 and
  * A/losses/ctc.py:68-82, without the [B,T,V] log-prob tensor and without a softmax backward pass): logits [B*T, ld] f32 with V

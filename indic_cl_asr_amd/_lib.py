@@ -248,6 +248,10 @@ SIGNATURES = {
     "ia_pack_prune_workspace_bytes": (_sz, [_i]),
     "ia_pack_prune": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _f, _i, _vp, _vp, _vp, _sz, _vp]),
     "ia_pack_apply": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp]),
+    "ia_merge_linear": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _f, _vp, _i, _vp, _vp]),
+    "ia_merge_trim_workspace_bytes": (_sz, [_i, _i]),
+    "ia_merge_trim": (_i, [_vp, _i64, _i, _vp, _i, _vp, _i, _f, _vp, _vp, _sz, _vp]),
+    "ia_merge_ties": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _i, _f, _vp, _i, _i, _vp, _vp, _vp]),
 }
 
 _lib = None

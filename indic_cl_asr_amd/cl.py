@@ -1111,6 +1111,349 @@ class PackNet:
 
 
 # ----------------------------------------------------------------------------- LwF
+MERGE_MAX_TASKS = 32       # IA_MERGE_MAX_TASKS of include/indicasr.h
+MERGE_METHODS = ("task_arithmetic", "average", "ties")
+MERGE_SCOPES = ("tensor", "model")
+
+
+def density_to_trim(density) -> float:
+    """TIES keeps the `density` largest-magnitude fraction of a task vector; the kernels take the trimmed fraction as a float:
+    trim = float32(1.0 - density), the difference formed in double.  ValueError unless 0 < density <= 1 and trim < 1."""
+    density = float(density)
+    if not 0.0 < density <= 1.0:
+        raise ValueError(f"TaskVectors: density {density} is outside (0, 1]")
+    trim = ctypes.c_float(1.0 - density).value
+    if not 0.0 <= trim < 1.0:
+        raise ValueError(f"TaskVectors: density {density} is too small: 1 - density rounds to 1 in fp32")
+    return trim
+
+
+class TaskVectors:
+    """Model merging, the fourth continual-learning family beside regularisation, replay and parameter isolation: one copy of
+    the model is fine-tuned per language from the same start, and the weight deltas ("task vectors", tau = theta - base) are
+    combined afterwards.  No importance epoch, no memory of old audio, no per-language mask at inference, and the languages can
+    be trained independently, on different nodes, and joined later.
+
+        tv = TaskVectors(model_or_flat)
+        tv.set_base(opt)                          # theta and the module buffers as they are now
+        for lang in languages:
+            ...fine-tune on lang...
+            tv.store(lang, opt)                   # row k of `vectors` <- theta - base; the language's buffers are kept
+            tv.restore_base(opt)                  # the next language starts from the same weights
+        tv.merge("ties", density=0.2, optimizer=opt)
+
+    `merge` writes the merged weights into `flat.theta` in place, refreshes every bf16 image and moves the weight epoch:
+      "task_arithmetic"  theta = base + scale * sum_k w_k tau_k (Ilharco et al., ICLR 2023); `weights` defaults to 1 each.
+      "average"          the same rule with w_k = 1 / K and scale = 1: the mean of the fine-tuned models.  The weight averaging of
+                         Vander Eeckt and Van hamme (ICASSP 2023) is its K = 2 case with base = the previous model: store the
+                         previous model itself (a zero task vector) and the newly adapted one.
+      "ties"             trim, elect sign, disjoint mean (Yadav et al., NeurIPS 2023): per language only the `density` fraction of
+                         largest magnitude stays (ties at the cutoff all stay); per weight the sign of the summed survivors is
+                         elected and the survivors that carry it are averaged; theta = base + scale * that mean.  scope="tensor"
+                         selects per tensor, scope="model" over the whole task vector, as the authors' code does.  Where the
+                         survivors cancel to exactly zero no sign is elected and the weight takes its base value (the authors'
+                         code gives such weights the majority sign of the whole model).
+    Floating-point module buffers (the BatchNorm running statistics) become the arithmetic mean of the merged languages' buffers,
+    integer buffers are those of the last listed language.  The arithmetic is ia_merge_linear / ia_merge_trim / ia_merge_ties:
+    every operation rounded on its own in the order of `languages`, so the result is reproducible bit for bit, and every rank
+    of a distributed run performs the same merge on its own (no collective).
+
+    Cost: `vectors` is [rows in use, flat.numel] fp32 on the device, grown on demand up to `max_tasks` rows (4 B * trainable
+    parameters per language), plus `base`.  An optimizer given to any call (or none: the weight caches are invalidated instead)
+    has its bf16 shadow rewritten; `restore_base` and `merge` also zero its moments and step counters, as PackNet does when the
+    weights change under it: the moments belong to a trajectory the new weights are not on."""
+
+    def __init__(self, model_or_flat, max_tasks=MERGE_MAX_TASKS):
+        if not 1 <= int(max_tasks) <= MERGE_MAX_TASKS:
+            raise ValueError(f"TaskVectors: max_tasks must be in 1..{MERGE_MAX_TASKS} (got {max_tasks})")
+        self.flat = _as_flat(model_or_flat)
+        self.max_tasks = int(max_tasks)
+        self.stride = (self.flat.numel + 3) // 4 * 4           # GEM's row convention: float4 loads of every row stay aligned
+        self.base: Optional[FlatDict] = None
+        self.base_buffers: Dict[str, torch.Tensor] = {}
+        self.vectors: Optional[torch.Tensor] = None             # [capacity, stride]; rows 0 .. len(_rows)-1 are in use
+        self._rows: Dict[str, int] = {}                         # language -> row, in order of first store
+        self.buffers: Dict[str, Dict[str, torch.Tensor]] = {}   # language -> its module buffers
+        self._optimizer = None
+        self._scopes: Dict[str, torch.Tensor] = {}
+        self._trim_ws = self._cutoffs = self._seg_counts = None
+        self.last_merge: Optional[dict] = None
+
+    # -- bookkeeping -----------------------------------------------------------------------------------------------
+    def languages(self) -> List[str]:
+        """The stored languages, in row order."""
+        return list(self._rows)
+
+    def _attached(self, optimizer=None):
+        if optimizer is not None:
+            if optimizer.flat is not self.flat:
+                raise ValueError("optimizer belongs to another FlatParams")
+            self._optimizer = weakref.ref(optimizer)
+        return self._optimizer() if self._optimizer is not None else None
+
+    def _weights_changed(self, opt, reset_moments=True):
+        """PackNet's convention: fresh moments and step counters, the weight epoch moves, the flat shadow views are registered."""
+        if opt is not None:
+            if reset_moments:
+                opt.exp_avg.zero_()
+                opt.exp_avg_sq.zero_()
+                opt.seg_step.zero_()
+            opt._after_update()
+        else:
+            from .ops import fast
+            fast.bump_weight_epoch()
+
+    def _snapshot_buffers(self) -> Dict[str, torch.Tensor]:
+        return {n: b.detach().clone() for n, b in self.flat.model.named_buffers()}
+
+    def _load_buffers(self, saved: Dict[str, torch.Tensor]):
+        live = dict(self.flat.model.named_buffers())
+        with torch.no_grad():
+            for n, t in saved.items():
+                live[n].copy_(t)
+
+    def _row_storage(self, rows: int) -> torch.Tensor:
+        """`vectors` with room for `rows` rows: grown by doubling, never beyond max_tasks; rows in use keep their contents."""
+        have = 0 if self.vectors is None else self.vectors.shape[0]
+        if rows > have:
+            grown = torch.zeros(min(self.max_tasks, max(rows, 2 * have)), self.stride, dtype=torch.float32,
+                                device=self.flat.theta.device)
+            if have:
+                grown[:have].copy_(self.vectors)
+            self.vectors = grown
+        return self.vectors
+
+    def set_base(self, optimizer: Optional["FusedAdamW"] = None):
+        """theta (after any deferred update) and the module buffers, as they are now, become the common start.  Task vectors
+        stored against an earlier base are dropped: they are differences from it."""
+        self._attached(optimizer)
+        flush_pending_updates()
+        if self.base is None:
+            self.base = FlatDict(self.flat, self.flat.theta.clone())
+        else:
+            self.base.flat.copy_(self.flat.theta)
+        self.base_buffers = self._snapshot_buffers()
+        self._rows, self.buffers = {}, {}
+
+    def _need_base(self, what):
+        if self.base is None:
+            raise RuntimeError(f"TaskVectors.{what}: no base has been set; call set_base() before fine-tuning")
+
+    def store(self, language: str, optimizer: Optional["FusedAdamW"] = None):
+        """tau = theta - base (fp32, one rounding per element, +0 in the alignment gaps) becomes the language's row, the next free
+        one on first use; the module buffers are kept with it.  Storing a language again overwrites its row."""
+        self._need_base("store")
+        if language not in self._rows and len(self._rows) >= self.max_tasks:
+            raise ValueError(f"TaskVectors: max_tasks = {self.max_tasks} languages are stored already; '{language}' would be one "
+                             "more")
+        self._attached(optimizer)
+        flush_pending_updates()
+        f = self.flat
+        row = self._rows.get(language, len(self._rows))
+        vectors = self._row_storage(row + 1)
+        torch.sub(f.theta, self.base.flat, out=vectors[row, :f.numel])
+        self._rows[language] = row
+        self.buffers[language] = self._snapshot_buffers()
+
+    def drop(self, language: str):
+        """Forget a language; the rows behind it move up, so the order of the others stays."""
+        if language not in self._rows:
+            raise ValueError(f"TaskVectors.drop: unknown language '{language}' (stored: {', '.join(self._rows) or 'none'})")
+        row, last = self._rows.pop(language), len(self._rows)
+        del self.buffers[language]
+        for r in range(row, last):
+            self.vectors[r].copy_(self.vectors[r + 1])
+        self.vectors[last].zero_()
+        self._rows = {lang: (r if r < row else r - 1) for lang, r in self._rows.items()}
+
+    def task_vector(self, language: str) -> FlatDict:
+        """name -> view into the language's row."""
+        if language not in self._rows:
+            raise ValueError(f"TaskVectors: unknown language '{language}' (stored: {', '.join(self._rows) or 'none'})")
+        return FlatDict(self.flat, self.vectors[self._rows[language], :self.flat.numel])
+
+    def restore_base(self, optimizer: Optional["FusedAdamW"] = None):
+        """theta and the module buffers go back to the base, bit for bit, for fine-tuning the next language from the same
+        start; the optimizer's bf16 shadow follows and its moments and step counters are zeroed."""
+        self._need_base("restore_base")
+        opt = self._attached(optimizer)
+        flush_pending_updates()
+        self.flat.theta.copy_(self.base.flat)
+        if opt is not None and opt.shadow is not None:
+            opt.shadow.copy_(self.flat.theta)
+        self._load_buffers(self.base_buffers)
+        self._weights_changed(opt)
+
+    # -- the merge -------------------------------------------------------------------------------------------------
+    def _checked_merge(self, method, languages, scale, weights, density, scope):
+        """(names, coefficients, trim) of a merge, or ValueError; nothing is launched and nothing is changed here."""
+        if method not in MERGE_METHODS:
+            raise ValueError(f"TaskVectors.merge: unknown method '{method}' (one of {', '.join(MERGE_METHODS)})")
+        if scope not in MERGE_SCOPES:
+            raise ValueError(f"TaskVectors.merge: unknown scope '{scope}' (one of {', '.join(MERGE_SCOPES)})")
+        names = self.languages() if languages is None else list(languages)
+        if not names:
+            raise ValueError("TaskVectors.merge: no language to merge")
+        if len(set(names)) != len(names):
+            raise ValueError("TaskVectors.merge: a language is listed twice")
+        for n in names:
+            if n not in self._rows:
+                raise ValueError(f"TaskVectors.merge: unknown language '{n}' (stored: {', '.join(self._rows) or 'none'})")
+        scale = float(scale)
+        if not math.isfinite(scale):
+            raise ValueError(f"TaskVectors.merge: scale must be finite (got {scale})")
+        if method != "task_arithmetic" and weights is not None:
+            raise ValueError(f"TaskVectors.merge: weights belong to 'task_arithmetic', not to '{method}'")
+        if method == "average" and scale != 1.0:
+            raise ValueError("TaskVectors.merge: 'average' is the mean of the fine-tuned models, its scale is 1; use "
+                             "'task_arithmetic' for a scaled sum")
+        if weights is None:
+            coef = [1.0 / len(names) if method == "average" else 1.0] * len(names)
+        else:
+            coef = [float(weights[n]) for n in names] if isinstance(weights, dict) else [float(w) for w in weights]
+            if len(coef) != len(names):
+                raise ValueError(f"TaskVectors.merge: {len(coef)} weights for {len(names)} languages")
+            if not all(math.isfinite(c) for c in coef):
+                raise ValueError("TaskVectors.merge: weights must be finite")
+        trim = density_to_trim(density) if method == "ties" else None
+        return names, coef, scale, trim
+
+    def _rows_of(self, names) -> torch.Tensor:
+        """The rows of `names`, in that order, as one [K, stride] tensor: a view when they are consecutive rows of `vectors`
+        (every language in row order is), a gathered copy otherwise."""
+        idx = [self._rows[n] for n in names]
+        if idx == list(range(idx[0], idx[0] + len(idx))):
+            return self.vectors[idx[0]:idx[0] + len(idx)]
+        return self.vectors.index_select(0, torch.tensor(idx, device=self.vectors.device))
+
+    def merged_buffers(self, names) -> Dict[str, torch.Tensor]:
+        """Floating-point buffers: the arithmetic mean over `names` (added in that order, then divided by their number, in the
+        buffer's dtype); every other buffer: the last listed language's."""
+        out = {}
+        for key, last in self.buffers[names[-1]].items():
+            if last.is_floating_point():
+                acc = self.buffers[names[0]][key].clone()
+                for n in names[1:]:
+                    acc = acc + self.buffers[n][key]
+                out[key] = acc / len(names)
+            else:
+                out[key] = last.clone()
+        return out
+
+    def _scope_map(self, scope) -> torch.Tensor:
+        if scope not in self._scopes:
+            nseg = len(self.flat.entries)
+            self._scopes[scope] = (torch.arange(nseg, dtype=torch.int32) if scope == "tensor"
+                                   else torch.zeros(nseg, dtype=torch.int32)).to(self.flat.theta.device)
+        return self._scopes[scope]
+
+    def merge(self, method: str, languages=None, *, scale=1.0, weights=None, density=0.2, scope="tensor",
+              optimizer: Optional["FusedAdamW"] = None) -> dict:
+        """Merge `languages` (default: all, in row order) into theta; see the class docstring for the methods.  `weights`: one
+        per listed language (a sequence, or a dict by language).  Returns {"method", "languages", "coefficients", "scale"} and,
+        for "ties", "density", "trim", "scope" and per tensor and in total the number of weights with a surviving entry
+        (`surviving`), with survivors of both signs (`conflicts`) and whose survivors cancelled to zero and so kept the base
+        value (`cancelled`): one small device-to-host read."""
+        self._need_base("merge")
+        names, coef, scale, trim = self._checked_merge(method, languages, scale, weights, density, scope)
+        f = self.flat
+        if not f.theta.is_cuda:
+            raise RuntimeError("TaskVectors.merge runs on the HIP kernels: the parameters are not on the device")
+        opt = self._attached(optimizer)
+        flush_pending_updates()
+        L, ptr, stream = _lib.lib(), _lib.ptr, _lib.stream_ptr()
+        rows, K = self._rows_of(names), len(names)
+        nchunks, nseg = f.chunk_table.shape[0], len(f.entries)
+        shadow = opt.shadow if opt is not None else None
+        stats = {"method": method, "languages": names, "coefficients": coef, "scale": scale}
+        if method == "ties":
+            seg_of_scope = self._scope_map(scope)
+            nscope = nseg if scope == "tensor" else 1
+            need = L.ia_merge_trim_workspace_bytes(K, nscope)
+            if self._trim_ws is None or self._trim_ws.numel() < need:
+                self._trim_ws = torch.empty(need, dtype=torch.uint8, device=f.theta.device)
+            if self._cutoffs is None:
+                self._cutoffs = torch.zeros(self.max_tasks * nseg, dtype=torch.int32, device=f.theta.device)
+                self._seg_counts = torch.zeros(nseg, 3, dtype=torch.int32, device=f.theta.device)
+            _lib.check(L.ia_merge_trim(ptr(rows), self.stride, K, ptr(f.chunk_table), nchunks, ptr(seg_of_scope), nscope, trim,
+                                       ptr(self._cutoffs), ptr(self._trim_ws), self._trim_ws.numel(), stream), "ia_merge_trim")
+            _lib.check(L.ia_merge_ties(ptr(f.theta), ptr(self.base.flat), ptr(rows), self.stride, K, ptr(self._cutoffs),
+                                       ptr(seg_of_scope), nscope, scale, ptr(f.chunk_table), nchunks, nseg, ptr(shadow),
+                                       ptr(self._seg_counts), stream), "ia_merge_ties")
+        else:
+            _lib.check(L.ia_merge_linear(ptr(f.theta), ptr(self.base.flat), ptr(rows), self.stride, K,
+                                         (ctypes.c_float * K)(*coef), scale, ptr(f.chunk_table), nchunks, ptr(shadow), stream),
+                       "ia_merge_linear")
+        self._load_buffers(self.merged_buffers(names))
+        self._weights_changed(opt)
+        if method == "ties":
+            counts = self._seg_counts.tolist()
+            per = {n: {"surviving": c[0], "conflicts": c[1], "cancelled": c[2] - (k - c[0])}
+                   for (n, _, k, _), c in zip(f.entries, counts)}
+            stats.update(density=float(density), trim=trim, scope=scope, tensors=per,
+                         **{key: sum(t[key] for t in per.values()) for key in ("surviving", "conflicts", "cancelled")})
+        self.last_merge = stats
+        return stats
+
+    def cutoffs(self, ntasks: int, scope="tensor") -> torch.Tensor:
+        """The magnitude cutoffs of the latest "ties" merge as int32 bit patterns [ntasks, scope segments] (a device view)."""
+        nscope = len(self.flat.entries) if scope == "tensor" else 1
+        return self._cutoffs[:ntasks * nscope].view(ntasks, nscope)
+
+    # -- reports and resumable state -------------------------------------------------------------------------------
+    def stats(self) -> dict:
+        """Host-side bookkeeping only (no device read): the languages in row order, the rows allocated, the bytes held on the
+        device and what the latest merge returned."""
+        rows = 0 if self.vectors is None else self.vectors.shape[0]
+        per_buffers = sum(b.numel() * b.element_size() for b in self.base_buffers.values())
+        return {"languages": self.languages(), "rows_in_use": len(self._rows), "rows_allocated": rows,
+                "max_tasks": self.max_tasks, "has_base": self.base is not None,
+                "bytes_vectors": 4 * rows * self.stride, "bytes_base": 4 * self.flat.numel if self.base is not None else 0,
+                "bytes_buffers": per_buffers * (len(self.buffers) + (self.base is not None)), "last_merge": self.last_merge}
+
+    def state_dict(self) -> dict:
+        flush_pending_updates()
+        cpu = lambda t: t.detach().to("cpu", copy=True)
+        k, n = len(self._rows), self.flat.numel
+        vectors = cpu(self.vectors[:k, :n]) if k else torch.zeros(0, n)
+        return {"entries": list(self.flat.entries), "max_tasks": self.max_tasks,
+                "base": cpu(self.base.flat) if self.base is not None else None,
+                "base_buffers": {key: cpu(t) for key, t in self.base_buffers.items()},
+                "task_languages": self.languages(), "vectors": vectors,
+                "buffers": {lang: {key: cpu(t) for key, t in b.items()} for lang, b in self.buffers.items()}}
+
+    def load_state_dict(self, sd: dict, source="state dict"):
+        """Inverse of state_dict(); refuses a state saved for another set of trainable tensors.  The weights are not part of
+        this state: `restore_base()` or `merge()` puts them in step with it."""
+        if [tuple(e[:3]) + (tuple(e[3]),) for e in sd["entries"]] != list(self.flat.entries):
+            raise ValueError(f"{source}: 'masks' was saved for a different set of trainable tensors")
+        if "vectors" not in sd or "task_languages" not in sd:
+            raise ValueError(f"{source}: 'masks' does not hold task vectors")
+        names = list(sd["task_languages"])
+        if len(names) > self.max_tasks:
+            raise ValueError(f"{source}: {len(names)} task vectors were saved, max_tasks here is {self.max_tasks}")
+        if tuple(sd["vectors"].shape) != (len(names), self.flat.numel):
+            raise ValueError(f"{source}: the saved task vectors are {tuple(sd['vectors'].shape)}, expected "
+                             f"{(len(names), self.flat.numel)}")
+        flush_pending_updates()
+        dev = self.flat.theta.device
+        if sd["base"] is None:
+            self.base = None
+        elif self.base is None:
+            self.base = FlatDict(self.flat, sd["base"].to(dev, copy=True))
+        else:
+            self.base.flat.copy_(sd["base"])
+        self.base_buffers = {key: t.to(dev, copy=True) for key, t in sd["base_buffers"].items()}
+        self._rows = {lang: r for r, lang in enumerate(names)}
+        if names:
+            vectors = self._row_storage(len(names))
+            vectors.zero_()
+            vectors[:len(names), :self.flat.numel].copy_(sd["vectors"])
+        elif self.vectors is not None:
+            self.vectors.zero_()
+        self.buffers = {lang: {key: t.to(dev, copy=True) for key, t in b.items()} for lang, b in sd["buffers"].items()}
+
+
 def lwf_kd_loss(loss, prob, prob_, pred_store_list, store_list, knowledge_distillation: float, kd_ctx: float):
     """R/cl_baseline_lwf.py:242-264.  Returns (total loss, rnnt_kd, ctc_kd) -- device tensors."""
     F = torch.nn.functional
