@@ -1136,9 +1136,35 @@ int ia_pack_apply(float* theta, const float* base, const uint8_t* owner, const i
  *                   DIVERGENCE from the authors' code: where the surviving entries cancel to a mass of exactly zero no sign is
  *                   elected and the element takes the base value; theirs gives such elements the majority sign of the whole
  *                   model, which would cost a second full pass for a case of measure zero.
+ * ia_merge_fisher   Fisher merging (Matena & Raffel 2022), sum_k coef_k F_k theta_k / sum_k coef_k F_k, in task-vector form
+ *                   (theta_k = base + tau_k).  importances: fp32 [max_tasks, stride] on the device, row k the diagonal Fisher (or
+ *                   any other per-parameter importance) of task k, laid out as `vectors`.  One pass, 8 K + 4 B read and 4 (+ 2) B
+ *                   written per element.  Per element, in task order:
+ *                     g_k = F_k > floor ? F_k : floor     (a select: a NaN or negative importance becomes the floor)
+ *                     a_k = coef_k * g_k
+ *                     num = a_0 * tau_0;  num = num + a_k * tau_k;   den = a_0;  den = den + a_k   for k = 1 .. K-1
+ *                     m   = den > 0 ? num / den : +0.0f   (IEEE division)
+ *                     theta = base + scale * m
+ *                   coef: a HOST array of ntasks floats (the lambda_k).  seg_counts: int32[2 * nseg] on the device, zeroed here;
+ *                   per tensor {elements where no F_k exceeded the floor: a plain coef-weighted mean, elements with den == 0:
+ *                   they took the base value}.  DIVERGENCES from the authors' code: the floor is a select, not an addition or a
+ *                   clamp of the sum, and an element whose denominator is zero takes the base value instead of 0 / 0.
+ * ia_merge_linear_dare, ia_merge_ties_dare   DARE (Yu et al. 2024) in front of ia_merge_linear's and ia_merge_ties' rule: entry i
+ *                   (its index in the flat buffer) of task k (its position among the merged rows) is first replaced by
+ *                     t = keep(seed, k, i) ? tau / keep_prob : +0.0f   (IEEE division; keep_prob = 1.0f: no rescaling)
+ *                     keep(seed, k, i) = h < keep_threshold,  h = H((uint32_t)i * 0x9E3779B1u + H(H(seed) ^ (uint32_t)(k + 1)))
+ *                   in 32-bit unsigned arithmetic, H the 32-bit finaliser x ^= x >> 16; x *= 0x85ebca6b; x ^= x >> 13;
+ *                   x *= 0xc2b2ae35; x ^= x >> 16 (ia_dm_hash32 of csrc/dropout_mask.h).  A 32-bit compare: keep probabilities
+ *                   down to 2^-32 are expressible.  No mask is stored; it is a pure function of (seed, k, i), so every rank of a
+ *                   distributed run and every repetition computes the same merge.  An entry whose h is 2^32 - 1 is dropped under
+ *                   every threshold, keep_threshold = 2^32 - 1 (a density of 1) included: one entry in 2^32, not special-cased.
+ *                   ia_merge_ties_dare takes no cutoffs and no scopes: the random drop replaces the magnitude trim, every kept
+ *                   entry takes part in the election; its seg_counts are ia_merge_ties' three.  Same traffic as the plain rules.
+ *                   DIVERGENCE from the authors' code: the mask is this hash, not a sampled Bernoulli tensor.
  * IA_INVALID_VALUE before any device work: a NULL required pointer, counts <= 0, ntasks outside 1..IA_MERGE_MAX_TASKS, a stride
- * that is not a positive multiple of 4, trim outside [0, 1) (NaN included), a non-finite scale, misaligned buffers (16 bytes for
- * theta, base, vectors, the chunk table and the trim workspace, 8 for the shadow, 4 for seg_of_scope, cutoffs and seg_counts). */
+ * that is not a positive multiple of 4, trim outside [0, 1) (NaN included), a non-finite scale, a floor that is negative or not
+ * finite, keep_prob outside (0, 1] (NaN included), misaligned buffers (16 bytes for theta, base, vectors, importances, the chunk
+ * table and the trim workspace, 8 for the shadow, 4 for seg_of_scope, cutoffs and seg_counts). */
 #define IA_MERGE_MAX_TASKS 32
 int ia_merge_linear(float* theta, const float* base, const float* vectors, int64_t stride, int ntasks, const float* coef,
                     float scale, const int32_t* chunk_table, int nchunks, void* shadow_bf16, ia_stream_t stream);
@@ -1149,6 +1175,15 @@ int ia_merge_trim(const float* vectors, int64_t stride, int ntasks, const int32_
 int ia_merge_ties(float* theta, const float* base, const float* vectors, int64_t stride, int ntasks, const uint32_t* cutoffs,
                   const int32_t* seg_of_scope, int nscope, float scale, const int32_t* chunk_table, int nchunks, int nseg,
                   void* shadow_bf16, int32_t* seg_counts, ia_stream_t stream);
+int ia_merge_fisher(float* theta, const float* base, const float* vectors, const float* importances, int64_t stride, int ntasks,
+                    const float* coef, float floor, float scale, const int32_t* chunk_table, int nchunks, int nseg,
+                    void* shadow_bf16, int32_t* seg_counts, ia_stream_t stream);
+int ia_merge_linear_dare(float* theta, const float* base, const float* vectors, int64_t stride, int ntasks, const float* coef,
+                         float scale, const int32_t* chunk_table, int nchunks, void* shadow_bf16, uint32_t seed,
+                         uint32_t keep_threshold, float keep_prob, ia_stream_t stream);
+int ia_merge_ties_dare(float* theta, const float* base, const float* vectors, int64_t stride, int ntasks, float scale,
+                       const int32_t* chunk_table, int nchunks, int nseg, void* shadow_bf16, int32_t* seg_counts, uint32_t seed,
+                       uint32_t keep_threshold, float keep_prob, ia_stream_t stream);
 
 /* ---- CTC head + loss on RAW logits (ConvASRDecoder.forward + CTCLoss.forward, A/modules/conv_asr.py:459-490 and
  * A/losses/ctc.py:68-82, without the [B,T,V] log-prob tensor and without a softmax backward pass): logits [B*T, ld] f32 with V

@@ -252,6 +252,9 @@ SIGNATURES = {
     "ia_merge_trim_workspace_bytes": (_sz, [_i, _i]),
     "ia_merge_trim": (_i, [_vp, _i64, _i, _vp, _i, _vp, _i, _f, _vp, _vp, _sz, _vp]),
     "ia_merge_ties": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _i, _f, _vp, _i, _i, _vp, _vp, _vp]),
+    "ia_merge_fisher": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _f, _f, _vp, _i, _i, _vp, _vp, _vp]),
+    "ia_merge_linear_dare": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _f, _vp, _i, _vp, _c.c_uint32, _c.c_uint32, _f, _vp]),
+    "ia_merge_ties_dare": (_i, [_vp, _vp, _vp, _i64, _i, _f, _vp, _i, _i, _vp, _vp, _c.c_uint32, _c.c_uint32, _f, _vp]),
 }
 
 _lib = None

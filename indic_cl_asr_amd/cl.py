@@ -1112,7 +1112,8 @@ class PackNet:
 
 # ----------------------------------------------------------------------------- LwF
 MERGE_MAX_TASKS = 32       # IA_MERGE_MAX_TASKS of include/indicasr.h
-MERGE_METHODS = ("task_arithmetic", "average", "ties")
+MERGE_METHODS = ("task_arithmetic", "average", "ties", "fisher", "dare_linear", "dare_ties")
+MERGE_WEIGHTED = ("task_arithmetic", "fisher", "dare_linear")      # the methods that take `weights`
 MERGE_SCOPES = ("tensor", "model")
 
 
@@ -1126,6 +1127,20 @@ def density_to_trim(density) -> float:
     if not 0.0 <= trim < 1.0:
         raise ValueError(f"TaskVectors: density {density} is too small: 1 - density rounds to 1 in fp32")
     return trim
+
+
+def density_to_keep(density, rescale=True):
+    """DARE keeps every task-vector entry with probability `density` and divides the kept ones by it.  The kernels compare a
+    32-bit hash with keep_threshold = min(floor(density * 2^32), 2^32 - 1), formed in double, and divide by
+    keep_prob = float32(density) (1.0 without `rescale`).  -> (keep_threshold, keep_prob).  ValueError unless 0 < density <= 1
+    and the threshold is at least 1 (density >= 2^-32)."""
+    density = float(density)
+    if not 0.0 < density <= 1.0:
+        raise ValueError(f"TaskVectors: density {density} is outside (0, 1]")
+    threshold = min(math.floor(density * 4294967296.0), 0xFFFFFFFF)
+    if threshold < 1:
+        raise ValueError(f"TaskVectors: density {density} is too small: below 2^-32 no entry would be kept")
+    return threshold, (ctypes.c_float(density).value if rescale else 1.0)
 
 
 class TaskVectors:
@@ -1153,13 +1168,27 @@ class TaskVectors:
                          selects per tensor, scope="model" over the whole task vector, as the authors' code does.  Where the
                          survivors cancel to exactly zero no sign is elected and the weight takes its base value (the authors'
                          code gives such weights the majority sign of the whole model).
+      "fisher"           the importance-weighted mean sum_k w_k F_k theta_k / sum_k w_k F_k (Matena & Raffel, NeurIPS 2022), as
+                         theta = base + scale * sum_k w_k F_k tau_k / sum_k w_k F_k.  F_k is the importance stored with the
+                         language: `store(lang, opt, importance=fish)` or `set_importance(lang, fish)` with the language's own
+                         diagonal Fisher (`fisher_finish(None, fish, N, 1.0)`), MAS's omega or SI's importance.  An importance
+                         that is not above `fisher_floor` counts as the floor (a select, so a NaN or negative one does too);
+                         where the denominator is zero (floor 0 and no importance anywhere) the weight takes its base value.
+                         `weights` are the lambda_k: > 0, 1 each by default.
+      "dare_linear"      drop and rescale (Yu et al., ICML 2024), then the task-arithmetic rule: every entry of every task
+                         vector is kept with probability `density` and divided by it (`rescale=False`: kept as it is), or
+                         becomes +0.  The mask is a hash of (`seed`, the language's position in `languages`, the element's
+                         flat index), never stored: the same seed gives the same merge, on every rank.
+      "dare_ties"        the same drop and rescale in place of TIES' magnitude trim, then its sign election and disjoint mean.
     Floating-point module buffers (the BatchNorm running statistics) become the arithmetic mean of the merged languages' buffers,
-    integer buffers are those of the last listed language.  The arithmetic is ia_merge_linear / ia_merge_trim / ia_merge_ties:
+    integer buffers are those of the last listed language.  The arithmetic is ia_merge_linear / ia_merge_trim / ia_merge_ties /
+    ia_merge_fisher / ia_merge_linear_dare / ia_merge_ties_dare:
     every operation rounded on its own in the order of `languages`, so the result is reproducible bit for bit, and every rank
     of a distributed run performs the same merge on its own (no collective).
 
     Cost: `vectors` is [rows in use, flat.numel] fp32 on the device, grown on demand up to `max_tasks` rows (4 B * trainable
-    parameters per language), plus `base`.  An optimizer given to any call (or none: the weight caches are invalidated instead)
+    parameters per language), plus `base`; `importances` is a second buffer of that shape, allocated when the first importance
+    is stored.  An optimizer given to any call (or none: the weight caches are invalidated instead)
     has its bf16 shadow rewritten; `restore_base` and `merge` also zero its moments and step counters, as PackNet does when the
     weights change under it: the moments belong to a trajectory the new weights are not on."""
 
@@ -1174,6 +1203,10 @@ class TaskVectors:
         self.vectors: Optional[torch.Tensor] = None             # [capacity, stride]; rows 0 .. len(_rows)-1 are in use
         self._rows: Dict[str, int] = {}                         # language -> row, in order of first store
         self.buffers: Dict[str, Dict[str, torch.Tensor]] = {}   # language -> its module buffers
+        self.importances: Optional[torch.Tensor] = None         # [capacity, stride], row-parallel to `vectors`; on first use
+        self._important: set = set()                            # the languages whose row of `importances` is filled
+        self._inside: Optional[torch.Tensor] = None             # bool [flat.numel]: inside a tensor (not an alignment gap)
+        self._fisher_counts = None
         self._optimizer = None
         self._scopes: Dict[str, torch.Tensor] = {}
         self._trim_ws = self._cutoffs = self._seg_counts = None
@@ -1221,7 +1254,51 @@ class TaskVectors:
             if have:
                 grown[:have].copy_(self.vectors)
             self.vectors = grown
+            if self.importances is not None:
+                self.importances = self._grown_like_vectors(self.importances)
         return self.vectors
+
+    def _grown_like_vectors(self, old: Optional[torch.Tensor]) -> torch.Tensor:
+        grown = torch.zeros_like(self.vectors)
+        if old is not None:
+            grown[:old.shape[0]].copy_(old)
+        return grown
+
+    def _checked_importance(self, importance) -> torch.Tensor:
+        f = self.flat
+        if not isinstance(importance, FlatDict) or list(importance.layout.entries) != list(f.entries):
+            raise ValueError("TaskVectors: importance must be a FlatDict of this layout (fisher_finish's result, MAS's omega, "
+                             "SI's importance)")
+        if importance.flat.device != f.theta.device or importance.flat.dtype != torch.float32 or importance.flat.numel() != f.numel:
+            raise ValueError(f"TaskVectors: importance must be {f.numel} float32 values on {f.theta.device}")
+        return importance.flat
+
+    def set_importance(self, language: str, importance: FlatDict):
+        """Keep a per-parameter importance of a stored language (its own diagonal Fisher from `fisher_finish(None, fish, N, 1.0)`,
+        not EWC's running sum over languages; MAS's omega; SI's importance) for merge("fisher"): copied into the language's row
+        of `importances`, +0 in the alignment gaps."""
+        if language not in self._rows:
+            raise ValueError(f"TaskVectors: unknown language '{language}' (stored: {', '.join(self._rows) or 'none'})")
+        values = self._checked_importance(importance)
+        f = self.flat
+        if self.importances is None or self.importances.shape != self.vectors.shape:
+            self.importances = self._grown_like_vectors(self.importances)
+        if self._inside is None:
+            inside = torch.zeros(f.numel, dtype=torch.bool)
+            for _, off, n, _ in f.entries:
+                inside[off:off + n] = True
+            self._inside = inside.to(f.theta.device)
+        row = self.importances[self._rows[language], :f.numel]
+        row.copy_(values)
+        row.masked_fill_(~self._inside, 0.0)
+        self._important.add(language)
+
+    def importance(self, language: str) -> FlatDict:
+        """name -> view into the language's row of `importances`."""
+        if language not in self._important:
+            raise ValueError(f"TaskVectors: no importance is stored for '{language}' "
+                             f"(with one: {', '.join(l for l in self._rows if l in self._important) or 'none'})")
+        return FlatDict(self.flat, self.importances[self._rows[language], :self.flat.numel])
 
     def set_base(self, optimizer: Optional["FusedAdamW"] = None):
         """theta (after any deferred update) and the module buffers, as they are now, become the common start.  Task vectors
@@ -1234,15 +1311,24 @@ class TaskVectors:
             self.base.flat.copy_(self.flat.theta)
         self.base_buffers = self._snapshot_buffers()
         self._rows, self.buffers = {}, {}
+        self._forget_importances()
+
+    def _forget_importances(self):
+        self._important = set()
+        if self.importances is not None:
+            self.importances.zero_()
 
     def _need_base(self, what):
         if self.base is None:
             raise RuntimeError(f"TaskVectors.{what}: no base has been set; call set_base() before fine-tuning")
 
-    def store(self, language: str, optimizer: Optional["FusedAdamW"] = None):
+    def store(self, language: str, optimizer: Optional["FusedAdamW"] = None, importance: Optional[FlatDict] = None):
         """tau = theta - base (fp32, one rounding per element, +0 in the alignment gaps) becomes the language's row, the next free
-        one on first use; the module buffers are kept with it.  Storing a language again overwrites its row."""
+        one on first use; the module buffers are kept with it.  Storing a language again overwrites its row.  `importance`: see
+        set_importance (checked before anything is stored); without one, an importance stored earlier stays."""
         self._need_base("store")
+        if importance is not None:
+            self._checked_importance(importance)
         if language not in self._rows and len(self._rows) >= self.max_tasks:
             raise ValueError(f"TaskVectors: max_tasks = {self.max_tasks} languages are stored already; '{language}' would be one "
                              "more")
@@ -1254,6 +1340,8 @@ class TaskVectors:
         torch.sub(f.theta, self.base.flat, out=vectors[row, :f.numel])
         self._rows[language] = row
         self.buffers[language] = self._snapshot_buffers()
+        if importance is not None:
+            self.set_importance(language, importance)
 
     def drop(self, language: str):
         """Forget a language; the rows behind it move up, so the order of the others stays."""
@@ -1261,9 +1349,12 @@ class TaskVectors:
             raise ValueError(f"TaskVectors.drop: unknown language '{language}' (stored: {', '.join(self._rows) or 'none'})")
         row, last = self._rows.pop(language), len(self._rows)
         del self.buffers[language]
-        for r in range(row, last):
-            self.vectors[r].copy_(self.vectors[r + 1])
-        self.vectors[last].zero_()
+        self._important.discard(language)
+        for buf in (self.vectors, self.importances):
+            if buf is not None:
+                for r in range(row, last):
+                    buf[r].copy_(buf[r + 1])
+                buf[last].zero_()
         self._rows = {lang: (r if r < row else r - 1) for lang, r in self._rows.items()}
 
     def task_vector(self, language: str) -> FlatDict:
@@ -1302,8 +1393,9 @@ class TaskVectors:
         scale = float(scale)
         if not math.isfinite(scale):
             raise ValueError(f"TaskVectors.merge: scale must be finite (got {scale})")
-        if method != "task_arithmetic" and weights is not None:
-            raise ValueError(f"TaskVectors.merge: weights belong to 'task_arithmetic', not to '{method}'")
+        if method not in MERGE_WEIGHTED and weights is not None:
+            raise ValueError(f"TaskVectors.merge: weights belong to 'task_arithmetic', 'fisher' and 'dare_linear', not to "
+                             f"'{method}'")
         if method == "average" and scale != 1.0:
             raise ValueError("TaskVectors.merge: 'average' is the mean of the fine-tuned models, its scale is 1; use "
                              "'task_arithmetic' for a scaled sum")
@@ -1318,13 +1410,35 @@ class TaskVectors:
         trim = density_to_trim(density) if method == "ties" else None
         return names, coef, scale, trim
 
-    def _rows_of(self, names) -> torch.Tensor:
+    def _checked_rule(self, method, names, coef, density, fisher_floor, seed, rescale) -> dict:
+        """What "fisher", "dare_linear" and "dare_ties" need beyond _checked_merge, or ValueError; nothing is launched."""
+        rule = {}
+        if method == "fisher":
+            if not all(c > 0.0 for c in coef):
+                raise ValueError("TaskVectors.merge: the weights of 'fisher' must be > 0")
+            floor = float(fisher_floor)
+            if not (math.isfinite(floor) and floor >= 0.0):
+                raise ValueError(f"TaskVectors.merge: fisher_floor must be finite and >= 0 (got {floor})")
+            missing = [n for n in names if n not in self._important]
+            if missing:
+                raise ValueError(f"TaskVectors.merge: 'fisher' needs an importance for every language; none is stored for "
+                                 f"{', '.join(repr(n) for n in missing)} (store(lang, opt, importance=...) or set_importance)")
+            rule["fisher_floor"] = floor
+        elif method in ("dare_linear", "dare_ties"):
+            if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 32:
+                raise ValueError(f"TaskVectors.merge: seed must be an int in [0, 2^32) (got {seed!r})")
+            rule["keep_threshold"], rule["keep_prob"] = density_to_keep(density, bool(rescale))
+            rule.update(seed=seed, density=float(density), rescale=bool(rescale))
+        return rule
+
+    def _rows_of(self, names, buffer: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The rows of `names`, in that order, as one [K, stride] tensor: a view when they are consecutive rows of `vectors`
-        (every language in row order is), a gathered copy otherwise."""
+        (every language in row order is), a gathered copy otherwise.  `buffer`: `importances` instead of `vectors`."""
+        buffer = self.vectors if buffer is None else buffer
         idx = [self._rows[n] for n in names]
         if idx == list(range(idx[0], idx[0] + len(idx))):
-            return self.vectors[idx[0]:idx[0] + len(idx)]
-        return self.vectors.index_select(0, torch.tensor(idx, device=self.vectors.device))
+            return buffer[idx[0]:idx[0] + len(idx)]
+        return buffer.index_select(0, torch.tensor(idx, device=buffer.device))
 
     def merged_buffers(self, names) -> Dict[str, torch.Tensor]:
         """Floating-point buffers: the arithmetic mean over `names` (added in that order, then divided by their number, in the
@@ -1348,14 +1462,18 @@ class TaskVectors:
         return self._scopes[scope]
 
     def merge(self, method: str, languages=None, *, scale=1.0, weights=None, density=0.2, scope="tensor",
-              optimizer: Optional["FusedAdamW"] = None) -> dict:
+              optimizer: Optional["FusedAdamW"] = None, fisher_floor=1e-6, seed=0, rescale=True) -> dict:
         """Merge `languages` (default: all, in row order) into theta; see the class docstring for the methods.  `weights`: one
         per listed language (a sequence, or a dict by language).  Returns {"method", "languages", "coefficients", "scale"} and,
         for "ties", "density", "trim", "scope" and per tensor and in total the number of weights with a surviving entry
         (`surviving`), with survivors of both signs (`conflicts`) and whose survivors cancelled to zero and so kept the base
-        value (`cancelled`): one small device-to-host read."""
+        value (`cancelled`): one small device-to-host read.  "dare_ties" returns the same counts, and with "dare_linear" `seed`,
+        `density` and `rescale`; "fisher" returns `fisher_floor` and, per tensor and in total, the weights where no language's
+        importance exceeded the floor (`floored`: a plain weighted mean) and those whose denominator was zero and so kept the
+        base value (`unweighted`)."""
         self._need_base("merge")
         names, coef, scale, trim = self._checked_merge(method, languages, scale, weights, density, scope)
+        rule = self._checked_rule(method, names, coef, density, fisher_floor, seed, rescale)
         f = self.flat
         if not f.theta.is_cuda:
             raise RuntimeError("TaskVectors.merge runs on the HIP kernels: the parameters are not on the device")
@@ -1374,24 +1492,50 @@ class TaskVectors:
                 self._trim_ws = torch.empty(need, dtype=torch.uint8, device=f.theta.device)
             if self._cutoffs is None:
                 self._cutoffs = torch.zeros(self.max_tasks * nseg, dtype=torch.int32, device=f.theta.device)
+            if self._seg_counts is None:
                 self._seg_counts = torch.zeros(nseg, 3, dtype=torch.int32, device=f.theta.device)
             _lib.check(L.ia_merge_trim(ptr(rows), self.stride, K, ptr(f.chunk_table), nchunks, ptr(seg_of_scope), nscope, trim,
                                        ptr(self._cutoffs), ptr(self._trim_ws), self._trim_ws.numel(), stream), "ia_merge_trim")
             _lib.check(L.ia_merge_ties(ptr(f.theta), ptr(self.base.flat), ptr(rows), self.stride, K, ptr(self._cutoffs),
                                        ptr(seg_of_scope), nscope, scale, ptr(f.chunk_table), nchunks, nseg, ptr(shadow),
                                        ptr(self._seg_counts), stream), "ia_merge_ties")
+        elif method == "fisher":
+            if self._fisher_counts is None:
+                self._fisher_counts = torch.zeros(nseg, 2, dtype=torch.int32, device=f.theta.device)
+            _lib.check(L.ia_merge_fisher(ptr(f.theta), ptr(self.base.flat), ptr(rows), ptr(self._rows_of(names, self.importances)),
+                                         self.stride, K, (ctypes.c_float * K)(*coef), rule["fisher_floor"], scale,
+                                         ptr(f.chunk_table), nchunks, nseg, ptr(shadow), ptr(self._fisher_counts), stream),
+                       "ia_merge_fisher")
+        elif method == "dare_linear":
+            _lib.check(L.ia_merge_linear_dare(ptr(f.theta), ptr(self.base.flat), ptr(rows), self.stride, K,
+                                              (ctypes.c_float * K)(*coef), scale, ptr(f.chunk_table), nchunks, ptr(shadow),
+                                              rule["seed"], rule["keep_threshold"], rule["keep_prob"], stream),
+                       "ia_merge_linear_dare")
+        elif method == "dare_ties":
+            if self._seg_counts is None:
+                self._seg_counts = torch.zeros(nseg, 3, dtype=torch.int32, device=f.theta.device)
+            _lib.check(L.ia_merge_ties_dare(ptr(f.theta), ptr(self.base.flat), ptr(rows), self.stride, K, scale,
+                                            ptr(f.chunk_table), nchunks, nseg, ptr(shadow), ptr(self._seg_counts),
+                                            rule["seed"], rule["keep_threshold"], rule["keep_prob"], stream),
+                       "ia_merge_ties_dare")
         else:
             _lib.check(L.ia_merge_linear(ptr(f.theta), ptr(self.base.flat), ptr(rows), self.stride, K,
                                          (ctypes.c_float * K)(*coef), scale, ptr(f.chunk_table), nchunks, ptr(shadow), stream),
                        "ia_merge_linear")
         self._load_buffers(self.merged_buffers(names))
         self._weights_changed(opt)
+        if method == "fisher":
+            per = {n: {"floored": c[0], "unweighted": c[1]} for (n, _, _, _), c in zip(f.entries, self._fisher_counts.tolist())}
+            stats.update(fisher_floor=rule["fisher_floor"], tensors=per,
+                         **{key: sum(t[key] for t in per.values()) for key in ("floored", "unweighted")})
+        if method in ("dare_linear", "dare_ties"):
+            stats.update(seed=rule["seed"], density=rule["density"], rescale=rule["rescale"])
         if method == "ties":
-            counts = self._seg_counts.tolist()
+            stats.update(density=float(density), trim=trim, scope=scope)
+        if method in ("ties", "dare_ties"):
             per = {n: {"surviving": c[0], "conflicts": c[1], "cancelled": c[2] - (k - c[0])}
-                   for (n, _, k, _), c in zip(f.entries, counts)}
-            stats.update(density=float(density), trim=trim, scope=scope, tensors=per,
-                         **{key: sum(t[key] for t in per.values()) for key in ("surviving", "conflicts", "cancelled")})
+                   for (n, _, k, _), c in zip(f.entries, self._seg_counts.tolist())}
+            stats.update(tensors=per, **{key: sum(t[key] for t in per.values()) for key in ("surviving", "conflicts", "cancelled")})
         self.last_merge = stats
         return stats
 
@@ -1408,6 +1552,8 @@ class TaskVectors:
         per_buffers = sum(b.numel() * b.element_size() for b in self.base_buffers.values())
         return {"languages": self.languages(), "rows_in_use": len(self._rows), "rows_allocated": rows,
                 "max_tasks": self.max_tasks, "has_base": self.base is not None,
+                "importance_languages": [lang for lang in self._rows if lang in self._important],
+                "bytes_importances": 0 if self.importances is None else 4 * self.importances.shape[0] * self.stride,
                 "bytes_vectors": 4 * rows * self.stride, "bytes_base": 4 * self.flat.numel if self.base is not None else 0,
                 "bytes_buffers": per_buffers * (len(self.buffers) + (self.base is not None)), "last_merge": self.last_merge}
 
@@ -1416,11 +1562,16 @@ class TaskVectors:
         cpu = lambda t: t.detach().to("cpu", copy=True)
         k, n = len(self._rows), self.flat.numel
         vectors = cpu(self.vectors[:k, :n]) if k else torch.zeros(0, n)
-        return {"entries": list(self.flat.entries), "max_tasks": self.max_tasks,
-                "base": cpu(self.base.flat) if self.base is not None else None,
-                "base_buffers": {key: cpu(t) for key, t in self.base_buffers.items()},
-                "task_languages": self.languages(), "vectors": vectors,
-                "buffers": {lang: {key: cpu(t) for key, t in b.items()} for lang, b in self.buffers.items()}}
+        sd = {"entries": list(self.flat.entries), "max_tasks": self.max_tasks,
+              "base": cpu(self.base.flat) if self.base is not None else None,
+              "base_buffers": {key: cpu(t) for key, t in self.base_buffers.items()},
+              "task_languages": self.languages(), "vectors": vectors,
+              "buffers": {lang: {key: cpu(t) for key, t in b.items()} for lang, b in self.buffers.items()}}
+        important = [lang for lang in self._rows if lang in self._important]
+        if important:                                            # only then: a state without importances keeps its key set
+            sd["importance_languages"] = important
+            sd["importances"] = cpu(self._rows_of(important, self.importances)[:, :n])
+        return sd
 
     def load_state_dict(self, sd: dict, source="state dict"):
         """Inverse of state_dict(); refuses a state saved for another set of trainable tensors.  The weights are not part of
@@ -1435,6 +1586,10 @@ class TaskVectors:
         if tuple(sd["vectors"].shape) != (len(names), self.flat.numel):
             raise ValueError(f"{source}: the saved task vectors are {tuple(sd['vectors'].shape)}, expected "
                              f"{(len(names), self.flat.numel)}")
+        important = list(sd.get("importance_languages", []))
+        if important and (not set(important) <= set(names) or "importances" not in sd or
+                          tuple(sd["importances"].shape) != (len(important), self.flat.numel)):
+            raise ValueError(f"{source}: the saved importances do not match the saved task vectors")
         flush_pending_updates()
         dev = self.flat.theta.device
         if sd["base"] is None:
@@ -1452,6 +1607,13 @@ class TaskVectors:
         elif self.vectors is not None:
             self.vectors.zero_()
         self.buffers = {lang: {key: t.to(dev, copy=True) for key, t in b.items()} for lang, b in sd["buffers"].items()}
+        self._forget_importances()
+        if important:
+            if self.importances is None or self.importances.shape != self.vectors.shape:
+                self.importances = self._grown_like_vectors(None)
+            for r, lang in enumerate(important):
+                self.importances[self._rows[lang], :self.flat.numel].copy_(sd["importances"][r])
+            self._important = set(important)
 
 
 def lwf_kd_loss(loss, prob, prob_, pred_store_list, store_list, knowledge_distillation: float, kd_ctx: float):
