@@ -1099,6 +1099,60 @@ int ia_pack_prune(float* theta, float* exp_avg, float* exp_avg_sq, uint8_t* owne
                   void* workspace, size_t workspace_bytes, ia_stream_t stream);
 int ia_pack_apply(float* theta, const float* base, const uint8_t* owner, const int32_t* chunk_table, int nchunks,
                   const int32_t* seg_kind, int nseg, int lo, int hi, void* shadow_bf16, ia_stream_t stream);
+/* LoRA (Hu et al. 2021; csrc/lora.hip): one fixed backbone `base` and, per language, a pair of thin factors per adapted tensor.
+ * Adapted tensor t is viewed as W[m, n], m = shape[0], n = numel / m, and theta holds base + s * B * A with B [m, r] and A [r, n],
+ * s = alpha / r.  Forward and backward are untouched: the backward leaves the full dW in grad and the step turns it into factor
+ * gradients.  The factor buffer is flat fp32 with, per adapted tensor, B then A, row-major, each on a 64-float boundary, +0 in the
+ * gaps; factor_grad and the factor moments share its layout.  It has a chunk table of its own in the convention of the flat
+ * buffers, one tensor ("factor") per B and per A: int32 [nfchunks][4] = {offset, count <= 4096, factor = 2 t or 2 t + 1, t}.
+ *   tensors     int64 [ntensors][8] on the device = {flat offset of the parent, m, n, offset of B, offset of A, workspace offset
+ *               of gB's partials, workspace offset of gA's partials, index of the parent in the flat layout}, offsets in floats.
+ *               A tensor's partials take ia_lora_workspace_bytes(m, n, rank) bytes: gB's [column tiles][m][r], then gA's
+ *               [row tiles][r][n]; the caller lays the tensors out back to back and owns the workspace.
+ *   tiles       int32 [ntiles][4] on the device = {t, row tile, column tile, 0}: every ia_lora_tile_rows() x ia_lora_tile_cols()
+ *               tile of every adapted tensor, once.
+ *   seg_tensor  int32 [nseg] on the device: the row of `tensors` of an adapted tensor of the flat layout, -1 for every other one.
+ * ia_lora_grad   G = grad * grad_scale [* norm_state[1] when norm_state is given], each product rounded to fp32;
+ *                factor_grad receives gB = s * (G * A^T) and gA = s * (B^T * G) from the factors as they are, fp32 accumulation.
+ *                Two launches: one workgroup per tile reads its part of G from HBM once and leaves partial sums in the workspace
+ *                with plain stores, and a finishing pass over the factor buffer adds them in ascending tile order.  No
+ *                floating-point atomic and no order that depends on scheduling: the same inputs give the same bits.
+ *                factor_active: int32 [2 * ntensors], zero on entry as the AdamW step leaves its flags; both factors of a tensor
+ *                are flagged when its gradient has a non-zero element (-0.0 counts as zero) or all_active is set: liveness is the
+ *                parent's, so A steps at the first step, where B = 0 makes gA all zeros.  With skip_nonfinite and a flagged
+ *                norm_state nothing is written, the flags included.  workspace_needed: the sum over the tensors of
+ *                ia_lora_workspace_bytes, which is what the offsets in `tensors` address; IA_WORKSPACE_TOO_SMALL when
+ *                workspace_bytes is below it.  4 B read per adapted element, about r * (1 / rows + 1 / cols) * 8 B of partials.
+ * ia_lora_apply  theta = base + s * (B * A) on adapted tensors: acc = fma(B[i, j], A[j, c], acc) over j = 0..r-1 in ascending
+ *                order, then fma(s, acc, base); shadow = bf16(theta) for every tensor when a shadow is given.  One launch, 4 B
+ *                read and 6 B written per adapted element.  With skip_nonfinite and a flagged norm_state (may be NULL) nothing
+ *                is written.
+ * The factors themselves are trained by ia_adamw_step_segmented_kinds on the factor buffer's table with flags_preset.
+ * ia_adamw_step_segmented_kinds  ia_adamw_step_segmented_grouped's plain step with two things left to the caller.  seg_kind (may
+ *                be NULL: every tensor takes part): IA_MASK_FREE tensors take the plain step bit for bit; every other tensor is
+ *                treated as IA_MASK_FROZEN (only its shadow is refreshed, its step counter stays, and the liveness pass does not
+                read its gradient, so its flag stays clear).  flags_preset: seg_active is
+ *                read as the caller set it and no liveness pass runs (not combinable with all_active).
+ * IA_INVALID_VALUE before any device work: a NULL required pointer, counts <= 0, rank outside 1..IA_LORA_MAX_RANK, misaligned
+ * buffers (16 bytes for the flat buffers, the factor buffers, the tables of int32 and the workspace, 8 for `tensors` and the
+ * shadow, 4 for seg_tensor, factor_active and norm_state).  ia_lora_workspace_bytes returns 0 for such arguments. */
+#define IA_LORA_MAX_RANK 64
+int ia_lora_tile_rows(void);
+int ia_lora_tile_cols(void);
+size_t ia_lora_workspace_bytes(int64_t m, int64_t n, int rank);
+int ia_lora_grad(const float* grad, const float* factors, float* factor_grad, const int64_t* tensors, int ntensors,
+                 const int32_t* tiles, int ntiles, const int32_t* factor_chunk_table, int nfchunks, int rank, float scale,
+                 float grad_scale, const float* norm_state, int skip_nonfinite, int all_active, int32_t* factor_active,
+                 void* workspace, size_t workspace_bytes, size_t workspace_needed, ia_stream_t stream);
+int ia_lora_apply(float* theta, const float* base, const float* factors, const int64_t* tensors, int ntensors,
+                  const int32_t* seg_tensor, const int32_t* chunk_table, int nchunks, int nseg, int rank, float scale,
+                  void* shadow_bf16, const float* norm_state, int skip_nonfinite, ia_stream_t stream);
+int ia_adamw_step_segmented_kinds(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq, const int32_t* chunk_table,
+                                  int nchunks, int32_t* seg_active, int32_t* seg_step, int nseg, int all_active, float beta1,
+                                  float beta2, float eps, float grad_scale, void* shadow_bf16, const int32_t* seg_group,
+                                  int ngroups, const float* group_lr, const float* group_weight_decay, const float* norm_state,
+                                  int skip_nonfinite, int32_t* counters, const int32_t* seg_kind, int flags_preset,
+                                  ia_stream_t stream);
 /* Model merging (csrc/merge.hip): one copy of the model is fine-tuned per language from the same `base`, and the weight deltas
  * ("task vectors", tau_k = theta_k - base) are combined afterwards.  vectors: fp32 [max_tasks, stride] on the device, row k the
  * task vector of task k laid out as theta (GEM's convention for `refs`: stride a multiple of 4 and at least the flat length, +0 in

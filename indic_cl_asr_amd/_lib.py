@@ -248,6 +248,13 @@ SIGNATURES = {
     "ia_pack_prune_workspace_bytes": (_sz, [_i]),
     "ia_pack_prune": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _f, _i, _vp, _vp, _vp, _sz, _vp]),
     "ia_pack_apply": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp]),
+    "ia_lora_tile_rows": (_i, []),
+    "ia_lora_tile_cols": (_i, []),
+    "ia_lora_workspace_bytes": (_sz, [_i64, _i64, _i]),
+    "ia_lora_grad": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _f, _f, _vp, _i, _i, _vp, _vp, _sz, _sz, _vp]),
+    "ia_lora_apply": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _i, _vp]),
+    "ia_adamw_step_segmented_kinds": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _f, _vp, _vp, _i, _vp, _vp,
+                                           _vp, _i, _vp, _vp, _i, _vp]),
     "ia_merge_linear": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _f, _vp, _i, _vp, _vp]),
     "ia_merge_trim_workspace_bytes": (_sz, [_i, _i]),
     "ia_merge_trim": (_i, [_vp, _i64, _i, _vp, _i, _vp, _i, _f, _vp, _vp, _sz, _vp]),

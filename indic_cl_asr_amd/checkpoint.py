@@ -191,12 +191,15 @@ def load_memory(memory, path):
 def save_masks(masks, path):
     """Persist cl.Piggyback.state_dict() (kinds, base, scores and every saved language's bits, free tensors and buffers) or
     cl.PackNet.state_dict() (kinds, base, the owner map, the open language and its phase, every finished language's free tensors
-    and buffers) or cl.TaskVectors.state_dict() (the base, the task vectors in language order and every language's buffers)."""
+    and buffers) or cl.LoRA.state_dict() (kinds, rank, alpha, seed, base, the live factors with their moments and step counters,
+    every saved language's factors, free tensors and buffers) or cl.TaskVectors.state_dict() (the base, the task vectors in
+    language order and every language's buffers)."""
     torch.save(masks.state_dict(), path)
 
 
 def load_masks(masks, path):
-    """Inverse of save_masks, in place; refuses a file whose tensor table differs from the model's.  The weights follow with
-    masks.activate(lang) or masks.begin_language(lang); for cl.TaskVectors with restore_base() or merge(...)."""
+    """Inverse of save_masks, in place; refuses a file whose tensor table differs from the model's (cl.LoRA also one saved with
+    another rank or other kinds: the factor layout follows from them).  The weights follow with masks.activate(lang) or
+    masks.begin_language(lang); for cl.TaskVectors with restore_base() or merge(...)."""
     masks.load_state_dict(torch.load(path, map_location="cpu"), source=path)
     return masks

@@ -1110,8 +1110,337 @@ class PackNet:
                         for lang, r in sd["languages"].items()}
 
 
+# ----------------------------------------------------------------------------- LoRA
+_LORA_KIND_NAMES = ("free", "adapted", "frozen")      # the numbering of _KIND_NAMES, `adapted` in the masked slot
+LORA_MAX_RANK = 64         # IA_LORA_MAX_RANK of include/indicasr.h
+
+
+class LoRA:
+    """LoRA (Hu et al. 2021): low-rank adaptation, one pair of thin factors per adapted matrix and language.  One fixed backbone
+    `base` is kept; adapted tensor W, viewed as [m, n] with m = shape[0] and n = numel / m (the view the bf16 shadow has), reads
+    `base + s * B @ A` with B [m, r], A [r, n] and s = alpha / r.  A language costs r * (m + n) numbers per matrix instead of
+    m * n, forgetting is exactly zero, and inference costs nothing: the factors are folded into `flat.theta` and its bf16 image.
+
+    The route is Piggyback's and PackNet's: forward and backward are left alone, the existing backward produces the full dW, and
+    the optimizer step turns it into factor gradients (ia_lora_grad), trains the factors with the shared AdamW rule and rewrites
+    the weights and the shadow (ia_lora_apply).  So LoRA's storage, zero-forgetting and zero-inference-cost properties are kept;
+    its training-FLOP saving is NOT: dW is still computed in full.
+
+    Every trainable tensor has a kind, fixed here (the vocabulary and numbering of Piggyback's `seg_kind`):
+      adapted  theta = base + s * B @ A; the optimizer trains B and A.  Default: tensors with dim() >= 2 that are not heads and
+               have min(m, n) >= 2 * rank.
+      free     plain AdamW, snapshotted per language.  Default: the per-language heads, as for Piggyback.
+      frozen   never written.  Default: everything else -- biases and norm parameters, and every dim() >= 2 tensor that is not a
+               head and is too small for the rank (the depthwise kernels [d, 1, k]).
+    `adapted=` / `frozen=` replace the default sets as `masked=` / `frozen=` do for Piggyback; an explicitly adapted tensor with
+    min(m, n) < rank raises ValueError.
+
+        lora = LoRA(model_or_flat, rank=8, alpha=16.0)
+        opt  = FusedAdamW(flat, ..., masks=lora)
+        lora.begin_language("hi", opt)      # B = 0, A ~ U(-1/sqrt(n), 1/sqrt(n)) (peft's kaiming_uniform_(a=sqrt(5))); theta = base
+        ...train...
+        lora.save_language()                # factors, free tensors and module buffers
+        lora.activate("hi")                 # theta = base + s * B @ A of "hi", heads and buffers restored
+
+    A is drawn on the CPU from a generator seeded by (seed, crc32(lang), tensor index): every rank draws the same values.
+
+    Limits: one language is active at a time, as with Piggyback.  There is no `lora_dropout`: the factors are folded into the
+    weights before the forward, so there is no separate low-rank branch whose input could be dropped.  Adapted tensors must be in
+    the flat layout, which holds trainable tensors only (requires_grad=True on the backbone matrices that are adapted).  The
+    optimizer's full-size moments of adapted tensors stay allocated and unused."""
+
+    def __init__(self, model_or_flat, rank=8, alpha=16.0, adapted=None, frozen=None, seed=0):
+        self.flat = _as_flat(model_or_flat)
+        f = self.flat
+        if int(rank) != rank or not 1 <= int(rank) <= LORA_MAX_RANK:
+            raise ValueError(f"LoRA: rank {rank} is outside 1..{LORA_MAX_RANK}")
+        self.rank, self.alpha, self.seed = int(rank), float(alpha), int(seed)
+        self.scale = ctypes.c_float(self.alpha / self.rank).value       # s as the kernels take it
+        kinds = _select_kinds(f, adapted, frozen, "LoRA", "adapted")
+        for k, (n, o, numel, shape) in enumerate(f.entries):
+            if kinds[k] != MASK_MASKED:
+                continue
+            small = min(shape[0], numel // shape[0])
+            if adapted is None:
+                if small < 2 * self.rank:
+                    kinds[k] = MASK_FROZEN
+            elif small < self.rank:
+                raise ValueError(f"LoRA: '{n}' viewed as [{shape[0]}, {numel // shape[0]}] is too small for rank {self.rank}")
+        self._kinds = kinds
+        if MASK_MASKED not in kinds:
+            raise ValueError(f"LoRA: no trainable tensor is adapted at rank {self.rank}")
+        dev = f.theta.device
+        self.seg_kind = torch.tensor(kinds, dtype=torch.int32, device=dev)
+        # what the plain step sees: an adapted tensor is not its to write
+        self.step_kind = torch.tensor([MASK_FREE if k == MASK_FREE else MASK_FROZEN for k in kinds], dtype=torch.int32, device=dev)
+        self._build_layout()
+        flush_pending_updates()
+        self.base = FlatDict(f, f.theta.clone())
+        nf = self.factor_numel
+        self.factors = torch.zeros(nf, dtype=torch.float32, device=dev)
+        self.factor_grad = torch.zeros(nf, dtype=torch.float32, device=dev)
+        self.factor_exp_avg = torch.zeros(nf, dtype=torch.float32, device=dev)
+        self.factor_exp_avg_sq = torch.zeros(nf, dtype=torch.float32, device=dev)
+        self.factor_step = torch.zeros(2 * len(self.adapted), dtype=torch.int32, device=dev)
+        self.factor_active = torch.zeros(2 * len(self.adapted), dtype=torch.int32, device=dev)
+        self.current: Optional[str] = None
+        self.records: Dict[str, dict] = {}    # lang -> {"factors": fp32 [factor_numel], "free": {name: tensor}, "buffers": {...}}
+        self._factors_lang: Optional[str] = None   # the language the live factors describe (None: nobody's yet)
+        self._stale = False                    # True while theta shows a language the live factors do not describe
+        self._optimizer = None                 # weak reference to the FusedAdamW that holds the bf16 shadow
+        self._workspace = None
+        self._factor_group = None              # (optimizer id, int32 [2 * adapted]): the parameter group of every factor's parent
+
+    def _build_layout(self):
+        """The factor buffer (per adapted tensor B [m, r] then A [r, n], each on a 64-float boundary), its chunk table, the tile
+        list of ia_lora_grad and where every tensor's partial sums lie in the workspace."""
+        f, r, L = self.flat, self.rank, _lib.lib()
+        rows_per, cols_per = L.ia_lora_tile_rows(), L.ia_lora_tile_cols()
+        up = lambda x: (x + _ALIGN - 1) // _ALIGN * _ALIGN
+        self.adapted = []                      # (name, index in the flat layout, m, n, offset of B, offset of A)
+        desc, tiles, chunks, seg_tensor = [], [], [], [-1] * len(f.entries)
+        off = ws = 0
+        for k, (name, o, numel, shape) in enumerate(f.entries):
+            if self._kinds[k] != MASK_MASKED:
+                continue
+            t, m = len(self.adapted), shape[0]
+            n = numel // m
+            b_off, a_off = off, off + up(m * r)
+            off = a_off + up(r * n)
+            nrt, nct = (m + rows_per - 1) // rows_per, (n + cols_per - 1) // cols_per
+            nbytes = L.ia_lora_workspace_bytes(m, n, r)
+            if nbytes < 4 * r * (nct * m + nrt * n) or nbytes % 4:
+                raise RuntimeError(f"ia_lora_workspace_bytes({m}, {n}, {r}) returned {nbytes}")
+            desc.append((o, m, n, b_off, a_off, ws, ws + nct * m * r, k))
+            ws += nbytes // 4
+            tiles += [(t, rt, ct, 0) for rt in range(nrt) for ct in range(nct)]
+            for which, (start, cnt) in enumerate(((b_off, m * r), (a_off, r * n))):
+                chunks += [(start + c0, min(4096, cnt - c0), 2 * t + which, t) for c0 in range(0, cnt, 4096)]
+            seg_tensor[k] = t
+            self.adapted.append((name, k, m, n, b_off, a_off))
+        dev = f.theta.device
+        self.factor_numel, self.workspace_bytes = off, 4 * ws
+        self.tensor_table = torch.tensor(desc, dtype=torch.int64, device=dev)
+        self.tile_table = torch.tensor(tiles, dtype=torch.int32, device=dev)
+        self.factor_table = torch.tensor(chunks, dtype=torch.int32, device=dev)
+        self.seg_tensor = torch.tensor(seg_tensor, dtype=torch.int32, device=dev)
+
+    # -- kinds -----------------------------------------------------------------------------------------------------
+    def kinds(self) -> Dict[str, str]:
+        return {n: _LORA_KIND_NAMES[k] for n, k in zip(self.flat.names, self._kinds)}
+
+    def _names_of(self, kind):
+        return [n for n, k in zip(self.flat.names, self._kinds) if k == kind]
+
+    def languages(self) -> List[str]:
+        return list(self.records)
+
+    def _shadow(self):
+        opt = self._optimizer() if self._optimizer is not None else None
+        return opt, (opt.shadow if opt is not None else None)
+
+    def factor_views(self, factors: Optional[torch.Tensor] = None) -> Dict[str, dict]:
+        """name -> {"lora_A": view [r, n], "lora_B": view [m, r]} into a factor buffer (default: the live one)."""
+        fb = self.factors if factors is None else factors
+        return {name: {"lora_A": fb[a:a + self.rank * n].view(self.rank, n), "lora_B": fb[b:b + m * self.rank].view(m, self.rank)}
+                for name, k, m, n, b, a in self.adapted}
+
+    # -- factors -> weights ------------------------------------------------------------------------------------------
+    def _materialise(self, factors, theta=None, base=None, shadow=None, norm_state=None, skip=False):
+        f = self.flat
+        st = _lib.lib().ia_lora_apply(_lib.ptr(f.theta if theta is None else theta), _lib.ptr(self.base.flat if base is None else base),
+                                      _lib.ptr(factors), _lib.ptr(self.tensor_table), len(self.adapted), _lib.ptr(self.seg_tensor),
+                                      _lib.ptr(f.chunk_table), f.chunk_table.shape[0], len(f.entries), self.rank, self.scale,
+                                      _lib.ptr(shadow), _lib.ptr(norm_state), int(skip), _lib.stream_ptr())
+        _lib.check(st, "ia_lora_apply")
+
+    def _apply_factors(self, factors):
+        """theta = base + s * B @ A on adapted tensors and the bf16 image of every tensor, one launch; then what
+        FusedAdamW._after_update does: the weight epoch moves and the flat shadow views are handed to the shadow cache."""
+        opt, shadow = self._shadow()
+        self._materialise(factors, shadow=shadow)
+        if opt is not None:
+            opt._after_update()
+        else:
+            from .ops import fast
+            fast.bump_weight_epoch()
+
+    def _seed_of(self, lang: str, index: int) -> int:
+        import zlib
+        x = self.seed & 0x7FFFFFFFFFFFFFFF
+        for v in (zlib.crc32(lang.encode("utf-8")), index):
+            x = (x * 6364136223846793005 + v + 1442695040888963407) & 0x7FFFFFFFFFFFFFFF
+        return x
+
+    # -- the per-language loop ---------------------------------------------------------------------------------------
+    def save_language(self, lang: Optional[str] = None):
+        """Record `lang` (default: the current language): its factors, the free tensors and every module buffer."""
+        lang = self.current if lang is None else lang
+        if lang is None:
+            raise ValueError("LoRA.save_language: no language is current; name one")
+        if self._stale:
+            raise RuntimeError(f"LoRA.save_language: the weights show '{self.current}' as activate() restored it, but the "
+                               "live factors belong to another language; call begin_language() before training and saving")
+        flush_pending_updates()
+        f = self.flat
+        self.records[lang] = {
+            "factors": self.factors.detach().clone(),
+            "free": {n: f._theta_views[n].detach().clone() for n in self._names_of(MASK_FREE)},
+            "buffers": {n: b.detach().clone() for n, b in f.model.named_buffers()}}
+        self.current = self._factors_lang = lang
+
+    def begin_language(self, lang: str, optimizer: Optional["FusedAdamW"] = None):
+        """Start training `lang`: B = 0 and A ~ U(-1/sqrt(n), 1/sqrt(n)), so theta equals base on the adapted tensors; the factor
+        moments and step counters are zeroed; the free tensors and buffers continue from where they are.  With an optimizer, its
+        moments and step counters of every tensor that is not frozen are zeroed too, as Piggyback does."""
+        flush_pending_updates()
+        if optimizer is not None and optimizer.flat is not self.flat:
+            raise ValueError("optimizer belongs to another FlatParams")
+        with torch.no_grad():
+            self.factors.zero_()
+            views = self.factor_views()
+            for name, k, m, n, b, a in self.adapted:
+                gen = torch.Generator().manual_seed(self._seed_of(lang, k))
+                bound = 1.0 / math.sqrt(n)
+                views[name]["lora_A"].copy_(torch.empty(self.rank, n, dtype=torch.float32).uniform_(-bound, bound, generator=gen))
+            self.factor_exp_avg.zero_()
+            self.factor_exp_avg_sq.zero_()
+            self.factor_step.zero_()
+            self.factor_active.zero_()
+        if optimizer is not None:
+            for k, (n, o, cnt, shape) in enumerate(self.flat.entries):
+                if self._kinds[k] != MASK_FROZEN:
+                    optimizer.exp_avg[o:o + cnt].zero_()
+                    optimizer.exp_avg_sq[o:o + cnt].zero_()
+            optimizer.seg_step.mul_((self.seg_kind == MASK_FROZEN).to(torch.int32))
+        self._apply_factors(self.factors)
+        self.current, self._factors_lang, self._stale = lang, lang, False
+
+    def activate(self, lang: str):
+        """Show `lang` to the network: its free tensors and buffers come back, then one launch rewrites the adapted weights from
+        its factors and the whole bf16 image.  The live factors and their moments are left alone: after save_language(x),
+        activate(other), ..., activate(x) training x continues where it was; progress that save_language() has not recorded is
+        lost for the heads, as with Piggyback."""
+        if lang not in self.records:
+            raise ValueError(f"LoRA.activate: unknown language '{lang}' (saved: {', '.join(self.records) or 'none'})")
+        flush_pending_updates()
+        rec, f = self.records[lang], self.flat
+        with torch.no_grad():
+            for n, t in rec["free"].items():
+                f._theta_views[n].copy_(t)
+            buffers = dict(f.model.named_buffers())
+            for n, t in rec["buffers"].items():
+                buffers[n].copy_(t)
+        self._apply_factors(rec["factors"])
+        self.current, self._stale = lang, lang != self._factors_lang
+
+    # -- the step (FusedAdamW._apply) ----------------------------------------------------------------------------------
+    def _groups_of_factors(self, opt) -> torch.Tensor:
+        if self._factor_group is None or self._factor_group[0] != id(opt):
+            parents = torch.tensor([k for _, k, *_ in self.adapted], dtype=torch.int64, device=opt.seg_group.device)
+            self._factor_group = (id(opt), opt.seg_group[parents].repeat_interleave(2).contiguous())
+        return self._factor_group[1]
+
+    def _step(self, opt, common, measured, skip, all_live, stream):
+        """ia_lora_grad (factor gradients from the task gradient, clipped as the free tensors' is), the plain step on the free
+        tensors, the shared AdamW rule on the factor buffer, ia_lora_apply.  `common` is what every segmented step takes."""
+        L, ptr, f = _lib.lib(), _lib.ptr, self.flat
+        norm_state = ptr(opt._norm_state) if measured else None
+        if self._workspace is None:
+            self._workspace = torch.empty(self.workspace_bytes, dtype=torch.uint8, device=f.theta.device)
+        nt, scale = len(self.adapted), common[13]
+        _lib.check(L.ia_lora_grad(ptr(f.grad), ptr(self.factors), ptr(self.factor_grad), ptr(self.tensor_table), nt,
+                                  ptr(self.tile_table), self.tile_table.shape[0], ptr(self.factor_table), self.factor_table.shape[0],
+                                  self.rank, self.scale, scale, norm_state, int(skip), int(all_live), ptr(self.factor_active),
+                                  ptr(self._workspace), self._workspace.numel(), self.workspace_bytes, stream), "ia_lora_grad")
+        # free tensors: the plain step; the shadow is left to ia_lora_apply, which writes every tensor's
+        _lib.check(L.ia_adamw_step_segmented_kinds(*common[:14], None, *common[15:], ptr(self.step_kind), 0, stream),
+                   "ia_adamw_step_segmented_kinds")
+        # the factors: liveness is the parent's (set by ia_lora_grad), lr / weight_decay its group's, G already carries scale and coef
+        _lib.check(L.ia_adamw_step_segmented_kinds(
+            ptr(self.factors), ptr(self.factor_grad), ptr(self.factor_exp_avg), ptr(self.factor_exp_avg_sq), ptr(self.factor_table),
+            self.factor_table.shape[0], ptr(self.factor_active), ptr(self.factor_step), 2 * nt, 0, *common[10:13], 1.0, None,
+            ptr(self._groups_of_factors(opt)), *common[16:19], None, 0, None, None, 1, stream), "ia_adamw_step_segmented_kinds")
+        self._materialise(self.factors, shadow=opt.shadow, norm_state=opt._norm_state if measured else None, skip=skip)
+
+    # -- reports ---------------------------------------------------------------------------------------------------
+    def delta(self, lang: Optional[str] = None) -> FlatDict:
+        """s * B @ A of `lang` (default: the live factors) as a FlatDict: +0 outside the adapted tensors.  The arithmetic is
+        ia_lora_apply's on a base of zeros."""
+        if lang is not None and lang not in self.records:
+            raise ValueError(f"LoRA.delta: unknown language '{lang}' (saved: {', '.join(self.records) or 'none'})")
+        flush_pending_updates()
+        out = self.flat.zeros()
+        self._materialise(self.factors if lang is None else self.records[lang]["factors"], theta=out.flat,
+                          base=torch.zeros_like(out.flat))
+        return out
+
+    def export(self, lang: Optional[str] = None) -> dict:
+        """A plain dict for interchange: {name: {"lora_A": A [r, n], "lora_B": B [m, r]}, ..., "r": rank, "alpha": alpha} with
+        copies of the factors of `lang` (default: the live ones).  W = base + (alpha / r) * lora_B @ lora_A viewed as [m, n]."""
+        if lang is not None and lang not in self.records:
+            raise ValueError(f"LoRA.export: unknown language '{lang}' (saved: {', '.join(self.records) or 'none'})")
+        flush_pending_updates()
+        views = self.factor_views(None if lang is None else self.records[lang]["factors"])
+        out = {name: {key: t.detach().clone() for key, t in fac.items()} for name, fac in views.items()}
+        out["r"], out["alpha"] = self.rank, self.alpha
+        return out
+
+    def bytes_per_language(self) -> dict:
+        """Bytes one saved language holds: the factors (r * (m + n) floats per adapted tensor; the record keeps them in the padded
+        factor buffer, `factors_padded`), the free tensors and the module buffers."""
+        f = self.flat
+        factors = sum(4 * self.rank * (m + n) for _, _, m, n, _, _ in self.adapted)
+        free = sum(e[2] * 4 for k, e in enumerate(f.entries) if self._kinds[k] == MASK_FREE)
+        buffers = sum(b.numel() * b.element_size() for b in f.model.buffers())
+        return {"factors": factors, "factors_padded": 4 * self.factor_numel, "free": free, "buffers": buffers,
+                "total": 4 * self.factor_numel + free + buffers}
+
+    # -- resumable state -------------------------------------------------------------------------------------------
+    def state_dict(self) -> dict:
+        flush_pending_updates()
+        cpu = lambda t: t.detach().to("cpu", copy=True)
+        return {"entries": list(self.flat.entries), "kinds": [_LORA_KIND_NAMES[k] for k in self._kinds], "rank": self.rank,
+                "alpha": self.alpha, "seed": self.seed, "base": cpu(self.base.flat), "factors": cpu(self.factors),
+                "factor_exp_avg": cpu(self.factor_exp_avg), "factor_exp_avg_sq": cpu(self.factor_exp_avg_sq),
+                "factor_step": cpu(self.factor_step), "current": self.current, "factors_language": self._factors_lang,
+                "languages": {lang: {"factors": cpu(r["factors"]), "free": {n: cpu(t) for n, t in r["free"].items()},
+                                     "buffers": {n: cpu(t) for n, t in r["buffers"].items()}}
+                              for lang, r in self.records.items()}}
+
+    def load_state_dict(self, sd: dict, source="state dict"):
+        """In place: base, the factors, their moments and the tables keep their addresses (an attached optimizer keeps pointing at
+        them).  The factor layout follows from the kinds and the rank, so a state saved with other kinds or another rank is
+        refused.  The weights are not part of this state: `activate(lang)` or `begin_language(lang)` puts them in step with it."""
+        if [tuple(e[:3]) + (tuple(e[3]),) for e in sd["entries"]] != list(self.flat.entries):
+            raise ValueError(f"{source}: 'masks' was saved for a different set of trainable tensors")
+        if "factors" not in sd:
+            raise ValueError(f"{source}: 'masks' does not hold LoRA factors")
+        kinds = [_LORA_KIND_NAMES.index(k) for k in sd["kinds"]]
+        if kinds != self._kinds or int(sd["rank"]) != self.rank or sd["factors"].numel() != self.factor_numel:
+            raise ValueError(f"{source}: 'masks' was saved for another factor layout (rank {sd['rank']}, "
+                             f"{sum(k == MASK_MASKED for k in kinds)} adapted tensors; here rank {self.rank}, {len(self.adapted)})")
+        for lang, r in sd["languages"].items():
+            if r["factors"].numel() != self.factor_numel:
+                raise ValueError(f"{source}: the factors of '{lang}' do not fit this factor layout")
+        flush_pending_updates()
+        dev = self.flat.theta.device
+        self.base.flat.copy_(sd["base"])
+        self.factors.copy_(sd["factors"])
+        self.factor_exp_avg.copy_(sd["factor_exp_avg"])
+        self.factor_exp_avg_sq.copy_(sd["factor_exp_avg_sq"])
+        self.factor_step.copy_(sd["factor_step"])
+        self.alpha, self.seed = float(sd["alpha"]), int(sd["seed"])
+        self.scale = ctypes.c_float(self.alpha / self.rank).value
+        self.current, self._factors_lang = sd["current"], sd["factors_language"]
+        self._stale = False                    # the weights are the caller's to restore
+        self.records = {lang: {"factors": r["factors"].to(dev), "free": {n: t.to(dev) for n, t in r["free"].items()},
+                               "buffers": {n: t.to(dev) for n, t in r["buffers"].items()}}
+                        for lang, r in sd["languages"].items()}
+
+
 # ----------------------------------------------------------------------------- LwF
-MERGE_MAX_TASKS = 32       # IA_MERGE_MAX_TASKS of include/indicasr.h
+MERGE_MAX_TASKS = 32      # IA_MERGE_MAX_TASKS of include/indicasr.h
 MERGE_METHODS = ("task_arithmetic", "average", "ties", "fisher", "dare_linear", "dare_ties")
 MERGE_WEIGHTED = ("task_arithmetic", "fisher", "dare_linear")      # the methods that take `weights`
 MERGE_SCOPES = ("tensor", "model")
@@ -1809,7 +2138,16 @@ class FusedAdamW(torch.optim.Optimizer):
         `masks=pn` (a `PackNet`): the step is ia_adamw_step_segmented_packed, after ia_grad_norm_packed when the norm is measured
         -- the norm of the gradient the step consumes: the trainable elements of packed tensors and the free tensors.  In a packed
         tensor the elements whose owner is `pn.train_owner` take the plain rule with the group's `lr` and `weight_decay`; every
-        other element keeps its weight and moments.  The same refusals and the same place outside the optimizer state."""
+        other element keeps its weight and moments.  The same refusals and the same place outside the optimizer state.
+
+        `masks=lora` (a `LoRA`): after ia_grad_norm when the norm is measured (the norm and coefficient are the task gradient's over
+        all tensors, as with Piggyback), the step is ia_lora_grad (the full dW of every adapted tensor becomes the gradients of
+        its factors, from the pre-step factors), ia_adamw_step_segmented_kinds on the flat buffers (free tensors take the plain
+        step bit for bit; frozen and adapted tensors' theta, full-size moments and step counters are not written),
+        ia_adamw_step_segmented_kinds on the factor buffer (the same update rule; a factor takes the `lr` and `weight_decay` of
+        its parent's group and is live when its parent received a gradient) and ia_lora_apply (theta = base + s * B @ A and the
+        bf16 image of every tensor).  The factors, their moments and step counters belong to the LoRA object.  The same refusals
+        and the same place outside the optimizer state."""
         self.flat = model_or_flat if isinstance(model_or_flat, FlatParams) else flat_of(model_or_flat)
         if masks is not None and (path_integral is not None or projection is not None):
             raise ValueError("masks cannot be combined with path_integral or projection: the masked weights do not move along "
@@ -2055,6 +2393,9 @@ class FusedAdamW(torch.optim.Optimizer):
         if isinstance(pb, PackNet):
             _lib.check(L.ia_adamw_step_segmented_packed(*common, ptr(pb.owner), ptr(pb.seg_kind), int(pb.train_owner), stream),
                        "ia_adamw_step_segmented_packed")
+            return self._after_update()
+        if isinstance(pb, LoRA):
+            pb._step(self, common, measured, skip, all_live, stream)
             return self._after_update()
         if pb is not None:
             _lib.check(L.ia_adamw_step_segmented_masked(*common, ptr(pb.base.flat), ptr(pb.scores.flat), ptr(pb.seg_kind),

@@ -26,6 +26,8 @@
 //                              theta = score >= threshold ? base : 0), free (the plain rule), frozen    ia_adamw_step_segmented_masked
 //       packed_step            PackNet, per tensor a kind: packed (the plain rule where owner == train_owner, nothing
 //                              elsewhere), free, frozen                                          ia_adamw_step_segmented_packed
+//       kinds_step             LoRA (csrc/lora.hip): free tensors take the plain rule, every other tensor is left alone; also
+//                              the plain rule on the factor buffer with the caller's liveness flags   ia_adamw_step_segmented_kinds
 //                              ia_adamw_step_segmented_grouped is the first four with lr and weight_decay per parameter group.
 //   consumed_norm_kernel<Source>   the clip norm of the gradient a consumed_step consumes, from the SAME gradient functor
 //                              (ia_grad_norm_projected, ia_grad_norm_gem, ia_grad_norm_packed); ia_grad_norm measures the raw gradient in the
@@ -187,10 +189,12 @@ __global__ __launch_bounds__(CL_THREADS) void adamw_kernel(float* __restrict__ p
 template <bool SUMSQ>
 __global__ __launch_bounds__(CL_THREADS) void seg_activity_kernel(const float* __restrict__ g, const int4* __restrict__ table,
                                                                   int nchunks, int* __restrict__ seg_active,
-                                                                  float* __restrict__ chunk_sumsq) {
+                                                                  float* __restrict__ chunk_sumsq,
+                                                                  const int* __restrict__ free_only_kind) {
     __shared__ float sh[CL_THREADS / 64];
     for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
         const int4 e = table[c];
+        if (!SUMSQ && free_only_kind && free_only_kind[e.z] != IA_MASK_FREE) continue;    // the step never looks at this flag
         const int off = e.x, cnt = e.y, n4 = cnt >> 2;
         unsigned nz = 0;
         float ss = 0.f;
@@ -919,6 +923,14 @@ struct packed_step {
     __device__ __forceinline__ owner_rule kind_rule() const { return {owner, train_owner}; }
 };
 
+// ---- Kinds alone (the LoRA step, csrc/lora.hip): free tensors take the plain rule and every other tensor is left to the caller.
+// seg_kind holds IA_MASK_FREE and IA_MASK_FROZEN only, so kind_rule() is never reached; it is the plain rule.
+struct kinds_step {
+    const int* seg_kind;
+    __device__ __forceinline__ kinds_step begin() const { return *this; }
+    __device__ __forceinline__ consumed_rule<scaled_grad> kind_rule() const { return {}; }
+};
+
 // A variant with per-tensor kinds has seg_kind and kind_rule(), the rule of its KIND_MASKED slot; its free tensors take the plain
 // rule and its frozen ones are never written.
 template <class Rule, class = void> struct has_kinds : std::false_type {};
@@ -1398,6 +1410,7 @@ struct step_extras {
     bool flags_preset;       // the variant's dots kernel has set seg_active from the task gradient: never an activity pass here
     const float* projected; int32_t* projected_count; const float* solved; int32_t* unsolved_count;
     const int32_t* seg_kind;  // the masked and packed steps: the SAME array as the variant's seg_kind, so that walker and advance agree
+    bool free_only;           // kinds_step: only free tensors are ever looked at, so the liveness pass skips the chunks of the others
 };
 
 // Every segmented step: liveness, the walker, the advance.  Arguments are validated by the callers.  Liveness: all_active marks
@@ -1409,7 +1422,7 @@ int run_step(const step_head& h, const group_table& gt, const Variant& variant, 
         if (hipMemsetAsync(h.seg_active, 1, (size_t)h.nseg * sizeof(int32_t), st) != hipSuccess) return IA_LAUNCH_FAILED;
     } else if (!h.norm_state && !x.flags_preset) {
         hipLaunchKernelGGL(seg_activity_kernel<false>, dim3(chunk_grid(h.nchunks)), dim3(CL_THREADS), 0, st, h.grad, h.table,
-                           h.nchunks, h.seg_active, (float*)nullptr);
+                           h.nchunks, h.seg_active, (float*)nullptr, x.free_only ? x.seg_kind : (const int32_t*)nullptr);
     }
     auto kernel = h.norm_state ? adamw_seg_kernel<true, Variant> : adamw_seg_kernel<false, Variant>;
     hipLaunchKernelGGL(kernel, dim3(chunk_grid(h.nchunks)), dim3(CL_THREADS), 0, st, h.theta, h.grad, h.exp_avg, h.exp_avg_sq,
@@ -1531,7 +1544,7 @@ extern "C" int ia_grad_norm(const float* grad, const int32_t* chunk_table, int n
     if (workspace_bytes < ia_grad_norm_workspace_bytes(nchunks)) return IA_WORKSPACE_TOO_SMALL;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(seg_activity_kernel<true>, dim3(chunk_grid(nchunks)), dim3(CL_THREADS), 0, st, grad,
-                       (const int4*)chunk_table, nchunks, seg_active, (float*)workspace);
+                       (const int4*)chunk_table, nchunks, seg_active, (float*)workspace, (const int32_t*)nullptr);
     hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(GN_THREADS), 0, st, (const float*)workspace, seg_chunk_begin, nseg,
                        fabsf(grad_scale), max_norm, seg_norm, norm_state, (const float*)nullptr);
     IA_RETURN_IF_LAUNCH_FAILED();
@@ -1724,6 +1737,28 @@ extern "C" int ia_adamw_step_segmented_masked(float* theta, const float* grad, f
                     (hipStream_t)stream);
 }
 
+// The plain grouped step with two things left to the caller: which tensors it may touch (seg_kind, NULL: all of them) and, with
+// flags_preset, the liveness flags themselves.  The walker, the update rule and the advance are those of every other step.
+extern "C" int ia_adamw_step_segmented_kinds(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq,
+                                             const int32_t* chunk_table, int nchunks, int32_t* seg_active, int32_t* seg_step,
+                                             int nseg, int all_active, float beta1, float beta2, float eps, float grad_scale,
+                                             void* shadow_bf16, const int32_t* seg_group, int ngroups, const float* group_lr,
+                                             const float* group_weight_decay, const float* norm_state, int skip_nonfinite,
+                                             int32_t* counters, const int32_t* seg_kind, int flags_preset, ia_stream_t stream) {
+    const step_head h = make_head(theta, grad, exp_avg, exp_avg_sq, chunk_table, nchunks, seg_active, seg_step, nseg, all_active,
+                                  beta1, beta2, eps, grad_scale, shadow_bf16, seg_group, norm_state, skip_nonfinite, counters);
+    if (!head_ok(h) || !groups_ok(seg_group, ngroups, group_lr, group_weight_decay) || (seg_kind && !ia_is_aligned(seg_kind, 4)) ||
+        (flags_preset && all_active))
+        return IA_INVALID_VALUE;
+    step_extras x = {};
+    x.flags_preset = flags_preset != 0;
+    x.seg_kind = seg_kind;
+    x.free_only = seg_kind != nullptr;
+    const group_table gt = make_group_table(ngroups, group_lr, group_weight_decay);
+    return seg_kind ? run_step(h, gt, kinds_step{seg_kind}, x, (hipStream_t)stream)
+                    : run_step(h, gt, plain_step{}, x, (hipStream_t)stream);
+}
+
 extern "C" int ia_mask_pack(const float* scores, const int32_t* chunk_table, int nchunks, const int32_t* seg_kind, int nseg,
                             float threshold, uint64_t* bits, int64_t nwords, int32_t* seg_kept, ia_stream_t stream) {
     if (!scores || !chunk_table || !seg_kind || !bits || nchunks <= 0 || nseg <= 0 || nwords <= 0) return IA_INVALID_VALUE;
@@ -1762,7 +1797,7 @@ extern "C" int ia_grad_norm_packed(const float* grad, const int32_t* chunk_table
     hipStream_t st = (hipStream_t)stream;
     if (seg_active)      // liveness is the raw gradient's, as in ia_grad_norm's first pass
         hipLaunchKernelGGL(seg_activity_kernel<false>, dim3(chunk_grid(nchunks)), dim3(CL_THREADS), 0, st, grad,
-                           (const int4*)chunk_table, nchunks, seg_active, (float*)nullptr);
+                           (const int4*)chunk_table, nchunks, seg_active, (float*)nullptr, (const int32_t*)nullptr);
     return run_consumed_norm(grad, chunk_table, nchunks, seg_chunk_begin, nseg, grad_scale, max_norm, seg_active, seg_norm,
                              norm_state, workspace, packed_source{owner, seg_kind, train_owner}, (const float*)nullptr, st);
 }

@@ -5,7 +5,9 @@ with layerwise_lr_groups + no-decay parameter groups (ia_adamw_step_segmented_gr
 kinds without clipping (ia_adamw_step_segmented_masked: matrices masked, heads free, the rest frozen), and `packed`: PackNet on the
 same kinds (ia_adamw_step_segmented_packed with every packed weight free and trained; `prune_us`: one ia_pack_prune at fraction
 0.5, each call from a zeroed owner map and the same weights, between its own two events; `packed_retrain_us`: the step after the
-pruning, when half of the packed weights move).  Per leg: `<leg>_us` device time of one
+pruning, when half of the packed weights move), and `lora`: LoRA on its default kinds at rank 16 without clipping (ia_lora_grad, the
+plain step on the free tensors, the AdamW rule on the factor buffer, ia_lora_apply; B is given seeded values so that both factor
+gradients are real work).  Per leg: `<leg>_us` device time of one
 _apply between two events, `<leg>_host_us` host wall-clock of one step() call with no synchronisation inside the timed loop
 (what the training loop's thread pays: Python, ctypes and the launches).  Developer tool; one JSON line.
 
@@ -50,7 +52,7 @@ def host_timeit(fn, warmup=5, n=50):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--legs", default="plain,clip,clip_all_live,si_first_task,si_penalty,grouped,masked,packed")
+    ap.add_argument("--legs", default="plain,clip,clip_all_live,si_first_task,si_penalty,grouped,masked,packed,lora")
     args = ap.parse_args()
     from indic_cl_asr_amd import cl
     from indic_cl_asr_amd.config import model_config
@@ -64,7 +66,8 @@ def main():
     for leg in args.legs.split(","):
         kw, live = {"plain": ({}, False), "clip": ({"max_grad_norm": 1.0}, False),
                     "clip_all_live": ({"max_grad_norm": 1.0}, True), "si_first_task": ({}, False),
-                    "si_penalty": ({}, True), "grouped": ({}, False), "masked": ({}, False), "packed": ({}, False)}[leg]
+                    "si_penalty": ({}, True), "grouped": ({}, False), "masked": ({}, False), "packed": ({}, False),
+                    "lora": ({}, False)}[leg]
         if leg == "grouped":
             kw["param_groups"] = cl.layerwise_lr_groups(flat, 1e-4, 0.9)
         if leg.startswith("si_"):
@@ -76,10 +79,20 @@ def main():
             kw["masks"] = cl.Piggyback(flat)
         if leg == "packed":
             kw["masks"] = pn = cl.PackNet(flat, prune=0.5)
+        if leg == "lora":
+            kw["masks"] = lora = cl.LoRA(flat, rank=16)
         opt = cl.FusedAdamW(flat, lr=1e-4, **kw)
         flat.grad.copy_(grad)
         if leg == "packed":
             pn.begin_language("bench", opt)
+        if leg == "lora":
+            lora.begin_language("bench", opt)
+            for fac in lora.factor_views().values():                       # B != 0, so gA is not a sum of zeros
+                fac["lora_B"].normal_(0.0, 1e-2)
+            out["lora_adapted_elements"] = sum(a[2] * a[3] for a in lora.adapted)
+            out["lora_factor_elements"] = sum(16 * (a[2] + a[3]) for a in lora.adapted)
+            out["lora_tiles"] = int(lora.tile_table.shape[0])
+            out["lora_workspace_bytes"] = lora.workspace_bytes
         if leg == "grouped":
             out["groups"] = len(opt.param_groups)
         out[leg + "_us"] = round(timeit(lambda: opt._apply(1.0, live)), 2)
