@@ -1239,6 +1239,43 @@ int ia_merge_ties_dare(float* theta, const float* base, const float* vectors, in
                        const int32_t* chunk_table, int nchunks, int nseg, void* shadow_bf16, int32_t* seg_counts, uint32_t seed,
                        uint32_t keep_threshold, float keep_prob, ia_stream_t stream);
 
+/* ---- Waveform augmentation (csrc/wave_augment.hip): speed, gain, shift and white noise of NeMo's train_ds.augmentor
+ * (A/parts/preprocessing/perturb.py: SpeedPerturbation :99-165, GainPerturbation :315-332, ShiftPerturbation :404-433,
+ * WhiteNoisePerturbation :808-826) on a padded batch in ONE launch, in front of ia_feat_preemph.  The host draws the chain per
+ * utterance and folds it into one ia_wave_params row; x [B, L_in] f32 -> y [B, L_out] f32, every element of y written, x != y.
+ *
+ *   in(k)  = xs(k) + [noise_stage == 1] amp N(k + noise_shift)      for 0 <= k < n_in, 0 outside;
+ *            xs(k) = x[k + shift_pre] where 0 <= k + shift_pre < n_in, else 0
+ *   r(j)   = in(j)                                                   when new_sr == 0 (n_out == n_in then), else
+ *            s sum_k in(k) (h[i] + e (h[i+1] - h[i])) over the k with i < Z P, where D = j sr - k new_sr (64-bit),
+ *            q = max(sr, new_sr), i = (|D| P) / q, e = ((|D| P) mod q) / q, s = min(1, new_sr / sr), P = 512: Smith's band-limited
+ *            interpolation with the Kaiser-windowed sinc table h [Z P + 1] (h[Z P] = 0) the host built, fp32, fma accumulation
+ *            outward from j sr / new_sr, the taps at or below it and the taps above it in a sum each, then added
+ *   y[m]   = gain rs(m) + [noise_stage == 0] amp N(m + noise_shift)  for 0 <= m < n_out, 0 for n_out <= m < L_out;
+ *            rs(m) = r(m + shift_post) where 0 <= m + shift_post < n_out, else 0
+ *   N(i)   = the counter-based normal of ia_feat_preemph's dither for (seed, row b, sample i) where 0 <= i < the stage's length
+ *            (n_in at stage 1, n_out at stage 0), else 0.  amp = 0: no noise is drawn.
+ *
+ * A workgroup owns ia_wave_augment_tile() consecutive output samples of one utterance and stages the input span they reach in LDS;
+ * the table (32 KB for Z = 16, 128 KB for Z = 64) is read through the cache.  No atomics: two launches on the same input agree bit
+ * for bit.  min_new_sr: the smallest non-zero new_sr of the batch (0: nothing is resampled; table may then be
+ * NULL), which sizes the LDS span; a row with a smaller new_sr, or one above 2^21, is written as NaN.
+ * IA_INVALID_VALUE before any device work: a NULL required pointer, x == y, B, L_in, L_out <= 0, sr outside 1..2^20, min_new_sr
+ * < 0 or above 2^21, zero_crossings other than 16 and 64 with min_new_sr > 0, buffers not 4-byte aligned; IA_UNSUPPORTED when
+ * the span of min_new_sr does not fit in LDS. */
+typedef struct ia_wave_params {
+    int32_t n_in, n_out;          /* valid samples of the row in x and in y */
+    int32_t new_sr;               /* 0: not resampled */
+    int32_t shift_pre, shift_post;
+    int32_t noise_shift, noise_stage;
+    uint32_t noise_seed;
+    float gain, noise_amp;
+    int32_t pad[2];
+} ia_wave_params;
+int ia_wave_augment_tile(void);
+int ia_wave_augment(const float* x, int B, int L_in, float* y, int L_out, const ia_wave_params* params, const float* table,
+                    int zero_crossings, int sr, int min_new_sr, ia_stream_t stream);
+
 /* ---- CTC head + loss on RAW logits (ConvASRDecoder.forward + CTCLoss.forward, A/modules/conv_asr.py:459-490 and
  * A/losses/ctc.py:68-82, without the [B,T,V] log-prob tensor and without a softmax backward pass): logits [B*T, ld] f32 with V
  * valid columns (the head GEMM's padded output), lse [B*T] = per-frame log-sum-exp over the V columns (ia_ctc_row_lse).

@@ -53,8 +53,16 @@ class BlockGrads(_c.Structure):
         "dw_w", "dw_b", "bn_g", "bn_b")]
 
 
+class WaveParams(_c.Structure):
+    """ia_wave_params of include/indicasr.h (one utterance's folded augmentation chain; augment.PARAMS_DTYPE is its numpy image)."""
+    _fields_ = ([(n, _c.c_int32) for n in ("n_in", "n_out", "new_sr", "shift_pre", "shift_post", "noise_shift", "noise_stage")]
+                + [("noise_seed", _c.c_uint32), ("gain", _c.c_float), ("noise_amp", _c.c_float), ("pad", _c.c_int32 * 2)])
+
+
 SIGNATURES = {
     "ia_version": (_c.c_char_p, []),
+    "ia_wave_augment_tile": (_i, []),
+    "ia_wave_augment": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
     "ia_gemm_bf16_ex2": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _f, _c.c_uint, _f, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp]),
     "ia_transpose16_multi": (_i, [_vp, _i, _vp]),
     "ia_swap01_cast": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),

@@ -170,11 +170,15 @@ def batch_indices(durations, batch_size, shuffle=False, seed=0, bucket=False, ra
 
 class BatchLoader:
     """Iterates device batches: collate on the host into pinned buffers, copy on a side stream one batch ahead, hand the
-    training loop (batch, host_lengths) so that training_step needs no device->host read."""
+    training loop (batch, host_lengths) so that training_step needs no device->host read.  `augmentor` (an
+    augment.AudioAugmentor): applied to each device batch after its copy has landed, one launch on the consumer's stream; the
+    loader then yields the augmented signal, its length tensor and the new host lengths."""
 
     def __init__(self, dataset: SpeechDataset, batch_size, device=None, shuffle=False, seed=0, bucket=False, rank=0, world=1,
-                 drop_last=False):
-        self.ds, self.device = dataset, device
+                 drop_last=False, augmentor=None):
+        self.ds, self.device, self.augmentor = dataset, device, augmentor
+        if augmentor is not None and (device is None or torch.device(device).type != "cuda"):
+            raise RuntimeError("BatchLoader(augmentor=...) needs a device: the waveform augmentation is a HIP kernel")
         self.batches = batch_indices(dataset.dur, batch_size, shuffle, seed, bucket, rank, world, drop_last)
 
     def __len__(self):
@@ -208,6 +212,8 @@ class BatchLoader:
                 torch.cuda.current_stream(dev).wait_event(ev)
                 for t in devb:
                     t.record_stream(torch.cuda.current_stream(dev))
+                if self.augmentor is not None:
+                    devb, lens = self.augmentor(devb, lens)
                 yield devb, lens
 
 

@@ -81,11 +81,12 @@ class TranscribeLoader:
     (signal [B,L] f32, signal_len [B] i64, tokens [B,U] i64, tokens_len [B] i64) -- the layout of NeMo's
     `_speech_collate_fn` (A/data/audio_to_text.py:57-116) -- resident on `device` when that is the MI355X."""
 
-    def __init__(self, dataset, batch_size, device, shuffle=False, sampler=None, seed=0):
+    def __init__(self, dataset, batch_size, device, shuffle=False, sampler=None, seed=0, augmentor=None):
         rank, world = 0, 1
         if sampler == "ddp" and torch.distributed.is_available() and torch.distributed.is_initialized():
             rank, world = torch.distributed.get_rank(), torch.distributed.get_world_size()
-        self.loader = D.BatchLoader(dataset, batch_size, device=device, shuffle=shuffle, seed=seed, rank=rank, world=world)
+        self.loader = D.BatchLoader(dataset, batch_size, device=device, shuffle=shuffle, seed=seed, rank=rank, world=world,
+                                    augmentor=augmentor)
         self.epoch = 0
 
     def __len__(self):
@@ -120,6 +121,10 @@ class TranscriptionMixin:
             audio = [audio]
         device = getattr(getattr(trcfg, "_internal", None), "device", None) or next(self.parameters()).device
         bs = int(getattr(trcfg, "batch_size", 4) or 4)
+        # TranscribeConfig.augmentor (hybrid_rnnt_ctc_models.py:448 reads it for the dataset): a `train_ds.augmentor` mapping
+        # or a ready augment.AudioAugmentor; applied to every device batch by the loader
+        from .augment import process_augmentations
+        augmentor = process_augmentations(getattr(trcfg, "augmentor", None), seed=self.seed, sample_rate=self.cfg.sample_rate)
         if isinstance(audio[0], str):
             files = list(audio)
             if transcripts is not None and self.tokenizer is None:
@@ -133,9 +138,11 @@ class TranscriptionMixin:
             if tmp:   # the reference leaves a manifest there (hybrid_rnnt_ctc_models.py:420-431): same file, same fields
                 D.write_manifest(os.path.join(tmp, "manifest.json"), files, transcripts, durations, language_id)
             ds = _FileDataset(files, transcripts, durations, self.tokenizer, language_id, self.cfg.sample_rate)
-            return TranscribeLoader(ds, min(bs, len(files)), device, shuffle=shuffle, sampler=sampler, seed=self.seed)
+            return TranscribeLoader(ds, min(bs, len(files)), device, shuffle=shuffle, sampler=sampler, seed=self.seed,
+                                    augmentor=augmentor)
         if isinstance(audio[0], (np.ndarray, torch.Tensor)):
-            return TranscribeLoader(_TensorDataset(audio), min(bs, len(audio)), device, shuffle=False, sampler=None)
+            return TranscribeLoader(_TensorDataset(audio), min(bs, len(audio)), device, shuffle=False, sampler=None,
+                                    augmentor=augmentor)
         raise ValueError(f"Input `audio` is of type {type(audio[0])}. Only `str` (path to audio file), `np.ndarray`, and "
                          "`torch.Tensor` are supported as input.")
 
