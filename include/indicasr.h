@@ -984,6 +984,44 @@ int ia_adamw_step_segmented_gem(float* theta, const float* grad, float* exp_avg,
                                 const float* group_lr, const float* group_weight_decay, const float* norm_state,
                                 int skip_nonfinite, int32_t* counters, const float* refs, int64_t stride, int ntasks,
                                 const float* gem_state, int32_t* gem_counters, ia_stream_t stream);
+/* ---- Orthogonal Gradient Descent (Farajtabar, Azizan, Mott, Li, AISTATS 2020): a resident orthonormal basis of earlier tasks'
+ * loss gradients instead of their data.  basis is ONE fp32 buffer [max_rows, stride], stride a multiple of 4 and >= numel (the
+ * flat buffers' length), every row laid out as grad; rows 0 .. nrows-1 are in use and orthonormal, 1 <= nrows <=
+ * IA_OGD_MAX_ROWS.  seg_scope: int32[nseg] on the device, 0 or 1: tensor k is projected iff seg_scope[k] != 0; rows are zero
+ * outside the scope.  Every step consumes x - sum_k <x, v_k> v_k: no sign test and no program.  No kernel uses a float atomic
+ * and every sum has a fixed order, so all results reproduce bit for bit; nothing is read back by any of the calls.
+ * ia_ogd_dots              two launches, (nrows + 1) * 4 B per element in scope.  (1) workgroup c keeps chunk c of x in registers,
+ *                          streams the rows in tiles of 16 and stores the fp32 sums of the chunk in workspace
+ *                          (ia_ogd_workspace_bytes(nchunks, max_rows) = (max_rows + 1) floats per chunk, laid out row by row);
+ *                          per row the reduction has the shape of ia_agem_dots.  A chunk of a tensor outside the scope reads no
+ *                          row and contributes zero.  (2) one workgroup PER ROW adds that row's partials in fp64 in a fixed order
+ *                          (the order of ia_agem_dots's second launch) and writes dots64[k] = <x, v_k> and dots32[k], the same
+ *                          value rounded once to fp32.  with_sq != 0: entry nrows of both is <x, x> over the scope (per chunk the
+ *                          reduction of ia_grad_norm).  When seg_active is not NULL, the liveness flags of ALL tensors, in scope or
+ *                          not, are set from x exactly as ia_agem_dots sets them.  dots64 / dots32 hold nrows + 1 entries.
+ * ia_ogd_project           one launch, (nrows + 2) * 4 B per element.  Per element of a tensor that is in scope and, when
+ *                          seg_active is not NULL, live (seg_active is only read), every product and difference rounded to fp32
+ *                          on its own:
+ *                            acc = x;   for k ascending: acc = acc - coef[k] * v_k;   dst = acc * alpha
+ *                          coef: nrows floats on the device (dots32 of ia_ogd_dots).  dst may be x itself (the step: alpha = 1)
+ *                          or another buffer laid out as x, such as the next free row of basis (the insert); it must not be one
+ *                          of the rows 0 .. nrows-1.  With dst != x the elements of tensors outside the scope are written as
+ *                          zero; with dst == x they are not touched.  Elements of in-scope tensors that are not live and the
+ *                          alignment gaps between tensors are left as they are.
+ * A live tensor whose projected gradient is exactly zero is still live: the liveness passes of ia_grad_norm and of the segmented
+ * steps only ever set flags, so what ia_ogd_dots set from the unprojected gradient survives them, and the tensor takes its AdamW
+ * step (counter, weight decay) as torch.optim.AdamW does with a zero .grad.
+ * IA_INVALID_VALUE before any device work: a NULL required pointer (seg_active is optional), nrows outside 1..IA_OGD_MAX_ROWS, a
+ * stride that is not a multiple of 4 or is below numel, misaligned buffers (16 bytes for x, dst, basis and the chunk table, 8
+ * for dots64). */
+#define IA_OGD_MAX_ROWS 4096
+size_t ia_ogd_workspace_bytes(int nchunks, int max_rows);
+int ia_ogd_dots(const float* x, const float* basis, int64_t stride, int64_t numel, int nrows, const int32_t* chunk_table,
+                int nchunks, int nseg, const int32_t* seg_scope, int32_t* seg_active, int with_sq, double* dots64,
+                float* dots32, void* workspace, size_t workspace_bytes, ia_stream_t stream);
+int ia_ogd_project(const float* x, const float* basis, int64_t stride, int64_t numel, int nrows, const float* coef, float alpha,
+                   const int32_t* chunk_table, int nchunks, int nseg, const int32_t* seg_scope, const int32_t* seg_active,
+                   float* dst, ia_stream_t stream);
 /* Parameter groups: per-tensor learning rate and weight decay for every kind of segmented step.  seg_group: int32[nseg] on the
  * device, tensor k belongs to group seg_group[k] (NULL: every tensor in group 0; entries outside 0..ngroups-1 are clamped).
  * group_lr / group_weight_decay: ngroups floats each in HOST memory, read during the call and handed to the kernel by value

@@ -244,6 +244,9 @@ SIGNATURES = {
     "ia_grad_norm_gem": (_i, [_vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp, _i64, _i, _vp, _vp]),
     "ia_adamw_step_segmented_gem": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _f, _vp, _vp, _i, _vp, _vp,
                                          _vp, _i, _vp, _vp, _i64, _i, _vp, _vp, _vp]),
+    "ia_ogd_workspace_bytes": (_sz, [_i, _i]),
+    "ia_ogd_dots": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "ia_ogd_project": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _f, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "ia_adamw_step_segmented_grouped": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _f, _vp, _vp, _i, _vp, _vp,
                                              _vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
     "ia_adamw_step_segmented_masked": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _f, _vp, _vp, _i, _vp, _vp,

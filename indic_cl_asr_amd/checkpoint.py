@@ -188,6 +188,19 @@ def load_memory(memory, path):
     return memory
 
 
+def save_projection(projection, path):
+    """Persist cl.OGD.state_dict(): the stored directions, the scope, the flat layout they belong to and the counters.  The basis
+    cannot be rebuilt without the earlier languages' data, so it is part of a resumable run (GEM's and A-GEM's references are
+    recomputed from the episodic memory at every step and are not saved)."""
+    torch.save(projection.state_dict(), path)
+
+
+def load_projection(projection, path):
+    """Inverse of save_projection, in place; refuses a file saved for another tensor table or another scope."""
+    projection.load_state_dict(torch.load(path, map_location="cpu"), source=path)
+    return projection
+
+
 def save_masks(masks, path):
     """Persist cl.Piggyback.state_dict() (kinds, base, scores and every saved language's bits, free tensors and buffers) or
     cl.PackNet.state_dict() (kinds, base, the owner map, the open language and its phase, every finished language's free tensors

@@ -562,6 +562,193 @@ class GEM:
                 "unsolved_steps": int(host[c + 1])}
 
 
+OGD_MAX_DIRECTIONS = 4096   # IA_OGD_MAX_ROWS of include/indicasr.h
+
+
+class OGD:
+    """Orthogonal Gradient Descent (Farajtabar, Azizan, Mott, Li, AISTATS 2020): the member of the gradient-projection family
+    that keeps no audio.  When a language is finished, a number of its loss gradients are orthonormalised and kept as the rows
+    v_k of `basis`; every later step consumes g - sum_k <g, v_k> v_k for the (data-parallel averaged) gradient g, so to first
+    order it does not move what those directions measured.  Use it where the earlier languages' recordings may not be retained;
+    `GEM` / `AveragedGEM` need them at every step.
+
+    Cost: `basis` [max_directions, numel] is allocated here, 4 B * trainable parameters * max_directions (69 MB per direction at
+    17.3 M trainable parameters: 4.4 GB for 64 directions, 35 GB for 512), plus (max_directions + 1) floats per 4096-element chunk
+    of workspace, allocated at first use.  `scope` selects the tensors that are projected, by a list of names or one regular
+    expression (re.search on the name); None: every trainable tensor.  Exclude the per-language heads: a later language cannot
+    move them anyway, and their part of a stored gradient would only spend the direction's norm.  Rows are zero outside the scope.
+
+    At the end of a language, for n batches: `opt.zero_grad()` -> `training_step` -> `backward()` -> `ogd.add_direction(opt)`.
+    Afterwards train as usual with `FusedAdamW(..., projection=ogd)`: once a row is stored the step runs ia_ogd_dots and
+    ia_ogd_project on the flat gradient after the data-parallel all-reduce, then the norm (if measured) and the usual step: project,
+    then clip.  Liveness is that of the unprojected gradient: a tensor whose projected gradient is exactly zero still takes its
+    AdamW step (counter, weight decay), as torch.optim.AdamW does with a zero `.grad`.  Nothing is read back unless `stats()` is
+    called.  The basis cannot be recomputed without the earlier languages' data, so unlike GEM's references it belongs in the
+    checkpoint: `state_dict()` / `checkpoint.save_projection`.  Not here: a bf16 basis, a compressed basis (PCA-OGD), per-logit
+    gradients (OGD-ALL) and OGD combined with GEM."""
+
+    def __init__(self, model_or_flat, max_directions, scope=None, tol=1e-3):
+        if not 1 <= int(max_directions) <= OGD_MAX_DIRECTIONS:
+            raise ValueError(f"OGD: max_directions must be in 1..{OGD_MAX_DIRECTIONS} (got {max_directions})")
+        if not (float(tol) > 0.0 and float(tol) < 1.0):
+            raise ValueError(f"OGD: tol must be in (0, 1) (got {tol})")
+        self.flat = f = model_or_flat if isinstance(model_or_flat, FlatParams) else flat_of(model_or_flat)
+        self.max_directions, self.tol = int(max_directions), float(tol)
+        self.scope_names = list(f.names) if scope is None else _select_names(f, scope, "scope=", "OGD")
+        in_scope = set(self.scope_names)
+        self.scope_names = [n for n in f.names if n in in_scope]          # layout order, each name once
+        dev = f.theta.device
+        self.seg_scope = torch.tensor([int(n in in_scope) for n in f.names], dtype=torch.int32, device=dev)
+        self.stride = (f.numel + 3) // 4 * 4                                # float4 loads of every row stay aligned
+        self.basis = torch.zeros(self.max_directions, self.stride, dtype=torch.float32, device=dev)
+        # <g, v_k> of the latest step and <g, g> over the scope behind them, as fp64 and as fp32 (what ia_ogd_project reads);
+        # the same for the gradient being inserted
+        self.dots64 = torch.zeros(self.max_directions + 1, dtype=torch.float64, device=dev)
+        self.dots32 = torch.zeros(self.max_directions + 1, dtype=torch.float32, device=dev)
+        self._ins64, self._ins32 = torch.zeros_like(self.dots64), torch.zeros_like(self.dots32)
+        self._ws = None
+        self._rows = 0              # rows in use
+        self._stat_rows = 0         # rows the latest step projected off: the valid entries of dots64
+        self.dependent = self.nonfinite = 0
+
+    @property
+    def directions(self) -> int:
+        return self._rows
+
+    @property
+    def has_reference(self) -> bool:
+        return self._rows > 0
+
+    def _device_only(self, what):
+        if not self.flat.theta.is_cuda:
+            raise RuntimeError(f"OGD.{what} runs on the HIP kernels: the parameters are not on the device")
+
+    def workspace(self, nchunks):
+        if self._ws is None:
+            self._ws = torch.empty(_lib.lib().ia_ogd_workspace_bytes(nchunks, self.max_directions), dtype=torch.uint8,
+                                   device=self.flat.theta.device)
+        return self._ws
+
+    def _dots(self, x, rows, nrows, live, out64, out32, with_sq=True):
+        f = self.flat
+        nchunks = f.chunk_table.shape[0]
+        ws = self.workspace(nchunks)
+        st = _lib.lib().ia_ogd_dots(_lib.ptr(x), _lib.ptr(rows), self.stride, f.numel, nrows, _lib.ptr(f.chunk_table), nchunks,
+                                    len(f.entries), _lib.ptr(self.seg_scope), live, int(with_sq), _lib.ptr(out64),
+                                    _lib.ptr(out32), _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
+        _lib.check(st, "ia_ogd_dots")
+
+    def _project(self, x, nrows, coef, live, dst, alpha=1.0):
+        f = self.flat
+        st = _lib.lib().ia_ogd_project(_lib.ptr(x), _lib.ptr(self.basis), self.stride, f.numel, nrows, _lib.ptr(coef),
+                                       float(alpha), _lib.ptr(f.chunk_table), f.chunk_table.shape[0], len(f.entries),
+                                       _lib.ptr(self.seg_scope), live, _lib.ptr(dst), _lib.stream_ptr())
+        _lib.check(st, "ia_ogd_project")
+
+    def project_step(self, live):
+        """The step's part (FusedAdamW._apply): the dots of the flat gradient with every row, which also set the liveness
+        flags, and the projection in place."""
+        g = self.flat.grad
+        self._dots(g, self.basis, self._rows, live, self.dots64, self.dots32)
+        self._project(g, self._rows, self.dots32, live, g)
+        self._stat_rows = self._rows
+
+    def add_direction(self, optimizer: Optional["FusedAdamW"] = None) -> bool:
+        """The flat gradient (of the batch just back-propagated) becomes a candidate direction.  Under data parallelism it is
+        averaged over `optimizer`'s group first (a synchronous fp32 all-reduce, then times 1/world), so every rank keeps the
+        same basis.  It is orthogonalised against the stored rows by classical Gram-Schmidt applied twice (dots, project, dots,
+        project), and its residual r is kept, normalised, as the next row when |r| > tol * |g| (norms over the scope): True.
+        Otherwise it is dropped and counted in `dependent` (a non-finite gradient: in `nonfinite`): False.  One small host read;
+        the flat gradient is zeroed afterwards.  A full basis raises ValueError."""
+        self._device_only("add_direction")
+        if self._rows >= self.max_directions:
+            raise ValueError(f"OGD: max_directions = {self.max_directions} directions are stored already")
+        flush_pending_updates()
+        f, n = self.flat, self._rows
+        g, cand = f.grad, self.basis[n]
+        if optimizer is not None:
+            ws = optimizer._world()
+            if ws > 1:
+                dist.all_reduce(g, group=optimizer.group)
+                g.mul_(1.0 / ws)
+        if n == 0:
+            cand[:f.numel].copy_(g)
+            for (name, off, k, _), s in zip(f.entries, self.seg_scope.tolist()):
+                if not s:
+                    cand[off:off + k].zero_()
+        else:
+            self._dots(g, self.basis, n, None, self._ins64, self._ins32)              # entry n: <g, g> over the scope
+            g_sq = self._ins64[n].clone()
+            self._project(g, n, self._ins32, None, cand)
+            self._dots(cand, self.basis, n, None, self._ins64, self._ins32, with_sq=False)
+            self._project(cand, n, self._ins32, None, cand)
+        self._dots(cand, cand, 1, None, self._ins64, self._ins32)                      # entries 0 and 1: <r, r>
+        r_sq = self._ins64[1]
+        g_sq, r_sq = torch.stack([r_sq if n == 0 else g_sq, r_sq]).tolist()            # the insert's one host read
+        f.zero_grad()
+        if not (math.isfinite(g_sq) and math.isfinite(r_sq)):
+            self.nonfinite += 1
+            return False
+        if not math.sqrt(r_sq) > self.tol * math.sqrt(g_sq):
+            self.dependent += 1
+            return False
+        # a true division by the norm (the root in fp64, rounded once to fp32): a one-element residual becomes exactly +-1
+        cand.div_(torch.tensor(math.sqrt(r_sq), dtype=torch.float32, device=cand.device))
+        self._rows = n + 1
+        return True
+
+    def clear(self):
+        """Forget every direction: the following steps are plain steps until the next add_direction() (a deferred update that
+        was issued with the basis is applied with it first).  The counters stay."""
+        flush_pending_updates()
+        self._rows = self._stat_rows = 0
+
+    def stats(self) -> dict:
+        """One small device-to-host read: `directions`; of the latest projected step `removed_fraction` = sum_k c_k^2 / |g|^2
+        over the scope (the share of the averaged gradient's energy that lay along stored directions; NaN before the first
+        projected step); and how many candidates were dropped as `dependent` / `nonfinite`."""
+        flush_pending_updates()
+        k = self._stat_rows
+        frac = float("nan")
+        if k:
+            host = self.dots64[:k + 1].cpu()
+            c, g_sq = host[:k], float(host[k])
+            frac = float((c * c).sum()) / g_sq if g_sq > 0.0 else float("nan")
+        return {"directions": self._rows, "removed_fraction": frac, "dependent": self.dependent, "nonfinite": self.nonfinite}
+
+    def coefficients(self) -> torch.Tensor:
+        """<g, v_k> of the latest projected step as the projection consumed them (fp32, on the host), one per row used."""
+        flush_pending_updates()
+        return self.dots32[:self._stat_rows].cpu()
+
+    def state_dict(self) -> dict:
+        """The rows in use (CPU), the scope, the flat layout they belong to and the counters."""
+        flush_pending_updates()
+        return {"entries": list(self.flat.entries), "scope": list(self.scope_names), "max_directions": self.max_directions,
+                "tol": self.tol, "basis": self.basis[:self._rows, :self.flat.numel].to("cpu", copy=True),
+                "dependent": self.dependent, "nonfinite": self.nonfinite}
+
+    def load_state_dict(self, sd: dict, source="state dict"):
+        """Inverse of state_dict(); refuses a state saved for another set of trainable tensors, another scope or more rows than
+        this object holds."""
+        if [tuple(e[:3]) + (tuple(e[3]),) for e in sd["entries"]] != list(self.flat.entries):
+            raise ValueError(f"{source}: 'projection' was saved for a different set of trainable tensors")
+        if list(sd["scope"]) != self.scope_names:
+            raise ValueError(f"{source}: 'projection' was saved for a different scope ({len(sd['scope'])} tensors saved, "
+                             f"{len(self.scope_names)} here, compared by names and order)")
+        rows = sd["basis"]
+        if rows.dim() != 2 or rows.shape[1] != self.flat.numel or rows.dtype != torch.float32:
+            raise ValueError(f"{source}: 'projection' holds a basis of shape {tuple(rows.shape)} and dtype {rows.dtype}; "
+                             f"expected [rows, {self.flat.numel}] float32")
+        if rows.shape[0] > self.max_directions:
+            raise ValueError(f"{source}: 'projection' holds {rows.shape[0]} directions, max_directions here is "
+                             f"{self.max_directions}")
+        flush_pending_updates()
+        self._rows, self._stat_rows = rows.shape[0], 0
+        self.basis[:self._rows, :self.flat.numel].copy_(rows)
+        self.dependent, self.nonfinite = int(sd["dependent"]), int(sd["nonfinite"])
+
+
 class EpisodicMemory:
     """Host-side episodic memory for replay methods: up to `per_language` utterances of every language seen, chosen by reservoir
     sampling (Vitter's algorithm R), so that each utterance of a language's stream is kept with equal probability.  Utterances
@@ -2120,6 +2307,9 @@ class FusedAdamW(torch.optim.Optimizer):
         above.  Not combinable with `path_integral`; projection state is not optimizer state and is not in state_dict().
         `projection=gem` (a `GEM`): the same place in the step, with one constraint per stored task -- ia_gem_dots, ia_gem_solve,
         ia_grad_norm_gem (if the norm is measured) and ia_adamw_step_segmented_gem, which takes the group table itself.
+        `projection=ogd` (an `OGD`): once a direction is stored, ia_ogd_dots and ia_ogd_project rewrite the averaged flat gradient
+        in place, and the norm and step described above run on it unchanged: project, then clip.  The basis is saved through
+        ogd.state_dict() / checkpoint.save_projection.
 
         `param_groups=[{...}, ...]`: dicts in torch's shape.  Each names its tensors with "params" (parameter names and / or
         the Parameter objects) or "match" (a regular expression, re.search on the parameter name), may override "lr" and / or
@@ -2340,8 +2530,8 @@ class FusedAdamW(torch.optim.Optimizer):
         return dict(zip(self.flat.names, self._seg_norm.tolist()))
 
     def _apply(self, scale, all_live=False, hyper=None):
-        """Dots (A-GEM / GEM: they also set the liveness flags) -> norm of the gradient the step consumes (when measured) ->
-        the step, all on the device.  One entry point per family of variants, for one or many parameter groups."""
+        """Dots (A-GEM / GEM / OGD: they also set the liveness flags; OGD projects here) -> norm of the gradient the step consumes
+        (when measured) -> the step, all on the device.  One entry point per family of variants, for one or many parameter groups."""
         self.step_count += 1
         g = self.param_groups[0]
         lrs, wds = self._group_hyper() if hyper is None else hyper
@@ -2353,6 +2543,7 @@ class FusedAdamW(torch.optim.Optimizer):
         all_live = bool(all_live) or penalised       # autograd on loss + surrogate gives every trainable tensor a gradient
         scale, nchunks, nseg, n = float(scale), f.chunk_table.shape[0], len(f.entries), len(lrs)
         proj = self.projection if self.projection is not None and self.projection.has_reference else None
+        ogd, proj = (proj, None) if isinstance(proj, OGD) else (None, proj)
         gem, agem = (proj, None) if isinstance(proj, GEM) else (None, proj)
         if measured and self._seg_norm is None:
             self._seg_norm = torch.zeros(nseg, dtype=torch.float32, device=f.theta.device)
@@ -2368,6 +2559,8 @@ class FusedAdamW(torch.optim.Optimizer):
         norm = (ptr(f.grad), ptr(f.chunk_table), nchunks, ptr(f.seg_chunk_begin), nseg, scale,
                 0.0 if max_norm is None else float(max_norm), live, ptr(self._seg_norm), ptr(self._norm_state),
                 ptr(self._norm_ws), self._norm_ws.numel()) if measured else None
+        if ogd is not None:      # rewrites the flat gradient; the flags its dots set survive the liveness passes below
+            ogd.project_step(live)
         if gem is not None:
             k, ws = len(gem.tasks()), gem.workspace(nchunks)
             rows = (ptr(gem.refs), gem.stride, k, ptr(gem.state))

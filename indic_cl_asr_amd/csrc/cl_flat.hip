@@ -36,6 +36,7 @@
 //   run_step                   liveness (activity pass or mark-all), the walker, the advance: three launches for every variant.
 //   ia_pack_prune, ia_pack_apply   PackNet's pruning (an exact per-tensor radix select on |theta|) and owner map -> weights.
 // The dots of A-GEM (ia_agem_dots) and GEM (ia_gem_dots, ia_gem_solve) run before their step and leave the decision on the device.
+// OGD (ia_ogd_dots, ia_ogd_project) rewrites the flat gradient before a step it does not change.
 // All are HBM-streaming kernels: 16-byte accesses, grid capped at 2048 workgroups, fp32 math.
 #include "ia_common.h"
 #include <type_traits>
@@ -797,6 +798,222 @@ struct gem_source {
     }
 };
 using gem_step = consumed_step<gem_source>;
+
+// ---- Orthogonal Gradient Descent (Farajtabar, Azizan, Mott, Li 2020): basis is [max_rows, stride] fp32, rows 0 .. nrows-1
+// orthonormal and laid out as grad, zero outside the scope (seg_scope[k] != 0: tensor k is projected).  Every step consumes
+// x - sum_k <x, v_k> v_k.  No sign test and no program: the dots, then the projection, both pure streaming.
+//   ogd_dots_kernel      workgroup c holds chunk c of x in registers (gem_dots_kernel's layout), streams the rows in tiles of
+//                        OGD_TILE and leaves the fp32 sums in partials[k * nchunks + c]: one line of the workspace per row, so
+//                        that the finisher reads each row's partials contiguously.  Per row the thread's partial, the DPP wave
+//                        sum and the four wave sums in order: the reduction shape of agem_dots_kernel.  SQ: line nrows holds
+//                        sum x*x of the chunk (the shape of seg_activity_kernel<true>).  A chunk outside the scope stores zeros
+//                        and reads x only for the liveness flags.
+//   ogd_finish_kernel    workgroup k adds line k in fp64 (agem_finish_kernel's order) and writes the sum as fp64 and, rounded
+//                        once, as fp32: one workgroup per row, so 4096 rows cost what 16 do per row.
+//   ogd_project_kernel   acc = x; for k ascending: acc = acc - c_k * v_k; dst = acc * alpha, every product and difference
+//                        rounded on its own.  x and dst may be the same buffer, so neither is __restrict__.
+constexpr int OGD_TILE = 16;   // rows between two barriers of the dots kernel
+constexpr int OGD_ROWS = 4;    // rows whose loads are issued together (dots and projection): 16 float4 in flight per thread
+
+struct ogd_chunk {             // chunk c of x as the thread holds it
+    float4 X[GEM_CHUNK_F4];
+    float xt;                  // one of the chunk's last cnt & 3 elements, or 0
+};
+
+__device__ __forceinline__ ogd_chunk ogd_load_chunk(const float* x, int off, int cnt) {
+    const int n4 = cnt >> 2, tail = (n4 << 2) + threadIdx.x;
+    ogd_chunk h;
+#pragma unroll
+    for (int u = 0; u < GEM_CHUNK_F4; ++u) {
+        const int q = threadIdx.x + u * CL_THREADS;
+        h.X[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (q < n4) h.X[u] = reinterpret_cast<const float4*>(x + off)[q];
+    }
+    h.xt = tail < cnt ? x[off + tail] : 0.f;
+    return h;
+}
+
+// the thread's share of <x, r> over one chunk; r points at the chunk's first element of the row
+__device__ __forceinline__ float ogd_row_partial(const ogd_chunk& h, const float* __restrict__ r, int cnt) {
+    const int n4 = cnt >> 2, tail = (n4 << 2) + threadIdx.x;
+    float4 y[GEM_CHUNK_F4];
+#pragma unroll
+    for (int u = 0; u < GEM_CHUNK_F4; ++u) {
+        const int q = threadIdx.x + u * CL_THREADS;
+        y[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (q < n4) y[u] = reinterpret_cast<const float4*>(r)[q];
+    }
+    float a = 0.f;
+#pragma unroll
+    for (int u = 0; u < GEM_CHUNK_F4; ++u)
+        if (threadIdx.x + u * CL_THREADS < n4) a += h.X[u].x * y[u].x + h.X[u].y * y[u].y + h.X[u].z * y[u].z + h.X[u].w * y[u].w;
+    if (tail < cnt) a += h.xt * r[tail];
+    return a;
+}
+
+template <bool SQ>
+__global__ __launch_bounds__(CL_THREADS) void ogd_dots_kernel(const float* __restrict__ x, const float* __restrict__ basis,
+                                                              int64_t stride, int nrows, const int4* __restrict__ table,
+                                                              int nchunks, const int* __restrict__ seg_scope,
+                                                              int* __restrict__ seg_active, float* __restrict__ partials) {
+    __shared__ float sh[OGD_TILE][CL_THREADS / 64];
+    __shared__ float sh_sq[CL_THREADS / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lines = nrows + (SQ ? 1 : 0);
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const int4 e = table[c];
+        const int off = e.x, cnt = e.y;                    // cnt <= CL_CHUNK: at most GEM_CHUNK_F4 float4 per thread
+        const bool in_scope = seg_scope[e.z] != 0;
+        if (!in_scope && !seg_active) {
+            for (int k = threadIdx.x; k < lines; k += CL_THREADS) partials[(int64_t)k * nchunks + c] = 0.f;
+            continue;
+        }
+        const ogd_chunk h = ogd_load_chunk(x, off, cnt);
+        if (seg_active) {
+            unsigned nz = __float_as_uint(h.xt);
+#pragma unroll
+            for (int u = 0; u < GEM_CHUNK_F4; ++u)
+                nz |= __float_as_uint(h.X[u].x) | __float_as_uint(h.X[u].y) | __float_as_uint(h.X[u].z) | __float_as_uint(h.X[u].w);
+            if (__any((nz & 0x7FFFFFFFu) != 0) && lane == 0) atomicOr(seg_active + e.z, 1);    // -0.0 counts as zero
+        }
+        if (!in_scope) {
+            for (int k = threadIdx.x; k < lines; k += CL_THREADS) partials[(int64_t)k * nchunks + c] = 0.f;
+            continue;
+        }
+        if constexpr (SQ) {
+            float ss = 0.f;
+#pragma unroll
+            for (int u = 0; u < GEM_CHUNK_F4; ++u)
+                ss += h.X[u].x * h.X[u].x + h.X[u].y * h.X[u].y + h.X[u].z * h.X[u].z + h.X[u].w * h.X[u].w;
+            ss += h.xt * h.xt;
+            const float t = block_sum(ss, sh_sq);
+            if (threadIdx.x == 0) partials[(int64_t)nrows * nchunks + c] = t;
+        }
+        for (int k0 = 0; k0 < nrows; k0 += OGD_TILE) {
+            const int kt = nrows - k0 < OGD_TILE ? nrows - k0 : OGD_TILE;
+            const float* r0 = basis + (int64_t)k0 * stride + off;
+            int k = 0;
+            for (; k + OGD_ROWS <= kt; k += OGD_ROWS) {
+                float a[OGD_ROWS];
+#pragma unroll
+                for (int j = 0; j < OGD_ROWS; ++j) a[j] = ogd_row_partial(h, r0 + (int64_t)(k + j) * stride, cnt);
+#pragma unroll
+                for (int j = 0; j < OGD_ROWS; ++j) {
+                    a[j] = ia_wave_sum_dpp(a[j]);
+                    if (lane == 0) sh[k + j][wave] = a[j];
+                }
+            }
+            for (; k < kt; ++k) {
+                const float a = ia_wave_sum_dpp(ogd_row_partial(h, r0 + (int64_t)k * stride, cnt));
+                if (lane == 0) sh[k][wave] = a;
+            }
+            __syncthreads();
+            if (threadIdx.x < kt) {
+                float t = 0.f;
+#pragma unroll
+                for (int i = 0; i < CL_THREADS / 64; ++i) t += sh[threadIdx.x][i];
+                partials[(int64_t)(k0 + threadIdx.x) * nchunks + c] = t;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+__global__ __launch_bounds__(GN_THREADS) void ogd_finish_kernel(const float* __restrict__ partials, int nchunks,
+                                                                double* __restrict__ dots64, float* __restrict__ dots32) {
+    __shared__ double sh_d[GN_THREADS / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float* line = partials + (int64_t)blockIdx.x * nchunks;
+    double d = 0.0;
+    for (int c = threadIdx.x; c < nchunks; c += GN_THREADS) d += (double)line[c];
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) d += __shfl_xor(d, s);
+    if (lane == 0) sh_d[wave] = d;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double sum = 0.0;
+        for (int w = 0; w < GN_THREADS / 64; ++w) sum += sh_d[w];
+        dots64[blockIdx.x] = sum;
+        dots32[blockIdx.x] = (float)sum;
+    }
+}
+
+__global__ __launch_bounds__(CL_THREADS) void ogd_project_kernel(const float* x, const float* __restrict__ basis, int64_t stride,
+                                                                 int nrows, const float* __restrict__ coef, float alpha,
+                                                                 const int4* __restrict__ table, int nchunks,
+                                                                 const int* __restrict__ seg_scope,
+                                                                 const int* __restrict__ seg_active, float* dst) {
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const int4 e = table[c];
+        const int off = e.x, cnt = e.y, n4 = cnt >> 2, tail = (n4 << 2) + threadIdx.x;
+        if (seg_scope[e.z] == 0) {
+            if (dst != x) {                                // a basis row is zero outside the scope
+#pragma unroll
+                for (int u = 0; u < GEM_CHUNK_F4; ++u) {
+                    const int q = threadIdx.x + u * CL_THREADS;
+                    if (q < n4) reinterpret_cast<float4*>(dst + off)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+                }
+                if (tail < cnt) dst[off + tail] = 0.f;
+            }
+            continue;
+        }
+        if (seg_active && seg_active[e.z] == 0) continue;
+        ogd_chunk h = ogd_load_chunk(x, off, cnt);
+        const float* r0 = basis + off;
+        int k = 0;
+        for (; k + OGD_ROWS <= nrows; k += OGD_ROWS) {
+            float4 y[OGD_ROWS][GEM_CHUNK_F4];
+            float yt[OGD_ROWS], ck[OGD_ROWS];
+#pragma unroll
+            for (int j = 0; j < OGD_ROWS; ++j) {
+                const float* r = r0 + (int64_t)(k + j) * stride;
+                ck[j] = coef[k + j];
+#pragma unroll
+                for (int u = 0; u < GEM_CHUNK_F4; ++u) {
+                    const int q = threadIdx.x + u * CL_THREADS;
+                    y[j][u] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (q < n4) y[j][u] = reinterpret_cast<const float4*>(r)[q];
+                }
+                yt[j] = tail < cnt ? r[tail] : 0.f;
+            }
+#pragma unroll
+            for (int j = 0; j < OGD_ROWS; ++j) {
+#pragma unroll
+                for (int u = 0; u < GEM_CHUNK_F4; ++u) {
+                    h.X[u].x = sub_rn(h.X[u].x, mul_rn(ck[j], y[j][u].x));
+                    h.X[u].y = sub_rn(h.X[u].y, mul_rn(ck[j], y[j][u].y));
+                    h.X[u].z = sub_rn(h.X[u].z, mul_rn(ck[j], y[j][u].z));
+                    h.X[u].w = sub_rn(h.X[u].w, mul_rn(ck[j], y[j][u].w));
+                }
+                h.xt = sub_rn(h.xt, mul_rn(ck[j], yt[j]));
+            }
+        }
+        for (; k < nrows; ++k) {
+            const float* r = r0 + (int64_t)k * stride;
+            const float ck = coef[k];
+#pragma unroll
+            for (int u = 0; u < GEM_CHUNK_F4; ++u) {
+                const int q = threadIdx.x + u * CL_THREADS;
+                if (q < n4) {
+                    const float4 y = reinterpret_cast<const float4*>(r)[q];
+                    h.X[u].x = sub_rn(h.X[u].x, mul_rn(ck, y.x));
+                    h.X[u].y = sub_rn(h.X[u].y, mul_rn(ck, y.y));
+                    h.X[u].z = sub_rn(h.X[u].z, mul_rn(ck, y.z));
+                    h.X[u].w = sub_rn(h.X[u].w, mul_rn(ck, y.w));
+                }
+            }
+            if (tail < cnt) h.xt = sub_rn(h.xt, mul_rn(ck, r[tail]));
+        }
+#pragma unroll
+        for (int u = 0; u < GEM_CHUNK_F4; ++u) {
+            const int q = threadIdx.x + u * CL_THREADS;
+            if (q < n4)
+                reinterpret_cast<float4*>(dst + off)[q] = make_float4(mul_rn(h.X[u].x, alpha), mul_rn(h.X[u].y, alpha),
+                                                                      mul_rn(h.X[u].z, alpha), mul_rn(h.X[u].w, alpha));
+        }
+        if (tail < cnt) dst[off + tail] = mul_rn(h.xt, alpha);
+    }
+}
 
 // ---- the clip norm of the gradient a consumed_step consumes, from the step's own gradient functor.
 // seg_activity_kernel<true>'s sum as the compiler emits it there, written out so that an un-projected step measures the norm
@@ -1717,6 +1934,54 @@ extern "C" int ia_adamw_step_segmented_gem(float* theta, const float* grad, floa
     x.unsolved_count = gem_counters + 1;
     return run_step(h, make_group_table(ngroups, group_lr, group_weight_decay), gem_step{{refs, stride, ntasks, gem_state}}, x,
                     (hipStream_t)stream);
+}
+
+extern "C" size_t ia_ogd_workspace_bytes(int nchunks, int max_rows) {
+    return nchunks > 0 && max_rows >= 1 && max_rows <= IA_OGD_MAX_ROWS ? (size_t)nchunks * (max_rows + 1) * sizeof(float) : 0;
+}
+
+namespace {
+inline bool ogd_operands_ok(const float* x, const float* basis, int64_t stride, int64_t numel, int nrows,
+                            const int32_t* chunk_table, int nchunks, int nseg, const int32_t* seg_scope) {
+    if (!x || !basis || !chunk_table || !seg_scope || nchunks <= 0 || nseg <= 0 || nrows < 1 || nrows > IA_OGD_MAX_ROWS ||
+        numel <= 0 || stride < numel || (stride & 3))
+        return false;
+    return ia_is_aligned(x, 16) && ia_is_aligned(basis, 16) && ia_is_aligned(chunk_table, 16) && ia_is_aligned(seg_scope, 4);
+}
+}  // namespace
+
+extern "C" int ia_ogd_dots(const float* x, const float* basis, int64_t stride, int64_t numel, int nrows,
+                           const int32_t* chunk_table, int nchunks, int nseg, const int32_t* seg_scope, int32_t* seg_active,
+                           int with_sq, double* dots64, float* dots32, void* workspace, size_t workspace_bytes,
+                           ia_stream_t stream) {
+    if (!ogd_operands_ok(x, basis, stride, numel, nrows, chunk_table, nchunks, nseg, seg_scope) || !dots64 || !dots32 ||
+        !workspace)
+        return IA_INVALID_VALUE;
+    if (!ia_is_aligned(dots64, 8) || !ia_is_aligned(dots32, 4) || !ia_is_aligned(workspace, 4) ||
+        (seg_active && !ia_is_aligned(seg_active, 4)))
+        return IA_INVALID_VALUE;
+    if (workspace_bytes < ia_ogd_workspace_bytes(nchunks, nrows)) return IA_WORKSPACE_TOO_SMALL;
+    hipStream_t st = (hipStream_t)stream;
+    auto kernel = with_sq ? ogd_dots_kernel<true> : ogd_dots_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(chunk_grid(nchunks)), dim3(CL_THREADS), 0, st, x, basis, stride, nrows,
+                       (const int4*)chunk_table, nchunks, seg_scope, seg_active, (float*)workspace);
+    hipLaunchKernelGGL(ogd_finish_kernel, dim3(nrows + (with_sq ? 1 : 0)), dim3(GN_THREADS), 0, st, (const float*)workspace,
+                       nchunks, dots64, dots32);
+    IA_RETURN_IF_LAUNCH_FAILED();
+    return IA_OK;
+}
+
+extern "C" int ia_ogd_project(const float* x, const float* basis, int64_t stride, int64_t numel, int nrows, const float* coef,
+                              float alpha, const int32_t* chunk_table, int nchunks, int nseg, const int32_t* seg_scope,
+                              const int32_t* seg_active, float* dst, ia_stream_t stream) {
+    if (!ogd_operands_ok(x, basis, stride, numel, nrows, chunk_table, nchunks, nseg, seg_scope) || !coef || !dst)
+        return IA_INVALID_VALUE;
+    if (!ia_is_aligned(coef, 4) || !ia_is_aligned(dst, 16) || (seg_active && !ia_is_aligned(seg_active, 4)))
+        return IA_INVALID_VALUE;
+    hipLaunchKernelGGL(ogd_project_kernel, dim3(chunk_grid(nchunks)), dim3(CL_THREADS), 0, (hipStream_t)stream, x, basis, stride,
+                       nrows, coef, alpha, (const int4*)chunk_table, nchunks, seg_scope, seg_active, dst);
+    IA_RETURN_IF_LAUNCH_FAILED();
+    return IA_OK;
 }
 
 extern "C" int ia_adamw_step_segmented_masked(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq,
