@@ -845,6 +845,43 @@ int ia_glu_bwd(const void* c2, const float* dG, const int64_t* lens, int B, int 
  * ia_si_consolidate        end of a task, one pass over n elements: omega += max(0, path_w / ((theta - theta_star)^2 + xi)),
  *                          path_w = 0, theta_star = theta; xi > 0 (IA_INVALID_VALUE otherwise).
  *
+ * Riemannian Walk (Chaudhry, Dokania, Ajanthan, Torr, ECCV 2018): a running Fisher kept inside the step (EWC++: no Fisher epoch)
+ * and a path score measured in that Fisher's metric, normalised and summed into one importance.  All buffers are flat fp32, laid
+ * out as theta, zero in the alignment gaps: fisher F (carried across languages), path_w w, anchor (theta at the last fold), score
+ * (of the current language), score_acc (mean normalised score of the finished languages), importance, theta_star.
+ * ia_adamw_step_segmented_rwalk  the segmented step with Riemannian Walk in the AdamW launch, with a group table as
+ *                          ia_adamw_step_segmented_gem takes it.  Per element of a live tensor, every product / difference / sum
+ *                          below rounded to fp32 on its own:
+ *                            ge = grad * grad_scale                               (the task gradient: no coef, no penalty)
+ *                            G  = ge * coef + (2*penalty_coef * importance) * (theta - theta_star)
+ *                            theta', exp_avg, exp_avg_sq = AdamW(theta, G)        (the routine of the other entries)
+ *                            F' = F + alpha * (ge*ge - F)                         (four roundings)
+ *                            w' = w - ge * (theta' - theta)                       (as ia_adamw_step_segmented_si)
+ *                            fold != 0:  d = theta' - anchor;  den = (0.5*F') * (d*d) + fold_eps
+ *                                        score += max(0, w') / den;  w = 0;  anchor = theta'
+ *                          The operands present select the variant, and a variant loads only what it needs (4 B per element
+ *                          read and 4 written for F and for w, 16 for anchor and score on a fold, 8 read for the penalty):
+ *                          path_w, anchor and score are all given or all NULL (EWC++ alone: F only, fold must be 0);
+ *                          importance and theta_star are both given (a language has been consolidated; the caller passes
+ *                          all_active != 0, as for SI) or both NULL (no penalty, penalty_coef ignored).  norm_state and
+ *                          counters: both NULL or both set, with the meaning of ia_adamw_step_segmented_clipped; liveness, the
+ *                          clip and the non-finite skip are launched as for ia_adamw_step_segmented_si.  A tensor that is not
+ *                          live keeps F, w, anchor and score; a skipped step writes none of them and ignores `fold` (w waits for
+ *                          the next fold).  0 < alpha <= 1, fold_eps > 0.
+ * ia_rwalk_consolidate     end of a language, at most three launches on `stream`, nothing read back, no float atomic:
+ *                          (1) with path_w, anchor, score and score_acc given, every element is folded once more with the
+ *                          arithmetic above (a dead tensor has w == 0 and adds +0), w = 0, anchor = theta; workgroup c leaves
+ *                          {max F, max score} of chunk c in workspace (ia_rwalk_workspace_bytes(nchunks) = two floats per chunk,
+ *                          8-byte aligned).  (2) one workgroup leaves maxima = {maxF, maxS} (two floats on the device; a maximum
+ *                          has no rounding, so any order gives the same bits; all buffers are >= 0 and the maxima start at 0).
+ *                          (3) over n elements: a = F / maxF and b = score / maxS, each 0 where its maximum is 0 (normalize ==
+ *                          0: a = F, b = score); score_acc = b when first != 0, else 0.5 * (score_acc + b); importance = a +
+ *                          score_acc; score = 0; theta_star = theta.  The four score buffers all NULL (EWC++ alone):
+ *                          importance = a, maxima[1] = 0.  F is not reset.  Non-finite maxima are not guarded: the step's
+ *                          skip_nonfinite is what keeps inf and NaN out of F and w.
+ * IA_INVALID_VALUE before any device work: a NULL required pointer, an incomplete operand group, fold != 0 without scores, alpha
+ * outside (0, 1], fold_eps <= 0, misaligned buffers (16 bytes for the flat buffers and the chunk table, 8 for the workspace).
+ *
  * Averaged GEM (Chaudhry, Ranzato, Rohrbach, Elhoseiny, ICLR 2019).  ref is the gradient of a batch drawn from an episodic
  * memory of earlier tasks, a flat buffer laid out as grad, stored already averaged and in true units; grad is still to be
  * multiplied by grad_scale (the step's scale: 1/world x the user's).  When the two point against each other the step consumes
@@ -912,6 +949,17 @@ int ia_adamw_step_segmented_si(float* theta, const float* grad, float* exp_avg, 
                                const float* omega, const float* theta_star, float penalty_coef, ia_stream_t stream);
 int ia_si_consolidate(const float* theta, float* theta_star, float* path_w, float* omega, float xi, int64_t n,
                       ia_stream_t stream);
+int ia_adamw_step_segmented_rwalk(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq,
+                                  const int32_t* chunk_table, int nchunks, int32_t* seg_active, int32_t* seg_step, int nseg,
+                                  int all_active, float beta1, float beta2, float eps, float grad_scale, void* shadow_bf16,
+                                  const int32_t* seg_group, int ngroups, const float* group_lr, const float* group_weight_decay,
+                                  const float* norm_state, int skip_nonfinite, int32_t* counters, float* fisher, float* path_w,
+                                  float* anchor, float* score, const float* importance, const float* theta_star,
+                                  float penalty_coef, float alpha, float fold_eps, int fold, ia_stream_t stream);
+size_t ia_rwalk_workspace_bytes(int nchunks);
+int ia_rwalk_consolidate(const float* theta, float* theta_star, const float* fisher, float* path_w, float* anchor, float* score,
+                         float* score_acc, float* importance, float* maxima, float fold_eps, int normalize, int first, int64_t n,
+                         const int32_t* chunk_table, int nchunks, void* workspace, size_t workspace_bytes, ia_stream_t stream);
 size_t ia_agem_workspace_bytes(int nchunks);
 int ia_agem_dots(const float* grad, const float* ref, const int32_t* chunk_table, int nchunks, int nseg, float grad_scale,
                  int32_t* seg_active, float* proj_state, void* workspace, size_t workspace_bytes, ia_stream_t stream);

@@ -233,6 +233,10 @@ SIGNATURES = {
     "ia_adamw_step_segmented_si": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _i,
                                         _vp, _vp, _vp, _vp, _f, _vp]),
     "ia_si_consolidate": (_i, [_vp, _vp, _vp, _vp, _f, _i64, _vp]),
+    "ia_adamw_step_segmented_rwalk": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _f, _f, _vp, _vp, _i, _vp, _vp,
+                                           _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _i, _vp]),
+    "ia_rwalk_workspace_bytes": (_sz, [_i]),
+    "ia_rwalk_consolidate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i64, _vp, _i, _vp, _sz, _vp]),
     "ia_agem_workspace_bytes": (_sz, [_i]),
     "ia_agem_dots": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),
     "ia_grad_norm_projected": (_i, [_vp, _vp, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),

@@ -390,6 +390,154 @@ class SynapticIntelligence:
         self.tasks_consolidated = int(sd["tasks_consolidated"])
 
 
+# ----------------------------------------------------------------------------- Riemannian Walk
+class RWalk:
+    """Riemannian Walk (Chaudhry, Dokania, Ajanthan, Torr, ECCV 2018): EWC with a Fisher that is maintained online, as a moving
+    average of the squared task gradient inside the optimizer step (the paper's EWC++: no Fisher epoch after a language), joined
+    with a path score -- SI's path integral measured in that Fisher's metric.  The two are normalised by their maxima and summed
+    into one importance.
+
+    Flat fp32 buffers over the layout: `fisher` F (carried across languages, never reset), `importance` (what the penalty
+    uses) and `theta_star` (the weights at the end of the previous language); with `scores=True` also `w` (the path integral of
+    the current interval), `anchor` (the weights at the last fold), `score` (of the current language) and `score_acc` (the mean
+    normalised score of the finished languages): 28 B per parameter, 12 with `scores=False` (EWC++ alone).  Attach it with
+    `FusedAdamW(..., path_integral=rw)`.  Every applied update then does, per element of a tensor that received a gradient, with
+    ge the (data-parallel averaged) task gradient:
+        F += alpha * (ge * ge - F);   w -= ge * (theta' - theta)
+    and every `interval`-th applied update (`calls % interval == 0`, deferred updates counted when they are applied) folds:
+        score += max(0, w) / (0.5 * F * (theta' - anchor)^2 + eps);   w = 0;   anchor = theta'
+    Once a language is consolidated the step adds `2 * rw_lambda * importance * (theta - theta_star)` to what AdamW consumes --
+    AFTER the clip, as for SynapticIntelligence, and every tensor is live then.  A step skipped as non-finite changes no buffer
+    and drops a fold that was due: `w` waits for the next one.
+
+    `consolidate()` at the end of a language, on the device with nothing read back: one more fold; maxF = max F and maxS = max
+    score; a = F / maxF and b = score / maxS (0 where the maximum is 0; F and score themselves with `normalize=False`);
+    `score_acc = b` for the first language, else `0.5 * (score_acc + b)`; `importance = a + score_acc` (a alone without
+    scores); `score = 0`, `w = 0`, `theta_star = anchor = theta`.  The maxima stay on the device in `last_maxima`.  Non-finite
+    maxima are not guarded: `skip_nonfinite` on the optimizer is what keeps inf and NaN out of F and w.
+
+    `importance` and `fisher` are FlatDicts: `TaskVectors.store(lang, opt, importance=rw.importance)` and the EWC helpers take
+    them as they take an epoch's Fisher."""
+
+    _BUFFERS = ("fisher", "importance", "theta_star", "w", "anchor", "score", "score_acc")
+
+    def __init__(self, model_or_flat, rw_lambda=1.0, alpha=0.9, interval=50, eps=1e-3, scores=True, normalize=True):
+        self._check(alpha, interval, eps, "RWalk")
+        self.flat = model_or_flat if isinstance(model_or_flat, FlatParams) else flat_of(model_or_flat)
+        self.rw_lambda, self.alpha, self.interval, self.eps = float(rw_lambda), float(alpha), int(interval), float(eps)
+        self.scores, self.normalize = bool(scores), bool(normalize)
+        flush_pending_updates()
+        self.fisher = self.flat.zeros()
+        self.importance = self.flat.zeros()
+        self.theta_star = FlatDict(self.flat, self.flat.theta.clone())
+        self.w = self.flat.zeros() if self.scores else None
+        self.anchor = FlatDict(self.flat, self.flat.theta.clone()) if self.scores else None
+        self.score = self.flat.zeros() if self.scores else None
+        self.score_acc = self.flat.zeros() if self.scores else None
+        self.last_maxima = torch.zeros(2, dtype=torch.float32, device=self.flat.theta.device)    # {maxF, maxS}
+        self._ws = None
+        self.calls = 0                      # updates applied by the attached optimizer
+        self.tasks_consolidated = 0
+
+    @staticmethod
+    def _check(alpha, interval, eps, who):
+        if not 0.0 < float(alpha) <= 1.0:
+            raise ValueError(f"{who}: alpha must be in (0, 1] (got {alpha})")
+        if not float(eps) > 0.0:
+            raise ValueError(f"{who}: eps must be > 0 (got {eps})")
+        if int(interval) != interval or int(interval) < 1:
+            raise ValueError(f"{who}: interval must be an integer >= 1 (got {interval})")
+
+    @classmethod
+    def from_config(cls, model_or_flat, config, **kw):
+        """`cl_config.rwalk_lambda` / `rwalk_alpha` / `rwalk_interval` / `rwalk_eps` when the config has them (the reference's
+        config.yaml has none of these keys)."""
+        cc = getattr(config, "cl_config", None) or {}
+        return cls(model_or_flat, rw_lambda=cc.get("rwalk_lambda", 1.0), alpha=cc.get("rwalk_alpha", 0.9),
+                   interval=cc.get("rwalk_interval", 50), eps=cc.get("rwalk_eps", 1e-3), **kw)
+
+    def _buffers(self) -> Dict[str, FlatDict]:
+        return {k: getattr(self, k) for k in self._BUFFERS if getattr(self, k) is not None}
+
+    def _next_fold(self) -> int:
+        """Called by the optimizer once per applied update: counts it and says whether this one folds."""
+        self.calls += 1
+        return int(self.scores and self.calls % self.interval == 0)
+
+    def penalty_value(self) -> torch.Tensor:
+        """Sum importance * (theta - theta_star)^2 as a 0-dim device tensor (un-weighted, as 'mass_loss').  One pass over three
+        flat buffers: call it only when the value is logged."""
+        flush_pending_updates()
+        f = self.flat
+        val = torch.zeros(1, dtype=torch.float32, device=f.theta.device)
+        st = _lib.lib().ia_cl_penalty(_lib.ptr(f.theta), _lib.ptr(self.theta_star.flat), _lib.ptr(self.importance.flat), 0.0, None,
+                                      0, _lib.ptr(f.chunk_table), f.chunk_table.shape[0], None, None, _lib.ptr(val),
+                                      _lib.stream_ptr())
+        _lib.check(st, "ia_cl_penalty")
+        return val[0]
+
+    def consolidate(self):
+        """End of a language (three launches, no host read).  Under data parallelism every rank holds the same buffers, so no
+        collective is needed."""
+        flush_pending_updates()
+        f, L, ptr = self.flat, _lib.lib(), _lib.ptr
+        nchunks = f.chunk_table.shape[0]
+        if self._ws is None:
+            self._ws = torch.empty(L.ia_rwalk_workspace_bytes(nchunks), dtype=torch.uint8, device=f.theta.device)
+        fp = lambda d: ptr(d.flat) if d is not None else None      # the score buffers are absent with scores=False
+        st = L.ia_rwalk_consolidate(ptr(f.theta), ptr(self.theta_star.flat), ptr(self.fisher.flat), fp(self.w), fp(self.anchor),
+                                    fp(self.score), fp(self.score_acc), ptr(self.importance.flat), ptr(self.last_maxima),
+                                    self.eps, int(self.normalize), int(self.tasks_consolidated == 0), f.numel,
+                                    ptr(f.chunk_table), nchunks, ptr(self._ws), self._ws.numel(), _lib.stream_ptr())
+        _lib.check(st, "ia_rwalk_consolidate")
+        self.tasks_consolidated += 1
+
+    def flat_dicts(self) -> Dict[str, FlatDict]:
+        """For `checkpoint.save_cl_state(path, **rw.flat_dicts())`; `load_flat_dicts(checkpoint.load_cl_state(path, flat))` is
+        the way back."""
+        flush_pending_updates()
+        return {"rw_" + k: d for k, d in self._buffers().items()}
+
+    def load_flat_dicts(self, dicts, tasks_consolidated=None, calls=0):
+        """Copies the buffers in place (an attached optimizer keeps pointing at them).  The file carries neither count: unless
+        given, the penalty counts as attached (tasks_consolidated = 1) when the loaded importance has a non-zero entry."""
+        flush_pending_updates()
+        mine = self.flat_dicts()
+        for key in mine:
+            if key not in dicts:
+                raise ValueError(f"'{key}' is missing (saved with scores={not self.scores}?)")
+            if dicts[key].layout.entries != self.flat.entries:
+                raise ValueError(f"'{key}' was saved for a different set of trainable tensors")
+        for key, d in mine.items():
+            d.flat.copy_(dicts[key].flat)
+        if tasks_consolidated is None:
+            tasks_consolidated = int(bool(self.importance.flat.any()))
+        self.tasks_consolidated, self.calls = int(tasks_consolidated), int(calls)
+
+    def state_dict(self) -> dict:
+        flush_pending_updates()
+        sd = {"entries": list(self.flat.entries), "rw_lambda": self.rw_lambda, "alpha": self.alpha, "interval": self.interval,
+              "eps": self.eps, "scores": self.scores, "normalize": self.normalize, "calls": self.calls,
+              "tasks_consolidated": self.tasks_consolidated}
+        for k, d in self._buffers().items():
+            sd[k] = d.flat.detach().to("cpu", copy=True)
+        return sd
+
+    def load_state_dict(self, sd: dict, source="state dict"):
+        if [tuple(e[:3]) + (tuple(e[3]),) for e in sd["entries"]] != list(self.flat.entries):
+            raise ValueError(f"{source}: 'rwalk' was saved for a different set of trainable tensors")
+        if bool(sd["scores"]) != self.scores:
+            raise ValueError(f"{source}: 'rwalk' was saved with scores={bool(sd['scores'])}, this one has scores={self.scores}")
+        self._check(sd["alpha"], sd["interval"], sd["eps"], source)
+        flush_pending_updates()
+        for k, d in self._buffers().items():
+            d.flat.copy_(sd[k])
+        self.rw_lambda, self.alpha, self.interval, self.eps = (float(sd["rw_lambda"]), float(sd["alpha"]), int(sd["interval"]),
+                                                               float(sd["eps"]))
+        self.normalize = bool(sd["normalize"])
+        self.calls, self.tasks_consolidated = int(sd["calls"]), int(sd["tasks_consolidated"])
+
+
 # ----------------------------------------------------------------------------- A-GEM
 class AveragedGEM:
     """Averaged GEM (Chaudhry, Ranzato, Rohrbach, Elhoseiny, ICLR 2019): the gradient `ref` of a batch drawn from an episodic
@@ -2289,7 +2437,7 @@ class FusedAdamW(torch.optim.Optimizer):
         on the device: `last_grad_norm`, `stats()`, `grad_norms()`.  With all three at their defaults the step is the plain
         ia_adamw_step_segmented.  `max_grad_norm` / `skip_nonfinite` live in param_groups[0] and are read per step, as lr is.
         The entry points named here and below are reached through ia_adamw_step_segmented_grouped (one group or many), whose
-        operands select the same step; only masks (Piggyback, PackNet) and GEM have entry points of their own.
+        operands select the same step; only masks (Piggyback, PackNet), GEM and RWalk have entry points of their own.
 
         `grad_exchange_dtype="bf16"` ("fp32 or bf16"): the data-parallel exchange all-reduces a bf16 image of the
         flat gradient (half the bytes over xGMI: 80 instead of 160 MB per step at 40 M trainable parameters); every rank
@@ -2300,6 +2448,10 @@ class FusedAdamW(torch.optim.Optimizer):
         the surrogate's gradient 2 * si_c * omega * (theta - theta_star) -- AFTER the clip: norm and coefficient stay those of
         the task gradient (torch's clip_grad_norm_ on `loss + surrogate` would clip the total).  Every tensor is live then.
         The SI buffers are not optimizer state: they are saved through si.state_dict() / si.flat_dicts().
+        `path_integral=rw` (an `RWalk`): the step runs ia_adamw_step_segmented_rwalk, which takes the group table itself.  It
+        keeps rw.fisher as a moving average of the squared averaged task gradient, integrates rw.w as SI does and, on every
+        rw.interval-th applied update, folds the path into rw.score; once rw.tasks_consolidated > 0 it adds
+        2 * rw_lambda * importance * (theta - theta_star) after the clip.  Saved through rw.state_dict() / rw.flat_dicts().
 
         `projection=agem` (an `AveragedGEM` on the same FlatParams): once agem.has_reference, the step runs ia_agem_dots,
         ia_grad_norm_projected (if the norm is measured) and ia_adamw_step_segmented_projected: the averaged task gradient is
@@ -2593,6 +2745,13 @@ class FusedAdamW(torch.optim.Optimizer):
         if pb is not None:
             _lib.check(L.ia_adamw_step_segmented_masked(*common, ptr(pb.base.flat), ptr(pb.scores.flat), ptr(pb.seg_kind),
                                                         pb.threshold, stream), "ia_adamw_step_segmented_masked")
+            return self._after_update()
+        if isinstance(si, RWalk):       # agem is None here: projection and path_integral are refused together
+            rw, fp = si, lambda d: ptr(d.flat) if d is not None else None
+            _lib.check(L.ia_adamw_step_segmented_rwalk(
+                *common, ptr(rw.fisher.flat), fp(rw.w), fp(rw.anchor), fp(rw.score),
+                ptr(rw.importance.flat) if penalised else None, ptr(rw.theta_star.flat) if penalised else None,
+                rw.rw_lambda, rw.alpha, rw.eps, rw._next_fold(), stream), "ia_adamw_step_segmented_rwalk")
             return self._after_update()
         # plain, clipped, SI or projected: the operands that are present select the variant
         _lib.check(L.ia_adamw_step_segmented_grouped(

@@ -6,6 +6,7 @@
 //   ia_cl_abs_accumulate ..... R/cl_baseline_mas.py:267-270  omega += |g|
 //   ia_adamw_step ............ torch.optim.AdamW single-tensor update (R/cl_baseline.py:137 defaults)
 //   ia_si_consolidate ........ end of a task: omega += max(0, w / ((theta-theta*)^2 + xi)), w = 0, theta* = theta
+//   ia_rwalk_consolidate ..... end of a language: last fold, device-side maxima, importance = F / max F + mean of score / max score
 //   ia_mask_pack, ia_mask_apply .. Piggyback's scores as one bit per weight, and the bits back to weights
 //
 // The per-tensor ("segmented") AdamW step, ia_adamw_step_segmented*, is ONE kernel, ONE update rule and ONE host routine:
@@ -20,6 +21,8 @@
 //       plain_step             consumed_step<scaled_grad>: g * grad_scale [* coef]           ia_adamw_step_segmented[_clipped]
 //       si_step<PEN>           Synaptic Intelligence: [+ 2c*omega*(theta-theta*)] after the clip, and the path integral
 //                              w -= ge * (theta' - theta)                                     ia_adamw_step_segmented_si
+//       rwalk_step<PEN, SCORES, FOLD>   Riemannian Walk: si_step's gradient and path integral, a running Fisher
+//                              F += alpha * (ge*ge - F) and, on a fold, the path score in F's metric    ia_adamw_step_segmented_rwalk
 //       agem_step              consumed_step<agem_source>: g * s - alpha * r when g.r < 0     ia_adamw_step_segmented_projected
 //       gem_step               consumed_step<gem_source>: g * s + sum_k v_k * r_k             ia_adamw_step_segmented_gem
 //       masked_step            Piggyback, per tensor a kind: masked (the scores are trained on g * base and
@@ -442,6 +445,187 @@ __global__ __launch_bounds__(CL_THREADS) void si_consolidate_kernel(const float*
             si_consolidate1(theta[i], S, W, O, xi);
             star[i] = S; path_w[i] = W; omega[i] = O;
         }
+}
+
+// ---- Riemannian Walk (Chaudhry, Dokania, Ajanthan, Torr 2018) inside the AdamW launch: a running Fisher (EWC++) and, with
+// SCORES, SI's path integral scored in that Fisher's metric.  Per element of a live tensor, each operation rounded on its own:
+//   ge, G, theta', m, v       as si_step: the penalty (PEN) uses the consolidated importance, added after the clip
+//   F' = F + alpha * (ge*ge - F)                       the moving average of the squared task gradient
+//   w' = si_path(w, ge, theta', theta)                 (SCORES)
+//   FOLD: score += max(0, w') / (0.5*F' * (theta' - anchor)^2 + eps);  w = 0;  anchor = theta'
+// A variant loads and stores only what its flags need: 8 B per element for F, 8 for w, 16 for anchor and score, 8 for the penalty.
+__device__ __forceinline__ float rw_fisher(float F, float ge, float alpha) {
+#pragma clang fp contract(off)
+    const float sq = ge * ge;
+    const float df = sq - F;
+    const float t = alpha * df;
+    return F + t;
+}
+
+// One fold of the path integral into the score: six roundings on the increment (0.5 * F is exact)
+__device__ __forceinline__ float rw_fold(float score, float w, float theta, float anchor, float F, float eps) {
+#pragma clang fp contract(off)
+    const float d = theta - anchor;
+    const float dd = d * d;
+    const float h = 0.5f * F;
+    const float u = h * dd;
+    const float den = u + eps;
+    const float q = fmaxf(0.f, w) / den;
+    return score + q;
+}
+
+template <bool PEN, bool SCORES, bool FOLD>
+struct rwalk_step {
+    static_assert(SCORES || !FOLD, "a fold needs the path integral");
+    float *fisher, *path_w, *anchor, *score; const float *omega, *star; float c2, alpha, fold_eps;
+    static constexpr bool reads_theta = true;
+    __device__ __forceinline__ rwalk_step begin() const { return *this; }
+    template <bool CLIP, int W>
+    __device__ __forceinline__ void apply(vecf<W>& P, const vecf<W>& G, vecf<W>& M, vecf<W>& V, int64_t at,
+                                          const chunk_consts& k) const {
+        vecf<W> F = ldv<W>(fisher, at), Pw = {}, A = {}, Sc = {}, O = {}, S = {};
+        if constexpr (SCORES) Pw = ldv<W>(path_w, at);
+        if constexpr (FOLD) { A = ldv<W>(anchor, at); Sc = ldv<W>(score, at); }
+        if constexpr (PEN) { O = ldv<W>(omega, at); S = ldv<W>(star, at); }
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            const float ge = mul_rn(G[j], k.grad_scale), p_old = P[j];
+            adamw1_rn<W == 1>(P[j], si_grad<PEN>(eff_grad<CLIP>(ge, k), p_old, O[j], S[j], c2), M[j], V[j], k.decay, k);
+            F[j] = rw_fisher(F[j], ge, alpha);
+            if constexpr (SCORES) Pw[j] = si_path(Pw[j], ge, P[j], p_old);
+            if constexpr (FOLD) {
+                Sc[j] = rw_fold(Sc[j], Pw[j], P[j], A[j], F[j], fold_eps);
+                Pw[j] = 0.f;
+            }
+        }
+        stv<W>(fisher, at, F);
+        if constexpr (SCORES) stv<W>(path_w, at, Pw);
+        if constexpr (FOLD) { stv<W>(anchor, at, P); stv<W>(score, at, Sc); }
+    }
+};
+
+// End of a language, three launches, nothing read back and no float atomic (a maximum has no rounding: any order gives the bits).
+//   rwalk_fold_max_kernel<SCORES>   workgroup c leaves {max F, max score} of chunk c in chunk_max[c]; with SCORES every element
+//                                   is folded once more first (rw_fold; a dead tensor has w == 0: +0), w = 0, anchor = theta
+//   rwalk_max_finish_kernel         one workgroup: maxima = {max F, max score} over all chunks
+//   rwalk_combine_kernel<SCORES>    a = F / maxF, b = score / maxS (0 where the maximum is 0; F and score themselves when
+//                                   !normalize); score_acc = first ? b : 0.5 * (score_acc + b); importance = a + score_acc
+//                                   (a without SCORES); score = 0; theta_star = theta
+// All buffers are >= 0 (F by its recurrence with alpha in (0, 1], score as a sum of max(0, .) quotients), so the maxima start at 0,
+// which is also the value of the alignment gaps the chunk table does not visit.
+__device__ __forceinline__ float block_max(float v, float* sh) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) v = fmaxf(v, __shfl_xor(v, d));
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 0) sh[wave] = v;
+    __syncthreads();
+    float t = sh[0];
+#pragma unroll
+    for (int i = 1; i < CL_THREADS / 64; ++i) t = fmaxf(t, sh[i]);
+    return t;
+}
+
+template <bool SCORES, int W>
+__device__ __forceinline__ void rwalk_fold_max_vec(const float* __restrict__ theta, const float* __restrict__ fisher,
+                                                   float* __restrict__ path_w, float* __restrict__ anchor,
+                                                   float* __restrict__ score, float eps, int at, float& mf, float& ms) {
+    const vecf<W> F = ldv<W>(fisher, at);
+#pragma unroll
+    for (int j = 0; j < W; ++j) mf = fmaxf(mf, F[j]);
+    if constexpr (SCORES) {
+        const vecf<W> T = ldv<W>(theta, at), Pw = ldv<W>(path_w, at), A = ldv<W>(anchor, at);
+        vecf<W> Sc = ldv<W>(score, at), Z = {};
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            Sc[j] = rw_fold(Sc[j], Pw[j], T[j], A[j], F[j], eps);
+            ms = fmaxf(ms, Sc[j]);
+        }
+        stv<W>(score, at, Sc);
+        stv<W>(path_w, at, Z);
+        stv<W>(anchor, at, T);
+    }
+}
+
+template <bool SCORES>
+__global__ __launch_bounds__(CL_THREADS) void rwalk_fold_max_kernel(const float* __restrict__ theta,
+                                                                    const float* __restrict__ fisher, float* __restrict__ path_w,
+                                                                    float* __restrict__ anchor, float* __restrict__ score,
+                                                                    float eps, const int4* __restrict__ table, int nchunks,
+                                                                    float2* __restrict__ chunk_max) {
+    __shared__ float sh[CL_THREADS / 64];
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const int4 e = table[c];
+        const int off = e.x, cnt = e.y, n4 = cnt >> 2;
+        float mf = 0.f, ms = 0.f;
+        for (int q = threadIdx.x; q < n4; q += CL_THREADS)
+            rwalk_fold_max_vec<SCORES, 4>(theta, fisher, path_w, anchor, score, eps, off + (q << 2), mf, ms);
+        for (int i = (n4 << 2) + threadIdx.x; i < cnt; i += CL_THREADS)
+            rwalk_fold_max_vec<SCORES, 1>(theta, fisher, path_w, anchor, score, eps, off + i, mf, ms);
+        mf = block_max(mf, sh);
+        if constexpr (SCORES) ms = block_max(ms, sh);
+        if (threadIdx.x == 0) chunk_max[c] = make_float2(mf, ms);
+    }
+}
+
+__global__ __launch_bounds__(CL_THREADS) void rwalk_max_finish_kernel(const float2* __restrict__ chunk_max, int nchunks,
+                                                                      float* __restrict__ maxima) {
+    __shared__ float sh[CL_THREADS / 64];
+    float mf = 0.f, ms = 0.f;
+    for (int c = threadIdx.x; c < nchunks; c += CL_THREADS) {
+        const float2 x = chunk_max[c];
+        mf = fmaxf(mf, x.x);
+        ms = fmaxf(ms, x.y);
+    }
+    mf = block_max(mf, sh);
+    ms = block_max(ms, sh);
+    if (threadIdx.x == 0) { maxima[0] = mf; maxima[1] = ms; }
+}
+
+__device__ __forceinline__ float rw_share(float x, float mx, bool normalize) {
+    return !normalize ? x : (mx == 0.f ? 0.f : x / mx);
+}
+
+template <bool SCORES, int W>
+__device__ __forceinline__ void rwalk_combine_vec(const float* __restrict__ theta, float* __restrict__ star,
+                                                  const float* __restrict__ fisher, float* __restrict__ score,
+                                                  float* __restrict__ score_acc, float* __restrict__ importance, float mf,
+                                                  float ms, bool normalize, bool first, int64_t at) {
+    const vecf<W> F = ldv<W>(fisher, at);
+    vecf<W> Om;
+    if constexpr (SCORES) {
+        const vecf<W> Sc = ldv<W>(score, at);
+        vecf<W> Acc = {}, Z = {};
+        if (!first) Acc = ldv<W>(score_acc, at);
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            const float b = rw_share(Sc[j], ms, normalize);
+            Acc[j] = first ? b : mul_rn(0.5f, add_rn(Acc[j], b));
+            Om[j] = add_rn(rw_share(F[j], mf, normalize), Acc[j]);
+        }
+        stv<W>(score_acc, at, Acc);
+        stv<W>(score, at, Z);
+    } else {
+#pragma unroll
+        for (int j = 0; j < W; ++j) Om[j] = rw_share(F[j], mf, normalize);
+    }
+    stv<W>(importance, at, Om);
+    stv<W>(star, at, ldv<W>(theta, at));
+}
+
+template <bool SCORES>
+__global__ __launch_bounds__(CL_THREADS) void rwalk_combine_kernel(const float* __restrict__ theta, float* __restrict__ star,
+                                                                   const float* __restrict__ fisher, float* __restrict__ score,
+                                                                   float* __restrict__ score_acc, float* __restrict__ importance,
+                                                                   const float* __restrict__ maxima, int normalize, int first,
+                                                                   int64_t n) {
+    const float mf = maxima[0], ms = maxima[1];
+    const int64_t n4 = n >> 2;
+    for (int64_t q = (int64_t)blockIdx.x * CL_THREADS + threadIdx.x; q < n4; q += (int64_t)gridDim.x * CL_THREADS)
+        rwalk_combine_vec<SCORES, 4>(theta, star, fisher, score, score_acc, importance, mf, ms, normalize, first, q << 2);
+    if (blockIdx.x == 0)
+        for (int64_t i = (n4 << 2) + threadIdx.x; i < n; i += CL_THREADS)
+            rwalk_combine_vec<SCORES, 1>(theta, star, fisher, score, score_acc, importance, mf, ms, normalize, first, i);
 }
 
 // ---- Averaged GEM (Chaudhry, Ranzato, Rohrbach, Elhoseiny 2019).  r is the gradient of a batch drawn from the episodic memory,
@@ -1612,6 +1796,15 @@ inline bool si_operands_ok(const float* path_w, const float* omega, const float*
     return ia_is_aligned(path_w, 16) && (!omega || (ia_is_aligned(omega, 16) && ia_is_aligned(theta_star, 16)));
 }
 
+inline bool rwalk_operands_ok(const float* fisher, const float* path_w, const float* anchor, const float* score,
+                              const float* importance, const float* theta_star) {
+    const bool scores = path_w || anchor || score;
+    if (!fisher || (scores && (!path_w || !anchor || !score)) || (importance == nullptr) != (theta_star == nullptr)) return false;
+    return ia_is_aligned(fisher, 16) && (!scores || (ia_is_aligned(path_w, 16) && ia_is_aligned(anchor, 16) &&
+                                                     ia_is_aligned(score, 16))) &&
+           (!importance || (ia_is_aligned(importance, 16) && ia_is_aligned(theta_star, 16)));
+}
+
 inline bool proj_operands_ok(const float* ref, const float* proj_state, const int32_t* proj_counters) {
     if (!ref || !proj_state || !proj_counters) return false;
     return ia_is_aligned(ref, 16) && ia_is_aligned(proj_state, 4) && ia_is_aligned(proj_counters, 4);
@@ -1798,6 +1991,73 @@ extern "C" int ia_si_consolidate(const float* theta, float* theta_star, float* p
         return IA_INVALID_VALUE;
     hipLaunchKernelGGL(si_consolidate_kernel, dim3(cap_grid(n >> 2, CL_THREADS * 4)), dim3(CL_THREADS), 0, (hipStream_t)stream,
                        theta, theta_star, path_w, omega, xi, n);
+    IA_RETURN_IF_LAUNCH_FAILED();
+    return IA_OK;
+}
+
+// The operands that are present select the variant: path_w, anchor and score together (scores) or none of them (EWC++ alone);
+// importance and theta_star together (a language has been consolidated) or neither; a fold only with scores.
+extern "C" int ia_adamw_step_segmented_rwalk(float* theta, const float* grad, float* exp_avg, float* exp_avg_sq,
+                                             const int32_t* chunk_table, int nchunks, int32_t* seg_active, int32_t* seg_step,
+                                             int nseg, int all_active, float beta1, float beta2, float eps, float grad_scale,
+                                             void* shadow_bf16, const int32_t* seg_group, int ngroups, const float* group_lr,
+                                             const float* group_weight_decay, const float* norm_state, int skip_nonfinite,
+                                             int32_t* counters, float* fisher, float* path_w, float* anchor, float* score,
+                                             const float* importance, const float* theta_star, float penalty_coef, float alpha,
+                                             float fold_eps, int fold, ia_stream_t stream) {
+    const step_head h = make_head(theta, grad, exp_avg, exp_avg_sq, chunk_table, nchunks, seg_active, seg_step, nseg, all_active,
+                                  beta1, beta2, eps, grad_scale, shadow_bf16, seg_group, norm_state, skip_nonfinite, counters);
+    const bool scores = path_w || anchor || score, pen = importance || theta_star;
+    if (!head_ok(h) || !groups_ok(seg_group, ngroups, group_lr, group_weight_decay) ||
+        !rwalk_operands_ok(fisher, path_w, anchor, score, importance, theta_star) || (fold && !scores) ||
+        !(alpha > 0.f && alpha <= 1.f) || !(fold_eps > 0.f))
+        return IA_INVALID_VALUE;
+    const group_table gt = make_group_table(ngroups, group_lr, group_weight_decay);
+    const float c2 = 2.f * penalty_coef;
+    const auto run = [&](auto p, auto s, auto f) {
+        return run_step(h, gt, rwalk_step<p(), s(), f()>{fisher, path_w, anchor, score, importance, theta_star, c2, alpha,
+                                                         fold_eps}, step_extras{}, (hipStream_t)stream);
+    };
+    constexpr std::true_type yes;
+    constexpr std::false_type no;
+    if (pen) return !scores ? run(yes, no, no) : fold ? run(yes, yes, yes) : run(yes, yes, no);
+    return !scores ? run(no, no, no) : fold ? run(no, yes, yes) : run(no, yes, no);
+}
+
+extern "C" size_t ia_rwalk_workspace_bytes(int nchunks) { return nchunks > 0 ? (size_t)nchunks * 2 * sizeof(float) : 0; }
+
+extern "C" int ia_rwalk_consolidate(const float* theta, float* theta_star, const float* fisher, float* path_w, float* anchor,
+                                    float* score, float* score_acc, float* importance, float* maxima, float fold_eps,
+                                    int normalize, int first, int64_t n, const int32_t* chunk_table, int nchunks, void* workspace,
+                                    size_t workspace_bytes, ia_stream_t stream) {
+    const bool scores = path_w || anchor || score || score_acc;
+    if (!theta || !theta_star || !fisher || !importance || !maxima || !chunk_table || !workspace || n <= 0 || nchunks <= 0 ||
+        (scores && (!path_w || !anchor || !score || !score_acc)) || !(fold_eps > 0.f))
+        return IA_INVALID_VALUE;
+    if (!ia_is_aligned(theta, 16) || !ia_is_aligned(theta_star, 16) || !ia_is_aligned(fisher, 16) ||
+        !ia_is_aligned(importance, 16) || !ia_is_aligned(maxima, 4) || !ia_is_aligned(chunk_table, 16) ||
+        !ia_is_aligned(workspace, 8) ||
+        (scores && (!ia_is_aligned(path_w, 16) || !ia_is_aligned(anchor, 16) || !ia_is_aligned(score, 16) ||
+                    !ia_is_aligned(score_acc, 16))))
+        return IA_INVALID_VALUE;
+    if (workspace_bytes < ia_rwalk_workspace_bytes(nchunks)) return IA_WORKSPACE_TOO_SMALL;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(chunk_grid(nchunks)), flat_grid(cap_grid(n >> 2, CL_THREADS * 4)), block(CL_THREADS);
+    const int4* table = (const int4*)chunk_table;
+    float2* chunk_max = (float2*)workspace;
+    if (scores)
+        hipLaunchKernelGGL(rwalk_fold_max_kernel<true>, grid, block, 0, st, theta, fisher, path_w, anchor, score, fold_eps, table,
+                           nchunks, chunk_max);
+    else
+        hipLaunchKernelGGL(rwalk_fold_max_kernel<false>, grid, block, 0, st, theta, fisher, path_w, anchor, score, fold_eps, table,
+                           nchunks, chunk_max);
+    hipLaunchKernelGGL(rwalk_max_finish_kernel, dim3(1), block, 0, st, (const float2*)chunk_max, nchunks, maxima);
+    if (scores)
+        hipLaunchKernelGGL(rwalk_combine_kernel<true>, flat_grid, block, 0, st, theta, theta_star, fisher, score, score_acc,
+                           importance, (const float*)maxima, normalize, first, n);
+    else
+        hipLaunchKernelGGL(rwalk_combine_kernel<false>, flat_grid, block, 0, st, theta, theta_star, fisher, score, score_acc,
+                           importance, (const float*)maxima, normalize, first, n);
     IA_RETURN_IF_LAUNCH_FAILED();
     return IA_OK;
 }
