@@ -1396,6 +1396,28 @@ int ia_ctc_align(const float* lp, int ld, const float* lse, const int64_t* targe
                  const int64_t* target_lens, int B, int T, int V, int S, int blank, int32_t* path, int32_t* spans, float* score,
                  void* workspace, size_t workspace_bytes, ia_stream_t stream);
 
+/* ---- CTC prefix beam search (csrc/ctc_beam.hip): the sum-product sibling of the aligner, the algorithm of Hannun et al. 2014
+ * (arXiv:1408.2873) in log space, one launch, one persistent workgroup per utterance.  The beam holds at most W distinct label
+ * prefixes, each with pb / pnb = log-probability of the alignments of the frames so far that collapse to it and end in blank /
+ * in a non-blank; start: the empty prefix, pb = 0, pnb = -inf.  Frame t < len, member l in slot i with last label e and
+ * p = pb (+) pnb:   stay: l gets pb' (+)= p + lp[t,blank] and, if non-empty, pnb' (+)= pnb + lp[t,e];
+ *                   extend by c != blank (skipped when lp[t,c] < token_min_logp): l+c gets pnb' (+)= (c == e ? pb : p) + lp[t,c].
+ * Candidates that denote the same prefix are ONE candidate and their contributions add (an extension that equals another beam
+ * member merges with that member's stay).  The new beam: the W candidates with the largest pb' (+) pnb', ties to the smaller
+ * candidate id i V + c (a stay uses c = blank; a merged candidate keeps its smallest id).  Prefix identity is exact: a
+ * canonical trie of (parent, token) nodes in the workspace, looked up through an open-addressing table.
+ *   x, ld, lse, in_lens: as ia_ctc_align (lse NULL: x holds log-probs; in_lens i64, clamped to [0,T], never followed).
+ *   tokens  [B,W,T] i32: the hypotheses by descending score (same tie rule), each padded with -1.
+ *   lengths [B,W] i32, -1 for slots the beam never filled;  scores [B,W] f32 = pb (+) pnb, -inf for unfilled slots.
+ *   len = 0 yields the empty prefix with score 0.  token_min_logp = -inf switches the pruning off.
+ *   workspace: ia_ctc_beam_workspace_bytes(B,T,V,W), 256-byte aligned; 0 when W > ia_ctc_beam_max_width() = 32 or V > 1024,
+ *   where ia_ctc_beam_search returns IA_UNSUPPORTED.  Two launches on the same input agree bit for bit (no float atomics). */
+int ia_ctc_beam_max_width(void);
+size_t ia_ctc_beam_workspace_bytes(int B, int T, int V, int W);
+int ia_ctc_beam_search(const float* x, const float* lse, const int64_t* in_lens, int B, int T, int ld, int V, int blank, int W,
+                       float token_min_logp, int32_t* tokens, int32_t* lengths, float* scores, void* workspace,
+                       size_t workspace_bytes, ia_stream_t stream);
+
 /* ---- Glue of the step's tail (csrc/tail_ops.hip): each replaces a handful of small ATen launches.
  * ia_select_rows_cast  rows [row0, row0+nrows) (+ extra_row if >= 0) of W [*, K] f32 (row stride ldw), times `scale`, as a 16-bit
  *                      operand out [rows_out, K] (bf16, or f16 when out_f16; rows beyond the selection zero); optionally the

@@ -9,10 +9,16 @@
   read per micro-step) -- greedy_rnnt_decode dispatches to it; the host-driven loop stays as greedy_rnnt_decode_host
   (CPU tensors, and the cross-check of the kernel in tests).
 * greedy_ctc_decode   -- GreedyCTCInfer (ctc_greedy_decoding.py:145-229): argmax, collapse repeats, drop blanks.
+* beam_ctc_decode     -- CTC prefix beam search without a language model (Hannun et al. 2014, arXiv:1408.2873), what
+  CTCBPEDecoding's `strategy: beam` stands for (NeMo delegates it to KenLM-backed ctc_decoders, pyctcdecode or flashlight; the
+  algorithm is reproduced, not their bits): N-best Hypothesis objects with scores.  Device tensors run csrc/ctc_beam.hip
+  (one launch per batch), CPU tensors the float64 host routine beam_ctc_decode_host of the same definition.
 * word_error_rate / WER -- A/metrics/wer.py:293-360: sum of edit distances over sum of reference lengths.  Hypotheses
   and references are sequences of tokens here; pass `detokenize` (ids -> str) to score words as the reference does
   (its SentencePiece models are not part of the repository).
 """
+import warnings
+from dataclasses import dataclass
 from typing import Callable, List, Optional, Sequence
 
 import torch
@@ -315,3 +321,174 @@ def greedy_ctc_decode(log_probs, lengths, blank: Optional[int] = None, defer: bo
         return PendingHyps(finish)
     host_k, host_keep = k.tolist(), keep.tolist()
     return [[v for v, m in zip(r, mk) if m] for r, mk in zip(host_k, host_keep)]
+
+
+# ---------------------------------------------------------------------------------------------------------- CTC prefix beam search
+@dataclass
+class Hypothesis:
+    """The fields of NeMo's rnnt_utils.Hypothesis that the search fills: `score` = log-probability of the labelling (all its
+    alignments), `y_sequence` = language-local token ids, `text` (filled by transcribe)."""
+    score: float
+    y_sequence: List[int]
+    text: Optional[str] = None
+
+
+@dataclass
+class NBestHypotheses:
+    """rnnt_utils.NBestHypotheses: the beam by descending score."""
+    n_best_hypotheses: Optional[List[Hypothesis]] = None
+
+
+_NEG_INF = float("-inf")
+_warned_beam_limit = False
+
+
+def beam_ctc_limits():
+    """(largest beam width, largest class count) csrc/ctc_beam.hip takes; beyond them beam_ctc_decode runs the host routine."""
+    from . import _lib
+    return int(_lib.lib().ia_ctc_beam_max_width()), 1024
+
+
+def beam_ctc_search_host(scores, lengths, beam_size=4, blank=None, lse=None, token_min_logp=None):
+    """CTC prefix beam search (Hannun et al. 2014, arXiv:1408.2873) in float64 on the host: the definition of
+    include/indicasr.h, which csrc/ctc_beam.hip follows too.  scores [B,T,V] log-probs, or logits with lse [B,T].
+    Returns per utterance a list of (token ids, score) by descending score, ties to the smaller candidate id.
+
+    Prefix identity is the node of a trie of (parent node, token) pairs kept in a dictionary; one frame is a [n, V] matrix
+    of candidate scores, the at most n extensions that denote a beam member folded into that member's stay."""
+    import numpy as np
+    x = scores.detach().double().cpu().numpy()
+    B, T, V = x.shape
+    blank = V - 1 if blank is None else int(blank)
+    W = int(beam_size)
+    if W < 1:
+        raise ValueError("Beam search size cannot be less than 1!")
+    if not 0 <= blank < V:
+        raise ValueError(f"blank={blank} outside the {V} classes")
+    if lse is not None:
+        x = x - lse.detach().double().cpu().numpy().reshape(B, T, 1)
+    lens = np.clip(lengths.detach().long().cpu().numpy().reshape(B), 0, T)
+    floor = _NEG_INF if token_min_logp is None else float(token_min_logp)
+    out = []
+    with np.errstate(invalid="ignore"):
+        for b in range(B):
+            parent, token, child = [-1], [-1], {}              # the trie: node -> (parent, token), (parent, token) -> node
+            node, pb, pnb = [0], np.array([0.0]), np.array([_NEG_INF])
+            for t in range(int(lens[b])):
+                lp = x[b, t]
+                n = len(node)
+                last = np.array([token[k] for k in node])
+                p = np.logaddexp(pb, pnb)
+                base = np.repeat(p[:, None], V, 1)
+                rows = np.nonzero(last >= 0)[0]
+                base[rows, last[rows]] = pb[rows]
+                c_pnb = base + lp[None, :]
+                c_pnb[:, lp < floor] = np.nan                  # not a candidate
+                c_pb = np.full((n, V), _NEG_INF)
+                c_pb[:, blank] = p + lp[blank]
+                c_pnb[:, blank] = _NEG_INF
+                c_pnb[rows, blank] = pnb[rows] + lp[last[rows]]
+                ids = np.arange(n * V).reshape(n, V)
+                slot = {k: i for i, k in enumerate(node)}
+                for j in rows:                                  # l_i + c is the beam member l_j: one candidate
+                    i = slot.get(parent[node[j]])
+                    c = last[j]
+                    if i is not None and not np.isnan(c_pnb[i, c]):
+                        c_pnb[j, blank] = np.logaddexp(c_pnb[j, blank], c_pnb[i, c])
+                        ids[j, blank] = min(ids[j, blank], ids[i, c])
+                        c_pnb[i, c] = np.nan
+                total = np.logaddexp(c_pb, c_pnb).ravel()
+                live = np.nonzero(~np.isnan(total))[0]
+                order = live[np.lexsort((ids.ravel()[live], -total[live]))][:W]
+                new_node, new_pb, new_pnb = [], [], []
+                for k in order:
+                    i, c = divmod(int(k), V)
+                    if c == blank:
+                        new_node.append(node[i])
+                    else:
+                        key = (node[i], c)
+                        if key not in child:
+                            child[key] = len(parent)
+                            parent.append(node[i]); token.append(c)
+                        new_node.append(child[key])
+                    new_pb.append(c_pb[i, c]); new_pnb.append(c_pnb[i, c])
+                node, pb, pnb = new_node, np.array(new_pb), np.array(new_pnb)
+            hyps = []
+            for k, s in zip(node, np.logaddexp(pb, pnb)):
+                y = []
+                while k > 0:
+                    y.append(int(token[k])); k = parent[k]
+                hyps.append((y[::-1], float(s)))
+            out.append(hyps)
+    return out
+
+
+def _beam_results(raw, return_best_hypothesis):
+    res = []
+    for hyps in raw:
+        hs = [Hypothesis(score=s, y_sequence=list(y)) for y, s in hyps]
+        res.append(hs[0] if return_best_hypothesis else NBestHypotheses(hs))
+    return res
+
+
+def beam_ctc_decode_host(scores, lengths, beam_size=4, blank=None, lse=None, token_min_logp=None, return_best_hypothesis=True):
+    """beam_ctc_decode on the host in float64 (CPU tensors; the cross-check of the kernel in tests)."""
+    return _beam_results(beam_ctc_search_host(scores, lengths, beam_size, blank, lse, token_min_logp), return_best_hypothesis)
+
+
+def _beam_device(scores, lengths, W, blank, lse, floor):
+    """One launch of csrc/ctc_beam.hip; the packed result [B*W*T tokens | B*W lengths | B*W scores] as one i32 device tensor."""
+    from . import _lib
+    from .align import _rows_in_place
+    L = _lib.lib()
+    x, ld = _rows_in_place(scores.detach())
+    B, T, V = x.shape
+    dev = x.device
+    il = lengths.detach().to(dev).long().contiguous()
+    z = None if lse is None else lse.detach().to(dev).float().contiguous()
+    n = L.ia_ctc_beam_workspace_bytes(B, T, V, W)
+    ws = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+    packed = torch.empty(B * W * T + 2 * B * W, dtype=torch.int32, device=dev)
+    tok, ln, sc = packed[:B * W * T], packed[B * W * T:B * W * T + B * W], packed[B * W * T + B * W:]
+    with torch.cuda.device(dev):
+        _lib.check(L.ia_ctc_beam_search(_lib.ptr(x), _lib.ptr(z), _lib.ptr(il), B, T, ld, V, int(blank), W, floor, _lib.ptr(tok),
+                                        _lib.ptr(ln), _lib.ptr(sc), _lib.ptr(ws), n, _lib.stream_ptr()), "ia_ctc_beam_search")
+    return packed
+
+
+@torch.no_grad()
+def beam_ctc_decode(scores, lengths, beam_size=4, blank=None, lse=None, token_min_logp=None, return_best_hypothesis=True):
+    """CTC prefix beam search without a language model: per utterance the best Hypothesis, or with
+    return_best_hypothesis=False the NBestHypotheses (at most beam_size of them, by descending score).
+
+    scores [B,T,V] f32: log-probs, or raw logits when `lse` [B,T] (their per-frame log-sum-exp) is given; lengths [B];
+    blank defaults to V - 1; token_min_logp (None = off): extensions by a token whose log-prob in the frame is below it are not
+    made.  Device tensors within the kernel's limits run csrc/ctc_beam.hip (one launch, one device-to-host copy of the packed
+    result); CPU tensors, and shapes beyond the limits (with a warning), run the float64 host routine.  A Hypothesis score is
+    the log-probability of the labelling as far as the beam kept its alignments, never more than its CTC log-likelihood."""
+    global _warned_beam_limit
+    if scores.dim() != 3:
+        raise ValueError(f"expected [B,T,V] log-probs or logits, got shape {tuple(scores.shape)}")
+    B, T, V = scores.shape
+    blank = V - 1 if blank is None else int(blank)
+    W = int(beam_size)
+    if W < 1:
+        raise ValueError("Beam search size cannot be less than 1!")
+    if not 0 <= blank < V:
+        raise ValueError(f"blank={blank} outside the {V} classes")
+    if not scores.is_cuda or B == 0 or T == 0:
+        return beam_ctc_decode_host(scores, lengths, W, blank, lse, token_min_logp, return_best_hypothesis)
+    max_w, max_v = beam_ctc_limits()
+    if W > max_w or V > max_v:
+        if not _warned_beam_limit:
+            warnings.warn(f"beam_ctc_decode: beam_size={W}, {V} classes exceed the kernel's limits (beam_size <= {max_w}, "
+                          f"classes <= {max_v}); searching on the host instead")
+            _warned_beam_limit = True
+        return beam_ctc_decode_host(scores, lengths, W, blank, lse, token_min_logp, return_best_hypothesis)
+    floor = _NEG_INF if token_min_logp is None else float(token_min_logp)
+    host = _beam_device(scores, lengths, W, blank, lse, floor).cpu()
+    tok = host[:B * W * T].view(B, W, T).numpy()
+    ln = host[B * W * T:B * W * T + B * W].view(B, W).numpy()
+    sc = host[B * W * T + B * W:].view(torch.float32).view(B, W).numpy()
+    raw = [[(tok[b, r, :ln[b, r]].tolist(), float(sc[b, r])) for r in range(W) if ln[b, r] >= 0] for b in range(B)]
+    return _beam_results(raw, return_best_hypothesis)

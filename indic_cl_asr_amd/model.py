@@ -143,6 +143,7 @@ class EncDecHybridRNNTCTCModel(TranscriptionMixin, nn.Module):
         # (an explicit training_step(compute_wer=...) wins)
         self.compute_wer_in_step = None
         self.cur_decoder = "rnnt"
+        self.decoding_strategy = {}      # change_decoding_strategy: {'rnnt': {...}, 'ctc': {...}}; empty: greedy on both heads
         self.language_masks = self.ctc_decoder.language_masks
         self._step = 0
         self.seed = 1234
@@ -189,6 +190,84 @@ class EncDecHybridRNNTCTCModel(TranscriptionMixin, nn.Module):
             self.cfg.att_context_size = [list(cs) for cs in enc.att_context_size_all] if multi else list(enc.att_context_size)
             self.cfg.att_context_style = enc.att_context_style
             self.cfg.att_context_probs = list(enc.att_context_probs) if multi else None
+
+    def change_decoding_strategy(self, decoding_cfg=None, decoder_type: str = None, lang_id: str = None):
+        """hybrid_rnnt_ctc_bpe_models.py:439-530: which head transcribe() decodes with, and how.  `decoding_cfg` is a mapping
+        or an attribute object with the fields of NeMo's CTCBPEDecodingConfig / RNNTBPEDecodingConfig that this model reads
+        (None: the strategy set before, greedy at first).  What it stores is `self.decoding_strategy[decoder_type]`.
+
+        decoder_type 'ctc':  strategy 'greedy', or 'beam' with beam.{beam_size, return_best_hypothesis, search_type, beam_alpha,
+          beam_beta, kenlm_path, token_min_logp}: search_type 'default' / 'nemo' without a language model is
+          decoding.beam_ctc_decode (CTC prefix beam search on csrc/ctc_beam.hip).  A kenlm_path, and the search types
+          'pyctcdecode' / 'flashlight' (also as strategies), raise NotImplementedError: there is no LM fusion here.
+        decoder_type None / 'rnnt':  strategy 'greedy' / 'greedy_batch' (greedy.max_symbols is stored); the transducer beam
+          strategies raise NotImplementedError.
+        `lang_id` is accepted as the reference accepts it; transcribe() takes the language per call."""
+        def get(cfg, key, default=None):
+            if cfg is None:
+                return default
+            return cfg.get(key, default) if hasattr(cfg, "get") else getattr(cfg, key, default)     # a mapping, or attributes
+
+        state = dict(getattr(self, "decoding_strategy", None) or {})
+        if decoder_type is None or decoder_type == "rnnt":
+            strategy = get(decoding_cfg, "strategy", state.get("rnnt", {}).get("strategy", "greedy_batch"))
+            beams = ["beam", "tsd", "alsd", "maes"]
+            if strategy in beams:
+                raise NotImplementedError(f"transducer decoding strategy `{strategy}` is not implemented: the transducer head "
+                                          "decodes greedily ('greedy', 'greedy_batch')")
+            if strategy not in ("greedy", "greedy_batch"):
+                raise ValueError(f"Decoding strategy must be one of {['greedy', 'greedy_batch'] + beams}\nbut was provided {strategy}")
+            max_symbols = get(get(decoding_cfg, "greedy"), "max_symbols", state.get("rnnt", {}).get("max_symbols", 10))
+            state["rnnt"] = dict(strategy=strategy, max_symbols=None if max_symbols is None else int(max_symbols))
+            self.decoding_strategy = state
+            self.cur_decoder = "rnnt"
+        elif decoder_type == "ctc":
+            if not hasattr(self, "ctc_decoder"):
+                raise ValueError("The model does not have the ctc_decoding module and does not support ctc decoding.")
+            prev = state.get("ctc", {})
+            strategy = get(decoding_cfg, "strategy", prev.get("strategy", "greedy"))
+            possible = ["greedy", "beam", "pyctcdecode", "flashlight"]
+            if strategy not in possible:
+                raise ValueError(f"Decoding strategy must be one of {possible}. Given {strategy}")
+            if strategy in ("pyctcdecode", "flashlight"):
+                raise NotImplementedError(f"CTC decoding strategy `{strategy}` needs an external decoder library and a language "
+                                          "model; use strategy 'beam' with search_type 'default'")
+            new = dict(strategy=strategy)
+            if strategy == "beam":
+                beam = get(decoding_cfg, "beam")
+                old = prev if prev.get("strategy") == "beam" else {}
+                timestamps = get(decoding_cfg, "compute_timestamps")
+                if timestamps is None:
+                    timestamps = get(beam, "compute_timestamps", False)
+                alignments = get(decoding_cfg, "preserve_alignments")
+                if alignments is None:
+                    alignments = get(beam, "preserve_alignments", False)
+                if timestamps or alignments:
+                    raise ValueError("Currently this flag is not supported for beam search algorithms.")
+                search_type = get(beam, "search_type", old.get("search_type", "default"))
+                if search_type in ("pyctcdecode", "flashlight"):
+                    raise NotImplementedError(f"The search type ({search_type}) needs an external decoder library; "
+                                              "this model implements (default, nemo) without a language model")
+                if search_type not in ("default", "nemo"):
+                    raise NotImplementedError(f"The search type ({search_type}) supplied is not supported!\n"
+                                              "Please use one of : (default, nemo, pyctcdecode)")
+                if get(beam, "kenlm_path") is not None:
+                    raise NotImplementedError("kenlm_path: language-model fusion is not implemented; the beam search runs on the "
+                                              "acoustic scores alone")
+                beam_size = int(get(beam, "beam_size", old.get("beam_size", 4)))
+                if beam_size < 1:
+                    raise ValueError("Beam search size cannot be less than 1!")
+                floor = get(beam, "token_min_logp", old.get("token_min_logp"))
+                new.update(beam_size=beam_size, search_type=search_type,
+                           return_best_hypothesis=bool(get(beam, "return_best_hypothesis", old.get("return_best_hypothesis", True))),
+                           beam_alpha=float(get(beam, "beam_alpha", old.get("beam_alpha", 1.0))),     # stored; no LM reads them
+                           beam_beta=float(get(beam, "beam_beta", old.get("beam_beta", 0.0))),
+                           token_min_logp=None if floor is None else float(floor))
+            state["ctc"] = new
+            self.decoding_strategy = state
+            self.cur_decoder = "ctc"
+        else:
+            raise ValueError(f"decoder_type={decoder_type} is not supported. Supported values: [ctc,rnnt]")
 
     def set_default_att_context_size(self, att_context_size):
         """The context that evaluation, transcribe() and align() use under multi-look-ahead (ConformerEncoder's)."""

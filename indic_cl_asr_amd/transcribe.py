@@ -177,6 +177,9 @@ class TranscriptionMixin:
         f.dither, f.pad_to = 0.0, 0
         self.eval()
         hyps, logits_list = [], []
+        strategy = getattr(self, "decoding_strategy", None) or {}     # change_decoding_strategy; nothing set: greedy
+        ctc_beam = strategy.get("ctc") if strategy.get("ctc", {}).get("strategy") == "beam" else None
+        beam_out = []          # CTC head + beam strategy: a Hypothesis / NBestHypotheses per utterance
         try:
             loader = self._transcribe_input_processing(audio, cfg, transcripts=None, language_id=language_id)
             for batch in loader:
@@ -186,7 +189,11 @@ class TranscriptionMixin:
                 langs = [language_id] * sig.shape[0]
                 encoded, encoded_len = self.forward(input_signal=sig, input_signal_length=sig_len)
                 if self.cur_decoder == "rnnt":
-                    ids = self.decode(encoded, encoded_len, langs)
+                    ids = self.decode(encoded, encoded_len, langs, **({"max_symbols": strategy["rnnt"]["max_symbols"]}
+                                                                      if "rnnt" in strategy else {}))
+                elif ctc_beam is not None and not logprobs:
+                    res, ids = self._ctc_beam_batch(encoded, encoded_len, language_id, ctc_beam, cfg.return_hypotheses)
+                    beam_out += res
                 else:
                     from .decoding import greedy_ctc_decode
                     lp = self.ctc_decoder(encoder_output=encoded, language_ids=langs)
@@ -201,7 +208,37 @@ class TranscriptionMixin:
             f.dither, f.pad_to = cfg._internal.dither_value, cfg._internal.pad_to_value
         if self.cur_decoder != "rnnt" and logprobs:
             return logits_list
+        if beam_out and cfg.return_hypotheses:
+            # ctc_decoder_predictions_tensor (ctc_decoding.py:381-382): the best hypotheses, and all of them
+            if ctc_beam["return_best_hypothesis"]:
+                return (beam_out, list(beam_out))
+            return ([nb.n_best_hypotheses[0] for nb in beam_out], beam_out)
         return (hyps, list(hyps))
+
+    def _ctc_beam_batch(self, encoded, encoded_len, language_id, beam, with_text):
+        """One batch through decoding.beam_ctc_decode: on the device the language's head logits and their row lse go to the
+        kernel as they are (what align() feeds the aligner).  Returns (Hypothesis / NBestHypotheses per utterance, best ids);
+        `_beam_keep`, when a list, receives (scores, lse or None, frame lengths) -- for tests."""
+        from . import align as A
+        from . import cl
+        from .decoding import beam_ctc_decode
+        cl.flush_pending_updates()
+        if encoded.is_cuda:
+            x = self.ctc_decoder.language_logits(encoded, language_id)
+            lse = A.row_lse(x)
+        else:
+            x, lse = self.ctc_decoder(encoder_output=encoded, language_ids=[language_id] * encoded.shape[0]), None
+        keep = getattr(self, "_beam_keep", None)
+        if keep is not None:
+            keep.append((x, lse, encoded_len))
+        res = beam_ctc_decode(x, encoded_len, beam_size=beam["beam_size"], blank=self.cfg.vocab_per_lang, lse=lse,
+                              token_min_logp=beam["token_min_logp"], return_best_hypothesis=beam["return_best_hypothesis"])
+        best = [r if beam["return_best_hypothesis"] else r.n_best_hypotheses[0] for r in res]
+        if with_text:
+            for r in res:
+                for h in ([r] if beam["return_best_hypothesis"] else r.n_best_hypotheses):
+                    h.text = self._ids_to_text(h.y_sequence, language_id)
+        return res, [h.y_sequence for h in best]
 
     # -------------------------------------------------------------------------------------------------- align
     @torch.no_grad()
