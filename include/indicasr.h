@@ -1418,6 +1418,43 @@ int ia_ctc_beam_search(const float* x, const float* lse, const int64_t* in_lens,
                        float token_min_logp, int32_t* tokens, int32_t* lengths, float* scores, void* workspace,
                        size_t workspace_bytes, ia_stream_t stream);
 
+/* ---- The same search with n-gram LM shallow fusion (csrc/ctc_beam_lm.hip).  ONE rule changes: extending l by c != blank gives
+ * l+c the term pnb' (+)= ((c == e ? pb : p) + lp[t,c]) + (alpha lm(l, c) + beta), lm(l, c) = ln P_LM(c | h(l)).  Stays get no LM
+ * term; an extension folded into a member's stay carries its LM term into it; token_min_logp still compares lp[t,c] alone;
+ * ranking, ties and ids are unchanged; the returned score is the fused total.  h(l) = the last order - 1 symbols of (<s>, l);
+ * </s> is never scored; the classes ARE the LM's tokens (the blank's entry is never read; a class >= n_tokens scores as <unk>).
+ * Back-off (KenLM's): for k = |h| .. 0: if h[-k:] + c is in the model, acc + its log p; otherwise acc += backoff(h[-k:]) (0 if
+ * that context is not in the model or k = 0).  A token without a unigram scores acc + log p(<unk>) and is followed by the empty
+ * history.  All values are natural logs in fp32.
+ *
+ * ia_ngram_lm, the flat image of the model (device pointers, all 4-byte aligned):
+ *   states   [n_states,3] i32  (back-off link, first arc, one past the last arc).  State 0 is the root (the empty context, no
+ *            arcs: its tokens are the unigram row); every other state is an n-gram of order < `order` of the model, a context.
+ *            The back-off link is the longest proper suffix of the context that is a state too (contexts that are not in the
+ *            model have back-off 0, so skipping them changes nothing).
+ *   backoff  [n_states] f32    the state's back-off weight.
+ *   arcs     [n_arcs,2] i32    (token, next state), sorted by token within a state: the n-grams `context + token`.  next = the
+ *            longest suffix of context + token that is a state.
+ *   arc_logp [n_arcs] f32      log p of that n-gram.
+ *   uni_logp [n_tokens] f32, uni_next [n_tokens] i32: the dense unigram row (log p(<unk>) and 0 for a token without a unigram).
+ *   unk_logp log p(<unk>);  start = the state of (<s>), or 0;  order = the model's order, <= ia_ctc_beam_lm_max_order() = 8.
+ * Every walk over the image is bounded (order - 1 back-off steps, n_arcs arcs) and every index read from it is clamped to its
+ * array: a corrupt image yields wrong scores, never an access out of range.
+ *   workspace: ia_ctc_beam_lm_workspace_bytes(B,T,V,W) (the trie + per utterance 2 W rows of V (value, next state) pairs),
+ *   256-byte aligned; 0 beyond W <= 32, V <= 1024.  IA_INVALID_VALUE: null or misaligned pointers, order < 1, NaN alpha / beta,
+ *   inconsistent counts; IA_UNSUPPORTED: beyond the limits; IA_WORKSPACE_TOO_SMALL -- all before any device work.  alpha = beta = 0
+ *   returns the bits of ia_ctc_beam_search; two launches agree bit for bit. */
+typedef struct ia_ngram_lm {
+    const int32_t* states; const float* backoff; const int32_t* arcs; const float* arc_logp; const float* uni_logp;
+    const int32_t* uni_next;
+    int32_t n_states, n_arcs, n_tokens, order, start; float unk_logp;
+} ia_ngram_lm;
+int ia_ctc_beam_lm_max_order(void);
+size_t ia_ctc_beam_lm_workspace_bytes(int B, int T, int V, int W);
+int ia_ctc_beam_search_lm(const float* x, const float* lse, const int64_t* in_lens, int B, int T, int ld, int V, int blank, int W,
+                          float token_min_logp, const ia_ngram_lm* lm, float alpha, float beta, int32_t* tokens, int32_t* lengths,
+                          float* scores, void* workspace, size_t workspace_bytes, ia_stream_t stream);
+
 /* ---- Glue of the step's tail (csrc/tail_ops.hip): each replaces a handful of small ATen launches.
  * ia_select_rows_cast  rows [row0, row0+nrows) (+ extra_row if >= 0) of W [*, K] f32 (row stride ldw), times `scale`, as a 16-bit
  *                      operand out [rows_out, K] (bf16, or f16 when out_f16; rows beyond the selection zero); optionally the

@@ -53,6 +53,12 @@ class BlockGrads(_c.Structure):
         "dw_w", "dw_b", "bn_g", "bn_b")]
 
 
+class NGramLM(_c.Structure):
+    """ia_ngram_lm of include/indicasr.h (the flat device image of a back-off n-gram model; ngram_lm.NGramLM.to builds it)."""
+    _fields_ = ([(n, _c.c_void_p) for n in ("states", "backoff", "arcs", "arc_logp", "uni_logp", "uni_next")]
+                + [(n, _c.c_int32) for n in ("n_states", "n_arcs", "n_tokens", "order", "start")] + [("unk_logp", _c.c_float)])
+
+
 class WaveParams(_c.Structure):
     """ia_wave_params of include/indicasr.h (one utterance's folded augmentation chain; augment.PARAMS_DTYPE is its numpy image)."""
     _fields_ = ([(n, _c.c_int32) for n in ("n_in", "n_out", "new_sr", "shift_pre", "shift_post", "noise_shift", "noise_stage")]
@@ -190,6 +196,10 @@ SIGNATURES = {
     "ia_ctc_beam_max_width": (_i, []),
     "ia_ctc_beam_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "ia_ctc_beam_search": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ia_ctc_beam_lm_max_order": (_i, []),
+    "ia_ctc_beam_lm_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "ia_ctc_beam_search_lm": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _c.POINTER(NGramLM), _f, _f, _vp, _vp, _vp, _vp, _sz,
+                                   _vp]),
     "ia_gemm_tn_scratch_elems": (_i64, [_i, _i, _i]),
     "ia_gemm_tn_bf16": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "ia_ffn_fused_supported": (_i, [_i, _i]),

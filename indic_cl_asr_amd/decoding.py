@@ -9,10 +9,11 @@
   read per micro-step) -- greedy_rnnt_decode dispatches to it; the host-driven loop stays as greedy_rnnt_decode_host
   (CPU tensors, and the cross-check of the kernel in tests).
 * greedy_ctc_decode   -- GreedyCTCInfer (ctc_greedy_decoding.py:145-229): argmax, collapse repeats, drop blanks.
-* beam_ctc_decode     -- CTC prefix beam search without a language model (Hannun et al. 2014, arXiv:1408.2873), what
-  CTCBPEDecoding's `strategy: beam` stands for (NeMo delegates it to KenLM-backed ctc_decoders, pyctcdecode or flashlight; the
-  algorithm is reproduced, not their bits): N-best Hypothesis objects with scores.  Device tensors run csrc/ctc_beam.hip
-  (one launch per batch), CPU tensors the float64 host routine beam_ctc_decode_host of the same definition.
+* beam_ctc_decode     -- CTC prefix beam search (Hannun et al. 2014, arXiv:1408.2873), alone or with a token-level n-gram LM
+  fused in (ngram_lm.NGramLM, read from ARPA text), what CTCBPEDecoding's `strategy: beam` stands for (NeMo delegates it to
+  KenLM-backed ctc_decoders, pyctcdecode or flashlight; the algorithm is reproduced, not their bits): N-best Hypothesis objects
+  with scores.  Device tensors run csrc/ctc_beam.hip / csrc/ctc_beam_lm.hip (one launch per batch), CPU tensors the float64
+  host routine beam_ctc_decode_host of the same definition.
 * word_error_rate / WER -- A/metrics/wer.py:293-360: sum of edit distances over sum of reference lengths.  Hypotheses
   and references are sequences of tokens here; pass `detokenize` (ids -> str) to score words as the reference does
   (its SentencePiece models are not part of the repository).
@@ -349,13 +350,23 @@ def beam_ctc_limits():
     return int(_lib.lib().ia_ctc_beam_max_width()), 1024
 
 
-def beam_ctc_search_host(scores, lengths, beam_size=4, blank=None, lse=None, token_min_logp=None):
+def beam_ctc_lm_max_order():
+    """The largest LM order csrc/ctc_beam_lm.hip takes (its other limits are beam_ctc_limits())."""
+    from . import _lib
+    return int(_lib.lib().ia_ctc_beam_lm_max_order())
+
+
+def beam_ctc_search_host(scores, lengths, beam_size=4, blank=None, lse=None, token_min_logp=None, lm=None, beam_alpha=1.0,
+                         beam_beta=0.0):
     """CTC prefix beam search (Hannun et al. 2014, arXiv:1408.2873) in float64 on the host: the definition of
     include/indicasr.h, which csrc/ctc_beam.hip follows too.  scores [B,T,V] log-probs, or logits with lse [B,T].
     Returns per utterance a list of (token ids, score) by descending score, ties to the smaller candidate id.
 
     Prefix identity is the node of a trie of (parent node, token) pairs kept in a dictionary; one frame is a [n, V] matrix
-    of candidate scores, the at most n extensions that denote a beam member folded into that member's stay."""
+    of candidate scores, the at most n extensions that denote a beam member folded into that member's stay.
+
+    lm (an ngram_lm.NGramLM): shallow fusion -- every extension by c != blank carries beam_alpha lm.score(l, c) + beam_beta, also
+    when it is folded into a member's stay; stays carry none; token_min_logp still looks at the acoustic log-prob alone."""
     import numpy as np
     x = scores.detach().double().cpu().numpy()
     B, T, V = x.shape
@@ -373,6 +384,7 @@ def beam_ctc_search_host(scores, lengths, beam_size=4, blank=None, lse=None, tok
     with np.errstate(invalid="ignore"):
         for b in range(B):
             parent, token, child = [-1], [-1], {}              # the trie: node -> (parent, token), (parent, token) -> node
+            tail = [()]                                        # with an LM: node -> its last order - 1 tokens, what h(l) needs
             node, pb, pnb = [0], np.array([0.0]), np.array([_NEG_INF])
             for t in range(int(lens[b])):
                 lp = x[b, t]
@@ -383,6 +395,8 @@ def beam_ctc_search_host(scores, lengths, beam_size=4, blank=None, lse=None, tok
                 rows = np.nonzero(last >= 0)[0]
                 base[rows, last[rows]] = pb[rows]
                 c_pnb = base + lp[None, :]
+                if lm is not None:
+                    c_pnb = c_pnb + np.stack([beam_alpha * lm.row(tail[k], V) + beam_beta for k in node])
                 c_pnb[:, lp < floor] = np.nan                  # not a candidate
                 c_pb = np.full((n, V), _NEG_INF)
                 c_pb[:, blank] = p + lp[blank]
@@ -410,6 +424,8 @@ def beam_ctc_search_host(scores, lengths, beam_size=4, blank=None, lse=None, tok
                         if key not in child:
                             child[key] = len(parent)
                             parent.append(node[i]); token.append(c)
+                            if lm is not None:
+                                tail.append((tail[node[i]] + (c,))[-(lm.order - 1):] if lm.order > 1 else ())
                         new_node.append(child[key])
                     new_pb.append(c_pb[i, c]); new_pnb.append(c_pnb[i, c])
                 node, pb, pnb = new_node, np.array(new_pb), np.array(new_pnb)
@@ -431,13 +447,16 @@ def _beam_results(raw, return_best_hypothesis):
     return res
 
 
-def beam_ctc_decode_host(scores, lengths, beam_size=4, blank=None, lse=None, token_min_logp=None, return_best_hypothesis=True):
+def beam_ctc_decode_host(scores, lengths, beam_size=4, blank=None, lse=None, token_min_logp=None, return_best_hypothesis=True,
+                         lm=None, beam_alpha=1.0, beam_beta=0.0):
     """beam_ctc_decode on the host in float64 (CPU tensors; the cross-check of the kernel in tests)."""
-    return _beam_results(beam_ctc_search_host(scores, lengths, beam_size, blank, lse, token_min_logp), return_best_hypothesis)
+    return _beam_results(beam_ctc_search_host(scores, lengths, beam_size, blank, lse, token_min_logp, lm, beam_alpha, beam_beta),
+                         return_best_hypothesis)
 
 
-def _beam_device(scores, lengths, W, blank, lse, floor):
-    """One launch of csrc/ctc_beam.hip; the packed result [B*W*T tokens | B*W lengths | B*W scores] as one i32 device tensor."""
+def _beam_device(scores, lengths, W, blank, lse, floor, lm=None, alpha=1.0, beta=0.0):
+    """One launch of csrc/ctc_beam.hip (with `lm`: csrc/ctc_beam_lm.hip); the packed result [B*W*T tokens | B*W lengths |
+    B*W scores] as one i32 device tensor."""
     from . import _lib
     from .align import _rows_in_place
     L = _lib.lib()
@@ -446,20 +465,30 @@ def _beam_device(scores, lengths, W, blank, lse, floor):
     dev = x.device
     il = lengths.detach().to(dev).long().contiguous()
     z = None if lse is None else lse.detach().to(dev).float().contiguous()
-    n = L.ia_ctc_beam_workspace_bytes(B, T, V, W)
+    n = (L.ia_ctc_beam_workspace_bytes if lm is None else L.ia_ctc_beam_lm_workspace_bytes)(B, T, V, W)
     ws = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
     packed = torch.empty(B * W * T + 2 * B * W, dtype=torch.int32, device=dev)
     tok, ln, sc = packed[:B * W * T], packed[B * W * T:B * W * T + B * W], packed[B * W * T + B * W:]
     with torch.cuda.device(dev):
+        if lm is not None:
+            import ctypes
+            _, image = lm.to(dev)
+            _lib.check(L.ia_ctc_beam_search_lm(_lib.ptr(x), _lib.ptr(z), _lib.ptr(il), B, T, ld, V, int(blank), W, floor,
+                                               ctypes.byref(image), float(alpha), float(beta), _lib.ptr(tok), _lib.ptr(ln),
+                                               _lib.ptr(sc), _lib.ptr(ws), n, _lib.stream_ptr()), "ia_ctc_beam_search_lm")
+            return packed
         _lib.check(L.ia_ctc_beam_search(_lib.ptr(x), _lib.ptr(z), _lib.ptr(il), B, T, ld, V, int(blank), W, floor, _lib.ptr(tok),
                                         _lib.ptr(ln), _lib.ptr(sc), _lib.ptr(ws), n, _lib.stream_ptr()), "ia_ctc_beam_search")
     return packed
 
 
 @torch.no_grad()
-def beam_ctc_decode(scores, lengths, beam_size=4, blank=None, lse=None, token_min_logp=None, return_best_hypothesis=True):
-    """CTC prefix beam search without a language model: per utterance the best Hypothesis, or with
-    return_best_hypothesis=False the NBestHypotheses (at most beam_size of them, by descending score).
+def beam_ctc_decode(scores, lengths, beam_size=4, blank=None, lse=None, token_min_logp=None, return_best_hypothesis=True,
+                    lm=None, beam_alpha=1.0, beam_beta=0.0):
+    """CTC prefix beam search, with `lm` (an ngram_lm.NGramLM) fused into it: per utterance the best Hypothesis, or with
+    return_best_hypothesis=False the NBestHypotheses (at most beam_size of them, by descending score).  With an LM every
+    extension by a token c carries beam_alpha ln P_LM(c | history) + beam_beta and the scores are the fused totals; the classes
+    are the LM's tokens.
 
     scores [B,T,V] f32: log-probs, or raw logits when `lse` [B,T] (their per-frame log-sum-exp) is given; lengths [B];
     blank defaults to V - 1; token_min_logp (None = off): extensions by a token whose log-prob in the frame is below it are not
@@ -477,16 +506,22 @@ def beam_ctc_decode(scores, lengths, beam_size=4, blank=None, lse=None, token_mi
     if not 0 <= blank < V:
         raise ValueError(f"blank={blank} outside the {V} classes")
     if not scores.is_cuda or B == 0 or T == 0:
-        return beam_ctc_decode_host(scores, lengths, W, blank, lse, token_min_logp, return_best_hypothesis)
+        return beam_ctc_decode_host(scores, lengths, W, blank, lse, token_min_logp, return_best_hypothesis, lm, beam_alpha, beam_beta)
     max_w, max_v = beam_ctc_limits()
+    if lm is not None and lm.order > beam_ctc_lm_max_order():
+        if not _warned_beam_limit:
+            warnings.warn(f"beam_ctc_decode: an LM of order {lm.order} exceeds the kernel's limit (order <= "
+                          f"{beam_ctc_lm_max_order()}); searching on the host instead")
+            _warned_beam_limit = True
+        return beam_ctc_decode_host(scores, lengths, W, blank, lse, token_min_logp, return_best_hypothesis, lm, beam_alpha, beam_beta)
     if W > max_w or V > max_v:
         if not _warned_beam_limit:
             warnings.warn(f"beam_ctc_decode: beam_size={W}, {V} classes exceed the kernel's limits (beam_size <= {max_w}, "
                           f"classes <= {max_v}); searching on the host instead")
             _warned_beam_limit = True
-        return beam_ctc_decode_host(scores, lengths, W, blank, lse, token_min_logp, return_best_hypothesis)
+        return beam_ctc_decode_host(scores, lengths, W, blank, lse, token_min_logp, return_best_hypothesis, lm, beam_alpha, beam_beta)
     floor = _NEG_INF if token_min_logp is None else float(token_min_logp)
-    host = _beam_device(scores, lengths, W, blank, lse, floor).cpu()
+    host = _beam_device(scores, lengths, W, blank, lse, floor, lm, beam_alpha, beam_beta).cpu()
     tok = host[:B * W * T].view(B, W, T).numpy()
     ln = host[B * W * T:B * W * T + B * W].view(B, W).numpy()
     sc = host[B * W * T + B * W:].view(torch.float32).view(B, W).numpy()

@@ -197,9 +197,12 @@ class EncDecHybridRNNTCTCModel(TranscriptionMixin, nn.Module):
         (None: the strategy set before, greedy at first).  What it stores is `self.decoding_strategy[decoder_type]`.
 
         decoder_type 'ctc':  strategy 'greedy', or 'beam' with beam.{beam_size, return_best_hypothesis, search_type, beam_alpha,
-          beam_beta, kenlm_path, token_min_logp}: search_type 'default' / 'nemo' without a language model is
-          decoding.beam_ctc_decode (CTC prefix beam search on csrc/ctc_beam.hip).  A kenlm_path, and the search types
-          'pyctcdecode' / 'flashlight' (also as strategies), raise NotImplementedError: there is no LM fusion here.
+          beam_beta, kenlm_path, token_min_logp}: search_type 'default' / 'nemo' is decoding.beam_ctc_decode (CTC prefix beam
+          search on csrc/ctc_beam.hip).  kenlm_path, a path ending in `.arpa` or a mapping {language_id: such a path}, fuses a
+          token-level n-gram model into the search (ngram_lm.NGramLM on csrc/ctc_beam_lm.hip, weights beam_alpha = 1.0 and
+          beam_beta = 0.0 as in NeMo): the file is read once here and its device image is kept per language.  Any other path
+          raises NotImplementedError (KenLM binaries are not read), a missing file FileNotFoundError.  The search types
+          'pyctcdecode' / 'flashlight' (also as strategies) raise NotImplementedError.
         decoder_type None / 'rnnt':  strategy 'greedy' / 'greedy_batch' (greedy.max_symbols is stored); the transducer beam
           strategies raise NotImplementedError.
         `lang_id` is accepted as the reference accepts it; transcribe() takes the language per call."""
@@ -251,23 +254,48 @@ class EncDecHybridRNNTCTCModel(TranscriptionMixin, nn.Module):
                 if search_type not in ("default", "nemo"):
                     raise NotImplementedError(f"The search type ({search_type}) supplied is not supported!\n"
                                               "Please use one of : (default, nemo, pyctcdecode)")
-                if get(beam, "kenlm_path") is not None:
-                    raise NotImplementedError("kenlm_path: language-model fusion is not implemented; the beam search runs on the "
-                                              "acoustic scores alone")
+                kenlm_path = get(beam, "kenlm_path", old.get("kenlm_path"))
+                lms = self._load_beam_lms(kenlm_path, old) if kenlm_path is not None else None
                 beam_size = int(get(beam, "beam_size", old.get("beam_size", 4)))
                 if beam_size < 1:
                     raise ValueError("Beam search size cannot be less than 1!")
                 floor = get(beam, "token_min_logp", old.get("token_min_logp"))
                 new.update(beam_size=beam_size, search_type=search_type,
                            return_best_hypothesis=bool(get(beam, "return_best_hypothesis", old.get("return_best_hypothesis", True))),
-                           beam_alpha=float(get(beam, "beam_alpha", old.get("beam_alpha", 1.0))),     # stored; no LM reads them
-                           beam_beta=float(get(beam, "beam_beta", old.get("beam_beta", 0.0))),
+                           beam_alpha=float(get(beam, "beam_alpha", old.get("beam_alpha", 1.0))),     # the LM's weight and the
+                           beam_beta=float(get(beam, "beam_beta", old.get("beam_beta", 0.0))),        # per-token bonus
                            token_min_logp=None if floor is None else float(floor))
+                if lms is not None:
+                    new.update(kenlm_path=kenlm_path, lms=lms)
             state["ctc"] = new
             self.decoding_strategy = state
             self.cur_decoder = "ctc"
         else:
             raise ValueError(f"decoder_type={decoder_type} is not supported. Supported values: [ctc,rnnt]")
+
+    def _load_beam_lms(self, kenlm_path, old):
+        """kenlm_path (a path, or a mapping language -> path) as {language or None: ngram_lm.NGramLM}; None = every language.
+        Nothing but `.arpa` names is looked at on disk; models of the strategy set before are kept, not read again."""
+        import os
+        from .ngram_lm import NGramLM
+        paths = dict(kenlm_path) if hasattr(kenlm_path, "items") else {None: kenlm_path}
+        for path in paths.values():
+            if not str(path).endswith(".arpa"):
+                raise NotImplementedError(f"kenlm_path: {path}: KenLM binary files are not read; give the model as ARPA text "
+                                          "(a file name ending in .arpa)")
+        for lang in paths:
+            if lang is not None and lang not in self.cfg.languages:
+                raise ValueError(f"kenlm_path: unknown language {lang!r}; the model has {list(self.cfg.languages)}")
+        lms = {}
+        for lang, path in paths.items():
+            path = str(path)
+            if not os.path.isfile(path):
+                raise FileNotFoundError(f"kenlm_path: {path} does not exist")
+            kept = (old.get("lms") or {}).get(lang)
+            same = kept is not None and getattr(kept, "path", None) == path and kept.mtime == os.path.getmtime(path)
+            lms[lang] = kept if same else NGramLM.from_arpa(path, self.cfg.vocab_per_lang)
+            lms[lang].path, lms[lang].mtime = path, os.path.getmtime(path)
+        return lms
 
     def set_default_att_context_size(self, att_context_size):
         """The context that evaluation, transcribe() and align() use under multi-look-ahead (ConformerEncoder's)."""

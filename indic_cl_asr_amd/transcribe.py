@@ -216,7 +216,8 @@ class TranscriptionMixin:
         return (hyps, list(hyps))
 
     def _ctc_beam_batch(self, encoded, encoded_len, language_id, beam, with_text):
-        """One batch through decoding.beam_ctc_decode: on the device the language's head logits and their row lse go to the
+        """One batch through decoding.beam_ctc_decode (with the language's n-gram model, if change_decoding_strategy loaded
+        one): on the device the language's head logits and their row lse go to the
         kernel as they are (what align() feeds the aligner).  Returns (Hypothesis / NBestHypotheses per utterance, best ids);
         `_beam_keep`, when a list, receives (scores, lse or None, frame lengths) -- for tests."""
         from . import align as A
@@ -231,8 +232,14 @@ class TranscriptionMixin:
         keep = getattr(self, "_beam_keep", None)
         if keep is not None:
             keep.append((x, lse, encoded_len))
+        lm, lms = None, beam.get("lms")
+        if lms:
+            lm = lms.get(language_id, lms.get(None))
+            if lm is None:
+                raise ValueError(f"kenlm_path holds no language model for the language {language_id!r} (it has {sorted(lms)})")
         res = beam_ctc_decode(x, encoded_len, beam_size=beam["beam_size"], blank=self.cfg.vocab_per_lang, lse=lse,
-                              token_min_logp=beam["token_min_logp"], return_best_hypothesis=beam["return_best_hypothesis"])
+                              token_min_logp=beam["token_min_logp"], return_best_hypothesis=beam["return_best_hypothesis"],
+                              lm=lm, beam_alpha=beam["beam_alpha"], beam_beta=beam["beam_beta"])
         best = [r if beam["return_best_hypothesis"] else r.n_best_hypotheses[0] for r in res]
         if with_text:
             for r in res:
