@@ -1455,6 +1455,39 @@ int ia_ctc_beam_search_lm(const float* x, const float* lse, const int64_t* in_le
                           float token_min_logp, const ia_ngram_lm* lm, float alpha, float beta, int32_t* tokens, int32_t* lengths,
                           float* scores, void* workspace, size_t workspace_bytes, ia_stream_t stream);
 
+/* ---- Transducer beam search (csrc/rnnt_beam.hip): alignment-length synchronous decoding (Saon et al. 2020; NeMo's
+ * align_length_sync_decoding as written, rnnt_beam_decoding.py:829-1068), one launch, one workgroup per utterance, on the operands
+ * of ia_greedy_rnnt_decode (f_all [B,T,Hj], EW [V+1,4Hp], W_hh [4Hp,Hp], W_pred [Hj,Hp], b_pred, head [V,Hj], b_head; blank = V-1).
+ * A hypothesis is a sequence S = (blank, y1..yu), a score and the steps at which its labels were emitted; its state is the LSTM
+ * cell applied along S from the zero state (EW[V-1] for the leading blank), g(S) = W_pred h(S) + b_pred, and
+ * logp(S,t) = log_softmax(W_head relu(f[t] + g(S)) + b_head).  beam = min(W, V-1); len = lens[b] clamped to [0,T]; u = u_max[b]
+ * clamped to [0, max_umax].  B = [((blank), 0, [])], F = [].  For i in 0 .. len + u - 1: the live members of B (t = i - |y| <= len-1,
+ * in B's order; none: stop) each append to A their blank candidate (S, score + logp[blank]; also appended to F when t = len-1,
+ * the same record) and then `beam` label candidates (S+k, score + logp[k], steps + [i]) by descending logp, equal values to the
+ * smaller id.  B = the first `beam` of A by descending score, stable; then, walking B in order, a member whose sequence equals an
+ * earlier first occurrence adds its score to that one (log-add-exp) and stays in B with its own.  Result: F by descending
+ * score / (|y| + 1) (score_norm) or score, stable; B as it stands when F is empty; len = 0: the empty hypothesis, score 0.
+ *   tokens, steps [B,K,T+max_umax] i32: the first K <= 16 of the result, each padded with -1; lengths [B,K] i32 (-1: no such
+ *   hypothesis), scores [B,K] f32 (the unnormalised score; -inf), n_finished [B] i32 = |F|.
+ *   fp32 weights: everything in fp32, Hp and Hj multiples of 4.  bf16 weights (W_hh, W_pred, head as bf16 images): relu(f + g) is
+ *   rounded to bf16 before the head, nothing else is rounded (h enters the matrix cores as an exact three-term bf16 split); Hp and Hj
+ *   multiples of 32.  W <= ia_rnnt_beam_max_width() = 16; the operand tile and the logits must fit the LDS (640 / 640 / 257 does).
+ *   workspace: ia_rnnt_beam_workspace_bytes(B,T,Hp,Hj,V,W,max_umax), 256-byte aligned (per utterance 33 state slots, the gates of
+ *   16 rows, 1 + W (T + max_umax) token records and trie nodes with their table, W (max_umax + 1) finished records); 0 beyond the
+ *   limits.  IA_INVALID_VALUE (null / misaligned pointers, counts < 1, V < 2), IA_UNSUPPORTED, IA_WORKSPACE_TOO_SMALL: all before
+ *   any device work.  Every index read from memory is clamped, every loop bounded; two launches agree bit for bit. */
+int ia_rnnt_beam_max_width(void);
+size_t ia_rnnt_beam_workspace_bytes(int B, int T, int Hp, int Hj, int V, int W, int max_umax);
+int ia_rnnt_beam_alsd(const float* f_all, const int64_t* lens, const int32_t* u_max, const float* EW, const float* Whh,
+                      const float* Wpred, const float* bpred, const float* Whead, const float* bhead, int B, int T, int Hp, int Hj,
+                      int V, int W, int K, int max_umax, int score_norm, int32_t* tokens, int32_t* steps, int32_t* lengths,
+                      float* scores, int32_t* n_finished, void* workspace, size_t workspace_bytes, ia_stream_t stream);
+int ia_rnnt_beam_alsd_bf16w(const float* f_all, const int64_t* lens, const int32_t* u_max, const float* EW, const void* Whh_bf16,
+                            const void* Wpred_bf16, const float* bpred, const void* Whead_bf16, const float* bhead, int B, int T,
+                            int Hp, int Hj, int V, int W, int K, int max_umax, int score_norm, int32_t* tokens, int32_t* steps,
+                            int32_t* lengths, float* scores, int32_t* n_finished, void* workspace, size_t workspace_bytes,
+                            ia_stream_t stream);
+
 /* ---- Glue of the step's tail (csrc/tail_ops.hip): each replaces a handful of small ATen launches.
  * ia_select_rows_cast  rows [row0, row0+nrows) (+ extra_row if >= 0) of W [*, K] f32 (row stride ldw), times `scale`, as a 16-bit
  *                      operand out [rows_out, K] (bf16, or f16 when out_f16; rows beyond the selection zero); optionally the

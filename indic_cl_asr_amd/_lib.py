@@ -200,6 +200,10 @@ SIGNATURES = {
     "ia_ctc_beam_lm_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "ia_ctc_beam_search_lm": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _c.POINTER(NGramLM), _f, _f, _vp, _vp, _vp, _vp, _sz,
                                    _vp]),
+    "ia_rnnt_beam_max_width": (_i, []),
+    "ia_rnnt_beam_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    "ia_rnnt_beam_alsd": (_i, [_vp] * 9 + [_i] * 9 + [_vp] * 6 + [_sz, _vp]),
+    "ia_rnnt_beam_alsd_bf16w": (_i, [_vp] * 9 + [_i] * 9 + [_vp] * 6 + [_sz, _vp]),
     "ia_gemm_tn_scratch_elems": (_i64, [_i, _i, _i]),
     "ia_gemm_tn_bf16": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "ia_ffn_fused_supported": (_i, [_i, _i]),

@@ -14,6 +14,10 @@
   KenLM-backed ctc_decoders, pyctcdecode or flashlight; the algorithm is reproduced, not their bits): N-best Hypothesis objects
   with scores.  Device tensors run csrc/ctc_beam.hip / csrc/ctc_beam_lm.hip (one launch per batch), CPU tensors the float64
   host routine beam_ctc_decode_host of the same definition.
+* beam_rnnt_decode    -- transducer beam search, NeMo's `strategy: alsd` (alignment-length synchronous decoding, Saon et al.
+  2020; rnnt_beam_decoding.py:829-1068 as written): Hypothesis objects with scores and alignment steps.  Device tensors run
+  csrc/rnnt_beam.hip (one launch per batch, one workgroup per utterance), CPU tensors the float64 host routine
+  beam_rnnt_alsd_host of the same definition.
 * word_error_rate / WER -- A/metrics/wer.py:293-360: sum of edit distances over sum of reference lengths.  Hypotheses
   and references are sequences of tokens here; pass `detokenize` (ids -> str) to score words as the reference does
   (its SentencePiece models are not part of the repository).
@@ -155,17 +159,16 @@ def device_decode_supported(model) -> bool:
 
 
 @torch.no_grad()
-def greedy_rnnt_decode_device(model, encoded, encoded_len, language_ids, max_symbols: Optional[int] = 10, defer: bool = False):
-    """The same decode in ONE launch (csrc/greedy_decode.hip).  Setup on the HIP fp32 GEMM: the joint's encoder projection of
-    all frames and the table EW = W_ih embedding[row] + b_ih + b_hh over the 257 rows the loop can feed the prediction
-    network (the language's labels by their ids as decoding.greedy_rnnt_decode_host feeds them, the blank / padding row, the
-    zero SOS input); one device->host copy of the token matrix at the end."""
-    from . import _lib
+def _rnnt_decode_operands(model, encoded, encoded_len, language_ids, defer: bool = False, who: str = "greedy_rnnt_decode"):
+    """What the device-resident transducer decodes (csrc/greedy_decode.hip, csrc/rnnt_beam.hip) multiply with: f_all [B,T,Hj] =
+    the joint's encoder projection of all frames, EW [V+1,4Hp] = W_ih embedding[row] + b_ih + b_hh over the language's labels,
+    the blank / padding row and the zero SOS input (both on the HIP fp32 GEMM for device tensors), the clamped-later lengths,
+    and W_hh / W_pred / the head with their biases -- as bf16 images for a model that computes in bf16 (`w16`).  CPU tensors
+    get the same operands from torch (the host routines)."""
     from . import cl
     cl.flush_pending_updates()
     if len(set(language_ids)) != 1:
-        raise NotImplementedError("greedy_rnnt_decode: one language per batch (as the CL scripts evaluate)")
-    L = _lib.lib()
+        raise NotImplementedError(f"{who}: one language per batch (as the CL scripts evaluate)")
     dec, joint = model.decoder, model.joint
     dev = encoded.device
     B, d, T = encoded.shape
@@ -178,22 +181,18 @@ def greedy_rnnt_decode_device(model, encoded, encoded_len, language_ids, max_sym
 
     def gemm32(a, w):   # a [M,K] @ w[N,K]^T on csrc/gemm_f32.hip
         a, w = a.float().contiguous(), w.float().contiguous()
-        if a.shape[1] % 16 != 0:
+        if a.shape[1] % 16 != 0 or not a.is_cuda:
             return a @ w.t()
+        from . import _lib
         out = torch.empty(a.shape[0], w.shape[0], dtype=torch.float32, device=dev)
-        _lib.check(L.ia_gemm_f32(_lib.ptr(a), a.shape[1], _lib.ptr(w), w.shape[1], a.shape[0], w.shape[0], a.shape[1], _lib.ptr(out),
-                                 w.shape[0], _lib.stream_ptr()), "ia_gemm_f32")
+        _lib.check(_lib.lib().ia_gemm_f32(_lib.ptr(a), a.shape[1], _lib.ptr(w), w.shape[1], a.shape[0], w.shape[0], a.shape[1],
+                                          _lib.ptr(out), w.shape[0], _lib.stream_ptr()), "ia_gemm_f32")
         return out
 
     f_all = (gemm32(encoded.transpose(1, 2).reshape(B * T, d), joint.enc.weight) + joint.enc.bias.float()).view(B, T, Hj).contiguous()
     rows = torch.cat([emb[:blank].float(), emb[dec.blank_idx:dec.blank_idx + 1].float(),
                       torch.zeros(1, Hp, dtype=torch.float32, device=dev)], 0)                      # [V + 1, Hp]
     EW = (gemm32(rows, lstm.weight_ih_l0) + (lstm.bias_ih_l0 + lstm.bias_hh_l0).float()).contiguous()
-    ms = int(max_symbols) if max_symbols is not None else 1 << 30
-    cap = T * (int(max_symbols) if max_symbols is not None else 8)
-    tokens = torch.empty(B, cap, dtype=torch.int32, device=dev)
-    counts = torch.zeros(B, dtype=torch.int32, device=dev)
-    overflow = torch.zeros(1, dtype=torch.int32, device=dev)
     out_len = encoded_len.to(dev).long().contiguous()
     # a model that trains in bf16 decodes on the bf16 images of W_hh / W_pred / the head (what its training step multiplies
     # with, kept current by the fused optimizer: ops/fast.bf16_shadow): half the bytes per emitted symbol of a loop bound by
@@ -202,15 +201,37 @@ def greedy_rnnt_decode_device(model, encoded, encoded_len, language_ids, max_sym
 
     def snap(p, image16=False):   # contiguous image; with `defer` a private COPY: the optimizer may rewrite the weights meanwhile
         if image16:
+            if not p.is_cuda:
+                return p.detach().float().bfloat16().contiguous()
             from .ops import fast
             t = fast.bf16_shadow(p)
             return t.clone() if defer else t
         t = p.detach().float().contiguous()
         return t.clone() if (defer and t.data_ptr() == p.data_ptr()) else t
 
-    Whh = snap(lstm.weight_hh_l0, w16)
-    Wp, bp = snap(joint.pred.weight, w16), snap(joint.pred.bias)
-    Wh, bh = snap(head.weight, w16), snap(head.bias)
+    return dict(B=B, T=T, Hp=Hp, Hj=Hj, V=V, blank=blank, w16=w16, f_all=f_all, EW=EW, out_len=out_len,
+                Whh=snap(lstm.weight_hh_l0, w16), Wp=snap(joint.pred.weight, w16), bp=snap(joint.pred.bias),
+                Wh=snap(head.weight, w16), bh=snap(head.bias))
+
+
+@torch.no_grad()
+def greedy_rnnt_decode_device(model, encoded, encoded_len, language_ids, max_symbols: Optional[int] = 10, defer: bool = False):
+    """The same decode in ONE launch (csrc/greedy_decode.hip).  Setup on the HIP fp32 GEMM: the joint's encoder projection of
+    all frames and the table EW = W_ih embedding[row] + b_ih + b_hh over the 257 rows the loop can feed the prediction
+    network (the language's labels by their ids as decoding.greedy_rnnt_decode_host feeds them, the blank / padding row, the
+    zero SOS input); one device->host copy of the token matrix at the end."""
+    from . import _lib
+    L = _lib.lib()
+    op = _rnnt_decode_operands(model, encoded, encoded_len, language_ids, defer)
+    dev = encoded.device
+    B, T, Hp, Hj, V, blank, w16 = op["B"], op["T"], op["Hp"], op["Hj"], op["V"], op["blank"], op["w16"]
+    f_all, EW, out_len = op["f_all"], op["EW"], op["out_len"]
+    Whh, Wp, bp, Wh, bh = op["Whh"], op["Wp"], op["bp"], op["Wh"], op["bh"]
+    ms = int(max_symbols) if max_symbols is not None else 1 << 30
+    cap = T * (int(max_symbols) if max_symbols is not None else 8)
+    tokens = torch.empty(B, cap, dtype=torch.int32, device=dev)
+    counts = torch.zeros(B, dtype=torch.int32, device=dev)
+    overflow = torch.zeros(1, dtype=torch.int32, device=dev)
     args = (_lib.ptr(f_all), _lib.ptr(out_len), _lib.ptr(EW), _lib.ptr(Whh), _lib.ptr(Wp), _lib.ptr(bp),
             _lib.ptr(Wh), _lib.ptr(bh), B, T, Hp, Hj, V, blank, blank, V, ms, _lib.ptr(tokens), cap,
             _lib.ptr(counts), _lib.ptr(overflow))
@@ -328,16 +349,20 @@ def greedy_ctc_decode(log_probs, lengths, blank: Optional[int] = None, defer: bo
 @dataclass
 class Hypothesis:
     """The fields of NeMo's rnnt_utils.Hypothesis that the search fills: `score` = log-probability of the labelling (all its
-    alignments), `y_sequence` = language-local token ids, `text` (filled by transcribe)."""
+    alignments), `y_sequence` = language-local token ids, `text` (filled by transcribe), `timestep` (the transducer beam
+    search: the alignment step at which each label was emitted, as NeMo's ALSD fills it)."""
     score: float
     y_sequence: List[int]
     text: Optional[str] = None
+    timestep: Optional[List[int]] = None
 
 
 @dataclass
 class NBestHypotheses:
-    """rnnt_utils.NBestHypotheses: the beam by descending score."""
+    """rnnt_utils.NBestHypotheses: the beam by descending score.  `n_finished` (the transducer beam search): how many
+    finished hypotheses the search ranked; the list holds the first beam_size of them."""
     n_best_hypotheses: Optional[List[Hypothesis]] = None
+    n_finished: Optional[int] = None
 
 
 _NEG_INF = float("-inf")
@@ -527,3 +552,284 @@ def beam_ctc_decode(scores, lengths, beam_size=4, blank=None, lse=None, token_mi
     sc = host[B * W * T + B * W:].view(torch.float32).view(B, W).numpy()
     raw = [[(tok[b, r, :ln[b, r]].tolist(), float(sc[b, r])) for r in range(W) if ln[b, r] >= 0] for b in range(B)]
     return _beam_results(raw, return_best_hypothesis)
+
+
+# ------------------------------------------------------------------------------------- transducer beam search (ALSD)
+class _AlsdSide:
+    """The decode operands in one precision (the dict of oracle.decode_ref.decode_reference: f_all [B,T,Hj], EW [V+1,4Hp], Whh,
+    Wp, bp, Wh, bh; optional f_all32 / EW32 = the fp32 images of operands given in fp64)."""
+
+    def __init__(self, case, dt):
+        s = "32" if dt == torch.float32 else ""
+        cpu = lambda t: t.detach().cpu().to(dt)
+        self.f_all, self.EW = cpu(case.get("f_all" + s, case["f_all"])), cpu(case.get("EW" + s, case["EW"]))
+        self.Whh, self.Wp, self.Wh = cpu(case["Whh"]), cpu(case["Wp"]), cpu(case["Wh"])
+        self.bp, self.bh = cpu(case["bp"]), cpu(case["bh"])
+        self.Hp = self.Whh.shape[1]
+        self.zero = torch.zeros(self.Hp, dtype=dt)
+
+    def cell(self, row, h, c):
+        Hp = self.Hp
+        g = self.Whh @ h + self.EW[row]
+        i, f, gg, o = torch.sigmoid(g[:Hp]), torch.sigmoid(g[Hp:2 * Hp]), torch.tanh(g[2 * Hp:3 * Hp]), torch.sigmoid(g[3 * Hp:])
+        cn = f * c + i * gg
+        hn = o * torch.tanh(cn)
+        return hn, cn, self.Wp @ hn + self.bp
+
+
+class _AlsdHyp:
+    __slots__ = ("seq", "score", "own", "ts", "slack", "parent")
+
+    def __init__(self, seq, score, ts, slack, parent):
+        self.seq, self.score, self.own, self.ts, self.slack, self.parent = seq, score, score, ts, slack, parent
+
+
+class _AlsdEval:
+    """What oracle.decode_ref._evaluate reads of a path: the frame and the pending (h, c, g) of both precisions."""
+    __slots__ = ("t", "pend")
+
+
+def alsd_u_max(alsd_max_target_len, length: int) -> int:
+    """NeMo's u_max: int(a * len) for a float a, int(a) for an int."""
+    a = alsd_max_target_len
+    return max(0, int(a * length) if isinstance(a, float) else int(a))
+
+
+def _alsd_utterance(S64, S32, b, length, W, u_max, score_norm, rounding, absW):
+    import math
+    V = S64.Wh.shape[0]
+    blank = V - 1
+    beam = min(W, V - 1)
+    sides = (S64,) if rounding is None else (S64, S32)
+    if rounding is not None:
+        from oracle.decode_ref import _evaluate
+    cache = {}
+
+    def state(h):                                   # a pure function of the sequence: computed once per sequence
+        st = cache.get(h.seq)
+        if st is None:
+            st = cache[h.seq] = tuple(S.cell(h.seq[-1], p[0], p[1]) for S, p in zip(sides, h.parent))
+        return st
+
+    Bm = [_AlsdHyp((blank,), 0.0, [], 0.0, tuple((S.zero, S.zero) for S in sides))]
+    F, undecided, steps, recomb, fin_recomb = [], [], 0, 0, 0
+    for i in range(length + u_max):
+        live = [h for h in Bm if i - (len(h.seq) - 1) <= length - 1]
+        if not live:
+            break
+        A, rows, fin_now = [], [], set()
+        for h in live:
+            t = i - (len(h.seq) - 1)
+            st = state(h)
+            if rounding is None:
+                z = S64.Wh @ torch.relu(S64.f_all[b, t] + st[0][2]) + S64.bh
+                step_tol = 0.0
+            else:
+                ev = _AlsdEval()
+                ev.t, ev.pend = t, st
+                z, tol, _, _ = _evaluate(S64, S32, b, ev, rounding, absW)
+                step_tol = 2.0 * float(tol.max())
+            lp = (z - torch.logsumexp(z, 0)).tolist()
+            slack = h.slack + step_tol
+            n = _AlsdHyp(h.seq, h.score + lp[blank], h.ts, slack, h.parent)
+            A.append(n)
+            if t == length - 1:
+                F.append(n)                           # the same record: a recombination of this step shows in F
+                fin_now.add(id(n))
+            order = sorted(range(blank), key=lambda k: (-lp[k], k))      # equal values: the smaller id
+            for k in order[:beam]:
+                A.append(_AlsdHyp(h.seq + (k,), h.score + lp[k], h.ts + [i], slack, st))
+            if blank > beam:
+                rows.append((len(A) - 1, lp[order[beam - 1]] - lp[order[beam]], 2.0 * slack))
+        order = sorted(range(len(A)), key=lambda j: -A[j].score)         # stable: ties keep A's order
+        Bm = [A[j] for j in order[:beam]]
+        if rounding is not None:
+            if len(A) > beam:
+                x, y = A[order[beam - 1]], A[order[beam]]
+                if 0.0 != x.score - y.score <= x.slack + y.slack:      # an exact tie is decided by the stable order
+                    undecided.append((i, "prune"))
+            won = set(order[:beam])
+            for last, gap, slack2 in rows:
+                if last in won and 0.0 != gap <= slack2:               # an exact tie goes to the smaller id
+                    undecided.append((i, "labels"))
+        first = {}
+        for h in Bm:
+            f = first.get(h.seq)
+            if f is None:
+                first[h.seq] = h
+                continue
+            recomb += 1
+            fin_recomb += id(f) in fin_now
+            if rounding is not None and abs(f.own - h.own) <= f.slack + h.slack:
+                undecided.append((i, "duplicates"))
+            f.score = float(f.score + math.log1p(math.exp(h.score - f.score))) if f.score >= h.score else \
+                float(h.score + math.log1p(math.exp(f.score - h.score)))
+            f.slack = max(f.slack, h.slack)
+        steps += 1
+    if F:
+        div = (lambda h: len(h.seq)) if score_norm else (lambda h: 1)
+        out = sorted(F, key=lambda h: -(h.score / div(h)))               # stable
+        key = lambda h: (h.score / div(h), h.slack / div(h))
+    else:
+        out = Bm
+        key = lambda h: (h.own, h.slack)
+    if rounding is not None:
+        for x, y in zip(out, out[1:]):
+            (kx, sx), (ky, sy) = key(x), key(y)
+            if abs(kx - ky) <= sx + sy:
+                undecided.append((-1, "ranking"))
+    return dict(hyps=[(list(h.seq[1:]), float(h.score), list(h.ts)) for h in out], slack=[h.slack for h in out],
+                n_finished=len(F), decided=not undecided, undecided=undecided, steps=steps, recombinations=recomb,
+                finished_recombined=fin_recomb)
+
+
+def beam_rnnt_alsd_host(case, beam_size=4, alsd_max_target_len=1.0, score_norm=True, rounding=None, n_best=None):
+    """Alignment-length synchronous decoding (Saon et al. 2020) as NeMo's align_length_sync_decoding computes it
+    (rnnt_beam_decoding.py:829-1068, its recombine_hypotheses -- which merges into the first occurrence and returns the
+    unmerged list -- included), in float64 on the host: the definition of include/indicasr.h that csrc/rnnt_beam.hip follows.
+
+    case: the decode operands (f_all [B,T,Hj], EW [V+1,4Hp] with rows labels / blank = padding row V-1 / SOS row V, Whh, Wp, bp,
+    Wh, bh, lens [B]).  A hypothesis is a sequence (blank, y1..yu) whose state is the LSTM cell applied along it from the zero
+    state; per step i every live member of the beam (t = i - u <= len - 1) contributes its blank candidate (also to the finished
+    list when t = len - 1) and its min(beam_size, V-1) best labels; the beam is the first `beam` candidates by descending score
+    (stable), and a member that repeats an earlier member's sequence adds its score to that one while staying in the beam.
+
+    rounding None: exact.  "gemv" / "mfma": the kernel's rounding points (oracle.decode_ref._evaluate: nothing rounded / the
+    head's operand rounded to bf16), with an fp32 twin of every sequence's state next to the fp64 one; each hypothesis then
+    carries a slack (its parent's plus twice the step's largest logit tolerance; a recombined score the larger of the two)
+    and the utterance a verdict `decided`: no pruning boundary, no row's beam-th label that won, no pair of duplicates and no
+    pair of neighbours in the final ranking is closer than the slacks' sum.  (A difference of exactly 0 at the pruning boundary
+    or between labels is decided: bit-equal fp64 values come from bit-equal operands -- copies of a head row -- which are
+    bit-equal in every precision, and the stable order / smaller id then rules.  When nothing finished, the neighbours of the
+    returned beam are compared by the scores the last pruning sorted them by.)
+
+    Returns per utterance a dict: hyps = [(token ids, score, alignment steps)] in result order (the finished list by
+    descending score / (u + 1) with score_norm, else by score; the beam as it stands when nothing finished; the first
+    `n_best` of them if given), slack, n_finished, decided, undecided, steps, recombinations, finished_recombined (recombinations into
+    a record that entered the finished list in the same step)."""
+    assert rounding in ("mfma", "gemv", None)
+    W = int(beam_size)
+    if W < 1:
+        raise ValueError("Beam search size cannot be less than 1!")
+    S64 = _AlsdSide(case, torch.float64)
+    S32 = None if rounding is None else _AlsdSide(case, torch.float32)
+    absW = S64.Wh.abs() if rounding == "mfma" else None
+    B, T, _ = S64.f_all.shape
+    lens = case["lens"] if "lens" in case else case["out_len"]
+    out = []
+    for b in range(B):
+        length = min(max(int(lens[b]), 0), T)
+        r = _alsd_utterance(S64, S32, b, length, W, alsd_u_max(alsd_max_target_len, length), bool(score_norm), rounding, absW)
+        if n_best is not None:
+            r["hyps"], r["slack"] = r["hyps"][:n_best], r["slack"][:n_best]
+        out.append(r)
+    return out
+
+
+def beam_rnnt_max_width():
+    """The largest beam width csrc/rnnt_beam.hip takes; beyond it beam_rnnt_decode runs the host routine."""
+    from . import _lib
+    return int(_lib.lib().ia_rnnt_beam_max_width())
+
+
+def beam_rnnt_alsd_device(op, beam_size, alsd_max_target_len=1.0, score_norm=True, n_best=None):
+    """One launch of csrc/rnnt_beam.hip on device operands (f_all, EW, Whh, Wp, bp, Wh, bh, lens; the three weight matrices
+    both bf16 or both fp32).  Returns None when the kernel refuses the shape as unsupported (before any device work), else the
+    device tensors (tokens [B,K,L], steps [B,K,L], lengths [B,K], scores [B,K], n_finished [B]), K = min(n_best or beam_size,
+    beam_size), L = T + the largest u_max."""
+    from . import _lib
+    L = _lib.lib()
+    f_all = op["f_all"].float().contiguous()
+    dev = f_all.device
+    B, T, Hj = f_all.shape
+    Whh, Wp, Wh = op["Whh"], op["Wp"], op["Wh"]
+    w16 = Whh.dtype == torch.bfloat16
+    if not w16:
+        Whh, Wp, Wh = Whh.float(), Wp.float(), Wh.float()
+    Whh, Wp, Wh = Whh.contiguous(), Wp.contiguous(), Wh.contiguous()
+    EW, bp, bh = op["EW"].float().contiguous(), op["bp"].float().contiguous(), op["bh"].float().contiguous()
+    Hp, V = Whh.shape[1], Wh.shape[0]
+    W = int(beam_size)
+    K = W if n_best is None else max(1, min(int(n_best), W))
+    lens = (op["lens"] if "lens" in op else op["out_len"]).to(dev).long().contiguous()
+    a = alsd_max_target_len
+    clamped = lens.clamp(0, T)
+    um = (clamped.double() * a).long() if isinstance(a, float) else torch.full_like(clamped, int(a))
+    um = um.clamp(min=0).to(torch.int32).contiguous()
+    max_umax = alsd_u_max(a, T)
+    n = int(L.ia_rnnt_beam_workspace_bytes(B, T, Hp, Hj, V, W, max_umax))
+    if n == 0:
+        return None
+    ws = torch.empty(n, dtype=torch.uint8, device=dev)
+    ml = T + max_umax
+    tokens = torch.empty(B, K, ml, dtype=torch.int32, device=dev)
+    steps = torch.empty(B, K, ml, dtype=torch.int32, device=dev)
+    lengths = torch.empty(B, K, dtype=torch.int32, device=dev)
+    scores = torch.empty(B, K, dtype=torch.float32, device=dev)
+    nfin = torch.empty(B, dtype=torch.int32, device=dev)
+    fn = L.ia_rnnt_beam_alsd_bf16w if w16 else L.ia_rnnt_beam_alsd
+    with torch.cuda.device(dev):
+        st = fn(_lib.ptr(f_all), _lib.ptr(lens), _lib.ptr(um), _lib.ptr(EW), _lib.ptr(Whh), _lib.ptr(Wp), _lib.ptr(bp), _lib.ptr(Wh),
+                _lib.ptr(bh), B, T, Hp, Hj, V, W, K, max_umax, int(bool(score_norm)), _lib.ptr(tokens), _lib.ptr(steps),
+                _lib.ptr(lengths), _lib.ptr(scores), _lib.ptr(nfin), _lib.ptr(ws), n, _lib.stream_ptr())
+    if st == -4:                                    # IA_UNSUPPORTED: refused before any device work
+        return None
+    _lib.check(st, "ia_rnnt_beam_alsd")
+    return tokens, steps, lengths, scores, nfin
+
+
+def alsd_unpack(raw):
+    """The device result as the host routine's lists: per utterance dict(hyps=[(token ids, score, steps)], n_finished)."""
+    tokens, steps, lengths, scores, nfin = (t.cpu() for t in raw)
+    out = []
+    for b in range(tokens.shape[0]):
+        hyps = []
+        for r in range(tokens.shape[1]):
+            n = int(lengths[b, r])
+            if n >= 0:
+                hyps.append((tokens[b, r, :n].tolist(), float(scores[b, r]), steps[b, r, :n].tolist()))
+        out.append(dict(hyps=hyps, n_finished=int(nfin[b])))
+    return out
+
+
+@torch.no_grad()
+def beam_rnnt_decode(model, encoded, encoded_len, language_ids, beam_size=4, return_best_hypothesis=True, score_norm=True,
+                     alsd_max_target_len=1.0):
+    """Transducer beam search, `strategy: alsd` of NeMo's RNNTBPEDecoding: per utterance the best Hypothesis (score,
+    y_sequence, timestep = the alignment step of each label), or with return_best_hypothesis=False the NBestHypotheses: the
+    first beam_size of the ranked list (NeMo returns every finished hypothesis; `n_finished` says how many there were).
+    The operands are those of greedy_rnnt_decode_device; device tensors run csrc/rnnt_beam.hip (one launch per language, one
+    device-to-host copy), CPU tensors and shapes beyond the kernel's limits (with a warning) the float64 host routine
+    beam_rnnt_alsd_host.  beam_size = 1 runs the same definition with one hypothesis (NeMo substitutes its greedy search)."""
+    global _warned_beam_limit
+    W = int(beam_size)
+    if W < 1:
+        raise ValueError("Beam search size cannot be less than 1!")
+    langs = list(language_ids)
+    if len(set(langs)) > 1:
+        out = [None] * len(langs)
+        for lang in dict.fromkeys(langs):
+            idx = [i for i, l in enumerate(langs) if l == lang]
+            sel = torch.tensor(idx, device=encoded.device)
+            sub = beam_rnnt_decode(model, encoded.index_select(0, sel), encoded_len.to(encoded.device).index_select(0, sel),
+                                   [lang] * len(idx), W, return_best_hypothesis, score_norm, alsd_max_target_len)
+            for i, h in zip(idx, sub):
+                out[i] = h
+        return out
+    op = _rnnt_decode_operands(model, encoded, encoded_len, langs, who="beam_rnnt_decode")
+    op["lens"] = op["out_len"]
+    res = None
+    if encoded.is_cuda and op["B"] > 0 and op["T"] > 0:
+        raw = beam_rnnt_alsd_device(op, W, alsd_max_target_len, score_norm) if W <= beam_rnnt_max_width() else None
+        if raw is None and not _warned_beam_limit:
+            warnings.warn(f"beam_rnnt_decode: beam_size={W}, pred_hidden={op['Hp']}, joint_hidden={op['Hj']}, {op['V']} classes "
+                          f"exceed the kernel's limits (beam_size <= {beam_rnnt_max_width()}); searching on the host instead")
+            _warned_beam_limit = True
+        res = alsd_unpack(raw) if raw is not None else None
+    if res is None:
+        res = beam_rnnt_alsd_host(op, W, alsd_max_target_len, score_norm, None, W)
+    out = []
+    for r in res:
+        hs = [Hypothesis(score=s, y_sequence=list(y), timestep=list(ts)) for y, s, ts in r["hyps"]]
+        out.append(hs[0] if return_best_hypothesis else NBestHypotheses(hs, n_finished=r["n_finished"]))
+    return out

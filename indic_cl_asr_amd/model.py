@@ -203,8 +203,11 @@ class EncDecHybridRNNTCTCModel(TranscriptionMixin, nn.Module):
           beam_beta = 0.0 as in NeMo): the file is read once here and its device image is kept per language.  Any other path
           raises NotImplementedError (KenLM binaries are not read), a missing file FileNotFoundError.  The search types
           'pyctcdecode' / 'flashlight' (also as strategies) raise NotImplementedError.
-        decoder_type None / 'rnnt':  strategy 'greedy' / 'greedy_batch' (greedy.max_symbols is stored); the transducer beam
-          strategies raise NotImplementedError.
+        decoder_type None / 'rnnt':  strategy 'greedy' / 'greedy_batch' (greedy.max_symbols is stored), or 'alsd' with
+          beam.{beam_size (required, as NeMo's config has no default), return_best_hypothesis, score_norm, alsd_max_target_len}:
+          alignment-length synchronous decoding, decoding.beam_rnnt_decode on csrc/rnnt_beam.hip.  softmax_temperature != 1,
+          preserve_alignments, compute_timestamps, ngram_lm_model and language_model are refused by name; 'beam', 'tsd' and
+          'maes' raise NotImplementedError.  A refusal changes no state.
         `lang_id` is accepted as the reference accepts it; transcribe() takes the language per call."""
         def get(cfg, key, default=None):
             if cfg is None:
@@ -215,13 +218,36 @@ class EncDecHybridRNNTCTCModel(TranscriptionMixin, nn.Module):
         if decoder_type is None or decoder_type == "rnnt":
             strategy = get(decoding_cfg, "strategy", state.get("rnnt", {}).get("strategy", "greedy_batch"))
             beams = ["beam", "tsd", "alsd", "maes"]
-            if strategy in beams:
+            if strategy in beams and strategy != "alsd":
                 raise NotImplementedError(f"transducer decoding strategy `{strategy}` is not implemented: the transducer head "
-                                          "decodes greedily ('greedy', 'greedy_batch')")
-            if strategy not in ("greedy", "greedy_batch"):
+                                          "decodes greedily ('greedy', 'greedy_batch') or with 'alsd'")
+            if strategy not in ("greedy", "greedy_batch", "alsd"):
                 raise ValueError(f"Decoding strategy must be one of {['greedy', 'greedy_batch'] + beams}\nbut was provided {strategy}")
-            max_symbols = get(get(decoding_cfg, "greedy"), "max_symbols", state.get("rnnt", {}).get("max_symbols", 10))
-            state["rnnt"] = dict(strategy=strategy, max_symbols=None if max_symbols is None else int(max_symbols))
+            prev = state.get("rnnt", {})
+            max_symbols = get(get(decoding_cfg, "greedy"), "max_symbols", prev.get("max_symbols", 10))
+            new = dict(strategy=strategy, max_symbols=None if max_symbols is None else int(max_symbols))
+            if strategy == "alsd":
+                beam = get(decoding_cfg, "beam")
+                old = prev if prev.get("strategy") == "alsd" else {}
+                beam_size = get(beam, "beam_size", old.get("beam_size"))
+                if beam_size is None:      # NeMo's config has no default either
+                    raise NotImplementedError("transducer decoding strategy `alsd` needs beam.beam_size: "
+                                              "decoding_cfg={'strategy': 'alsd', 'beam': {'beam_size': N}}")
+                if int(beam_size) < 1:
+                    raise ValueError("Beam search size cannot be less than 1!")
+                temperature = get(beam, "softmax_temperature", get(decoding_cfg, "temperature", 1.0))
+                if temperature is not None and float(temperature) != 1.0:
+                    raise NotImplementedError("alsd: softmax_temperature != 1 is not implemented")
+                for key in ("preserve_alignments", "compute_timestamps", "ngram_lm_model", "language_model"):
+                    if get(decoding_cfg, key) or get(beam, key):
+                        raise NotImplementedError(f"alsd: {key} is not implemented")
+                max_len = get(beam, "alsd_max_target_len", old.get("alsd_max_target_len", 1.0))
+                if isinstance(max_len, bool) or not isinstance(max_len, (int, float)) or max_len < 0:
+                    raise ValueError(f"alsd_max_target_len must be a non-negative float (times the length) or int, got {max_len!r}")
+                new.update(beam_size=int(beam_size),
+                           return_best_hypothesis=bool(get(beam, "return_best_hypothesis", old.get("return_best_hypothesis", True))),
+                           score_norm=bool(get(beam, "score_norm", old.get("score_norm", True))), alsd_max_target_len=max_len)
+            state["rnnt"] = new
             self.decoding_strategy = state
             self.cur_decoder = "rnnt"
         elif decoder_type == "ctc":

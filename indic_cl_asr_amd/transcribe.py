@@ -179,7 +179,9 @@ class TranscriptionMixin:
         hyps, logits_list = [], []
         strategy = getattr(self, "decoding_strategy", None) or {}     # change_decoding_strategy; nothing set: greedy
         ctc_beam = strategy.get("ctc") if strategy.get("ctc", {}).get("strategy") == "beam" else None
-        beam_out = []          # CTC head + beam strategy: a Hypothesis / NBestHypotheses per utterance
+        rnnt_beam = strategy.get("rnnt") if strategy.get("rnnt", {}).get("strategy") == "alsd" else None
+        beam_cfg = rnnt_beam if self.cur_decoder == "rnnt" else ctc_beam
+        beam_out = []          # beam strategy of the current head: a Hypothesis / NBestHypotheses per utterance
         try:
             loader = self._transcribe_input_processing(audio, cfg, transcripts=None, language_id=language_id)
             for batch in loader:
@@ -188,7 +190,10 @@ class TranscriptionMixin:
                     sig, sig_len = sig.to(cfg._internal.device), sig_len.to(cfg._internal.device)
                 langs = [language_id] * sig.shape[0]
                 encoded, encoded_len = self.forward(input_signal=sig, input_signal_length=sig_len)
-                if self.cur_decoder == "rnnt":
+                if self.cur_decoder == "rnnt" and rnnt_beam is not None:
+                    res, ids = self._rnnt_beam_batch(encoded, encoded_len, langs, rnnt_beam, cfg.return_hypotheses)
+                    beam_out += res
+                elif self.cur_decoder == "rnnt":
                     ids = self.decode(encoded, encoded_len, langs, **({"max_symbols": strategy["rnnt"]["max_symbols"]}
                                                                       if "rnnt" in strategy else {}))
                 elif ctc_beam is not None and not logprobs:
@@ -210,10 +215,27 @@ class TranscriptionMixin:
             return logits_list
         if beam_out and cfg.return_hypotheses:
             # ctc_decoder_predictions_tensor (ctc_decoding.py:381-382): the best hypotheses, and all of them
-            if ctc_beam["return_best_hypothesis"]:
+            if beam_cfg["return_best_hypothesis"]:
                 return (beam_out, list(beam_out))
             return ([nb.n_best_hypotheses[0] for nb in beam_out], beam_out)
         return (hyps, list(hyps))
+
+    def _rnnt_beam_batch(self, encoded, encoded_len, langs, beam, with_text):
+        """One batch through decoding.beam_rnnt_decode (strategy `alsd`).  Returns (Hypothesis / NBestHypotheses per utterance,
+        best ids); `_beam_keep`, when a list, receives (encoder output, frame lengths) -- for tests."""
+        from .decoding import beam_rnnt_decode
+        keep = getattr(self, "_beam_keep", None)
+        if keep is not None:
+            keep.append((encoded, encoded_len))
+        res = beam_rnnt_decode(self, encoded, encoded_len, langs, beam_size=beam["beam_size"],
+                               return_best_hypothesis=beam["return_best_hypothesis"], score_norm=beam["score_norm"],
+                               alsd_max_target_len=beam["alsd_max_target_len"])
+        best = [r if beam["return_best_hypothesis"] else r.n_best_hypotheses[0] for r in res]
+        if with_text:
+            for r in res:
+                for h in ([r] if beam["return_best_hypothesis"] else r.n_best_hypotheses):
+                    h.text = self._ids_to_text(h.y_sequence, langs[0])
+        return res, [h.y_sequence for h in best]
 
     def _ctc_beam_batch(self, encoded, encoded_len, language_id, beam, with_text):
         """One batch through decoding.beam_ctc_decode (with the language's n-gram model, if change_decoding_strategy loaded
