@@ -1396,6 +1396,19 @@ int ia_ctc_align(const float* lp, int ld, const float* lse, const int64_t* targe
                  const int64_t* target_lens, int B, int T, int V, int S, int blank, int32_t* path, int32_t* spans, float* score,
                  void* workspace, size_t workspace_bytes, ia_stream_t stream);
 
+/* ---- CTC forced alignment of long transcripts (csrc/ctc_align_long.hip): the definition, arguments, checks and outputs of
+ * ia_ctc_align, bit-equal results, for every 0 <= S <= ia_ctc_align_long_max_targets() = 8191.  One workgroup of W waves per
+ * utterance, K states per lane: K = 4 up to L = 2S+1 <= 4096, then the smallest of {8, 16} with L <= 1024 K; W the smallest
+ * power of two with L <= 64 K W.  One workgroup barrier per frame; workgroups never wait for each other.
+ *   workspace: ia_ctc_align_long_workspace_bytes(B,T,S) = B * T * (64 W K / 4) bytes rounded up to 256 (2 bits per state: frame t
+ *   of utterance b is a row of 64 W words of 2K bits at word index (b T + t) 64 W), 256-byte aligned; 0 when S is beyond the limit,
+ *   where ia_ctc_align_long returns IA_UNSUPPORTED. */
+int ia_ctc_align_long_max_targets(void);
+size_t ia_ctc_align_long_workspace_bytes(int B, int T, int S);
+int ia_ctc_align_long(const float* lp, int ld, const float* lse, const int64_t* targets, const int64_t* input_lens,
+                      const int64_t* target_lens, int B, int T, int V, int S, int blank, int32_t* path, int32_t* spans, float* score,
+                      void* workspace, size_t workspace_bytes, ia_stream_t stream);
+
 /* ---- CTC prefix beam search (csrc/ctc_beam.hip): the sum-product sibling of the aligner, the algorithm of Hannun et al. 2014
  * (arXiv:1408.2873) in log space, one launch, one persistent workgroup per utterance.  The beam holds at most W distinct label
  * prefixes, each with pb / pnb = log-probability of the alignments of the frames so far that collapse to it and end in blank /

@@ -193,6 +193,9 @@ SIGNATURES = {
     "ia_ctc_align_max_targets": (_i, []),
     "ia_ctc_align_workspace_bytes": (_sz, [_i, _i, _i]),
     "ia_ctc_align": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ia_ctc_align_long_max_targets": (_i, []),
+    "ia_ctc_align_long_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ia_ctc_align_long": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ia_ctc_beam_max_width": (_i, []),
     "ia_ctc_beam_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "ia_ctc_beam_search": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -3,8 +3,9 @@
 The semantics are those of the forced aligner the reference's NeMo ships for this model family
 (tools/nemo_forced_aligner: utils/viterbi_decoding.py:19-136 run on one utterance alone, the time rule of
 utils/data_prep.py:588-672, the CTM lines of utils/make_ctm_files.py:82-119).  What differs in HOW: the Viterbi pass is one
-launch of csrc/ctc_align.hip (one wave per utterance, backpointers and backtrace on the device) instead of T Python
-iterations of batched torch ops and a host backtrace, and it reads the CTC head's raw logits + per-frame log-sum-exp.
+launch of csrc/ctc_align.hip (one wave per utterance, backpointers and backtrace on the device; transcripts beyond its 255
+tokens: one workgroup per utterance, csrc/ctc_align_long.hip) instead of T Python iterations of batched torch ops and a host
+backtrace, and it reads the CTC head's raw logits + per-frame log-sum-exp.
 
   v_t(s) = max(v_{t-1}(s), v_{t-1}(s-1), v_{t-1}(s-2) if s is odd and label(s) != label(s-2)) + q_t(label(s))
 
@@ -160,10 +161,11 @@ def _carve(packed, B, T, S):
             packed[n_path + n_spans:].view(torch.float32))
 
 
-def _align_device(x, input_lens, targets, target_lens, blank, lse):
+def _align_device(x, input_lens, targets, target_lens, blank, lse, entry="ia_ctc_align"):
     """One launch; (packed i32 [B*T + 2*B*S + B], path, spans, score) -- the three outputs are views of `packed`, so one copy
     brings them to the host."""
     L = _lib.lib()
+    launch, ws_bytes = getattr(L, entry), getattr(L, entry + "_workspace_bytes")
     x, ld = _rows_in_place(x.detach())
     B, T, V = x.shape
     dev = x.device
@@ -172,15 +174,20 @@ def _align_device(x, input_lens, targets, target_lens, blank, lse):
     il = input_lens.detach().to(dev).long().contiguous()
     tl = target_lens.detach().to(dev).long().contiguous()
     z = None if lse is None else lse.detach().to(dev).float().contiguous()
-    n = L.ia_ctc_align_workspace_bytes(B, T, S)
+    n = ws_bytes(B, T, S)
     ws = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
     packed = torch.empty(B * T + 2 * B * S + B, dtype=torch.int32, device=dev)
     path, spans, score = _carve(packed, B, T, S)
     with torch.cuda.device(dev):
-        _lib.check(L.ia_ctc_align(_lib.ptr(x), ld, _lib.ptr(z), _lib.ptr(tg), _lib.ptr(il), _lib.ptr(tl), B, T, V, S, int(blank),
-                                  _lib.ptr(path), _lib.ptr(spans) if S > 0 else None, _lib.ptr(score), _lib.ptr(ws), n,
-                                  _lib.stream_ptr()), "ia_ctc_align")
+        _lib.check(launch(_lib.ptr(x), ld, _lib.ptr(z), _lib.ptr(tg), _lib.ptr(il), _lib.ptr(tl), B, T, V, S, int(blank),
+                          _lib.ptr(path), _lib.ptr(spans) if S > 0 else None, _lib.ptr(score), _lib.ptr(ws), n,
+                          _lib.stream_ptr()), entry)
     return packed, path, spans, score
+
+
+def _align_device_long(x, input_lens, targets, target_lens, blank, lse):
+    """_align_device on csrc/ctc_align_long.hip (one workgroup per utterance): any S <= max_targets_long()."""
+    return _align_device(x, input_lens, targets, target_lens, blank, lse, entry="ia_ctc_align_long")
 
 
 def ctc_forced_align(logits_or_log_probs, input_lens, targets, target_lens, blank, lse=None):
@@ -207,6 +214,37 @@ def ctc_forced_align(logits_or_log_probs, input_lens, targets, target_lens, blan
         out = ctc_forced_align_host(x, input_lens, targets, target_lens, blank, lse)
         return tuple(t.to(x.device) for t in out)
     return _align_device(x, input_lens, targets, target_lens, blank, lse)[1:]
+
+
+_warned_limit_long = False
+
+
+def max_targets_long():
+    """Longest transcript (tokens) the workgroup kernel takes; beyond it ctc_forced_align_long runs the host routine."""
+    return int(_lib.lib().ia_ctc_align_long_max_targets())
+
+
+def ctc_forced_align_long(logits_or_log_probs, input_lens, targets, target_lens, blank, lse=None):
+    """ctc_forced_align for long transcripts: same arguments, same return values, bit-equal results.  CUDA tensors run
+    csrc/ctc_align_long.hip (one workgroup per utterance) for any S <= max_targets_long(), short transcripts included; beyond
+    that the host routine, with a one-time warning.  CPU tensors run the host routine."""
+    global _warned_limit_long
+    x = logits_or_log_probs
+    if x.dim() != 3:
+        raise ValueError(f"expected [B,T,V] log-probs or logits, got shape {tuple(x.shape)}")
+    if not 0 <= int(blank) < x.shape[2]:
+        raise ValueError(f"blank={blank} outside the {x.shape[2]} classes")
+    if not x.is_cuda:
+        return ctc_forced_align_host(x, input_lens, targets, target_lens, blank, lse)
+    S = targets.reshape(x.shape[0], -1).shape[1]
+    if S > max_targets_long():
+        if not _warned_limit_long:
+            warnings.warn(f"ctc_forced_align_long: transcripts padded to {S} tokens exceed the workgroup kernel's limit of "
+                          f"{max_targets_long()} (extended length 2S+1 <= 16384); aligning on the host instead")
+            _warned_limit_long = True
+        out = ctc_forced_align_host(x, input_lens, targets, target_lens, blank, lse)
+        return tuple(t.to(x.device) for t in out)
+    return _align_device_long(x, input_lens, targets, target_lens, blank, lse)[1:]
 
 
 # ---------------------------------------------------------------------------------------------------------- results

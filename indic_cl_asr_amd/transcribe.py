@@ -278,7 +278,8 @@ class TranscriptionMixin:
         `transcripts` (strings, tokenised by the attached data.MultilingualTokenizer in the loader) or `token_ids` (a list of
         id lists local to the language: tensor audio, models without a tokenizer) -- exactly one of them.  Always the CTC
         head, whatever `cur_decoder` says.  Per batch on the MI355X: forward, the language's head logits, ia_ctc_row_lse,
-        ia_ctc_align, one device-to-host copy of path, spans and score.  (`_keep`, a list: receives each batch's
+        ia_ctc_align (transcripts beyond its 255 tokens: ia_ctc_align_long, up to 8191), one device-to-host copy of path,
+        spans and score.  (`_keep`, a list: receives each batch's
         (scores fed to the aligner, lse or None, frame lengths, targets, target lengths) -- for tests.)"""
         from . import align as A
         from . import cl
@@ -331,8 +332,11 @@ class TranscriptionMixin:
                 if encoded.is_cuda and tg.shape[1] <= A.max_targets():
                     packed, path, spans, score = A._align_device(x, encoded_len, tg, tg_len, blank, lse)
                     path, spans, score = A._carve(packed.cpu(), *path.shape, spans.shape[1])
-                else:   # the host routine (for device tensors beyond the kernel's limit: with ctc_forced_align's warning)
-                    path, spans, score = A.ctc_forced_align(x, encoded_len, tg, tg_len, blank, lse)
+                elif encoded.is_cuda and tg.shape[1] <= A.max_targets_long():    # one workgroup per utterance
+                    packed, path, spans, score = A._align_device_long(x, encoded_len, tg, tg_len, blank, lse)
+                    path, spans, score = A._carve(packed.cpu(), *path.shape, spans.shape[1])
+                else:   # the host routine (for device tensors beyond the kernels' limit: with ctc_forced_align_long's warning)
+                    path, spans, score = A.ctc_forced_align_long(x, encoded_len, tg, tg_len, blank, lse)
                 if _keep is not None:
                     _keep.append((x, lse, encoded_len, tg, tg_len))
                 results += A.build_alignments(path, spans, score, ids, frame_s, self.tokenizer, language_id)
